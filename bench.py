@@ -15,6 +15,12 @@ inputs already resident in HBM when the timed region starts:
       batch of 1024 queries over this rank's 10M x 768 f32 shard (row-range sharding, weak scaling),
       then for N > 1 the RCCL all-gather of the per-shard [Q, k] results and the host-side merge on rank 0.
 
+A plain run does what the headline `value` needs: the embed workload (or the scan alone under `--workload scan`) is set up,
+warmed up, timed over --steps steps, and its line printed.  `--full` adds everything else the benchmark reports: the scan
+under the default `--workload both`, its batch-size sweep and clustered corpora, the IVF_FLAT block (N = 1) and the CPU
+baselines.  `--dump-outputs DIR` writes what the timed steps returned in their last step as DIR/<name>.npy (inputs are
+seeded: the same arguments give the same inputs on every run).
+
 Rank 0 prints ONE JSON line.  The CPU oracle is used only for the `cpu_baseline` legs (bounded samples,
 rank 0, N = 1) -- never on the measured path.
 """
@@ -40,7 +46,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--workload", default="both", choices=["both", "embed", "scan"], help="both = embed + scan (+ the IVF_FLAT block at N = 1)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline: scan, sweeps, IVF_FLAT block, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (f32 / f64, at most 64 MB in all)")
+    ap.add_argument("--workload", default="both", choices=["both", "embed", "scan"], help="both = embed (+ with --full: scan and the IVF_FLAT block at N = 1)")
     # embed
     ap.add_argument("--batch", type=int, default=256, help="chunks per step per GPU")
     ap.add_argument("--seq", type=int, default=256, help="tokens per chunk")
@@ -60,7 +68,10 @@ def parse():
     ap.add_argument("--ivf-dim", type=int, default=3072)
     ap.add_argument("--ivf-nlist", type=int, default=4096)
     ap.add_argument("--ivf-nprobe", type=int, default=64)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Ctx:
@@ -176,6 +187,7 @@ def bench_embed(ctx, args) -> dict:
     attn_ms, attn_n = ctx.rt.profile_read(3)
     ctx.rt.set_profiling(False)
     assert bool(torch.isfinite(out).all()), "encoder produced non-finite values"
+    pooled = out.cpu().numpy()
     enc.close()
 
     gemm_fl, attn_fl = encoder_flops_per_chunk(S)
@@ -194,6 +206,7 @@ def bench_embed(ctx, args) -> dict:
                      "attention_avg_launch_ms": attn_ms / max(1, attn_n),
                      "end_to_end_tflops": chunks_s / ctx.world * (gemm_fl + attn_fl) / 1e12,
                      "end_to_end_frac": chunks_s / ctx.world * (gemm_fl + attn_fl) / 1e12 / MFMA_BF16_PEAK_TFLOPS},
+        "outputs": {"embed_pooled": pooled},
     }
     return res
 
@@ -255,6 +268,7 @@ def bench_scan(ctx, args) -> dict:
 
     merger = ThreadPoolExecutor(max_workers=1) if world > 1 and rank == 0 else None
     pending = []
+    merged = [None]  # rank 0: the last merged (distances, rows) -- what a caller of the sharded search receives
     merge_time = [0.0, 0]
 
     def host_merge(gd, gr):
@@ -266,12 +280,12 @@ def bench_scan(ctx, args) -> dict:
 
     def submit_merge(gd, gr):
         while pending:  # at most one merge in flight behind the step that produced it
-            pending.pop().result()
+            merged[0] = pending.pop().result()
         pending.append(merger.submit(host_merge, gd.cpu().numpy(), gr.cpu().numpy()))
 
     def merge_drain():
         while pending:
-            pending.pop().result()
+            merged[0] = pending.pop().result()
 
     ctx.drain = merge_drain if merger else None
 
@@ -311,6 +325,7 @@ def bench_scan(ctx, args) -> dict:
     scan_ms, scan_n = rt.profile_read(0)
     merge_ms, merge_n = rt.profile_read(1)
     rt.set_profiling(False)
+    top = merged[0] if world > 1 else (out_d.cpu().numpy(), out_r.cpu().numpy())  # None on ranks other than 0
     st = ix.last_search_stats()
     path, unc = st["path"], st["uncertified"]
     coarse_bits, handed = st.get("coarse_bits", 16), st.get("handed_to_bf16", 0)
@@ -319,7 +334,7 @@ def bench_scan(ctx, args) -> dict:
     # Batch-size sweep: the scan is HBM-bound for small batches (exact f32 kernel, one corpus pass per <= 16 queries)
     # and MFMA-bound at Q = 1024.  The exact kernel's own launches are bracketed by hipEvents like the coarse kernel's above.
     sweep, exact_roof = None, None
-    if not args.no_sweep:
+    if args.full and not args.no_sweep:
         sweep = []
         # (1 and 16 queries also with the exact f32 scan forced: the HBM roofline block below is that kernel's; the planner itself
         # answers such batches through the int8 narrow kernel where an int8 shadow may exist)
@@ -362,7 +377,7 @@ def bench_scan(ctx, args) -> dict:
     # exact scores before every phase, every key within the cut kept (up to 4 096 per query) -- which answers in one pass.
     # Reported: the steady-state batch (after three searches).
     clustered = None
-    if not args.no_sweep and world == 1:
+    if args.full and not args.no_sweep and world == 1:
         clustered = {}
         for tag, spread in (("spread_0.5", 0.5), ("spread_0.1", 0.1)):
             cx = _native.Index(rt, dim, metric=args.metric_type, kind="FLAT")
@@ -429,6 +444,7 @@ def bench_scan(ctx, args) -> dict:
         "dtype": (("int8" if coarse_bits == 8 else "bf16") + " coarse + f32 exact re-rank") if path == "batched" else "f32",
         "path": path, "uncertified_queries_last_step": unc,
         "roofline": roof,
+        "outputs": {"topk_distances": top[0], "topk_ids": top[1]} if top else {},
     }
     if world > 1:
         res["host_merge_ms_per_step"] = (1e3 * merge_time[0] / merge_time[1]) if merge_time[1] else None  # rank 0, overlapped with the next step's scan
@@ -610,7 +626,27 @@ def bench_ivf(ctx, args) -> dict:
                                                   "achieved_tflops": 2.0 * Q * nprobe * (rows / nlist) * dim / ex_kern_s / 1e12 if ex_kern_s else None,
                                                   "note": "exact f32 scores of every (query, probed row) pair on v_mfma_f32_16x16x4_f32"}},
             "exhaustive": {"ms_per_batch": 1e3 * t_bf, "qps": Q / t_bf, "path": bf_stats["path"], "uncertified": bf_stats["uncertified"]},
-            "single_query_ms": 1e3 * t_one, "single_query_path": one_path}
+            "single_query_ms": 1e3 * t_one, "single_query_path": one_path,
+            "outputs": {"ivf_distances": auto["dist"], "ivf_ids": auto["ids"]}}
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(dirname: str, outputs: dict) -> None:
+    """outputs {name: array} -> DIR/<name>.npy: floats as f32, row ids as f64 (exact below 2^53).  Above DUMP_LIMIT bytes in all,
+    every array keeps the same fixed, seeded sample of its rows (in order), so two builds still compare row for row."""
+    import numpy as np
+
+    arrs = {n: np.asarray(a, dtype=np.float64 if np.issubdtype(np.asarray(a).dtype, np.integer) else np.float32) for n, a in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrs.items():
+        if total > DUMP_LIMIT:
+            keep = max(1, len(a) * DUMP_LIMIT // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(out / f"{name}.npy", a)
 
 
 # ------------------------------------------------------------------------------------------- main
@@ -679,10 +715,14 @@ def main() -> None:
     with torch.cuda.stream(stream):
         if args.workload in ("both", "embed"):
             embed = bench_embed(ctx, args)
-        if args.workload in ("both", "scan"):
+        if args.workload == "scan" or (args.workload == "both" and args.full):
             scan = bench_scan(ctx, args)
-        if args.workload == "both" and ctx.world == 1 and not args.no_ivf:
+        if args.workload == "both" and args.full and ctx.world == 1 and not args.no_ivf:
             ivf = bench_ivf(ctx, args)
+    outputs = {}
+    for res in (embed, scan, ivf):
+        if res:
+            outputs.update(res.pop("outputs"))
 
     line = {
         "metric": "chunks/sec embed (256-tok) + top-k QPS over 10M x 768",
@@ -710,7 +750,9 @@ def main() -> None:
         if "sweep" in scan:
             line["sweep"] = scan["sweep"]
     if ctx.rank == 0:
-        if ctx.world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline:
             if embed:
                 line["cpu_baseline"] = cpu_baseline_embed(args)
                 if scan:

@@ -7,12 +7,12 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp && cd "$root"
 out=gpurun_out/measure_$tag
 mkdir -p "$out"
-timeout -k 10 500 python3 bench.py > "$out/bench.log" 2>&1
+timeout -k 10 500 python3 bench.py --full > "$out/bench.log" 2>&1
 echo "bench done" && tail -c 300 "$out/bench.log"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o "$tag" -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$out/stats.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o "$tag" -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/stats.log" 2>&1
 echo "stats done"
 # counter passes: one counter family per run, no ivf / sweep (thousands of serialised launches under PMC)
-PMC_ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep"
+PMC_ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_f" -o f -- python3 bench.py $PMC_ARGS > "$out/pmc_f.log" 2>&1
 echo "pmc fetch done"
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/pmc_w" -o w -- python3 bench.py $PMC_ARGS > "$out/pmc_w.log" 2>&1

@@ -1,7 +1,7 @@
 """rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES CSV -> profiles/<round>_pmc_mfma.json.
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES --output-format csv -d DIR -o m -- \\
-        python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep
+        python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep
     python scripts/pmc_mfma_summary.py --csv DIR/.../m_counter_collection.csv --out profiles/r2a_pmc_mfma.json
 
 What the counters are (MI355X_MICROARCH.md, cycle-constants table and DVFS section): SQ_VALU_MFMA_BUSY_CYCLES counts matrix-pipe
@@ -47,7 +47,7 @@ expected = {
     "gemm256_bf16_kernel<0, 0>": 2.0 * M * 2304 * 768 / 16384 * 16,    # QKV, bias
     "gemm256_bf16_kernel<1, 0>": 2.0 * M * 3072 * 768 / 16384 * 16,    # FFN1, bias + GELU
 }
-res = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES on `bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep`, MI355X; "
+res = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES on `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-ivf --no-sweep`, MI355X; "
                  "profiled passes clock ~3-5 % lower than unprofiled ones (MI355X_MICROARCH.md DVFS item 2); built by scripts/pmc_mfma_summary.py. " + a.note,
        "kernels": {}}
 for name, ds in sorted(groups.items(), key=lambda kv: -sum(x.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0) for x in kv[1])):

@@ -1,8 +1,8 @@
 """rocprofv3 --pmc CSVs -> profiles/<round>_pmc_traffic.json (the `traffic` figures bench.py reports).
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d DIR_F -o f -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d DIR_W -o w -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d DIR_E -o e -- python3 bench.py --workload scan --queries 16 --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d DIR_F -o f -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d DIR_W -o w -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d DIR_E -o e -- python3 bench.py --full --workload scan --queries 16 --steps 3 --warmup 1 --no-cpu-baseline
     python scripts/pmc_summary.py --fetch DIR_F/.../f_counter_collection.csv --write DIR_W/.../w_counter_collection.csv \\
         --fetch-exact DIR_E/.../e_counter_collection.csv --out profiles/r1r_pmc_traffic.json
 
@@ -53,7 +53,7 @@ ap.add_argument("--note", default="")
 a = ap.parse_args()
 F, W = per_kernel(a.fetch), per_kernel(a.write)
 res = {"csrc_sha": csrc_sha(), "commit": os.environ.get("SC_COMMIT", "?"),
-       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --steps 3 --warmup 1 --no-cpu-baseline`, "
+       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`, "
                  "MI355X; FETCH_SIZE doubled for 16 B/lane streaming reads as MI355X_MICROARCH.md prescribes; built by scripts/pmc_summary.py. " + a.note}
 g_f, g_w = pick(F, "gemm256_bf16_kernel"), pick(W, "gemm256_bf16_kernel")
 if g_f and g_w:
