@@ -235,6 +235,28 @@ sc_status sc_index_put_rows(sc_index* ix, const float* vecs, const int64_t* rows
  * the runtime's stream (the embed -> store hand-over without a trip through host memory); the call itself
  * waits for the stream before returning, because `rows` is the caller's pageable memory. */
 sc_status sc_index_put_rows_dev(sc_index* ix, const float* vecs_dev, const int64_t* rows, int64_t n);
+/* Delete rows: replaces Collection.delete(expr) of pymilvus.  (The reference never calls it -- its re-index only upserts,
+ * src/semcode/services/indexer.py:185-188, so chunks whose key changed stay searchable for ever; MilvusVectorStore.delete /
+ * delete_where and ingest_chunks(prune=True) close that gap on top of this call.)
+ * rows: n distinct local row numbers in [0, rows).  They are removed and the survivors are renumbered densely in their order:
+ * new number = old number - (deleted rows below it).  Afterwards the index answers every call as one into which only the
+ * surviving vectors had been put in that order -- same results bit for bit on every search path; a trained IVF_FLAT index
+ * stays trained with the same centroid bits and every survivor in its list (no k-means, no re-assignment, no re-layout; a
+ * list may become empty).  Every per-row array is compacted in place on the device by stored position (corpus, norms, the
+ * bf16 / int8 / centred shadows as far as they are valid, the IVF position map and list offsets); shadows that were valid
+ * stay valid, pending per-row repairs stay pending.  Scratch is bounded (< 256 MiB) whatever the corpus size, plus 4 - 8 B
+ * per deleted row for the delete list itself.
+ * Everything is validated before anything changes: a row outside [0, rows), a repeated row or rows == NULL with n > 0 give
+ * SC_ERR_INVALID and leave the index bit for bit as it was.  n == 0 is SC_OK and does nothing.  Deleting every row leaves
+ * the index as freshly created (IVF lists dropped).  row_base is unchanged: the renumbering is local to this index.
+ * Serialised with searches and upserts by the index lock, like sc_index_put_rows; synchronises the stream before returning.
+ * Sharded collections (sc_index_*_sharded, storage/sharded.py) have no delete: out of scope here. */
+sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int64_t n);
+/* After sc_index_delete_rows: survivors above the first deleted stored position (`rows_moved`), bytes moved over all per-row
+ * arrays (`bytes_moved`; each is read once and written once, twice where a chunk goes through the bounce buffer), and the
+ * shadows that were valid before the call as bit sets (1 bf16, 2 int8, 4 centred IVF): `shadows_kept` were compacted,
+ * `shadows_dropped` invalidated -- 0 unless every row was deleted. */
+sc_status sc_index_last_delete_stats(sc_index* ix, int64_t* rows_moved, int64_t* bytes_moved, int32_t* shadows_kept, int32_t* shadows_dropped);
 /* Copy rows [first, first+n) back to the host as [n,dim] (persistence, tests). */
 sc_status sc_index_get_rows(sc_index* ix, int64_t first, int64_t n, float* out);
 /* Resize to n rows and fill them on device with sc_synth_fill_dev(seed, first_row). */

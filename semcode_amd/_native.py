@@ -87,6 +87,8 @@ SIGNATURES = {
     "sc_index_overwrite": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "sc_index_put_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "sc_index_put_rows_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "sc_index_delete_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sc_index_last_delete_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sc_index_get_rows": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "sc_index_fill_synthetic": (C.c_int32, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64]),
     "sc_index_fill_synthetic_clustered": (C.c_int32, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_int32, C.c_float]),
@@ -302,6 +304,20 @@ class Index:
         """Same with a DEVICE pointer to tight [n, dim] f32 vectors (e.g. a torch tensor's data_ptr())."""
         r = np.ascontiguousarray(rows, dtype=np.int64)
         _check(lib().sc_index_put_rows_dev(self.handle, C.c_void_p(int(vecs_ptr)), r.ctypes.data_as(C.c_void_p), r.shape[0]))
+
+    def delete_rows(self, rows) -> None:
+        """Remove the given rows (distinct, in [0, len)); the survivors keep their order and are renumbered densely:
+        new number = old number - deleted rows below it.  Nothing changes if the call fails."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        _check(lib().sc_index_delete_rows(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0]))
+
+    def last_delete_stats(self) -> dict:
+        """What the last delete_rows moved: `rows_moved` (survivors above the first deleted stored position), `bytes_moved` (over every
+        per-row array), and the shadows that were valid before it as bit sets (1 bf16, 2 int8, 4 centred IVF): `shadows_kept`
+        were compacted with the rows, `shadows_dropped` invalidated (only when every row was deleted)."""
+        rows, nbytes, kept, dropped = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        _check(lib().sc_index_last_delete_stats(self.handle, C.byref(rows), C.byref(nbytes), C.byref(kept), C.byref(dropped)))
+        return {"rows_moved": int(rows.value), "bytes_moved": int(nbytes.value), "shadows_kept": int(kept.value), "shadows_dropped": int(dropped.value)}
 
     def get_rows(self, first: int, n: int) -> np.ndarray:
         out = np.empty((n, self.dim), dtype=np.float32)

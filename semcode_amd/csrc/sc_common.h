@@ -216,4 +216,8 @@ void sc_launch_centroid_mean(const float* X, int ld, int dim, const int64_t* mem
                              const float* C_old, int ldc_old, hipStream_t s);
 void sc_launch_permute_rows(const float* X, const float* xnorm, const uint32_t* perm, int64_t n, int ld, float* Xo, float* xnorm_o, hipStream_t s);
 void sc_launch_rows_to_sample(const float* X, int ld, int dim, const int64_t* rows, int64_t n, float* out_tight, hipStream_t s);
+// compact.hip: in-place compaction after sc_index_delete_rows
+void sc_launch_delete_map(const uint32_t* del_dev, int64_t lo, int64_t hi, int64_t c0, uint32_t cn, uint32_t* flags, uint32_t* tile_sum, uint32_t* src, hipStream_t s);
+void sc_launch_move_rows(const void* in, int64_t row0, const uint32_t* src, uint32_t m, size_t row_bytes, void* dst, hipStream_t s);
+void sc_launch_renumber_ids(uint32_t* ids, int64_t n, const uint32_t* del_dev, int64_t ndel, hipStream_t s);
 void sc_launch_reseed_centroids(float* C_tight, int dim, const int32_t* moves_dev, int m, hipStream_t s);

@@ -120,6 +120,9 @@ struct sc_index {
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
     int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major
     int last_uncertified = 0;
+    // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (1 bf16, 2 int8, 4 centred) of the shadows kept / dropped
+    int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
+    int last_del_kept = 0, last_del_dropped = 0;
     double uncert_frac = -1.0;                    // share of queries the last batched exhaustive search had to re-run exactly (-1 = never ran)
     std::mutex mu;
 };

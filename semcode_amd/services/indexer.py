@@ -76,7 +76,8 @@ def build_payloads(repo_name: str, repo_path: Path, chunks: Sequence[Any], embed
 
 def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedding_client: Any, vector_store: Any,
                   embed_progress: Optional[Callable[[int, int], None]] = None,
-                  upsert_progress: Optional[Callable[[int, int], None]] = None, batch_size: Optional[int] = None) -> int:
+                  upsert_progress: Optional[Callable[[int, int], None]] = None, batch_size: Optional[int] = None,
+                  prune: bool = False) -> int:
     """`_build_payloads` + `upsert_embeddings` (indexer.py:94-114) as one pipelined pass for the MI355X backend.
 
     What differs from the reference's two loops, and only in speed: (1) no `list[float]` is ever built -- a batch goes
@@ -88,12 +89,20 @@ def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedd
     progress protocols -- (0, total) first, then the cumulative count after every batch; total == 0 reports (0, 0) only
     and calls nothing.  A primary key that occurs more than once keeps its LAST chunk, as sequential upserts would.
     Returns the number of chunks embedded and stored.
+
+    prune=True makes the call a re-index of the WHOLE repository: once the last batch is stored, every row whose `repo` column
+    is repo_name and whose primary key is not one of this call's chunk ids is deleted (vector_store.delete).  The key is
+    md5(repo:path:start:end), so an edit that shifts line numbers, a removed or a renamed file leave rows behind that no
+    chunk of the new tree maps to; the reference never removes them (its re-index only upserts).  Nothing is pruned if the
+    ingest raises.  The default keeps the reference's behaviour: upsert only.
     """
     total = len(chunks)
     for cb in (embed_progress, upsert_progress):
         if cb:
             cb(0, total)
     if total == 0:
+        if prune:  # the repository has no chunks any more: none of its rows is current
+            vector_store.delete_where(repo=repo_name)
         return 0
     ids = [make_chunk_id(repo_name, c.path, c.start_line, c.end_line) for c in chunks]
     last = {pk: i for i, pk in enumerate(ids)}
@@ -144,4 +153,7 @@ def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedd
                 q.get_nowait()
             except queue.Empty:
                 worker.join(0.05)
+    if prune:  # (only reached when every batch was stored and waited for)
+        current = set(ids)
+        vector_store.delete([pk for pk in vector_store.keys_where(repo=repo_name) if pk not in current])
     return len(keep)

@@ -11,6 +11,8 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
                                                    settings.milvus_upsert_batch_size
     .search(vector, top_k=10)                   -> iterable of Hits; hit.entity.get(field), hit.distance,
                                                    hit.score, hit.id  (pymilvus SearchResult shape)
+    .delete(ids) / .delete_where(repo=, path=, language=)
+                                                -> Collection.delete(expr): rows removed, survivors renumbered densely
 
 What lives where: vectors and their norms in HBM (sc_index); the scalar columns of the reference
 schema (id, repo, path, language, text, metadata; milvus_store.py:59-74) and the md5 -> row map in
@@ -51,7 +53,10 @@ class _Entity:
 
 
 class Hit:
-    """One search hit: .id (primary key), .distance == .score (metric value), .entity.get(field)."""
+    """One search hit: .id (primary key), .distance == .score (metric value), .entity.get(field).
+
+    .row is the row number at the time of the search: a later delete() / delete_where() renumbers the rows behind the deleted
+    ones, so the .row of a hit obtained before it is stale afterwards (.id stays valid for as long as the key is stored)."""
 
     __slots__ = ("id", "distance", "entity", "row")
 
@@ -292,6 +297,56 @@ class MilvusVectorStore:
             # that batch then hold undefined vectors and the caller must upsert them again
             embedding_client.embed_ids_into(self, token_ids, lens, rows, wait=wait)
             self.commit_rows(ids, rows, texts, metadatas)
+
+    # ------------------------------------------------------------------ delete (Collection.delete(expr) of pymilvus)
+    def delete(self, ids: Sequence[str]) -> int:
+        """Remove the rows of these primary keys; unknown (and repeated) keys are ignored.  Returns the number of rows removed.
+        The rows behind a removed row move up (row numbers stay dense): Hit.row values obtained before the call are stale."""
+        if self._collection is None:
+            raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
+        with self._lock:
+            return self._delete_rows(sorted({self._row_of[pk] for pk in ids if pk in self._row_of}))
+
+    def _rows_where(self, repo: Optional[str], path: Optional[str], language: Optional[str]) -> "list[int]":
+        if repo is None and path is None and language is None:
+            raise ValueError("give at least one of repo, path, language")
+        return [r for r in range(len(self._ids))
+                if (repo is None or self._repos[r] == repo) and (path is None or self._paths[r] == path)
+                and (language is None or self._languages[r] == language)]
+
+    def keys_where(self, *, repo: Optional[str] = None, path: Optional[str] = None, language: Optional[str] = None) -> List[str]:
+        """Primary keys of the rows whose scalar columns equal ALL the given values (what delete_where would remove), in row order."""
+        with self._lock:
+            return [self._ids[r] for r in self._rows_where(repo, path, language)]
+
+    def delete_where(self, *, repo: Optional[str] = None, path: Optional[str] = None, language: Optional[str] = None) -> int:
+        """Remove every row whose scalar columns equal ALL the given values (`repo == .. and path == ..`, the expr of
+        Collection.delete); at least one must be given.  Returns the number of rows removed.  Hit.row values obtained before
+        the call are stale afterwards, as with delete()."""
+        if self._collection is None:
+            raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
+        with self._lock:
+            return self._delete_rows(self._rows_where(repo, path, language))
+
+    def _delete_rows(self, rows: "list[int]") -> int:
+        """rows: ascending, distinct.  One native call, then the columns: committed only after the call has succeeded, so a
+        failure leaves the vectors and the columns as they were (caller holds the lock)."""
+        ix = self._collection
+        if not hasattr(ix, "delete_rows"):
+            raise NotImplementedError(f"{type(ix).__name__} has no delete_rows(rows): this vector index cannot delete")
+        if not rows:
+            return 0
+        ix.delete_rows(np.asarray(rows, dtype=np.int64))
+        gone = np.zeros(len(self._ids), dtype=bool)
+        gone[rows] = True
+        keep = np.flatnonzero(~gone).tolist()
+        for name in ("_ids", "_texts", "_metadata", "_repos", "_paths", "_languages"):
+            col = getattr(self, name)
+            setattr(self, name, [col[r] for r in keep])
+        self._row_of = {pk: r for r, pk in enumerate(self._ids)}
+        if hasattr(ix, "__len__") and len(ix) != len(self._ids):
+            raise RuntimeError(f"vector index holds {len(ix)} rows after the delete, the collection's columns expect {len(self._ids)}")
+        return len(rows)
 
     # ------------------------------------------------------------------ search
     def search(self, vector: "list[float]", top_k: int = 10) -> SearchResult:
