@@ -291,7 +291,7 @@ extern "C" sc_status sc_index_search_sharded(sc_index* ix, sc_comm* c, const flo
         const size_t qb = ((size_t)Q * ix->dim * 4 + 255) & ~(size_t)255, db = (W * n * 4 + 255) & ~(size_t)255;
         // (the staging buffer is the one allocation in front of the collective that can fail on ONE rank: sc_comm_create reserves
         // nothing for it because its size depends on the call; a rank that cannot get it still has to answer the others)
-        sc_status st = sc_grow(ix, (void**)&ix->io, &ix->io_cap, qb + db + W * n * 8);
+        sc_status st = sc_grow(ix, ix->io, qb + db + W * n * 8);
         if (st) {
             // no room for the gathered arrays: take part with the status word alone would leave the payload gathers unmatched, so
             // this rank reports through the status exchange of a zero-payload round -- every rank runs the same two rounds
@@ -308,9 +308,9 @@ extern "C" sc_status sc_index_search_sharded(sc_index* ix, sc_comm* c, const flo
             ex = worst_status(c, all, SC_OK, "sc_index_search_sharded (staging buffer)");
             if (ex) return ex;
         }
-        float* dq = (float*)ix->io;
-        float* all_d = (float*)((char*)ix->io + qb);
-        int64_t* all_r = (int64_t*)((char*)ix->io + qb + db);
+        float* dq = ix->io.as<float>();
+        float* all_d = (float*)(ix->io.as<char>() + qb);
+        int64_t* all_r = (int64_t*)(ix->io.as<char>() + qb + db);
         SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
         st = search_and_gather_locked(ix, c, dq, Q, k, nprobe, all_d, all_r, "sc_index_search_sharded");
         if (st) return st;

@@ -1,6 +1,7 @@
 // sc_internal.h -- handle structs shared by the host-side translation units.
 #pragma once
 #include <atomic>
+#include <cstdlib>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -43,6 +44,38 @@ void sc_runtime_release(sc_runtime* rt);  // frees the runtime when the last ref
 void sc_prof_begin(sc_runtime* rt, int which, hipEvent_t* a, hipEvent_t* b);
 void sc_prof_end(sc_runtime* rt, int which, hipEvent_t a, hipEvent_t b);
 
+// A growable device allocation: sc_grow makes room (contents lost), sc_buf_free returns it.
+struct sc_buf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// device allocation released on scope exit unless handed over with take()
+struct sc_devbuf {
+    void* p = nullptr;
+    ~sc_devbuf() { hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
+    template <class T> T* take() { T* q = (T*)p; p = nullptr; return q; }
+};
+
+// A lazily built per-row mirror of the corpus, indexed by stored position.  One life cycle for all three (sc_index_state.cpp):
+// allocate for the capacity -> build rows [rows, n) -> zero the padding rows -> re-build the rows overwritten since ->
+// move / zero / renumber on delete (sc_delete.cpp) -> invalidate when the layout changes.
+struct sc_shadow {
+    sc_buf arr[2];                 // bf16: {Xb}; int8: {Xq, xscale}; centred: {Xc8, xcs}
+    size_t row_bytes[2] = {0, 0};  // ld * 2 | ld8, 4 | ld8, 16  (0: array not used)
+    int64_t rows = 0;              // stored positions [0, rows) are valid
+    int64_t tail_pad = 0;          // rows of zero padding kept beyond `rows` rounded up to 256 (centred: 256 -- a list's last tile reads up to 255 rows beyond its end)
+    unsigned* maxima = nullptr;    // device: running maxima over the rows (xnorm_max | xnorm_max8 | list_stats, below)
+    // Rows overwritten in place since the shadow was built (stored positions below `rows`): the next search re-builds the shadow rows of
+    // exactly these instead of the whole shadow (8 ms int8 / 54 ms centred at 10M x 768 for one upsert batch of 128:
+    // scripts/upsert_search_interleave.py).  The running maxima only grow in between, which keeps every bound valid; a full rebuild
+    // (layout change, more than SC_SHADOW_DIRTY_MAX rows) clears the list.
+    std::vector<int64_t> dirty;
+    int stat_bit = 0;              // 1 | 2 | 4 in sc_index_last_delete_stats
+};
+
 struct sc_index {
     sc_runtime* rt = nullptr;
     int dim = 0, ld = 0;
@@ -54,21 +87,13 @@ struct sc_index {
     float* X = nullptr;      // [capacity, ld]
     float* xnorm = nullptr;  // [capacity]
     bool trained = false;
-    // scratch (grown on demand)
-    void* stage = nullptr;   size_t stage_cap = 0;
-    float* qpad = nullptr;   size_t qpad_cap = 0;
-    float* qnorm = nullptr;  size_t qnorm_cap = 0;
-    uint64_t* partial = nullptr; size_t partial_cap = 0;
-    void* io = nullptr;      size_t io_cap = 0;
-    // batched path: bf16 shadow of X (rows padded to 128), per-batch scratch
-    void* Xb = nullptr;      size_t xb_cap = 0;   // bytes
-    int64_t shadow_rows = 0;                      // rows [0, shadow_rows) of Xb are valid
-    unsigned* xnorm_max = nullptr;                // device: bits of max |x|^2
-    // int8 coarse stage: int8 shadow (rows of ld8 = ld rounded up to 128 bytes, rows padded to 256) + per-row scale
-    void* Xq = nullptr;      size_t xq_cap = 0;   // bytes
-    float* xscale = nullptr; size_t xscale_cap = 0;
-    int64_t shadow8_rows = 0;
-    unsigned* xnorm_max8 = nullptr;               // device: bits of {max |x|^2, max |x - s q|^2, max relative}
+    // scratch (grown on demand); every sc_buf of the index is listed in SC_INDEX_BUFS below
+    sc_buf stage, qpad, qnorm, partial, io;
+    // batched path: bf16 shadow of X (rows padded to 128), per-batch scratch.  arr[0] = Xb; maxima = xnorm_max: bits of max |x|^2
+    sc_shadow sh_b16;
+    // int8 coarse stage: int8 shadow (rows of ld8 = ld rounded up to 128 bytes, rows padded to 256) + per-row scale.
+    // arr = {Xq, xscale}; maxima = xnorm_max8: bits of {max |x|^2, max |x - s q|^2, max relative}
+    sc_shadow sh_i8;
     int coarse_mode = 0;                          // sc_index_set_coarse_stage: 0 auto (int8 first), 8 int8 only, 16 bf16 only
     bool i8_off = false;                          // the int8 certificate failed for most of a batch on this corpus: use the bf16 stage
     int last_coarse_bits = 0;                     // 8 / 16: coarse stage of the last batched search
@@ -79,11 +104,10 @@ struct sc_index {
     double cost_i8_first = 0.0;                   // seconds per query of the batch that switched the int8 stage off (0 = none pending)
     bool collect_off8 = false, collect_off16 = false;  // the collect pass of that stage resolved less than half of a sub-batch: skip it on this corpus
     int last_collect_tried = 0, last_collect_resolved = 0;  // queries of the last batched search that went through a collect pass / that it answered
-    void* bscratch = nullptr; size_t bscratch_cap = 0;
-    void* fb = nullptr;      size_t fb_cap = 0;   // fallback staging (queries + results) of the first stage's uncertified queries
-    void* fb2 = nullptr;     size_t fb2_cap = 0;
-    void* tailbuf = nullptr; size_t tailbuf_cap = 0;  // two [Q][k] result sets of a search that answers from the lists and from the tail (sc_api.cpp)
-    int64_t last_tail_rows = 0;                   // rows the last search scanned behind the lists (0: none)  // the same for the second stage (int8 -> bf16 -> exact)
+    sc_buf bscratch;
+    sc_buf fb, fb2;                               // fallback staging (queries + results) of the first stage's uncertified queries; the same for the second stage (int8 -> bf16 -> exact)
+    sc_buf tailbuf;                               // two [Q][k] result sets of a search that answers from the lists and from the tail (sc_search.cpp)
+    int64_t last_tail_rows = 0;                   // rows the last search scanned behind the lists (0: none)
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -99,19 +123,15 @@ struct sc_index {
     int64_t ivf_rows = 0;
     int64_t perm_rows = 0;                        // entries of `perm` (== ivf_rows unless sc_ivf_cover_tail_locked extended it)
     std::vector<int64_t> dirty_rows;
-    void* ivf_scratch = nullptr; size_t ivf_scratch_cap = 0;
-    // int8 coarse stage of list-major probing (L2; ivf_coarse.hip): every list quantised relative to its centroid
-    void* Xc8 = nullptr;     size_t xc8_cap = 0;  // [ivf_rows padded to 256][ld8] int8 of x - c_list
-    float* xcs = nullptr;    size_t xcsn_cap = 0; // [rows][4] f32 per row: {|x - c_list|^2, int8 scale, 2 |dx|, 2 (|x'| + |dx|)}
-    unsigned* list_stats = nullptr;               // [nlist][2] bits of {max |x' - xq|^2, max |x'|^2} + [4] bits of max |x|^2 behind them
-    // Rows overwritten in place since a shadow was built (stored positions below the shadow's row count): the next search re-builds the
-    // shadow rows of exactly these instead of the whole shadow (8 ms int8 / 54 ms centred at 10M x 768 for one upsert batch of 128:
-    // scripts/upsert_search_interleave.py).  The shadows' running maxima only grow in between, which keeps every bound valid; a
-    // full rebuild (layout change, more than SC_SHADOW_DIRTY_MAX rows) clears the lists.
-    std::vector<int64_t> dirty_b16, dirty_i8, dirty_c8;
+    sc_buf ivf_scratch;
+    // int8 coarse stage of list-major probing (L2; ivf_coarse.hip): every list quantised relative to its centroid.
+    // arr[0] = Xc8: [ivf_rows padded to 256][ld8] int8 of x - c_list; arr[1] = xcs: [rows][4] f32 per row: {|x - c_list|^2, int8 scale,
+    // 2 |dx|, 2 (|x'| + |dx|)}; rows == ivf_rows when valid; maxima = list_stats: [nlist][2] bits of {max |x' - xq|^2, max |x'|^2} + [4]
+    // bits of max |x|^2 behind them (allocated by ivfc_ensure_shadow, freed by sc_index_destroy only)
+    sc_shadow sh_c8;
+    sc_shadow* const shadows[3] = {&sh_b16, &sh_i8, &sh_c8};
     static constexpr int64_t SC_SHADOW_DIRTY_MAX = 8192;
-    int64_t shadowc_rows = 0;                     // rows covered by the centred shadow (== ivf_rows when valid)
-    void* ivfc_scratch = nullptr; size_t ivfc_scratch_cap = 0;
+    sc_buf ivfc_scratch;
     bool ivfc_off = false;                        // the coarse stage left most of a batch uncertified on this index: probe exactly
     int last_ivfc_uncertified = 0;
     int last_probed_lists = 0;
@@ -120,15 +140,46 @@ struct sc_index {
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
     int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major
     int last_uncertified = 0;
-    // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (1 bf16, 2 int8, 4 centred) of the shadows kept / dropped
+    // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (sc_shadow::stat_bit) of the shadows kept / dropped
     int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
     int last_del_kept = 0, last_del_dropped = 0;
     double uncert_frac = -1.0;                    // share of queries the last batched exhaustive search had to re-run exactly (-1 = never ran)
     std::mutex mu;
 };
 
-// sc_api.cpp internals used by sc_ivf.cpp (caller holds ix->mu)
-sc_status sc_grow(sc_index* ix, void** p, size_t* cap, size_t need);
+// The scratch buffers of an index (the shadows' arrays are reached through sc_index::shadows).  released: sc_index_release_scratch frees
+// it; the others are the small per-call query / result buffers, which stay.  sc_index_destroy frees all of them.
+struct sc_index_buf { sc_buf sc_index::*buf; bool released; };
+inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
+    {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
+    {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
+    {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},
+};
+
+static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
+// A/B knobs of the environment; every call site keeps the value in a function-local static (read once per process).
+// sc_env_flag: a knob that is on by default goes off by a leading '0', one that is off by default goes on by a leading '1'.
+static inline int64_t sc_env_i64(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : dflt; }
+static inline bool sc_env_flag(const char* name, bool dflt) { const char* e = getenv(name); return !e ? dflt : dflt ? e[0] != '0' : e[0] == '1'; }
+
+// sc_index_state.cpp (caller holds ix->mu)
+sc_status sc_grow(sc_index* ix, sc_buf& b, size_t need);  // grow a device scratch buffer: synchronises, contents not preserved
+void sc_buf_free(sc_buf& b);
+void sc_shadow_invalidate(sc_shadow& sh);  // stale: the next ensure builds it whole (which covers the pending rows)
+void sc_shadow_release(sc_shadow& sh);     // ... and its arrays are freed (the maxima stay)
+void sc_invalidate_shadows(sc_index* ix);  // all three: the rows or their layout changed wholesale
+// rows[i] (ids, rows below old_n existed before) were written at stored position pos[i]: remember those the shadow covers
+void sc_shadow_note_overwritten(sc_shadow& sh, const int64_t* rows, const int64_t* pos, int64_t n, int64_t old_n);
+sc_status sc_ensure_shadow_b16(sc_index* ix);  // bring the bf16 / int8 shadow up to date with rows [0, n)
+sc_status sc_ensure_shadow_i8(sc_index* ix);
+// sc_search.cpp
+sc_status sc_prep_queries(sc_index* ix, const float* q_dev, int32_t Q);  // tight [Q, dim] queries padded into ix->qpad, their norms into ix->qnorm
+// Staging of the R queries `which` of a batch that go through another pass: buf = [queries | dist | rows | index], queries gathered
+struct sc_subbatch { float* q; float* d; int64_t* r; int32_t* idx; int R; };
+sc_status sc_subbatch_stage(sc_index* ix, sc_buf& buf, const float* q_dev, const std::vector<int>& which, int k, sc_subbatch* sb);
+sc_status sc_subbatch_scatter(sc_index* ix, const sc_subbatch& sb, int k, float* out_dist, int64_t* out_rows);  // results back to the batch's rows; synchronises
+
+// search and IVF internals shared between sc_search.cpp and sc_ivf.cpp (caller holds ix->mu)
 sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
 sc_status sc_search_flat_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, float* out_dist, int64_t* out_rows);
 sc_status sc_ivf_search_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);

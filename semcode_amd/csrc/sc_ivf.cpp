@@ -33,10 +33,10 @@ static sc_status assign_rows(sc_index* ix, const float* q_dev_tight, int64_t n, 
     sc_index* qz = ix->quant;
     hipStream_t s = ix->rt->stream;
     out.resize((size_t)n);
-    sc_status st = sc_grow(ix, &ix->ivf_scratch, &ix->ivf_scratch_cap, (size_t)ASSIGN_CHUNK * 12);
+    sc_status st = sc_grow(ix, ix->ivf_scratch, (size_t)ASSIGN_CHUNK * 12);
     if (st) return st;
-    float* dd = (float*)ix->ivf_scratch;
-    int64_t* dr = (int64_t*)((char*)ix->ivf_scratch + (size_t)ASSIGN_CHUNK * 4);
+    float* dd = ix->ivf_scratch.as<float>();
+    int64_t* dr = (int64_t*)(ix->ivf_scratch.as<char>() + (size_t)ASSIGN_CHUNK * 4);
     std::vector<int64_t> host((size_t)ASSIGN_CHUNK);
     for (int64_t r0 = 0; r0 < n; r0 += ASSIGN_CHUNK) {
         const int m = (int)std::min<int64_t>(ASSIGN_CHUNK, n - r0);
@@ -57,15 +57,6 @@ static sc_status assign_rows(sc_index* ix, const float* q_dev_tight, int64_t n, 
     return SC_OK;
 }
 
-namespace {
-struct Dev {  // device allocation released on scope exit unless handed over with take()
-    void* p = nullptr;
-    ~Dev() { hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    template <class T> T* take() { T* q = (T*)p; p = nullptr; return q; }
-};
-}  // namespace
-
 void sc_ivf_drop_lists_locked(sc_index* ix) {
     if (ix->perm) hipStreamSynchronize(ix->rt->stream);
     hipFree(ix->perm);
@@ -79,24 +70,19 @@ void sc_ivf_drop_lists_locked(sc_index* ix) {
     ix->dirty_rows.clear();
     ix->ivf_rows = 0;
     ix->trained = false;
-    ix->shadow_rows = 0;
-    ix->shadow8_rows = 0;
-    ix->shadowc_rows = 0;  // the centred shadow of the coarse stage mirrors the lists
+    sc_invalidate_shadows(ix);  // (the centred shadow of the coarse stage mirrors the lists)
     ix->ivfc_off = false;
 }
 
 // Xo[pos] = X[g[pos]] for the n stored rows, into fresh corpus-sized buffers that replace X / xnorm on success.
-// Needs a second copy of the corpus for the duration of the move: the rebuildable buffers (bf16 shadow) are freed first.
-static sc_status ivf_move_rows_locked(sc_index* ix, const std::vector<uint32_t>& g, Dev& d_g) {
+// Needs a second copy of the corpus for the duration of the move: the bf16 and int8 shadows are freed first.
+static sc_status ivf_move_rows_locked(sc_index* ix, const std::vector<uint32_t>& g, sc_devbuf& d_g) {
     hipStream_t s = ix->rt->stream;
     const int64_t n = ix->n;
     SC_HIP(hipStreamSynchronize(s));
-    hipFree(ix->Xb);  // the layout changes: the shadows are rebuilt anyway
-    hipFree(ix->Xq);
-    ix->Xb = ix->Xq = nullptr;
-    ix->xb_cap = ix->xq_cap = 0;
-    ix->shadow_rows = ix->shadow8_rows = 0;
-    Dev nx, nn;
+    sc_shadow_release(ix->sh_b16);  // the layout changes: the shadows are rebuilt anyway
+    sc_shadow_release(ix->sh_i8);
+    sc_devbuf nx, nn;
     if (nx.alloc((size_t)ix->capacity * ix->ld * sizeof(float)) != hipSuccess || nn.alloc((size_t)ix->capacity * sizeof(float)) != hipSuccess ||
         d_g.alloc((size_t)n * 4) != hipSuccess)
         return sc_fail(SC_ERR_NOMEM, "ivf: hipMalloc of the re-ordered corpus (%lld rows x %d) failed", (long long)ix->capacity, ix->ld);
@@ -119,7 +105,7 @@ sc_status sc_ivf_untrain_locked(sc_index* ix) {
     if (ix->n > 0) {  // Xo[row] = X[position of row]
         std::vector<uint32_t> g((size_t)ix->n);
         for (int64_t r = 0; r < ix->n; ++r) g[(size_t)r] = (uint32_t)sc_ivf_pos(ix, r);
-        Dev d_g;
+        sc_devbuf d_g;
         sc_status st = ivf_move_rows_locked(ix, g, d_g);
         if (st) return st;  // nothing was changed: the lists stay valid
     }
@@ -146,7 +132,7 @@ static sc_status ivf_install_lists_locked(sc_index* ix, int nlist, std::vector<i
             g[(size_t)pos] = ix->perm ? (uint32_t)sc_ivf_pos(ix, i) : (uint32_t)i;  // where row i sits now
         }
     }
-    Dev d_perm, d_off, d_g;
+    sc_devbuf d_perm, d_off, d_g;
     if (d_perm.alloc((size_t)n * 4) != hipSuccess || d_off.alloc((size_t)(nlist + 1) * 8) != hipSuccess)
         return sc_fail(SC_ERR_NOMEM, "ivf: hipMalloc of the list tables failed");
     SC_HIP(hipMemcpyAsync(d_perm.p, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
@@ -164,8 +150,7 @@ static sc_status ivf_install_lists_locked(sc_index* ix, int nlist, std::vector<i
     ix->ivf_rows = n;
     ix->dirty_rows.clear();
     ix->nlist_trained = nlist;
-    ix->shadow_rows = ix->shadow8_rows = 0;
-    ix->shadowc_rows = 0;  // new lists (a re-train over the same rows included): the centred shadow is rebuilt on the next coarse probe
+    sc_invalidate_shadows(ix);  // new lists (a re-train over the same rows included): the centred shadow too is rebuilt, on the next coarse probe
     ix->ivfc_off = false;
     ix->uncert_frac = -1.0;
     ix->trained = true;
@@ -185,7 +170,7 @@ sc_status sc_ivf_cover_tail_locked(sc_index* ix) {
     const int64_t have = ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows;
     if (have >= ix->n) return SC_OK;
     hipStream_t s = ix->rt->stream;
-    Dev d_new;
+    sc_devbuf d_new;
     if (d_new.alloc((size_t)ix->n * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "ivf: hipMalloc of the extended row map failed");
     SC_HIP(hipMemcpyAsync(d_new.p, ix->perm, (size_t)have * 4, hipMemcpyDeviceToDevice, s));
     std::vector<uint32_t> tail((size_t)(ix->n - have));
@@ -213,7 +198,7 @@ sc_status sc_ivf_refresh_locked(sc_index* ix, bool keep_tail) {
     std::vector<int32_t> new_list(rows.size());
     bool changed = !keep_tail && ix->n > ix->ivf_rows;
     const int64_t CH = 65536;
-    Dev d_pos, d_tight;
+    sc_devbuf d_pos, d_tight;
     const int64_t chmax = std::min<int64_t>(CH, (int64_t)rows.size());
     if (d_pos.alloc((size_t)chmax * 8) != hipSuccess || d_tight.alloc((size_t)chmax * ix->dim * 4) != hipSuccess)
         return sc_fail(SC_ERR_NOMEM, "ivf refresh: hipMalloc failed");
@@ -248,7 +233,7 @@ sc_status sc_ivf_refresh_locked(sc_index* ix, bool keep_tail) {
 static sc_status ivf_assign_all_and_install_locked(sc_index* ix, int nlist) {
     hipStream_t s = ix->rt->stream;
     const int64_t n = ix->n;
-    Dev d_tight;
+    sc_devbuf d_tight;
     const float* all_tight = ix->X;
     if (ix->ld != ix->dim) {
         SC_HIP(hipMalloc(&d_tight.p, (size_t)n * ix->dim * 4));
@@ -280,7 +265,7 @@ extern "C" sc_status sc_index_train(sc_index* ix, int32_t niter, uint64_t seed) 
     // ---- sample (tight [ns, dim]) and initial centroids
     std::vector<int64_t> srows((size_t)ns);
     for (int64_t i = 0; i < ns; ++i) srows[(size_t)i] = (int64_t)(((__int128)i * n) / ns);
-    Dev d_srows, d_sample, d_cinit, d_members, d_moff, d_cnew;
+    sc_devbuf d_srows, d_sample, d_cinit, d_members, d_moff, d_cnew;
     SC_HIP(hipMalloc(&d_srows.p, (size_t)ns * 8));
     SC_HIP(hipMalloc(&d_sample.p, (size_t)ns * dim * 4));
     SC_HIP(hipMemcpyAsync(d_srows.p, srows.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
@@ -311,7 +296,7 @@ extern "C" sc_status sc_index_train(sc_index* ix, int32_t niter, uint64_t seed) 
         std::lock_guard<std::mutex> gq(qz->mu);
         sc_launch_ingest_rows(c_tight, nullptr, 0, nlist, dim, qz->X, qz->ld, qz->xnorm, s);
         qz->n = nlist;
-        qz->shadow_rows = qz->shadow8_rows = 0;  // the centroids changed: both coarse shadows are stale
+        sc_invalidate_shadows(qz);  // the centroids changed: both coarse shadows are stale
     };
     set_centroids((const float*)d_cnew.p);
 
@@ -370,7 +355,7 @@ extern "C" sc_status sc_index_train(sc_index* ix, int32_t niter, uint64_t seed) 
                 std::push_heap(heap.begin(), heap.end(), less_big);
             }
             if (!moves.empty()) {
-                Dev d_moves;
+                sc_devbuf d_moves;
                 SC_HIP(hipMalloc(&d_moves.p, moves.size() * 4));
                 SC_HIP(hipMemcpyAsync(d_moves.p, moves.data(), moves.size() * 4, hipMemcpyHostToDevice, s));
                 sc_launch_reseed_centroids((float*)d_cnew.p, dim, (const int32_t*)d_moves.p, (int)(moves.size() / 2), s);
@@ -408,9 +393,9 @@ sc_status sc_ivf_search_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_pd = carve((size_t)Q * nprobe * 4), o_pr = carve((size_t)Q * nprobe * 8), o_sb = carve((size_t)Q * (nprobe + 1) * 4),
                  o_sr = carve((size_t)Q * nprobe * 16);
-    sc_status st = sc_grow(ix, &ix->ivf_scratch, &ix->ivf_scratch_cap, off);
+    sc_status st = sc_grow(ix, ix->ivf_scratch, off);
     if (st) return st;
-    char* b = (char*)ix->ivf_scratch;
+    char* b = ix->ivf_scratch.as<char>();
     float* pd = (float*)(b + o_pd);
     int64_t* pr = (int64_t*)(b + o_pr);
     int* sb = (int*)(b + o_sb);
@@ -424,18 +409,16 @@ sc_status sc_ivf_search_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
         if (st) return st;
     }
     sc_launch_ivf_plan(pr, Q, nprobe, ix->list_off, nlist, sb, sr, s);
-    st = sc_grow(ix, (void**)&ix->qpad, &ix->qpad_cap, (size_t)Q * ix->ld * 4);
+    st = sc_prep_queries(ix, q_dev, Q);
     if (st) return st;
-    st = sc_grow(ix, (void**)&ix->qnorm, &ix->qnorm_cap, (size_t)Q * 4);
+    st = sc_grow(ix, ix->partial, std::max<size_t>(plan.partial_bytes, 16));
     if (st) return st;
-    st = sc_grow(ix, (void**)&ix->partial, &ix->partial_cap, std::max<size_t>(plan.partial_bytes, 16));
-    if (st) return st;
-    sc_launch_ingest_rows(q_dev, nullptr, 0, Q, ix->dim, ix->qpad, ix->ld, ix->qnorm, s);
+    uint64_t* partial = ix->partial.as<uint64_t>();
     hipEvent_t e0, e1;
     sc_prof_begin(rt, SC_PROF_SCAN, &e0, &e1);
-    sc_launch_scan_exact((int)ix->metric, ix->X, ix->xnorm, ix->n, ix->ld, ix->qpad, ix->qnorm, Q, k, plan, ix->partial, ix->perm, sb, sr, nprobe, s);
+    sc_launch_scan_exact((int)ix->metric, ix->X, ix->xnorm, ix->n, ix->ld, ix->qpad.as<float>(), ix->qnorm.as<float>(), Q, k, plan, partial, ix->perm, sb, sr, nprobe, s);
     sc_prof_end(rt, SC_PROF_SCAN, e0, e1);
-    sc_launch_topk_merge((int)ix->metric, ix->partial, plan.groups, plan.lists, plan.qt, Q, k, ix->row_base, out_dist, out_rows, s);
+    sc_launch_topk_merge((int)ix->metric, partial, plan.groups, plan.lists, plan.qt, Q, k, ix->row_base, out_dist, out_rows, s);
     SC_HIP(hipGetLastError());
     ix->last_path = 3;
     ix->last_probed_lists = nprobe;
@@ -508,9 +491,9 @@ sc_status sc_ivf_search_listmajor_locked(sc_index* ix, const float* q_dev, int32
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_pd = carve(npairs * 4), o_pr = carve(npairs * 8);
-    sc_status st = sc_grow(ix, &ix->ivf_scratch, &ix->ivf_scratch_cap, off);
+    sc_status st = sc_grow(ix, ix->ivf_scratch, off);
     if (st) return st;
-    char* b = (char*)ix->ivf_scratch;
+    char* b = ix->ivf_scratch.as<char>();
     {
         std::lock_guard<std::mutex> gq(qz->mu);
         const sc_metric saved = qz->metric;
@@ -651,9 +634,9 @@ sc_status sc_ivf_search_listmajor_locked(sc_index* ix, const float* q_dev, int32
     const size_t o_src = carve(src.size() * 4), o_qmap = carve((size_t)G * qt * 4 + 16), o_sb = carve((size_t)G * 2 * 4 + 16),
                  o_sr = carve((size_t)G * 2 * 8 + 16), o_qmap_w = carve((size_t)Gw * qw * 4 + 16), o_sr_w = carve((size_t)Gw * 2 * 8 + 16),
                  o_qmap_w2 = carve((size_t)Gw2 * qw2 * 4 + 16), o_sr_w2 = carve((size_t)Gw2 * 2 * 8 + 16);
-    st = sc_grow(ix, &ix->ivf_scratch, &ix->ivf_scratch_cap, off);
+    st = sc_grow(ix, ix->ivf_scratch, off);
     if (st) return st;
-    b = (char*)ix->ivf_scratch;
+    b = ix->ivf_scratch.as<char>();
     SC_HIP(hipMemcpyAsync(b + o_src, src.data(), src.size() * 4, hipMemcpyHostToDevice, s));
     if (G > 0) {
         SC_HIP(hipMemcpyAsync(b + o_qmap, qmap.data(), (size_t)G * qt * 4, hipMemcpyHostToDevice, s));
@@ -668,20 +651,19 @@ sc_status sc_ivf_search_listmajor_locked(sc_index* ix, const float* q_dev, int32
         SC_HIP(hipMemcpyAsync(b + o_qmap_w2, qmap_w2.data(), (size_t)Gw2 * qw2 * 4, hipMemcpyHostToDevice, s));
         SC_HIP(hipMemcpyAsync(b + o_sr_w2, sr_w2.data(), (size_t)Gw2 * 2 * 8, hipMemcpyHostToDevice, s));
     }
-    st = sc_grow(ix, (void**)&ix->qpad, &ix->qpad_cap, (size_t)Q * ix->ld * 4);
+    st = sc_prep_queries(ix, q_dev, Q);
     if (st) return st;
-    st = sc_grow(ix, (void**)&ix->qnorm, &ix->qnorm_cap, (size_t)Q * 4);
+    st = sc_grow(ix, ix->partial, std::max<size_t>(((size_t)lists_w + (size_t)G * qt) * k * 8, 16));
     if (st) return st;
-    st = sc_grow(ix, (void**)&ix->partial, &ix->partial_cap, std::max<size_t>(((size_t)lists_w + (size_t)G * qt) * k * 8, 16));
-    if (st) return st;
-    sc_launch_ingest_rows(q_dev, nullptr, 0, Q, ix->dim, ix->qpad, ix->ld, ix->qnorm, s);
+    float *const qpad = ix->qpad.as<float>(), *const qnorm = ix->qnorm.as<float>();
+    uint64_t* const partial = ix->partial.as<uint64_t>();
     // 4. one workgroup per group (grid.y is limited to 65535 groups per launch); the wide class goes first: its workgroups are
     // the long ones
     hipEvent_t e0, e1;
     sc_prof_begin(rt, SC_PROF_SCAN, &e0, &e1);
-    sc_launch_scan_listgemm((int)ix->metric, qw, ix->X, ix->xnorm, ix->ld, ix->qpad, ix->qnorm, k, Gw, ix->partial, ix->perm,
+    sc_launch_scan_listgemm((int)ix->metric, qw, ix->X, ix->xnorm, ix->ld, qpad, qnorm, k, Gw, partial, ix->perm,
                             (const int64_t*)(b + o_sr_w), (const int32_t*)(b + o_qmap_w), s);
-    sc_launch_scan_listgemm((int)ix->metric, qw2, ix->X, ix->xnorm, ix->ld, ix->qpad, ix->qnorm, k, Gw2, ix->partial + (size_t)Gw * qw * k, ix->perm,
+    sc_launch_scan_listgemm((int)ix->metric, qw2, ix->X, ix->xnorm, ix->ld, qpad, qnorm, k, Gw2, partial + (size_t)Gw * qw * k, ix->perm,
                             (const int64_t*)(b + o_sr_w2), (const int32_t*)(b + o_qmap_w2), s);
     for (int cls = 0; cls < 2; ++cls)
       for (int g0 = cls ? G_big : 0, hi = cls ? G : G_big; g0 < hi; g0 += 65535) {
@@ -691,13 +673,13 @@ sc_status sc_ivf_search_listmajor_locked(sc_index* ix, const float* q_dev, int32
         p.nwg = 1;
         p.lists = 1;
         p.gstride = qt;
-        sc_launch_scan_exact((int)ix->metric, ix->X, ix->xnorm, ix->n, ix->ld, ix->qpad, ix->qnorm, gn * qt, k, p,
-                             ix->partial + ((size_t)lists_w + (size_t)g0 * qt) * k, ix->perm, (const int*)(b + o_sb) + (size_t)g0 * 2,
+        sc_launch_scan_exact((int)ix->metric, ix->X, ix->xnorm, ix->n, ix->ld, qpad, qnorm, gn * qt, k, p,
+                             partial + ((size_t)lists_w + (size_t)g0 * qt) * k, ix->perm, (const int*)(b + o_sb) + (size_t)g0 * 2,
                              (const int64_t*)(b + o_sr) + (size_t)g0 * 2, 1, s, (const int32_t*)(b + o_qmap) + (size_t)g0 * qt);
     }
     sc_prof_end(rt, SC_PROF_SCAN, e0, e1);
     // 5. a query's result = merge of the nprobe (group, slot) lists it took part in
-    sc_launch_topk_gather_merge((int)ix->metric, ix->partial, (const int32_t*)(b + o_src), L, Q, k, ix->row_base, out_dist, out_rows, s);
+    sc_launch_topk_gather_merge((int)ix->metric, partial, (const int32_t*)(b + o_src), L, Q, k, ix->row_base, out_dist, out_rows, s);
     SC_HIP(hipGetLastError());
     SC_HIP(hipStreamSynchronize(s));  // the host plan vectors go out of scope
     if (trace) {
@@ -822,10 +804,9 @@ extern "C" sc_status sc_index_ivf_info(sc_index* ix, int32_t* nlist, float* cent
 static const int IVFC_CAP = 8192;  // survivors per query, phase A (everything it sees: 2 KP + one prefix at most)
 static const int IVFC_CAPB = 16384; // ... and phase B (the rest of a long nearest list against the prefix's bound can be thousands)
 static const int64_t IVFC_PREFIX = 4096;  // rows of one list that phase A takes (all of them are kept: cap > 2 KP + prefix)
-static int ivfc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }
 
 bool sc_ivf_coarse_applicable(const sc_index* ix, int Q, int k, int nprobe) {
-    static const bool env_off = [] { const char* e = getenv("SC_IVF_COARSE"); return e && e[0] == '0'; }();
+    static const bool env_off = !sc_env_flag("SC_IVF_COARSE", true);
     if (ix->kind != SC_INDEX_IVF_FLAT || !ix->trained || !ix->quant || !ix->perm || (ix->metric != SC_METRIC_L2 && ix->metric != SC_METRIC_IP && ix->metric != SC_METRIC_COSINE)) return false;
     if (nprobe < 2 || nprobe > 512 || nprobe >= ix->nlist_trained || k < 1 || k > sc_batched_kprime8() / 2) return false;
     if (ix->search_mode == 5) return Q >= 1;
@@ -846,48 +827,47 @@ bool sc_ivf_coarse_applicable(const sc_index* ix, int Q, int k, int nprobe) {
 static int g_ivfc_nomem = 0;  // sc_diag_set_option("ivf_coarse_nomem", 1): the centred shadow cannot be allocated (tests of the fallback to the exact probe)
 void sc_ivf_set_coarse_nomem(int v) { g_ivfc_nomem = v; }
 static sc_status ivfc_ensure_shadow(sc_index* ix) {
-    if (ix->shadowc_rows == ix->ivf_rows && ix->Xc8) {
-        if (ix->dirty_c8.empty()) return SC_OK;
+    sc_shadow& sh = ix->sh_c8;  // arr = {Xc8, xcs}, maxima = list_stats
+    hipStream_t s = ix->rt->stream;
+    const int ld8 = sc_ld8(ix), nlist = ix->nlist_trained;
+    const bool unit = ix->metric == SC_METRIC_COSINE;  // the IP form on normalised rows and centroids
+    if (sh.rows == ix->ivf_rows && sh.arr[0].p) {
+        if (sh.dirty.empty()) return SC_OK;
         // rows of the lists overwritten in place and still in their lists (sc_ivf_refresh_locked found nothing to move, or the layout
         // would have been rebuilt and this shadow with it): their shadow rows alone; the per-list maxima keep accumulating
-        hipStream_t s = ix->rt->stream;
-        std::vector<int64_t>& d = ix->dirty_c8;
+        std::vector<int64_t>& d = sh.dirty;
         std::sort(d.begin(), d.end());
         d.erase(std::unique(d.begin(), d.end()), d.end());
-        while (!d.empty() && d.back() >= ix->shadowc_rows) d.pop_back();
+        while (!d.empty() && d.back() >= sh.rows) d.pop_back();
         if (!d.empty()) {
-            sc_status st = sc_grow(ix, (void**)&ix->stage, &ix->stage_cap, d.size() * 8);
+            sc_status st = sc_grow(ix, ix->stage, d.size() * 8);
             if (st) return st;
-            SC_HIP(hipMemcpyAsync(ix->stage, d.data(), d.size() * 8, hipMemcpyHostToDevice, s));
-            const bool unit = ix->metric == SC_METRIC_COSINE;
-            sc_launch_ivf_center_shadow(ix->X, (int64_t)d.size(), ix->ld, ivfc_ld8(ix), ix->quant->X, ix->quant->ld, ix->list_off, ix->nlist_trained, ix->Xc8, ix->xcs,
-                                        ix->list_stats, s, unit ? ix->xnorm : nullptr, unit ? ix->quant->xnorm : nullptr, (const int64_t*)ix->stage);
-            sc_launch_norm_max(ix->xnorm, ix->shadowc_rows, ix->list_stats + (size_t)ix->nlist * 2, s);
+            SC_HIP(hipMemcpyAsync(ix->stage.p, d.data(), d.size() * 8, hipMemcpyHostToDevice, s));
+            sc_launch_ivf_center_shadow(ix->X, (int64_t)d.size(), ix->ld, ld8, ix->quant->X, ix->quant->ld, ix->list_off, nlist, sh.arr[0].p, sh.arr[1].as<float>(),
+                                        sh.maxima, s, unit ? ix->xnorm : nullptr, unit ? ix->quant->xnorm : nullptr, ix->stage.as<int64_t>());
+            sc_launch_norm_max(ix->xnorm, sh.rows, sh.maxima + (size_t)ix->nlist * 2, s);
             SC_HIP(hipGetLastError());
             SC_HIP(hipStreamSynchronize(s));  // (the position list is a host temporary behind an asynchronous copy)
         }
         d.clear();
         return SC_OK;
     }
-    ix->dirty_c8.clear();  // a full build covers them
+    sh.dirty.clear();  // a full build covers them
     if (g_ivfc_nomem) return sc_fail(SC_ERR_NOMEM, "ivf coarse stage: out of device memory (forced by sc_diag_set_option)");
-    hipStream_t s = ix->rt->stream;
-    const int ld8 = ivfc_ld8(ix), nlist = ix->nlist_trained;
-    const int64_t rows = ix->ivf_rows, rows_pad = (rows + 255) / 256 * 256 + 256;  // (a list's last tile reads up to 255 rows beyond its end)
-    sc_status st = sc_grow(ix, &ix->Xc8, &ix->xc8_cap, (size_t)rows_pad * ld8);
-    if (st) return st;
-    st = sc_grow(ix, (void**)&ix->xcs, &ix->xcsn_cap, (size_t)rows_pad * 16);
-    if (st) return st;
-    if (!ix->list_stats) SC_HIP(hipMalloc((void**)&ix->list_stats, ((size_t)ix->nlist * 2 + 4) * 4));
-    SC_HIP(hipMemsetAsync(ix->list_stats, 0, ((size_t)ix->nlist * 2 + 4) * 4, s));
-    SC_HIP(hipMemsetAsync((char*)ix->Xc8 + (size_t)rows * ld8, 0, (size_t)(rows_pad - rows) * ld8, s));
-    SC_HIP(hipMemsetAsync(ix->xcs + rows * 4, 0, (size_t)(rows_pad - rows) * 16, s));
-    const bool unit = ix->metric == SC_METRIC_COSINE;  // the IP form on normalised rows and centroids
-    sc_launch_ivf_center_shadow(ix->X, rows, ix->ld, ld8, ix->quant->X, ix->quant->ld, ix->list_off, nlist, ix->Xc8, ix->xcs, ix->list_stats, s,
+    const int64_t rows = ix->ivf_rows, rows_pad = (rows + 255) / 256 * 256 + sh.tail_pad;
+    for (int i = 0; i < 2; ++i) {
+        const sc_status st = sc_grow(ix, sh.arr[i], (size_t)rows_pad * sh.row_bytes[i]);
+        if (st) return st;
+    }
+    if (!sh.maxima) SC_HIP(hipMalloc((void**)&sh.maxima, ((size_t)ix->nlist * 2 + 4) * 4));
+    SC_HIP(hipMemsetAsync(sh.maxima, 0, ((size_t)ix->nlist * 2 + 4) * 4, s));
+    for (int i = 0; i < 2; ++i)
+        SC_HIP(hipMemsetAsync(sh.arr[i].as<char>() + (size_t)rows * sh.row_bytes[i], 0, (size_t)(rows_pad - rows) * sh.row_bytes[i], s));
+    sc_launch_ivf_center_shadow(ix->X, rows, ix->ld, ld8, ix->quant->X, ix->quant->ld, ix->list_off, nlist, sh.arr[0].p, sh.arr[1].as<float>(), sh.maxima, s,
                                 unit ? ix->xnorm : nullptr, unit ? ix->quant->xnorm : nullptr);
-    sc_launch_norm_max(ix->xnorm, rows, ix->list_stats + (size_t)ix->nlist * 2, s);  // bits of max |x|^2: the re-rank's rounding allowance
+    sc_launch_norm_max(ix->xnorm, rows, sh.maxima + (size_t)ix->nlist * 2, s);  // bits of max |x|^2: the re-rank's rounding allowance
     SC_HIP(hipGetLastError());
-    ix->shadowc_rows = rows;
+    sh.rows = rows;
     return SC_OK;
 }
 
@@ -895,7 +875,7 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
     sc_runtime* rt = ix->rt;
     hipStream_t s = rt->stream;
     sc_index* qz = ix->quant;
-    const int nlist = ix->nlist_trained, ld = ix->ld, ld8 = ivfc_ld8(ix), KP = sc_batched_kprime8();
+    const int nlist = ix->nlist_trained, ld = ix->ld, ld8 = sc_ld8(ix), KP = sc_batched_kprime8();
     sc_status st = ivfc_ensure_shadow(ix);
     if (st) return st;
     const size_t npairs = (size_t)Q * nprobe;
@@ -904,9 +884,9 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
         size_t off = 0;
         auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
         const size_t o_pd = carve(npairs * 4), o_pr = carve(npairs * 8);
-        st = sc_grow(ix, &ix->ivf_scratch, &ix->ivf_scratch_cap, off);
+        st = sc_grow(ix, ix->ivf_scratch, off);
         if (st) return st;
-        char* b = (char*)ix->ivf_scratch;
+        char* b = ix->ivf_scratch.as<char>();
         std::lock_guard<std::mutex> gq(qz->mu);
         const sc_metric saved = qz->metric;
         qz->metric = ix->metric;
@@ -915,7 +895,7 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
         if (st) return st;
     }
     std::vector<int64_t> probes(npairs);
-    SC_HIP(hipMemcpyAsync(probes.data(), (char*)ix->ivf_scratch + ((npairs * 4 + 255) & ~(size_t)255), npairs * 8, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(probes.data(), ix->ivf_scratch.as<char>() + ((npairs * 4 + 255) & ~(size_t)255), npairs * 8, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     // 2. plan.  Phase A = every query's nearest list(s) -- of a long list only its first IVFC_PREFIX rows: any subset gives a valid
     // bound, and phase A keeps every row it sees --, phase B = the other lists and what is left of the phase-A lists; per kind the pairs are
@@ -1046,9 +1026,9 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
                  o_ek2 = carve((size_t)Q * WCAP * 8);
     const size_t hit_bytes = (size_t)2048 * (4 + 8192 * 16) + 256;
     const size_t o_hits = carve(hit_bytes);
-    st = sc_grow(ix, &ix->ivfc_scratch, &ix->ivfc_scratch_cap, off);
+    st = sc_grow(ix, ix->ivfc_scratch, off);
     if (st) return st;
-    char* b = (char*)ix->ivfc_scratch;
+    char* b = ix->ivfc_scratch.as<char>();
     int32_t *d_sq = (int32_t*)(b + o_sq), *d_sl = (int32_t*)(b + o_sl), *d_sd = (int32_t*)(b + o_sd);
     float *d_qs = (float*)(b + o_qs), *d_qn = (float*)(b + o_qn), *d_st = (float*)(b + o_st), *d_stf = (float*)(b + o_stf), *d_qb = (float*)(b + o_qb),
           *d_qd = (float*)(b + o_qd), *d_se = (float*)(b + o_se);
@@ -1065,32 +1045,33 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
         SC_HIP(hipMemcpyAsync(b + o_items + items[0].size() * sizeof(Item), items[1].data(), items[1].size() * sizeof(Item), hipMemcpyHostToDevice, s));
     if (!items[2].empty())
         SC_HIP(hipMemcpyAsync(b + o_items + (items[0].size() + items[1].size()) * sizeof(Item), items[2].data(), items[2].size() * sizeof(Item), hipMemcpyHostToDevice, s));
-    st = sc_grow(ix, (void**)&ix->qpad, &ix->qpad_cap, (size_t)Q * ld * 4);
+    st = sc_prep_queries(ix, q_dev, Q);
     if (st) return st;
-    st = sc_grow(ix, (void**)&ix->qnorm, &ix->qnorm_cap, (size_t)Q * 4);
-    if (st) return st;
-    sc_launch_ingest_rows(q_dev, nullptr, 0, Q, ix->dim, ix->qpad, ld, ix->qnorm, s);
+    float *const qpad = ix->qpad.as<float>(), *const qnorm = ix->qnorm.as<float>();
+    const void* const Xc8 = ix->sh_c8.arr[0].p;
+    const float* const xcs = ix->sh_c8.arr[1].as<float>();
+    const unsigned* const list_stats = ix->sh_c8.maxima;
     const int metric = (int)ix->metric;  // L2; IP (rows centred only); COSINE (the IP form on unit vectors) -- ivf_coarse.hip
     const int kmetric = metric == SC_METRIC_COSINE ? (int)SC_METRIC_IP : metric;  // what the streaming kernel computes
-    sc_launch_ivf_pair_query(ix->qpad, ld, ld8, qz->X, qz->ld, d_sq, d_sl, nslots, ix->list_stats, b + o_qc, d_qs, d_qn, d_qb, d_qd, d_se, s, metric, ix->qnorm, qz->xnorm);
+    sc_launch_ivf_pair_query(qpad, ld, ld8, qz->X, qz->ld, d_sq, d_sl, nslots, list_stats, b + o_qc, d_qs, d_qn, d_qb, d_qd, d_se, s, metric, qnorm, qz->xnorm);
     sc_launch_scan_batched_init(thr, tf, Qpad, best, cnt, ovf, Q, kpa, s);
     // phase A is dense: every row of its lists survives, at a known place of survA; the counts are known here
     SC_HIP(hipMemcpyAsync(cnt, cntA.data(), (size_t)Q * 4, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(cntA_d, cntA.data(), (size_t)Q * 4, hipMemcpyHostToDevice, s));
-    const unsigned* xmax_bits = ix->list_stats + (size_t)ix->nlist * 2;  // bits of max |x|^2: the rounding allowance of the exact scores
+    const unsigned* xmax_bits = list_stats + (size_t)ix->nlist * 2;  // bits of max |x|^2: the rounding allowance of the exact scores
     hipEvent_t e0, e1;
     // 4. phase A: lower bounds of the nearest list(s) -> the kpa best re-scored exactly -> T = their k-th exact distance + allowance
     if (!items[0].empty()) {
         sc_launch_ivf_slot_thr(d_sq, d_qn, d_se, thr, nslots, d_st, d_stf, s);  // (+inf everywhere; the dense form tests nothing)
         sc_prof_begin(rt, SC_PROF_SCAN, &e0, &e1);
-        sc_launch_ivf_coarse(ix->Xc8, ix->xcs, ld8, b + o_qc, b + o_items, (int)items[0].size(), d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survA, cnt, IVFC_CAP,
+        sc_launch_ivf_coarse(Xc8, xcs, ld8, b + o_qc, b + o_items, (int)items[0].size(), d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survA, cnt, IVFC_CAP,
                              b + o_hits, hit_bytes, s, d_sd, kmetric);
         sc_prof_end(rt, SC_PROF_SCAN, e0, e1);
     }
     sc_prof_begin(rt, SC_PROF_MERGE, &e0, &e1);
-    sc_launch_scan_select(metric, survA, cnt, IVFC_CAP, best, ix->qnorm, thr, tf, ovf, Q, kpa, s);  // (resets cnt: phase B counts from 0)
-    sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, ix->qpad, ix->qnorm, best, nullptr, kpa, ix->perm, ekeysA, Q, s);
-    sc_launch_ivf_bound(metric, ekeysA, kpa, k, ix->qnorm, xmax_bits, ld, thr, Q, s);
+    sc_launch_scan_select(metric, survA, cnt, IVFC_CAP, best, qnorm, thr, tf, ovf, Q, kpa, s);  // (resets cnt: phase B counts from 0)
+    sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, qpad, qnorm, best, nullptr, kpa, ix->perm, ekeysA, Q, s);
+    sc_launch_ivf_bound(metric, ekeysA, kpa, k, qnorm, xmax_bits, ld, thr, Q, s);
     sc_prof_end(rt, SC_PROF_MERGE, e0, e1);
     // 5. phase B: the other lists (and the rest of long phase-A lists) against T
     size_t b_first = items[0].size(), b_count = items[1].size() + items[2].size();
@@ -1101,17 +1082,17 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
         sc_prof_begin(rt, SC_PROF_MERGE, &e0, &e1);
         SC_HIP(hipMemcpyAsync(cntT, cnt, (size_t)Q * 4, hipMemcpyDeviceToDevice, s));  // (the selection resets the counts; the survivors stay where they are)
         SC_HIP(hipMemsetAsync(bestT, 0xFF, (size_t)Q * kpa * 8, s));
-        sc_launch_scan_select(metric, survB, cnt, IVFC_CAPB, bestT, ix->qnorm, (float*)(b + o_thrT), (float*)(b + o_tfT), ovf, Q, kpa, s);
+        sc_launch_scan_select(metric, survB, cnt, IVFC_CAPB, bestT, qnorm, (float*)(b + o_thrT), (float*)(b + o_tfT), ovf, Q, kpa, s);
         SC_HIP(hipMemcpyAsync(cnt, cntT, (size_t)Q * 4, hipMemcpyDeviceToDevice, s));
-        sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, ix->qpad, ix->qnorm, bestT, nullptr, kpa, ix->perm, ekeysT, Q, s);
-        sc_launch_ivf_bound(metric, ekeysA, kpa, k, ix->qnorm, xmax_bits, ld, thr, Q, s, ekeysT, true);
+        sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, qpad, qnorm, bestT, nullptr, kpa, ix->perm, ekeysT, Q, s);
+        sc_launch_ivf_bound(metric, ekeysA, kpa, k, qnorm, xmax_bits, ld, thr, Q, s, ekeysT, true);
         sc_prof_end(rt, SC_PROF_MERGE, e0, e1);
         return SC_OK;
     };
     if (two_level) {  // the tails first: most neighbours live there, and what they yield tightens T for the other lists
         sc_launch_ivf_slot_thr(d_sq, d_qn, d_se, thr, nslots, d_st, d_stf, s);
         sc_prof_begin(rt, SC_PROF_SCAN, &e0, &e1);
-        sc_launch_ivf_coarse(ix->Xc8, ix->xcs, ld8, b + o_qc, b + o_items + b_first * sizeof(Item), (int)items[1].size(), d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survB,
+        sc_launch_ivf_coarse(Xc8, xcs, ld8, b + o_qc, b + o_items + b_first * sizeof(Item), (int)items[1].size(), d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survB,
                              cnt, IVFC_CAPB, b + o_hits, hit_bytes, s, nullptr, kmetric);
         sc_prof_end(rt, SC_PROF_SCAN, e0, e1);
         st = tighten();
@@ -1122,7 +1103,7 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
     if (b_count > 0) {
         sc_launch_ivf_slot_thr(d_sq, d_qn, d_se, thr, nslots, d_st, d_stf, s);
         sc_prof_begin(rt, SC_PROF_SCAN, &e0, &e1);
-        sc_launch_ivf_coarse(ix->Xc8, ix->xcs, ld8, b + o_qc, b + o_items + b_first * sizeof(Item), (int)b_count, d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survB, cnt,
+        sc_launch_ivf_coarse(Xc8, xcs, ld8, b + o_qc, b + o_items + b_first * sizeof(Item), (int)b_count, d_stf, d_st, d_qn, d_qs, d_sq, d_qb, d_qd, survB, cnt,
                              IVFC_CAPB, b + o_hits, hit_bytes, s, nullptr, kmetric);
         sc_prof_end(rt, SC_PROF_SCAN, e0, e1);
     }
@@ -1133,7 +1114,7 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
     // 6. refine: every row whose lower bound is within T, re-scored exactly; exact top-k
     sc_prof_begin(rt, SC_PROF_MERGE, &e0, &e1);
     sc_launch_ivf_candidates(metric, survA, cntA_d, best, kpa, survB, cnt, IVFC_CAP, thr, cand2, ncand, flags, Q, g_ivf_refine_cap < WCAP ? g_ivf_refine_cap : WCAP, s, IVFC_CAPB);
-    sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, ix->qpad, ix->qnorm, cand2, ncand, WCAP, ix->perm, ekeys2, Q, s);
+    sc_launch_scan_rerank_keys(metric, ix->X, ix->xnorm, ld, qpad, qnorm, cand2, ncand, WCAP, ix->perm, ekeys2, Q, s);
     sc_launch_ivf_refine_finalize(metric, ekeysA, kpa, ekeys2, ncand, flags, k, ix->row_base, out_dist, out_rows, Q, s);
     sc_prof_end(rt, SC_PROF_MERGE, e0, e1);
     SC_HIP(hipGetLastError());
@@ -1178,24 +1159,17 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
     ix->last_streamed_rows = streamed_rows;
     ix->last_groups = (int)(nslots / 64);
     if (R > 0) {  // probed again exactly: the sub-batch gets its own staging (queries + results)
-        const size_t qb = ((size_t)R * ix->dim * 4 + 255) & ~(size_t)255, db = ((size_t)R * k * 4 + 255) & ~(size_t)255, rb = ((size_t)R * k * 8 + 255) & ~(size_t)255;
-        st = sc_grow(ix, &ix->fb, &ix->fb_cap, qb + db + rb + (size_t)R * 4);
+        sc_subbatch sb;
+        st = sc_subbatch_stage(ix, ix->fb, q_dev, redo, k, &sb);
         if (st) return st;
-        float* fq = (float*)ix->fb;
-        float* fd = (float*)((char*)ix->fb + qb);
-        int64_t* frw = (int64_t*)((char*)ix->fb + qb + db);
-        int32_t* fidx = (int32_t*)((char*)ix->fb + qb + db + rb);
-        SC_HIP(hipMemcpyAsync(fidx, redo.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-        sc_launch_copy_rows_indexed(q_dev, fq, fidx, R, (size_t)ix->dim * 4, false, s);
         const int saved_mode = ix->search_mode;
         ix->search_mode = 4;
-        if (R >= 2) st = sc_ivf_search_listmajor_locked(ix, fq, R, k, nprobe, fd, frw);
-        else st = sc_ivf_search_locked(ix, fq, R, k, nprobe, fd, frw);
+        if (R >= 2) st = sc_ivf_search_listmajor_locked(ix, sb.q, R, k, nprobe, sb.d, sb.r);
+        else st = sc_ivf_search_locked(ix, sb.q, R, k, nprobe, sb.d, sb.r);
         ix->search_mode = saved_mode;
         if (st) return st;
-        sc_launch_copy_rows_indexed(fd, out_dist, fidx, R, (size_t)k * 4, true, s);
-        sc_launch_copy_rows_indexed(frw, out_rows, fidx, R, (size_t)k * 8, true, s);
-        SC_HIP(hipStreamSynchronize(s));
+        st = sc_subbatch_scatter(ix, sb, k, out_dist, out_rows);
+        if (st) return st;
         ix->last_ivfc_uncertified = R;
         ix->last_uncertified = R;
     }

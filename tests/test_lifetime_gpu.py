@@ -78,6 +78,27 @@ def test_teardown_after_fallback_release_scratch_and_train():
             rt2.close()
 
 
+def test_release_scratch_frees_the_centred_shadow_and_the_coarse_stage_rebuilds_it():
+    """release_scratch() drops everything rebuildable, the centred int8 shadow of the IVF coarse stage and that stage's scratch
+    included: the same search through the coarse stage afterwards rebuilds them and returns the same ids and the same f32 bits."""
+    rt2 = _native.Runtime(device=0)
+    ix = _native.Index(rt2, 96, metric="L2", kind="IVF_FLAT", nlist=16)
+    base = orc.synth(20_000, 96, seed=3)
+    ix.add(base)
+    ix.train(niter=3)
+    Q = orc.synth(40, 96, seed=5)
+    ix.set_search_mode("ivf_coarse")
+    d, r = ix.search(Q, k=10, nprobe=4)
+    assert ix.last_search_stats()["path"] == "ivf_coarse"
+    ix.release_scratch()
+    d2, r2 = ix.search(Q, k=10, nprobe=4)
+    assert ix.last_search_stats()["path"] == "ivf_coarse"
+    assert np.array_equal(r, r2) and np.array_equal(bits(d), bits(d2))
+    ix.release_scratch()  # ... and with nothing but the rows left the teardown is clean
+    ix.close()
+    rt2.close()
+
+
 def test_interpreter_exit_with_live_handles_is_clean():
     """A script that never closes anything and lets interpreter shutdown collect its handles must exit with status 0."""
     code = textwrap.dedent("""
