@@ -109,16 +109,21 @@ typedef struct sc_encoder_cfg {
     int32_t normalize;    /* 1 = L2-normalise the pooled vector                               */
     uint64_t synth_seed;  /* used only when no weight blob is given (benchmarks)              */
     int32_t pos_type;     /* 0 = learned absolute position table (BERT); 1 = ALiBi: no table, scores get
-                             -slope_h * |i - j| (jina-embeddings-v2 family named in the reference README) */
+                             -slope_h * |i - j| (jina-embeddings-v2 family named in the reference README);
+                             2 = rotary (nomic-bert): no table, Q and K rotated by position ("rotate-half" pairing
+                             (j, j + 32) of a head, angle p * rope_theta^(-2j/64)); max_pos bounds the sequence length */
     int32_t ffn_type;     /* 0 = Linear-GELU-Linear (BERT); 1 = GEGLU: W1 is [2*ffn, H] (gate rows first, then up
-                             rows), hidden = gelu(gate) * up, b1 is [2*ffn] (zeros for bias-free models)      */
+                             rows), hidden = gelu(gate) * up, b1 is [2*ffn] (zeros for bias-free models);
+                             2 = SwiGLU (nomic-bert): the same layout, hidden = silu(gate) * up                */
+    float rope_theta;     /* pos_type 2: rotary base (1000 for nomic-embed-text); 0 = 10000                   */
 } sc_encoder_cfg;
 
 /* Size in bytes of the f32 weight blob sc_encoder_create expects for cfg.  Blob order (all f32,
  * torch.nn.Linear layout [out, in]): word_emb [vocab,H], pos_emb [max_pos,H], type_emb [type_vocab,H],
  * emb_ln_gamma [H], emb_ln_beta [H], then per layer: Wq [H,H], bq, Wk, bk, Wv, bv, Wo [H,H], bo,
  * ln1_gamma, ln1_beta, W1 [ffn,H], b1 [ffn], W2 [H,ffn], b2 [H], ln2_gamma, ln2_beta.
- * pos_type 1 drops pos_emb from the blob; ffn_type 1 makes W1 [2*ffn,H] and b1 [2*ffn]. */
+ * pos_type 1 and 2 drop pos_emb from the blob; ffn_type 1 and 2 make W1 [2*ffn,H] (gate rows, then up rows) and b1 [2*ffn].
+ * Bias-free models (nomic-bert) keep their bias slots, filled with zeros. */
 sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out);
 /* Replaces EmbeddingProviderFactory.create() loading a model (providers.py:69-100): uploads the
  * weights (converted to bf16 on device).  weights_blob == NULL: synthetic weights 0.02*N(0,1) from
@@ -207,6 +212,13 @@ sc_status sc_diag_encoder_read(sc_encoder* enc, int32_t which, void* out, size_t
  * cannot allocate its centred shadow (the search must then probe exactly instead of failing); "ivf_refine_cap":
  * rows per query the IVF coarse stage's refine step takes on (-1 = default 4096; a small value sends queries to the exact re-probe). */
 sc_status sc_diag_set_option(const char* name, int32_t value);
+/* "rope_fused" of sc_diag_set_option: how the batch pipeline of a rotary encoder rotates Q and K (-1 = default, 0 = the stand-alone
+ * kernel after the QKV projection, 1 = inside that projection's epilogue); the two agree to bf16 rounding, not bit for bit.
+ * sc_diag_rope: the stand-alone rotation kernel on qk [rows, heads*64] f32, in place (rounded to bf16 on device first; row r is
+ * position r % S, S a power of two; theta <= 0 = 10000).  sc_diag_swiglu: h [rows, 2F] f32 (gate | up) -> out [rows, F] =
+ * silu(gate) * up through the SwiGLU kernel (F a multiple of 8). */
+sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta);
+sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out);
 /* qkv [B*S, 3*heads*64] rows = [Q | K | V]; lens [B]; out [B*S, heads*64] = softmax(QK^T/8 + mask) V. */
 sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out);
 

@@ -36,7 +36,7 @@ class _Cfg(C.Structure):
 class EncoderCfg(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32),
                 ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float), ("normalize", C.c_int32),
-                ("synth_seed", C.c_uint64), ("pos_type", C.c_int32), ("ffn_type", C.c_int32)]
+                ("synth_seed", C.c_uint64), ("pos_type", C.c_int32), ("ffn_type", C.c_int32), ("rope_theta", C.c_float)]
 
 
 _lib = None
@@ -79,6 +79,8 @@ SIGNATURES = {
     "sc_diag_gemm_i8": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_encoder_read": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
     "sc_diag_attention": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
+    "sc_diag_swiglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_index_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "sc_index_destroy": (C.c_int32, [C.c_void_p]),
     "sc_index_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -495,7 +497,7 @@ class Comm:
 
 
 BERT_BASE = dict(vocab=30522, hidden=768, layers=12, heads=12, ffn=3072, max_pos=512, type_vocab=2, ln_eps=1e-12)
-SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: position-free (ALiBi) encoders, or a position table that long
+SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: ALiBi or rotary encoders (no position table), or a position table that long
 
 
 class Encoder:
@@ -505,9 +507,14 @@ class Encoder:
                  synth_seed: int = 0):
         c = dict(BERT_BASE)
         c.update(cfg or {})
+        if c.get("rotary") and c.get("alibi"):
+            raise ValueError("encoder configuration: rotary and alibi are two position schemes, pick one")
+        if c.get("swiglu") and c.get("geglu"):
+            raise ValueError("encoder configuration: swiglu and geglu are two feed-forward gates, pick one")
         self.cfg = EncoderCfg(vocab=c["vocab"], hidden=c["hidden"], layers=c["layers"], heads=c["heads"], ffn=c["ffn"],
                               max_pos=c["max_pos"], type_vocab=c["type_vocab"], ln_eps=c["ln_eps"], normalize=1 if normalize else 0,
-                              synth_seed=synth_seed, pos_type=1 if c.get("alibi") else 0, ffn_type=1 if c.get("geglu") else 0)
+                              synth_seed=synth_seed, pos_type=2 if c.get("rotary") else 1 if c.get("alibi") else 0,
+                              ffn_type=2 if c.get("swiglu") else 1 if c.get("geglu") else 0, rope_theta=float(c.get("rope_theta") or 0.0))
         self.rt = rt
         self.hidden = c["hidden"]
         self.max_pos = c["max_pos"]
@@ -676,6 +683,25 @@ def diag_attention(rt: Runtime, qkv, lens, B: int, S: int, heads: int) -> np.nda
     out = np.empty((B * S, heads * 64), np.float32)
     _check(lib().sc_diag_attention(rt.handle, qkv.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S, heads,
                                    out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def diag_rope(rt: Runtime, qk, S: int, heads: int, theta: float) -> np.ndarray:
+    """The stand-alone rotary kernel on qk [rows, heads * 64] (row r = position r % S): the rotated values, bf16-rounded."""
+    out = np.array(qk, dtype=np.float32, order="C")
+    rows = out.shape[0]
+    if out.shape != (rows, heads * 64):
+        raise ValueError("qk must be [rows, heads * 64]")
+    _check(lib().sc_diag_rope(rt.handle, out.ctypes.data_as(C.c_void_p), rows, int(S), int(heads), float(theta)))
+    return out
+
+
+def diag_swiglu(rt: Runtime, h) -> np.ndarray:
+    """The SwiGLU kernel on h [rows, 2F] (gate | up): silu(gate) * up, bf16-rounded, [rows, F]."""
+    h = np.ascontiguousarray(h, np.float32)
+    rows, F = h.shape[0], h.shape[1] // 2
+    out = np.empty((rows, F), np.float32)
+    _check(lib().sc_diag_swiglu(rt.handle, h.ctypes.data_as(C.c_void_p), rows, F, out.ctypes.data_as(C.c_void_p)))
     return out
 
 

@@ -15,6 +15,8 @@
 //                                  column, softmax in registers, P feeds P V straight from the
 //                                  accumulator registers, V fragments by ds_read_b64_tr_b16
 //   mean_pool_kernel  HBM-bound  : 1 workgroup / chunk, masked mean (+ optional L2 normalise) -> f32
+//   glu_kernel<ACT>   HBM-bound  : gated feed-forward act(gate) * up between the FFN GEMMs (GEGLU: jina-bert-v2, SwiGLU: nomic-bert)
+//   rope_qk_kernel    HBM-bound  : rotary position embedding of Q and K, in place on the blocked QKV buffer (nomic-bert)
 #include <cstdlib>
 
 #include "gemm_tile.h"  // bf16 helpers, LDS-DMA pointer types
@@ -746,8 +748,21 @@ void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int
     }
 #undef SC_ATTN_CASE
 }
-// GEGLU (jina-bert-v2 GLUMLP): out[m][j] = gelu(h[m][j]) * h[m][F + j], h = [tokens, 2F] bf16 -> out [tokens, F] bf16
-__global__ __launch_bounds__(256) void geglu_kernel(const bf16_t* __restrict__ h, int64_t tokens, int F, bf16_t* __restrict__ out) {
+// Gated feed-forward: out[m][j] = act(h[m][j]) * h[m][F + j], h = [tokens, 2F] bf16 -> out [tokens, F] bf16.
+// GEGLU (jina-bert-v2 GLUMLP): act = erf-GELU.  SwiGLU (nomic-bert): act = silu(g) = g / (1 + exp(-g)) on the hardware exp2 / rcp
+// (v_exp_f32, v_rcp_f32: 1 ulp each, in front of a bf16 rounding); exp(-g) overflows to +inf for g < -88.7 and g * rcp(inf) is a
+// signed zero -- the limit of silu there -- never NaN.
+struct ActGelu {
+    static __device__ __forceinline__ f32x2 apply(f32x2 g) { return gelu_erf_fast2(g); }
+};
+struct ActSilu {
+    static __device__ __forceinline__ float one(float g) {
+        return g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.44269504088896340736f));
+    }
+    static __device__ __forceinline__ f32x2 apply(f32x2 g) { return f32x2{one(g[0]), one(g[1])}; }
+};
+template <class ACT>
+__global__ __launch_bounds__(256) void glu_kernel(const bf16_t* __restrict__ h, int64_t tokens, int F, bf16_t* __restrict__ out) {
     const int64_t total = tokens * (int64_t)(F / 8);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t m = i / (F / 8);
@@ -758,7 +773,7 @@ __global__ __launch_bounds__(256) void geglu_kernel(const bf16_t* __restrict__ h
         u32x4 o;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const f32x2 gg = gelu_erf_fast2(f32x2{bf2f((bf16_t)g[2 * c]), bf2f((bf16_t)g[2 * c + 1])});
+            const f32x2 gg = ACT::apply(f32x2{bf2f((bf16_t)g[2 * c]), bf2f((bf16_t)g[2 * c + 1])});
             o[c] = pack_bf16x2(gg[0] * bf2f((bf16_t)u[2 * c]), gg[1] * bf2f((bf16_t)u[2 * c + 1]));
         }
         *reinterpret_cast<u32x4*>(out + m * F + j) = o;
@@ -767,7 +782,49 @@ __global__ __launch_bounds__(256) void geglu_kernel(const bf16_t* __restrict__ h
 void sc_launch_geglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
     int64_t blocks = (tokens * (F / 8) + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(geglu_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)h, tokens, F, (bf16_t*)out);
+    hipLaunchKernelGGL(glu_kernel<ActGelu>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)h, tokens, F, (bf16_t*)out);
+}
+void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
+    int64_t blocks = (tokens * (F / 8) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(glu_kernel<ActSilu>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)h, tokens, F, (bf16_t*)out);
+}
+
+// Rotary position embedding ("rotate-half", GPT-NeoX) of Q and K in place on the blocked QKV buffer [blocks][M][64] bf16 the QKV
+// projections write: a (head, token) vector is 128 contiguous bytes.  HBM-bound (read + write of 2/3 of QKV).  A lane owns columns
+// c .. c + 7 and c + 32 .. c + 39 of one row (two 16-byte loads), so both members of every rotated pair (j, j + 32) sit in its
+// registers; 4 lanes per row, 16 rows per wave.  cos / sin [>= S][32] f32 (sc_encoder_create); position = row & (S - 1), S a power
+// of two, so that padding rows (>= the real tokens, content irrelevant) stay inside the table.  f32 math, one rounding back to bf16.
+__global__ __launch_bounds__(256) void rope_qk_kernel(bf16_t* __restrict__ qkv, int64_t M, int nblocks, int smask, const float* __restrict__ cos_t,
+                                                       const float* __restrict__ sin_t) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int64_t total = (int64_t)nblocks * M * 4;  // (block, row, quarter)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t vec = i >> 2;            // block * M + row
+        const int c = (int)(i & 3) * 8;
+        const int p = (int)((vec % M) & smask);
+        bf16_t* v = qkv + vec * 64 + c;
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(v), hi = *reinterpret_cast<const u32x4*>(v + 32);
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cos_t + p * 32 + c), c1 = *reinterpret_cast<const f32x4*>(cos_t + p * 32 + c + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sin_t + p * 32 + c), s1 = *reinterpret_cast<const f32x4*>(sin_t + p * 32 + c + 4);
+        u32x4 olo, ohi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a0 = __builtin_bit_cast(float, lo[k] << 16), a1 = __builtin_bit_cast(float, lo[k] & 0xFFFF0000u);
+            const float b0 = __builtin_bit_cast(float, hi[k] << 16), b1 = __builtin_bit_cast(float, hi[k] & 0xFFFF0000u);
+            const float cc0 = k < 2 ? c0[2 * k] : c1[2 * k - 4], cc1 = k < 2 ? c0[2 * k + 1] : c1[2 * k - 3];
+            const float ss0 = k < 2 ? s0[2 * k] : s1[2 * k - 4], ss1 = k < 2 ? s0[2 * k + 1] : s1[2 * k - 3];
+            olo[k] = pack_bf16x2(fmaf(a0, cc0, -b0 * ss0), fmaf(a1, cc1, -b1 * ss1));
+            ohi[k] = pack_bf16x2(fmaf(b0, cc0, a0 * ss0), fmaf(b1, cc1, a1 * ss1));
+        }
+        *reinterpret_cast<u32x4*>(v) = olo;
+        *reinterpret_cast<u32x4*>(v + 32) = ohi;
+    }
+}
+void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* cos_t, const float* sin_t, hipStream_t s) {
+    int64_t blocks = ((int64_t)nblocks * M * 4 + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(rope_qk_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (bf16_t*)qkv, M, nblocks, S - 1, cos_t, sin_t);
 }
 // Unnormalised pooling with more parallelism than one workgroup per chunk (which ran at 1.3 TB/s): a workgroup owns 256
 // columns of one chunk, thread (cc, rg) sums the rows rg, rg + 8, ... of 8 columns with 16-byte loads, LDS combines the 8 row groups

@@ -32,7 +32,9 @@
 // c2[n] = b[n] + sum_k beta[k] W[n,k] -- the normalisation becomes two FMAs in the epilogue and the LayerNorm kernel disappears.
 // EPI_RESLN_STATS: bias + LayerNorm(residual) applied on the fly ((r - mu) rs g + beta, beta folded into the bias), and the
 // row sums / sums of squares of THIS output (after its bf16 rounding) written per 256-column tile for the consumer's statistics.
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5 };
+// EPI_LNA_BIAS_ROPE: EPI_LNA_BIAS of a QKV projection with the rotary position embedding (rotate-half) applied to the Q and K
+// columns in the accumulator registers, before the one rounding to bf16.
+enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5, EPI_LNA_BIAS_ROPE = 6 };
 
 struct GemmArgs {
     const bf16_t* A;   // [M, lda]
@@ -58,6 +60,11 @@ struct GemmArgs {
     const float* gam;        // EPI_RESLN_STATS: [N] gamma of the residual's LayerNorm (its beta is folded into bias)
     float* stats_out;        // EPI_RESLN_STATS: [N / 256][M][2] partial sums of this output's rows
     float ln_eps;
+    // rotary positions (EPI_LNA_BIAS_ROPE): cos / sin tables [>= rope_smask + 1][32] f32, position of row m = m & rope_smask
+    // (sequence length a power of two), column tiles below rope_ncols (= 2 H: Q and K) are rotated
+    const float* rope_cos;
+    const float* rope_sin;
+    int rope_smask, rope_ncols;
 };
 
 // address of C[m][n] (n % 4 == 0 where vectors are stored): row-major, or 64-column blocks that are contiguous over the rows --
@@ -313,6 +320,10 @@ static __device__ __forceinline__ void gemm256_epilogue(const GemmArgs& a, int m
 }
 
 // ---- LayerNorm-folded epilogues --------------------------------------------------------------------------------------
+// EPI_LNA_BIAS_ROPE: a wave owns 64 output columns = one head of Q, K or V, and lane (fr, fq) holds columns ni 16 + 4 fq + {0..3},
+// ni = 0..3, of row fr of each mi block: columns j and j + 32 of the head are acc[ni][mi][c] and acc[ni + 2][mi][c] of the SAME lane,
+// so the rotation t'[j] = t[j] cos - t[j + 32] sin, t'[j + 32] = t[j + 32] cos + t[j] sin needs no exchange: 8 cos + 8 sin values per
+// (lane, mi) from the table row of that output row's position.  Scalar FMAs (packed f32 with a broadcast operand: tests/test_isa.py).
 // EPI_LNA_BIAS / EPI_LNA_GELU: out = rs_m (acc - mu_m c1[n]) + c2[n] (+ GELU).  (mu, rs) of a row come from the partial sums the
 // producing GEMM left per 256-column tile of the A tensor (LnaTailHook put this wave's 128 rows x slots into its pipeline slice);
 // the column tile n0 == 0 also publishes them finalised ([M][2]) for the residual epilogue of the next GEMM.
@@ -361,7 +372,7 @@ static __device__ __forceinline__ void gemm256_epilogue_lna(const GemmArgs& a, i
         SC_OPAQUE_PAIR(nrm);  // broadcasts as real register pairs, see SC_OPAQUE_PAIR
         SC_OPAQUE_PAIR(rs2);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
+        for (int ni = 0; ni < (EPI == EPI_LNA_BIAS_ROPE ? 0 : 4); ++ni) {  // (the rotary form keeps all four ni in registers: below)
             // rs (acc - mu c1) + c2  as  rs acc + (c2 - rs mu c1): two packed FMAs per pair of values (the epilogue is VALU bound: every
             // op per value costs ~0.55 us per tile)
             const f32x2 d01 = __builtin_elementwise_fma(nrm, f32x2{c1v[ni][0], c1v[ni][1]}, f32x2{c2v[ni][0], c2v[ni][1]});
@@ -374,6 +385,34 @@ static __device__ __forceinline__ void gemm256_epilogue_lna(const GemmArgs& a, i
                 v = f32x4{g0[0], g0[1], g1[0], g1[1]};
             }
             *reinterpret_cast<u32x2*>(stg + fr * T_EPI_ROW + (ni * 16 + 4 * fq) * 2) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+        }
+        if constexpr (EPI == EPI_LNA_BIAS_ROPE) {
+            f32x4 v[4];
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                const f32x2 d01 = __builtin_elementwise_fma(nrm, f32x2{c1v[ni][0], c1v[ni][1]}, f32x2{c2v[ni][0], c2v[ni][1]});
+                const f32x2 d23 = __builtin_elementwise_fma(nrm, f32x2{c1v[ni][2], c1v[ni][3]}, f32x2{c2v[ni][2], c2v[ni][3]});
+                const f32x2 v01 = __builtin_elementwise_fma(rs2, f32x2{acc[ni][mi][0], acc[ni][mi][1]}, d01);
+                const f32x2 v23 = __builtin_elementwise_fma(rs2, f32x2{acc[ni][mi][2], acc[ni][mi][3]}, d23);
+                v[ni] = f32x4{v01[0], v01[1], v23[0], v23[1]};
+            }
+            if (n0 + wn * 64 < a.rope_ncols) {  // wave-uniform: this wave's head belongs to Q or K
+                const size_t p = (size_t)((m0 + wm * 128 + mi * 16 + fr) & a.rope_smask) * 32 + 4 * fq;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const f32x4 cs = *reinterpret_cast<const f32x4*>(a.rope_cos + p + 16 * h);
+                    const f32x4 sn = *reinterpret_cast<const f32x4*>(a.rope_sin + p + 16 * h);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float x = v[h][c], y = v[h + 2][c];
+                        v[h][c] = fmaf(x, cs[c], -(y * sn[c]));
+                        v[h + 2][c] = fmaf(y, cs[c], x * sn[c]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                *reinterpret_cast<u32x2*>(stg + fr * T_EPI_ROW + (ni * 16 + 4 * fq) * 2) = u32x2{pack_bf16x2(v[ni][0], v[ni][1]), pack_bf16x2(v[ni][2], v[ni][3])};
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -534,7 +573,7 @@ __global__ __launch_bounds__(512) void gemm256_bf16_kernel(GemmArgs a) {
                                          ResLnTailHook{ResidualTailHook{a.R + (size_t)m0 * a.ldr + n0, a.ldr, w, lane, smem},
                                                        a.fin + (size_t)(m0 + (w >> 2) * 128) * 2}, a_kstep);
     }
-    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU)
+    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU || EPI == EPI_LNA_BIAS_ROPE)
         gemm256_mainloop_sel<PP, ML>(a, lda, m0, n0, smem, acc, w, lane,
                                      LnaTailHook{a.stats_in + (size_t)(m0 + (w >> 2) * 128) * 2, (size_t)a.M * 2, a.stat_slots, w, lane, smem}, a_kstep);
     else
@@ -550,7 +589,7 @@ __global__ __launch_bounds__(512) void gemm256_bf16_kernel(GemmArgs a) {
         return;
     }
     if (EPI == EPI_RESLN_STATS) gemm256_epilogue_resln<COOP>(a, m0, n0, smem, w, lane, acc);
-    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU) gemm256_epilogue_lna<EPI>(a, m0, n0, smem, w, lane, acc);
+    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU || EPI == EPI_LNA_BIAS_ROPE) gemm256_epilogue_lna<EPI>(a, m0, n0, smem, w, lane, acc);
     else gemm256_epilogue<EPI, COOP && !(DBG & 31)>(a, m0, n0, smem, w, lane, acc);
     if (a.trace) {
         gemm256_stamp(a, blockIdx.x, 4);
@@ -700,8 +739,10 @@ static void launch256_epi(int epi, const GemmArgs& a, dim3 grid, dim3 block, hip
 // statistics come in one slot per 256 columns of A).  epi = EPI_LNA_BIAS / EPI_LNA_GELU: bias = c2; EPI_RESLN_STATS: bias = b + beta.
 bool sc_gemm_ln_supported(int M, int N, int K) { return M > 0 && (M % T_BM) == 0 && (N % T_BN) == 0 && (K % 256) == 0; }
 void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C, int ldc, int M,
-                            int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps) {
+                            int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps,
+                            const float* rope_cos, const float* rope_sin, int rope_S, int rope_ncols) {
     GemmArgs a;
+    a.rope_cos = rope_cos; a.rope_sin = rope_sin; a.rope_smask = rope_S - 1; a.rope_ncols = rope_ncols;
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = bias; a.R = (const bf16_t*)R; a.C = (bf16_t*)C;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldr = ldr; a.ldc = ldc;
     a.cblock = ldc == SC_LDC_BLOCKED64 ? 1 : 0;
@@ -717,6 +758,7 @@ void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int 
     a.c1 = c1; a.stats_in = stats_in; a.stat_slots = K / 256; a.fin = fin; a.gam = gam; a.stats_out = stats_out; a.ln_eps = eps;
     dim3 grid((unsigned)a.ntiles), block(512);
     if (epi == EPI_LNA_BIAS) launch256<EPI_LNA_BIAS, 0>(a, grid, block, s);
+    else if (epi == EPI_LNA_BIAS_ROPE) launch256<EPI_LNA_BIAS_ROPE, 0>(a, grid, block, s);
     else if (epi == EPI_LNA_GELU) launch256<EPI_LNA_GELU, 0>(a, grid, block, s);
     else launch256<EPI_RESLN_STATS, 0>(a, grid, block, s);
 }
@@ -725,6 +767,7 @@ void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw
                          int ldc, int M, int N, int K, hipStream_t s, void* splitk_scratch, size_t splitk_scratch_bytes) {
     GemmArgs a;
     a.c1 = nullptr; a.stats_in = nullptr; a.stat_slots = 0; a.fin = nullptr; a.gam = nullptr; a.stats_out = nullptr; a.ln_eps = 0.f;
+    a.rope_cos = nullptr; a.rope_sin = nullptr; a.rope_smask = 0; a.rope_ncols = 0;
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = bias; a.R = (const bf16_t*)R; a.C = (bf16_t*)C;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldr = ldr; a.ldc = ldc;
     a.cblock = ldc == SC_LDC_BLOCKED64 ? 1 : 0;

@@ -29,10 +29,15 @@ void sc_launch_layernorm(const void* in, int tokens, int H, const float* g, cons
 bool sc_attention_supported(int S, int H, int heads);
 void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0);
 void sc_launch_geglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+// rotary positions: in-place rotation of the first `nblocks` 64-column blocks (Q and K heads) of a blocked buffer [blocks][M][64];
+// cos / sin [>= S][32] f32, row r is position r % S
+void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* cos_t, const float* sin_t, hipStream_t s);
 // LayerNorm-folded batch pipeline (gemm_bf16.hip EPI_LNA_* / EPI_RESLN_STATS, encoder_ops.hip)
 bool sc_gemm_ln_supported(int M, int N, int K);
 void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C, int ldc, int M,
-                            int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps);
+                            int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps,
+                            const float* rope_cos = nullptr, const float* rope_sin = nullptr, int rope_S = 0, int rope_ncols = 0);
 void sc_launch_embed_raw(const int32_t* ids, int tokens, int tokens_pad, int S, int H, int vocab, int max_pos, const float* wemb, const float* pemb,
                          const float* temb, void* out, float* stats, int slots, hipStream_t s);
 void sc_launch_fold_ln_weights(const float* W, const float* gamma, const float* beta, const float* bias, int N, int K, void* Wf, float* c1, float* c2,
@@ -51,7 +56,7 @@ void sc_gemm_set_pp(int v);
 void sc_gemm_set_trace(unsigned long long* dev);
 void sc_gemm_force_tile128(bool on);
 
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5 };
+enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5, EPI_LNA_BIAS_ROPE = 6 };
 
 struct LayerW {
     void* wqkv;  // bf16 [3H, H]
@@ -79,6 +84,7 @@ struct sc_encoder {
     size_t params_bytes = 0;
     float *wemb = nullptr, *pemb = nullptr, *temb = nullptr, *embg = nullptr, *embb = nullptr;
     float* slopes = nullptr;  // ALiBi head slopes (device) or NULL
+    float *rope_cos = nullptr, *rope_sin = nullptr;  // rotary positions: [max_pos][32] f32 each (device) or NULL
     std::vector<LayerW> layers;
     // workspace for `ws_tokens` (multiple of 256) tokens
     int64_t ws_tokens = 0;
@@ -107,10 +113,22 @@ struct sc_encoder {
 
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// ffn_type 1 (GEGLU) and 2 (SwiGLU): W1 holds gate and up rows, an element-wise kernel sits between the two FFN GEMMs
+static bool ffn_gated(const sc_encoder_cfg& c) { return c.ffn_type == 1 || c.ffn_type == 2; }
+static void launch_gate(const sc_encoder_cfg& c, const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
+    if (c.ffn_type == 2) sc_launch_swiglu(h, tokens, F, out, s);
+    else sc_launch_geglu(h, tokens, F, out, s);
+}
+// batch pipeline of rotary models ("rope_fused" of sc_diag_set_option): -1 = default, 0 = rope_qk_kernel after the QKV GEMM,
+// 1 = rotation in that GEMM's epilogue (EPI_LNA_BIAS_ROPE)
+// Default: fused -- 14.9k against 14.5k chunks/s at 256 x 256 tokens, 12 layers (+2.7 %, run-to-run spread 0.25 %: profiles/nomic_bench.log).
+static int g_rope_fused = -1;
+static const int ROPE_FUSED_DEFAULT = 1;
+
 // number of f32 values in the weight blob, in blob order (see include/semcode_hip.h)
 static int64_t blob_floats(const sc_encoder_cfg& c) {
-    const int64_t H = c.hidden, F = c.ffn, F1 = c.ffn_type == 1 ? 2 * F : F;
-    int64_t n = (int64_t)c.vocab * H + (c.pos_type == 1 ? 0 : (int64_t)c.max_pos * H) + (int64_t)c.type_vocab * H + 2 * H;
+    const int64_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F;
+    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (int64_t)c.type_vocab * H + 2 * H;
     n += (int64_t)c.layers * (4 * (H * H + H) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
     return n;
 }
@@ -128,7 +146,8 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
     if (c.hidden % 128 || c.ffn % 128 || c.hidden > 2048)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: hidden (<=2048) and ffn must be multiples of 128 (got %d, %d)", c.hidden, c.ffn);
     if (!(c.ln_eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: ln_eps must be > 0");
-    if (c.pos_type < 0 || c.pos_type > 1 || c.ffn_type < 0 || c.ffn_type > 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown pos_type / ffn_type");
+    if (c.pos_type < 0 || c.pos_type > 2 || c.ffn_type < 0 || c.ffn_type > 2) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown pos_type / ffn_type");
+    if (c.pos_type == 2 && !(c.rope_theta >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta must be >= 0 (0 = 10000)");
     return SC_OK;
 }
 
@@ -147,8 +166,8 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     e->rt = rt;
     sc_runtime_retain(rt);
     e->cfg = *cfg;
-    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = cfg->ffn_type == 1 ? 2 * F : F;
-    const bool alibi = cfg->pos_type == 1;
+    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = ffn_gated(*cfg) ? 2 * F : F;
+    const bool alibi = cfg->pos_type == 1, rotary = cfg->pos_type == 2, no_table = cfg->pos_type != 0;
 
     // staging copy of the f32 blob on device (freed after conversion)
     float* blob = nullptr;
@@ -168,8 +187,8 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     // parameter arena: f32 tables + per-layer {bf16 matrices, f32 vectors}
     size_t total = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += align256(bytes); return o; };
-    const size_t o_wemb = reserve((size_t)cfg->vocab * H * 4), o_pemb = reserve(alibi ? 16 : (size_t)cfg->max_pos * H * 4),
-                 o_slopes = reserve((size_t)cfg->heads * 4),
+    const size_t o_wemb = reserve((size_t)cfg->vocab * H * 4), o_pemb = reserve(no_table ? 16 : (size_t)cfg->max_pos * H * 4),
+                 o_slopes = reserve((size_t)cfg->heads * 4), o_rope = reserve(rotary ? (size_t)cfg->max_pos * 32 * 4 * 2 : 16),
                  o_temb = reserve((size_t)cfg->type_vocab * H * 4), o_eg = reserve(H * 4), o_eb = reserve(H * 4);
     struct LO { size_t wqkv, bqkv, wo, bo, l1g, l1b, w1, b1, w2, b2, l2g, l2b, wqkv_f, c1q, c2q, w1_f, c1f, c2f, bb_o, bb_2; };
     std::vector<LO> lo(L);
@@ -213,7 +232,7 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
         return d;
     };
     e->wemb = put_f32(o_wemb, take((int64_t)cfg->vocab * H), (int64_t)cfg->vocab * H, 0);
-    e->pemb = alibi ? nullptr : put_f32(o_pemb, take((int64_t)cfg->max_pos * H), (int64_t)cfg->max_pos * H, 0);
+    e->pemb = no_table ? nullptr : put_f32(o_pemb, take((int64_t)cfg->max_pos * H), (int64_t)cfg->max_pos * H, 0);
     if (alibi) {  // ALiBi head slopes (Press et al.; the non-power-of-two rule of the jina-bert implementation)
         std::vector<float> sl((size_t)cfg->heads);
         auto pow2_slopes = [](int n, std::vector<float>& out, int take, int stride) {
@@ -231,6 +250,22 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
         e->slopes = (float*)(e->params + o_slopes);
         hipMemcpyAsync(e->slopes, sl.data(), sl.size() * 4, hipMemcpyHostToDevice, s);
         hipStreamSynchronize(s);  // sl goes out of scope
+    }
+    if (rotary) {  // rotate-half (GPT-NeoX) angles p * theta^(-2 i / 64), i < 32, computed in double
+        const double theta = cfg->rope_theta > 0.f ? (double)cfg->rope_theta : 10000.0;
+        const size_t n = (size_t)cfg->max_pos * 32;
+        std::vector<float> tab(2 * n);  // cos table, then sin table
+        for (int i = 0; i < 32; ++i) {
+            const double f = std::pow(theta, -2.0 * i / 64.0);
+            for (int64_t p = 0; p < cfg->max_pos; ++p) {
+                tab[(size_t)p * 32 + i] = (float)std::cos((double)p * f);
+                tab[n + (size_t)p * 32 + i] = (float)std::sin((double)p * f);
+            }
+        }
+        e->rope_cos = (float*)(e->params + o_rope);
+        e->rope_sin = e->rope_cos + n;
+        hipMemcpyAsync(e->rope_cos, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s);
+        hipStreamSynchronize(s);  // tab goes out of scope
     }
     e->temb = put_f32(o_temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, 0);
     e->embg = put_f32(o_eg, take(H), H, 1);
@@ -313,12 +348,12 @@ static sc_status ensure_ws(sc_encoder* e, int64_t B, int64_t S) {
     e->ws = nullptr;
     e->ws_tokens = 0;
     e->ws_batch = 0;
-    const int64_t H = e->cfg.hidden, F = e->cfg.ffn, F1 = e->cfg.ffn_type == 1 ? 2 * F : F;
+    const int64_t H = e->cfg.hidden, F = e->cfg.ffn, F1 = ffn_gated(e->cfg) ? 2 * F : F;
     const int64_t nb = B > e->ws_batch ? B : e->ws_batch;
     size_t total = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += align256(bytes); return o; };
     const size_t ox = reserve(tokens * H * 2), ox1 = reserve(tokens * H * 2), oy = reserve(tokens * H * 2), oqkv = reserve(tokens * 3 * H * 2),
-                 octx = reserve(tokens * H * 2), ohm = reserve(tokens * F1 * 2), ohg = reserve(e->cfg.ffn_type == 1 ? tokens * F * 2 : 16),
+                 octx = reserve(tokens * H * 2), ohm = reserve(tokens * F1 * 2), ohg = reserve(ffn_gated(e->cfg) ? tokens * F * 2 : 16),
                  oids = reserve(tokens * 4), olens = reserve(nb * 4), opool = reserve(nb * H * 4);
     const size_t slots = (size_t)H / 256;
     const size_t osa = reserve(e->foldable ? slots * tokens * 8 : 16), osb = reserve(e->foldable ? slots * tokens * 8 : 16),
@@ -356,15 +391,22 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     // statistics buffers are laid out for ws_tokens rows; this call uses the first M rows of every slot: slot stride must be M, so
     // they are addressed as [slots][M][2] inside the (larger or equal) allocation
     static const char* env_fb = getenv("SC_FFN_BLOCKED");
-    const bool ffn_blocked = c.ffn_type != 1 && !(env_fb && env_fb[0] == '0');
+    const bool gated = ffn_gated(c);
+    const bool ffn_blocked = !gated && !(env_fb && env_fb[0] == '0');
+    const bool rope = c.pos_type == 2, rope_fused = rope && (g_rope_fused < 0 ? ROPE_FUSED_DEFAULT : g_rope_fused) != 0;
     sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
         hipEvent_t g0, g1;
         sc_prof_begin(rt, SC_PROF_GEMM, &g0, &g1);
-        sc_launch_gemm_bf16_ln(EPI_LNA_BIAS, e->x, H, w.wqkv_f, H, w.c2q, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, w.c1q, e->stat_b, e->fin_b, nullptr,
-                               nullptr, c.ln_eps);
+        if (rope_fused)
+            sc_launch_gemm_bf16_ln(EPI_LNA_BIAS_ROPE, e->x, H, w.wqkv_f, H, w.c2q, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, w.c1q, e->stat_b, e->fin_b,
+                                   nullptr, nullptr, c.ln_eps, e->rope_cos, e->rope_sin, S, 2 * H);
+        else
+            sc_launch_gemm_bf16_ln(EPI_LNA_BIAS, e->x, H, w.wqkv_f, H, w.c2q, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, w.c1q, e->stat_b, e->fin_b, nullptr,
+                                   nullptr, c.ln_eps);
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
+        if (rope && !rope_fused) sc_launch_rope_qk(e->qkv, M, 2 * c.heads, S, e->rope_cos, e->rope_sin, s);
         hipEvent_t a0, a1;
         sc_prof_begin(rt, SC_PROF_ATTN, &a0, &a1);
         sc_launch_attention(e->qkv, lens_dev, B, S, H, e->slopes, e->ctx, s, M);
@@ -374,18 +416,18 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
         const void* ffn_in = e->hm;
         sc_prof_begin(rt, SC_PROF_GEMM, &g0, &g1);
-        if (c.ffn_type == 1)
+        if (gated)
             sc_launch_gemm_bf16_ln(EPI_LNA_BIAS, e->y, H, w.w1_f, H, w.c2f, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, w.c1f, e->stat_a, e->fin_a, nullptr, nullptr, c.ln_eps);
         else
             sc_launch_gemm_bf16_ln(EPI_LNA_GELU, e->y, H, w.w1_f, H, w.c2f, nullptr, 0, e->hm, ffn_blocked ? SC_LDC_BLOCKED64 : F, M, F, H, s, w.c1f, e->stat_a,
                                    e->fin_a, nullptr, nullptr, c.ln_eps);
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
-        if (c.ffn_type == 1) {
-            sc_launch_geglu(e->hm, M, F, e->hg, s);
+        if (gated) {
+            launch_gate(c, e->hm, M, F, e->hg, s);
             ffn_in = e->hg;
         }
         sc_prof_begin(rt, SC_PROF_GEMM, &g0, &g1);
-        sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, ffn_in, (ffn_blocked && c.ffn_type != 1) ? SC_LDC_BLOCKED64 : F, w.w2, F, w.bb_2, e->y, H, e->x, H, M, H, F, s, nullptr,
+        sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, ffn_in, ffn_blocked ? SC_LDC_BLOCKED64 : F, w.w2, F, w.bb_2, e->y, H, e->x, H, M, H, F, s, nullptr,
                                nullptr, e->fin_a, w.ln1g, e->stat_b, c.ln_eps);
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
     }
@@ -423,7 +465,8 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     // apart).  Only the 256-tile kernel reads that layout: not with split-K (small M), not on the GEGLU path (element-wise kernel
     // in between), and only when F divides into 256-column tiles.
     static const char* env_fb = getenv("SC_FFN_BLOCKED");
-    const bool ffn_blocked = !sk && c.ffn_type != 1 && (F % 256) == 0 && (H % 256) == 0 && !(env_fb && env_fb[0] == '0');
+    const bool gated = ffn_gated(c);
+    const bool ffn_blocked = !sk && !gated && (F % 256) == 0 && (H % 256) == 0 && !(env_fb && env_fb[0] == '0');
     sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
@@ -432,6 +475,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
         // QKV in 64-column blocks, i.e. [3 heads][tokens][64]: attention reads each (chunk, head) operand as one contiguous block
         sc_launch_gemm_bf16(EPI_BIAS, e->x, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, sk, skb);
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
+        if (c.pos_type == 2) sc_launch_rope_qk(e->qkv, M, 2 * c.heads, S, e->rope_cos, e->rope_sin, s);
         hipEvent_t a0, a1;
         sc_prof_begin(rt, SC_PROF_ATTN, &a0, &a1);
         sc_launch_attention(e->qkv, lens_dev, B, S, H, e->slopes, e->ctx, s, M);
@@ -442,11 +486,11 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
         sc_launch_layernorm(e->y, tokens, H, w.ln1g, w.ln1b, c.ln_eps, e->x1, s);
         const void* ffn_in = e->hm;
         sc_prof_begin(rt, SC_PROF_GEMM, &g0, &g1);
-        if (c.ffn_type == 1) sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb);
+        if (gated) sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb);
         else sc_launch_gemm_bf16(EPI_BIAS_GELU, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, ffn_blocked ? SC_LDC_BLOCKED64 : F, M, F, H, s, sk, skb);
         sc_prof_end(rt, SC_PROF_GEMM, g0, g1);
-        if (c.ffn_type == 1) {  // GEGLU: gelu(gate) * up
-            sc_launch_geglu(e->hm, M, F, e->hg, s);
+        if (gated) {  // GEGLU: gelu(gate) * up; SwiGLU: silu(gate) * up
+            launch_gate(c, e->hm, M, F, e->hg, s);
             ffn_in = e->hg;
         }
         sc_prof_begin(rt, SC_PROF_GEMM, &g0, &g1);
@@ -464,7 +508,7 @@ static sc_status check_embed_args(sc_encoder* e, const void* ids, const void* le
     if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "embed: batch %d out of range", B);
     if (!sc_attention_supported(S, e->cfg.hidden, e->cfg.heads))
         return sc_fail(SC_ERR_UNSUPPORTED, "embed: sequence length %d not in {32,64,128,256,512,1024,2048} (pad on the host)", S);
-    if (S > e->cfg.max_pos && e->cfg.pos_type == 0) return sc_fail(SC_ERR_INVALID, "embed: sequence length %d exceeds max_pos %d", S, e->cfg.max_pos);
+    if (S > e->cfg.max_pos && e->cfg.pos_type != 1) return sc_fail(SC_ERR_INVALID, "embed: sequence length %d exceeds max_pos %d", S, e->cfg.max_pos);
     return SC_OK;
 }
 
@@ -692,6 +736,7 @@ extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
     else if (!strcmp(name, "wide_candidates")) sc_set_wide_force(value);
     else if (!strcmp(name, "ivf_tail_rows")) sc_set_ivf_tail_rows(value);
     else if (!strcmp(name, "delete_chunk_rows")) sc_set_delete_chunk_rows(value);
+    else if (!strcmp(name, "rope_fused")) g_rope_fused = value < 0 ? -1 : (value ? 1 : 0);
     else return sc_fail(SC_ERR_INVALID, "sc_diag_set_option: unknown option '%s'", name);
     return SC_OK;
 }
@@ -730,6 +775,57 @@ extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const i
     sc_launch_bf16_to_f32(dc.p, (float*)fo.p, tokens * H, s);
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(out, fo.p, (size_t)tokens * H * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
+// rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],
+// rotated in place, widened and laid out row-major again.
+extern "C" sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta) {
+    if (!rt || !qk || rows < 1 || heads < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_rope: bad argument");
+    if (S < 1 || S > 65536 || (S & (S - 1))) return sc_fail(SC_ERR_INVALID, "sc_diag_rope: S must be a power of two");
+    if (!(theta > 0.f)) theta = 10000.f;
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    const int64_t n = (int64_t)rows * heads * 64;
+    std::vector<float> blk((size_t)n), tab((size_t)S * 64);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int h = 0; h < heads; ++h) memcpy(&blk[((size_t)h * rows + r) * 64], qk + ((size_t)r * heads + h) * 64, 256);
+    for (int i = 0; i < 32; ++i) {  // as sc_encoder_create builds it
+        const double f = std::pow((double)theta, -2.0 * i / 64.0);
+        for (int p = 0; p < S; ++p) {
+            tab[(size_t)p * 32 + i] = (float)std::cos((double)p * f);
+            tab[(size_t)S * 32 + (size_t)p * 32 + i] = (float)std::sin((double)p * f);
+        }
+    }
+    DevBuf fb, db, dt, fo;
+    sc_status st = upload_bf16(blk.data(), n, fb, db, s);
+    if (st) return st;
+    if (dt.alloc(tab.size() * 4) != hipSuccess || fo.alloc((size_t)n * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    SC_HIP(hipMemcpyAsync(dt.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    sc_launch_rope_qk(db.p, rows, heads, S, (const float*)dt.p, (const float*)dt.p + (size_t)S * 32, s);
+    sc_launch_bf16_to_f32(db.p, (float*)fo.p, n, s);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(blk.data(), fo.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    for (int64_t r = 0; r < rows; ++r)
+        for (int h = 0; h < heads; ++h) memcpy(qk + ((size_t)r * heads + h) * 64, &blk[((size_t)h * rows + r) * 64], 256);
+    return SC_OK;
+}
+
+// swiglu_kernel on its own: h [rows, 2F] f32 (gate | up) -> bf16 -> out [rows, F] = silu(gate) * up
+extern "C" sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) {
+    if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "sc_diag_swiglu: bad argument (F must be a multiple of 8)");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fh, dh, dc, fo;
+    sc_status st = upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s);
+    if (st) return st;
+    if (dc.alloc((size_t)rows * F * 2) != hipSuccess || fo.alloc((size_t)rows * F * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    sc_launch_swiglu(dh.p, rows, F, dc.p, s);
+    sc_launch_bf16_to_f32(dc.p, (float*)fo.p, (int64_t)rows * F, s);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(out, fo.p, (size_t)rows * F * 4, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }

@@ -21,9 +21,14 @@ Tensor names: llama.cpp's `bert` / `jina-bert-v2` architectures (gguf-py tensor_
 token_types, token_embd_norm, blk.N.{attn_q, attn_k, attn_v, attn_output, attn_output_norm, ffn_up, ffn_gate, ffn_down,
 layer_output_norm}.  jina-bert-v2 has no position table (ALiBi) and a gated feed-forward without bias: the converter splits the
 checkpoint's `mlp.gated_layers` [2F, H] into ffn_gate (first F rows, the activated half) and ffn_up; the blob wants them
-stacked again, gate first.  PARITY STATUS: no GGUF file and no llama.cpp exist offline, so the name mapping and the vocabulary
+stacked again, gate first.  nomic-bert (nomic-embed-text-v1 / v1.5: rotary positions, SwiGLU, no Linear bias) has no position
+table either; its converter keeps the checkpoint's fused projection as blk.N.attn_qkv [3H, H] (Q rows, then K, then V -- split
+attn_q / attn_k / attn_v are accepted too), and stores ffn_gate (the SiLU-activated half) and ffn_up; the rotary base is
+`nomic-bert.rope.freq_base`.  PARITY STATUS: no GGUF file and no llama.cpp exist offline, so the name mapping and the vocabulary
 convention below are restated from the published converter and exercised only on files this repository writes
-(tests/test_gguf.py) -- "parity unpinned" against a real jina / BERT GGUF.
+(tests/test_gguf.py, tests/test_nomic_weights.py) -- "parity unpinned" against a real jina / BERT / nomic GGUF (SURVEY.md section
+8 f-4).  For nomic-bert the ARCHITECTURE is pinned (transformers' NomicBertModel, tests/golden/nomic_golden.npz) and so is the
+.safetensors mapping; the GGUF tensor names and the order of the fused attn_qkv rows are not.
 """
 from __future__ import annotations
 
@@ -136,23 +141,26 @@ def tensor_f32(tensors: dict, name: str) -> np.ndarray:
 
 
 def gguf_config(meta: dict) -> dict:
-    """Encoder configuration stated by the file's metadata (keys of llama.cpp's bert / jina-bert-v2 architectures)."""
+    """Encoder configuration stated by the file's metadata (keys of llama.cpp's bert / jina-bert-v2 / nomic-bert architectures).
+    nomic-bert: rotary + swiglu, max_pos = nomic-bert.context_length (2048 when absent), rope_theta = nomic-bert.rope.freq_base --
+    1000 when the key is absent, the value of nomic-embed-text and transformers' default for the family (not llama.cpp's 10000)."""
     arch = str(meta.get("general.architecture", ""))
     if arch not in ("bert", "jina-bert-v2", "nomic-bert"):
-        raise GGUFError(f"GGUF architecture {arch!r} is not an encoder this backend runs (bert, jina-bert-v2)")
-    if arch == "nomic-bert":
-        raise GGUFError("nomic-bert (rotary positions, SwiGLU) is not implemented by this backend")
+        raise GGUFError(f"GGUF architecture {arch!r} is not an encoder this backend runs (bert, jina-bert-v2, nomic-bert)")
 
     def need(key: str):
         if f"{arch}.{key}" not in meta:
             raise GGUFError(f"GGUF metadata lacks {arch}.{key}")
         return meta[f"{arch}.{key}"]
 
-    jina = arch == "jina-bert-v2"
+    jina, nomic = arch == "jina-bert-v2", arch == "nomic-bert"
     cfg = {"hidden": int(need("embedding_length")), "layers": int(need("block_count")), "heads": int(need("attention.head_count")),
-           "ffn": int(need("feed_forward_length")), "max_pos": int(meta.get(f"{arch}.context_length", 512)),
+           "ffn": int(need("feed_forward_length")), "max_pos": int(meta.get(f"{arch}.context_length", 2048 if nomic else 512)),
            "ln_eps": float(meta.get(f"{arch}.attention.layer_norm_epsilon", 1e-12)), "alibi": jina, "geglu": jina}
+    if nomic:
+        cfg.update(rotary=True, swiglu=True, rope_theta=float(meta.get("nomic-bert.rope.freq_base", 1000.0)))
     return cfg
+
 
 
 def gguf_vocab(meta: dict) -> Optional[list]:
@@ -180,12 +188,15 @@ def gguf_to_blob(path: "str | Path", cfg: Optional[dict] = None) -> "tuple[np.nd
     build the encoder with -- every field the file states must agree with it."""
     meta, T = read_gguf(path)
     fcfg = gguf_config(meta)
-    jina = fcfg["geglu"]
+    jina, nomic = fcfg["geglu"], bool(fcfg.get("rotary"))
 
     def get(name: str) -> np.ndarray:
         if name not in T:
             raise GGUFError(f"{path}: tensor {name!r} not found")
         return tensor_f32(T, name)
+
+    def bias(name: str, n: int) -> np.ndarray:  # nomic-bert: a Linear layer's bias is used when the file has one, zeros when not
+        return get(name).reshape(-1) if (name in T or not nomic) else np.zeros(n, np.float32)
 
     word = get("token_embd.weight")
     fcfg["vocab"] = int(word.shape[0])
@@ -195,12 +206,13 @@ def gguf_to_blob(path: "str | Path", cfg: Optional[dict] = None) -> "tuple[np.nd
         for key in ("hidden", "layers", "heads", "ffn", "vocab", "type_vocab"):
             if key in cfg and int(cfg[key]) != int(fcfg[key]):
                 raise ValueError(f"{path}: the file says {key} = {fcfg[key]}, the encoder configuration {cfg[key]}")
-        if bool(cfg.get("alibi")) != jina or bool(cfg.get("geglu")) != jina:
-            raise ValueError(f"{path} is a {'jina-bert-v2 (ALiBi + GEGLU)' if jina else 'BERT'} model but the encoder configuration says "
-                             f"alibi={bool(cfg.get('alibi'))}, geglu={bool(cfg.get('geglu'))}")
+        if bool(cfg.get("alibi")) != jina or bool(cfg.get("geglu")) != jina or bool(cfg.get("rotary")) != nomic or bool(cfg.get("swiglu")) != nomic:
+            kind = "nomic-bert (rotary + SwiGLU)" if nomic else "jina-bert-v2 (ALiBi + GEGLU)" if jina else "BERT"
+            raise ValueError(f"{path} is a {kind} model but the encoder configuration says "
+                             f"alibi={bool(cfg.get('alibi'))}, geglu={bool(cfg.get('geglu'))}, rotary={bool(cfg.get('rotary'))}, swiglu={bool(cfg.get('swiglu'))}")
     H, F = fcfg["hidden"], fcfg["ffn"]
     parts = [word.reshape(-1)]
-    if not jina:
+    if not jina and not nomic:
         pos = get("position_embd.weight")
         want = int(cfg["max_pos"]) if cfg and "max_pos" in cfg else int(pos.shape[0])
         if pos.shape[0] < want:
@@ -210,14 +222,26 @@ def gguf_to_blob(path: "str | Path", cfg: Optional[dict] = None) -> "tuple[np.nd
     parts += [types.reshape(-1), get("token_embd_norm.weight").reshape(-1), get("token_embd_norm.bias").reshape(-1)]
     for l in range(fcfg["layers"]):
         p = f"blk.{l}."
-        for n in ("attn_q", "attn_k", "attn_v", "attn_output"):
-            parts += [get(p + n + ".weight").reshape(-1), get(p + n + ".bias").reshape(-1)]
+        if nomic and p + "attn_qkv.weight" in T:  # fused projection [3H, H]: Q rows, K rows, V rows
+            qkv = get(p + "attn_qkv.weight")
+            if qkv.shape != (3 * H, H):
+                raise GGUFError(f"{path}: {p}attn_qkv.weight is {qkv.shape}, expected {(3 * H, H)}")
+            bqkv = bias(p + "attn_qkv.bias", 3 * H)
+            for i in range(3):
+                parts += [qkv[i * H:(i + 1) * H].reshape(-1), bqkv[i * H:(i + 1) * H]]
+        else:
+            for n in ("attn_q", "attn_k", "attn_v"):
+                parts += [get(p + n + ".weight").reshape(-1), bias(p + n + ".bias", H)]
+        parts += [get(p + "attn_output.weight").reshape(-1), bias(p + "attn_output.bias", H)]
         parts += [get(p + "attn_output_norm.weight").reshape(-1), get(p + "attn_output_norm.bias").reshape(-1)]
         if jina:  # gate (the activated half) first, then up; no bias
             parts += [get(p + "ffn_gate.weight").reshape(-1), get(p + "ffn_up.weight").reshape(-1), np.zeros(2 * F, np.float32)]
+        elif nomic:
+            parts += [get(p + "ffn_gate.weight").reshape(-1), get(p + "ffn_up.weight").reshape(-1),
+                      bias(p + "ffn_gate.bias", F), bias(p + "ffn_up.bias", F)]
         else:
             parts += [get(p + "ffn_up.weight").reshape(-1), get(p + "ffn_up.bias").reshape(-1)]
-        parts += [get(p + "ffn_down.weight").reshape(-1), get(p + "ffn_down.bias").reshape(-1),
+        parts += [get(p + "ffn_down.weight").reshape(-1), bias(p + "ffn_down.bias", H),
                   get(p + "layer_output_norm.weight").reshape(-1), get(p + "layer_output_norm.bias").reshape(-1)]
     blob = np.concatenate(parts).astype(np.float32, copy=False)
     return blob, fcfg, meta

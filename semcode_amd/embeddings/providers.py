@@ -49,6 +49,34 @@ _JINA_LAYER = ["attention.self.query.weight", "attention.self.query.bias", "atte
                "mlp.wo.weight", "mlp.wo.bias", "mlp.layernorm.weight", "mlp.layernorm.bias"]
 
 
+# transformers NomicBertModel names (nomic-embed-text-v1 / v1.5 as `nomic_bert`): no position table (rotary), no Linear bias,
+# gate_proj (SiLU-activated) and up_proj stacked into W1 = [2F, H], gate rows first.  Checked against NomicBertModel itself
+# (tests/test_nomic_weights.py).  Second member: the blob's bias slot after that matrix, which the file has no tensor for (H or 2F zeros).
+_NOMIC_HEAD = ["embeddings.word_embeddings.weight", "embeddings.token_type_embeddings.weight", "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"]
+_NOMIC_LAYER = [("self_attn.q_proj.weight", "H"), ("self_attn.k_proj.weight", "H"), ("self_attn.v_proj.weight", "H"), ("self_attn.o_proj.weight", "H"),
+                ("post_attention_layernorm.weight", None), ("post_attention_layernorm.bias", None),
+                ("mlp.gate_proj.weight", None), ("mlp.up_proj.weight", "2F"), ("mlp.down_proj.weight", "H"),
+                ("post_mlp_layernorm.weight", None), ("post_mlp_layernorm.bias", None)]
+
+
+def _nomic_blob(path, tensors: dict, layers: int) -> np.ndarray:
+    def get(name: str) -> np.ndarray:
+        for key in (name, "nomic_bert." + name):
+            if key in tensors:
+                return np.asarray(tensors[key], dtype=np.float32)
+        raise KeyError(f"{path}: tensor {name!r} not found")
+
+    parts = [get(n).reshape(-1) for n in _NOMIC_HEAD]
+    H = get(_NOMIC_HEAD[2]).shape[0]
+    for l in range(layers):
+        F = get(f"layers.{l}.mlp.gate_proj.weight").shape[0]
+        for n, zeros in _NOMIC_LAYER:
+            parts.append(get(f"layers.{l}.{n}").reshape(-1))
+            if zeros:  # the bias slot that follows this matrix in blob order
+                parts.append(np.zeros(H if zeros == "H" else 2 * F, np.float32))
+    return np.concatenate(parts)
+
+
 def tensors_rows(tensors: dict, name: str) -> int:
     """Number of rows (output features) of a 2-D checkpoint tensor, with or without the "bert." prefix."""
     for key in (name, "bert." + name):
@@ -59,9 +87,10 @@ def tensors_rows(tensors: dict, name: str) -> int:
 
 def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None) -> np.ndarray:
     """Flat f32 blob in ABI order from `.npy` (already flat), `.gguf` (llama.cpp's bert / jina-bert-v2 tensor names, F32 / F16 /
-    BF16; embeddings/gguf.py) or `.safetensors` (HF BERT names, or jina-bert-v2 names when the
-    file holds `mlp.gated_layers`; optional "bert." prefix).  cfg: the encoder configuration the blob is for (checked
-    against the checkpoint's architecture: a jina file needs alibi + geglu, a BERT file neither)."""
+    BF16; embeddings/gguf.py) or `.safetensors` (HF BERT names, jina-bert-v2 names when the file holds `mlp.gated_layers`, or
+    transformers' NomicBert names when it holds `layers.0.mlp.gate_proj`; optional "bert." / "nomic_bert." prefix).  cfg: the
+    encoder configuration the blob is for (checked against the checkpoint's architecture: a jina file needs alibi + geglu, a
+    nomic file rotary + swiglu, a BERT file none of them)."""
     path = Path(path)
     if path.suffix == ".npy":
         return np.load(path, allow_pickle=False).astype(np.float32).reshape(-1)
@@ -77,9 +106,14 @@ def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None
             raise KeyError(f"{path}: tensor {name!r} not found")
 
         jina = any(k.endswith("encoder.layer.0.mlp.gated_layers.weight") for k in tensors)
-        if cfg is not None and (bool(cfg.get("alibi")) != jina or bool(cfg.get("geglu")) != jina):
-            raise ValueError(f"{path} is a {'jina-bert-v2 (ALiBi + GEGLU)' if jina else 'BERT'} checkpoint but the encoder configuration says "
-                             f"alibi={bool(cfg.get('alibi'))}, geglu={bool(cfg.get('geglu'))}")
+        nomic = any(k in ("layers.0.mlp.gate_proj.weight", "nomic_bert.layers.0.mlp.gate_proj.weight") for k in tensors)
+        if cfg is not None and (bool(cfg.get("alibi")) != jina or bool(cfg.get("geglu")) != jina or bool(cfg.get("rotary")) != nomic
+                                or bool(cfg.get("swiglu")) != nomic):
+            kind = "nomic-bert (rotary + SwiGLU)" if nomic else "jina-bert-v2 (ALiBi + GEGLU)" if jina else "BERT"
+            raise ValueError(f"{path} is a {kind} checkpoint but the encoder configuration says alibi={bool(cfg.get('alibi'))}, "
+                             f"geglu={bool(cfg.get('geglu'))}, rotary={bool(cfg.get('rotary'))}, swiglu={bool(cfg.get('swiglu'))}")
+        if nomic:
+            return _nomic_blob(path, tensors, layers)
         head, layer = (_JINA_HEAD, _JINA_LAYER) if jina else (_HF_HEAD, _HF_LAYER)
         parts = [get(n) for n in head]
         for l in range(layers):
@@ -105,13 +139,17 @@ class MI355XEmbeddings:
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,
                  normalize: bool = False, batch_size: int = 256, runtime: Any = None, synth_seed: int = 0,
-                 allow_synthetic: Optional[bool] = None) -> None:
+                 allow_synthetic: Optional[bool] = None, document_prefix: Optional[str] = None, query_prefix: Optional[str] = None) -> None:
         from .. import _native  # raises loudly when libsemcode_hip.so is missing: there is no CPU fallback
 
         settings = _resolve_settings()
         self.model = model or getattr(settings, "embedding_model", None)
         self.max_tokens = int(max_tokens or getattr(settings, "mi355x_max_tokens", 512))
         self.batch_size = int(batch_size)
+        # task prefixes (nomic-embed-text expects "search_document: " / "search_query: "); llama.cpp behind LangChain adds none,
+        # so none is the default
+        self.document_prefix = str(document_prefix if document_prefix is not None else getattr(settings, "mi355x_document_prefix", "") or "")
+        self.query_prefix = str(query_prefix if query_prefix is not None else getattr(settings, "mi355x_query_prefix", "") or "")
         # Like the reference's llama.cpp branch, which refuses to start without a model path (providers.py:77-81), a client
         # without weights or without a vocabulary is an error: random-init weights and the hash tokenizer produce vectors that
         # index and search without any error and mean nothing.  Benchmarks and tests opt in explicitly.
@@ -142,6 +180,8 @@ class MI355XEmbeddings:
             fcfg["type_vocab"] = int(tens["token_types.weight"][1][0])
             if fcfg["alibi"]:
                 fcfg["max_pos"] = max(int(fcfg["max_pos"]), int(self._cfg["max_pos"]))
+            elif fcfg.get("rotary"):
+                pass  # the file's context length stands: it bounds the sequence length and sizes the cos / sin table
             elif "position_embd.weight" in tens:
                 fcfg["max_pos"] = int(tens["position_embd.weight"][1][0])
             self._cfg.update(fcfg)
@@ -189,7 +229,7 @@ class MI355XEmbeddings:
             self.truncated_texts += cut
             if before == 0 or (self.truncated_texts.bit_length() != before.bit_length()):
                 log.warning("mi355x embeddings: %d of %d texts so far reached max_tokens=%d and were truncated (raise SEMCODE_MI355X_MAX_TOKENS up to "
-                            "the model's context -- 1024 / 2048 need a position-free (ALiBi) encoder -- or shrink the chunker's max_lines)",
+                            "the model's context -- 1024 / 2048 need an encoder without a position table (ALiBi or rotary) or a table that long -- or shrink the chunker's max_lines)",
                             self.truncated_texts, self.total_texts, self.max_tokens)
 
     # ---- LangChain Embeddings surface (lists of Python floats)
@@ -197,19 +237,25 @@ class MI355XEmbeddings:
         return self.embed_documents_array(texts).tolist()
 
     def embed_query(self, text: str) -> List[float]:
-        return self.embed_documents_array([text])[0].tolist()
+        return self.embed_documents_array([text], kind="query")[0].tolist()
 
     # ---- array fast paths
-    def embed_documents_array(self, texts: Sequence[str]) -> np.ndarray:
+    def embed_documents_array(self, texts: Sequence[str], kind: str = "document") -> np.ndarray:
         """texts -> [n, hidden] f32; tokenise on the host, forward on the device in batches."""
         out = np.empty((len(texts), self.dimension), dtype=np.float32)
         for start in range(0, len(texts), self.batch_size):
-            ids, lens = self.tokenize(texts[start:start + self.batch_size])
+            ids, lens = self.tokenize(texts[start:start + self.batch_size], kind=kind)
             out[start:start + len(lens)] = self._encoder.embed_ids(ids, lens)
         return out
 
-    def tokenize(self, texts: Sequence[str]) -> "tuple[np.ndarray, np.ndarray]":
-        """texts -> (ids [n, S] int32 padded to the smallest sequence bucket that fits, lens [n])."""
+    def tokenize(self, texts: Sequence[str], kind: str = "document") -> "tuple[np.ndarray, np.ndarray]":
+        """texts -> (ids [n, S] int32 padded to the smallest sequence bucket that fits, lens [n]).  kind "document" | "query" picks
+        the task prefix put in front of every text (both empty by default: the ids are then those of the bare texts)."""
+        if kind not in ("document", "query"):
+            raise ValueError(f"tokenize: kind must be 'document' or 'query', not {kind!r}")
+        prefix = self.query_prefix if kind == "query" else self.document_prefix
+        if prefix:
+            texts = [prefix + t for t in texts]
         if self._fast_tokenizer is None:
             toks = [self.tokenizer.encode(t, self.max_tokens) for t in texts]
             ids, lens = pack(toks, getattr(self.tokenizer, "pad_id", 0), self.max_tokens)
