@@ -222,6 +222,48 @@ sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F
 /* qkv [B*S, 3*heads*64] rows = [Q | K | V]; lens [B]; out [B*S, heads*64] = softmax(QK^T/8 + mask) V. */
 sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out);
 
+/* Single-kernel diagnostics of the LayerNorm-folded batch pipeline and of the stand-alone encoder kernels (tests/test_fold_kernels_gpu.py).
+ * Same pattern as above: host f32 in, activations rounded to bf16 on the device, ONE launch through the product's own launcher, the
+ * result widened to f32; synchronous; outputs are pre-filled with NaN so that an element the kernel leaves unwritten shows.
+ * "gemm_nt" of sc_diag_set_option: C stores of the 256-tile GEMMs (-1 = default: non-temporal from 64 MiB of output, or the SC_GEMM_NT
+ * environment variable; 0 = never; 1 = always) -- lets a small shape take the non-temporal store path; results are identical.
+ * sc_diag_fold_ln: W [N,K], gamma / beta [K], bias [N] or NULL -> Wf [N,K] = bf16(W diag(gamma)) widened, c1 [N] = row sums of Wf,
+ *   c2 [N] = bias + W beta (K a multiple of 4).
+ * sc_diag_gemm_lna: epi 3 (EPI_LNA_BIAS), 4 (EPI_LNA_GELU) or 6 (EPI_LNA_BIAS_ROPE): C [M,N] = LN(A) W^T + b computed as
+ *   rs (A Wf^T - mu c1) + c2 from the raw rows A [M,K], Wf / c1 / c2 as sc_diag_fold_ln returns them and the caller's partial row
+ *   statistics stats_in [K/256][M][2] = (sum, sum of squares) per 256-column slot; fin [M][2] = the (mu, rs) the kernel publishes.
+ *   flags bit 0: C is written (and returned) in 64-column blocks [N/64][M][64].  Rotary form: row r has position r & (rope_S - 1),
+ *   rope_S a power of two, the first rope_ncols columns (multiple of 64) are rotated, theta <= 0 = 10000.  M, N, K multiples of 256.
+ * sc_diag_gemm_resln: EPI_RESLN_STATS: C [M,N] = A W^T + bias + (R - mu) rs gam with (mu, rs) = fin [M][2] of the raw residual R [M,N]
+ *   (bias already holds + beta); stats_out [N/256][M][2] = (sum, sum of squares) of the bf16 C per 256-column tile.  flags bit 0: A is
+ *   given in 64-column blocks [K/64][M][64].
+ * sc_diag_attention_ex: sc_diag_attention with the product's layout and bias: blocked_rows > 0 = qkv is [3 heads][blocked_rows][64]
+ *   (blocked_rows >= B*S: the rows of the projection that wrote it), 0 = row-major; slopes = NULL or [heads] ALiBi slopes.
+ * sc_diag_layernorm: x [tokens,H] -> LayerNorm rows (H a multiple of 8, <= 2048).  sc_diag_geglu: h [rows,2F] (gate | up) -> gelu(gate) up.
+ * sc_diag_mean_pool: x [B*S,H] -> out [B,H] f32, masked mean over the first lens[b] rows (lens clamped to 1..S); normalize 0 = the
+ *   sliced kernel, 1 = the one-workgroup kernel with L2 normalisation.  sc_diag_mean_pool_ln: the same of LayerNorm(y) from raw rows
+ *   y [tokens_pad,H] and their partial statistics stats [slots][tokens_pad][2].
+ * sc_diag_embed: ln 0 = embed_raw_kernel: rows [tokens_pad,H] = bf16((word + position) + type), stats [slots][tokens_pad][2] (slot 0 the
+ *   sums of the rounded row, other slots and padding rows zero); ln 1 = embed_ln_kernel: rows [tokens,H] = LayerNorm of that sum.
+ *   ids [tokens] are clamped to [0, vocab), position = token % S clamped to max_pos - 1; pemb NULL = no position table. */
+sc_status sc_diag_fold_ln(sc_runtime* rt, const float* W, const float* gamma, const float* beta, const float* bias, int32_t N, int32_t K,
+                          float* Wf, float* c1, float* c2);
+sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* Wf, const float* c1, const float* c2,
+                           const float* stats_in, float eps, int32_t M, int32_t N, int32_t K, int32_t rope_S, float rope_theta,
+                           int32_t rope_ncols, float* C, float* fin);
+sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
+                             const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out);
+sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                               const float* slopes, float* out);
+sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
+sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
+sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,
+                               const float* beta, float eps, const int32_t* lens, int32_t B, int32_t S, int32_t H, float* out);
+sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out);
+sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* ids, int32_t tokens, int32_t S, int32_t H, int32_t vocab, int32_t max_pos,
+                        const float* wemb, const float* pemb, const float* temb, const float* gamma, const float* beta, float eps,
+                        int32_t tokens_pad, int32_t slots, float* rows, float* stats);
+
 /* -------------------------------------------------------------- vector index ---- */
 
 /* Replaces Collection(...)+create_index(IVF_FLAT, metric, nlist) (milvus_store.py:59-84).

@@ -81,6 +81,18 @@ SIGNATURES = {
     "sc_diag_attention": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     "sc_diag_swiglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_fold_ln": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "sc_diag_gemm_lna": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_gemm_resln": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_geglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_embed": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 +
+                                 [C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_index_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
     "sc_index_destroy": (C.c_int32, [C.c_void_p]),
     "sc_index_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -703,6 +715,143 @@ def diag_swiglu(rt: Runtime, h) -> np.ndarray:
     out = np.empty((rows, F), np.float32)
     _check(lib().sc_diag_swiglu(rt.handle, h.ctypes.data_as(C.c_void_p), rows, F, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+# ---- single-kernel diagnostics of the LayerNorm-folded pipeline and the stand-alone encoder kernels (tests/test_fold_kernels_gpu.py)
+EPI_LNA_BIAS, EPI_LNA_GELU, EPI_RESLN_STATS, EPI_LNA_BIAS_ROPE = 3, 4, 5, 6
+
+
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def block64(a: np.ndarray) -> np.ndarray:
+    """[M, N] row-major -> [N / 64, M, 64]: the 64-column blocks the QKV and FFN1 epilogues write (SC_LDC_BLOCKED64)."""
+    M, N = a.shape
+    return np.ascontiguousarray(a.reshape(M, N // 64, 64).transpose(1, 0, 2))
+
+
+def unblock64(a: np.ndarray, M: int, N: int) -> np.ndarray:
+    """Inverse of block64."""
+    return np.ascontiguousarray(np.asarray(a).reshape(N // 64, M, 64).transpose(1, 0, 2).reshape(M, N))
+
+
+def diag_fold_ln(rt: Runtime, W, gamma, beta, bias=None):
+    """fold_ln_weights_kernel: (Wf [N,K] bf16 values, c1 [N], c2 [N])."""
+    W, gamma, beta = _f32(W), _f32(gamma), _f32(beta)
+    bias = None if bias is None else _f32(bias)
+    N, K = W.shape
+    Wf, c1, c2 = np.empty((N, K), np.float32), np.empty(N, np.float32), np.empty(N, np.float32)
+    _check(lib().sc_diag_fold_ln(rt.handle, _ptr(W), _ptr(gamma), _ptr(beta), _ptr(bias), N, K, _ptr(Wf), _ptr(c1), _ptr(c2)))
+    return Wf, c1, c2
+
+
+def diag_gemm_lna(rt: Runtime, epi: int, A, Wf, c1, c2, stats_in, eps: float, blocked: bool = False, rope_S: int = 0, rope_theta: float = 0.0,
+                  rope_ncols: int = 0):
+    """One EPI_LNA_* GEMM launch: (C [M,N], fin [M,2]).  stats_in [K/256, M, 2]; blocked: C written in 64-column blocks (un-blocked here)."""
+    A, Wf, c1, c2, stats_in = _f32(A), _f32(Wf), _f32(c1), _f32(c2), _f32(stats_in)
+    M, K = A.shape
+    N = Wf.shape[0]
+    if stats_in.shape != (K // 256, M, 2) or Wf.shape != (N, K) or c1.shape != (N,) or c2.shape != (N,):
+        raise ValueError("diag_gemm_lna: shapes")
+    Cc, fin = np.empty((M, N), np.float32), np.empty((M, 2), np.float32)
+    _check(lib().sc_diag_gemm_lna(rt.handle, epi, 1 if blocked else 0, _ptr(A), _ptr(Wf), _ptr(c1), _ptr(c2), _ptr(stats_in), float(eps), M, N, K,
+                                  int(rope_S), float(rope_theta), int(rope_ncols), _ptr(Cc), _ptr(fin)))
+    return (unblock64(Cc, M, N) if blocked else Cc), fin
+
+
+def diag_gemm_resln(rt: Runtime, A, W, bias, gam, R, fin, eps: float, a_blocked: bool = False):
+    """One EPI_RESLN_STATS GEMM launch: (C [M,N], stats_out [N/256, M, 2]).  a_blocked: A handed over in 64-column blocks."""
+    A, W, bias, gam, R, fin = _f32(A), _f32(W), _f32(bias), _f32(gam), _f32(R), _f32(fin)
+    M, K = A.shape
+    N = W.shape[0]
+    if W.shape != (N, K) or R.shape != (M, N) or fin.shape != (M, 2) or bias.shape != (N,) or gam.shape != (N,):
+        raise ValueError("diag_gemm_resln: shapes")
+    Ad = block64(A) if a_blocked else A
+    Cc, st = np.empty((M, N), np.float32), np.empty((N // 256, M, 2), np.float32)
+    _check(lib().sc_diag_gemm_resln(rt.handle, 1 if a_blocked else 0, _ptr(Ad), _ptr(W), _ptr(bias), _ptr(gam), _ptr(R), _ptr(fin), float(eps), M, N, K,
+                                    _ptr(Cc), _ptr(st)))
+    return Cc, st
+
+
+def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocked_rows: int = 0, slopes=None) -> np.ndarray:
+    """sc_launch_attention as the pipelines call it: blocked_rows > 0 lays qkv [B*S, 3H] out as [3 heads][blocked_rows][64] (rows beyond
+    B*S zero); slopes [heads] = ALiBi."""
+    qkv = _f32(qkv)
+    lens = np.ascontiguousarray(lens, np.int32)
+    H = heads * 64
+    if blocked_rows:
+        pad = np.zeros((blocked_rows, 3 * H), np.float32)
+        pad[: B * S] = qkv
+        qkv = block64(pad)
+    sl = None if slopes is None else _f32(slopes)
+    out = np.empty((B * S, H), np.float32)
+    _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    return out
+
+
+def diag_layernorm(rt: Runtime, x, gamma, beta, eps: float) -> np.ndarray:
+    x, gamma, beta = _f32(x), _f32(gamma), _f32(beta)
+    out = np.empty_like(x)
+    _check(lib().sc_diag_layernorm(rt.handle, _ptr(x), x.shape[0], x.shape[1], _ptr(gamma), _ptr(beta), float(eps), _ptr(out)))
+    return out
+
+
+def diag_mean_pool(rt: Runtime, x, lens, S: int, normalize: bool) -> np.ndarray:
+    """x [B*S, H] -> [B, H] f32 (normalize False: the sliced kernel; True: the one-workgroup kernel + L2 normalisation)."""
+    x = _f32(x)
+    lens = np.ascontiguousarray(lens, np.int32)
+    B, H = lens.size, x.shape[1]
+    out = np.empty((B, H), np.float32)
+    _check(lib().sc_diag_mean_pool(rt.handle, _ptr(x), _ptr(lens), B, int(S), H, 1 if normalize else 0, _ptr(out)))
+    return out
+
+
+def diag_mean_pool_ln(rt: Runtime, y, stats, gamma, beta, eps: float, lens, S: int) -> np.ndarray:
+    """y [tokens_pad, H] raw rows, stats [slots, tokens_pad, 2] -> [B, H] f32 = masked mean of LayerNorm(y)."""
+    y, stats, gamma, beta = _f32(y), _f32(stats), _f32(gamma), _f32(beta)
+    lens = np.ascontiguousarray(lens, np.int32)
+    B, (tp, H) = lens.size, y.shape
+    if stats.shape[1:] != (tp, 2):
+        raise ValueError("diag_mean_pool_ln: stats must be [slots, tokens_pad, 2]")
+    out = np.empty((B, H), np.float32)
+    _check(lib().sc_diag_mean_pool_ln(rt.handle, _ptr(y), _ptr(stats), stats.shape[0], tp, _ptr(gamma), _ptr(beta), float(eps), _ptr(lens), B, int(S), H,
+                                      _ptr(out)))
+    return out
+
+
+def diag_geglu(rt: Runtime, h) -> np.ndarray:
+    """The GEGLU kernel on h [rows, 2F] (gate | up): gelu(gate) * up, bf16-rounded, [rows, F]."""
+    h = _f32(h)
+    rows, F = h.shape[0], h.shape[1] // 2
+    out = np.empty((rows, F), np.float32)
+    _check(lib().sc_diag_geglu(rt.handle, _ptr(h), rows, F, _ptr(out)))
+    return out
+
+
+def diag_embed(rt: Runtime, ids, wemb, pemb, temb, max_pos: int, ln=None, tokens_pad: int = 0, slots: int = 1):
+    """The embedding kernels on ids [B, S].  ln None: embed_raw_kernel -> (rows [tokens_pad, H], stats [slots, tokens_pad, 2]);
+    ln = (gamma, beta, eps): embed_ln_kernel -> rows [B*S, H].  pemb None: no position table."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    S, tokens = ids.shape[1], ids.size
+    wemb, temb = _f32(wemb), _f32(temb)
+    pemb = None if pemb is None else _f32(pemb)
+    vocab, H = wemb.shape
+    if ln is None:
+        tp = max(int(tokens_pad), tokens)
+        rows, stats = np.empty((tp, H), np.float32), np.empty((slots, tp, 2), np.float32)
+        _check(lib().sc_diag_embed(rt.handle, 0, _ptr(ids), tokens, S, H, vocab, int(max_pos), _ptr(wemb), _ptr(pemb), _ptr(temb), None, None, 0.0, tp,
+                                   int(slots), _ptr(rows), _ptr(stats)))
+        return rows, stats
+    gamma, beta = _f32(ln[0]), _f32(ln[1])
+    rows = np.empty((tokens, H), np.float32)
+    _check(lib().sc_diag_embed(rt.handle, 1, _ptr(ids), tokens, S, H, vocab, int(max_pos), _ptr(wemb), _ptr(pemb), _ptr(temb), _ptr(gamma), _ptr(beta),
+                               float(ln[2]), 0, 0, _ptr(rows), None))
+    return rows
 
 
 def topk_merge_host(metric: str, dist: np.ndarray, rows: np.ndarray) -> tuple[np.ndarray, np.ndarray]:

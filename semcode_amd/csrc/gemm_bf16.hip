@@ -712,6 +712,14 @@ static int gemm_pp() {
     static const char* env = getenv("SC_GEMM_PP");
     return g_gemm_pp >= 0 ? g_gemm_pp : env ? atoi(env) : SC_GEMM_PP_DEFAULT;
 }
+// non-temporal C stores of the 256-tile kernels ("gemm_nt" of sc_diag_set_option): -1 = outputs of 64 MiB and more (or SC_GEMM_NT),
+// 0 = never, 1 = always -- so that a small test shape can take the store path of the batch step
+static int g_gemm_nt = -1;
+void sc_gemm_set_nt(int v) { g_gemm_nt = v < 0 ? -1 : (v ? 1 : 0); }
+static int gemm_nt(int M, int N) {
+    static const char* env_nt = getenv("SC_GEMM_NT");
+    return g_gemm_nt >= 0 ? g_gemm_nt : env_nt ? atoi(env_nt) : ((size_t)M * (size_t)N * 2 >= ((size_t)64 << 20));
+}
 template <int EPI, int DBG, int PP>
 static void launch256_pp(const GemmArgs& a, dim3 grid, dim3 block, hipStream_t s) {
     static ScDeviceOnce once;  // one per instantiation (and device)
@@ -750,7 +758,7 @@ void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int 
     static const char* env_order = getenv("SC_GEMM_ORDER");
     a.order = env_order ? atoi(env_order) : ((size_t)N * (size_t)K * 2 <= ((size_t)8 << 20) ? 0 : 16);
     a.trace = nullptr;
-    { static const char* env_nt = getenv("SC_GEMM_NT"); a.nt = env_nt ? atoi(env_nt) : ((size_t)M * (size_t)N * 2 >= ((size_t)64 << 20)); }
+    a.nt = gemm_nt(M, N);
     a.tiles_n = N / T_BN;
     a.ntiles = (M / T_BM) * a.tiles_n;
     a.splitk = 1;
@@ -775,7 +783,7 @@ void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw
     static const char* env_order = getenv("SC_GEMM_ORDER");  // A/B experiments
     a.order = env_order ? atoi(env_order) : g_gemm_order >= 0 ? g_gemm_order : ((size_t)N * (size_t)K * 2 <= ((size_t)8 << 20) ? 0 : 16);
     a.trace = g_gemm_trace;
-    { static const char* env_nt = getenv("SC_GEMM_NT"); a.nt = env_nt ? atoi(env_nt) : ((size_t)M * (size_t)N * 2 >= ((size_t)64 << 20)); }
+    a.nt = gemm_nt(M, N);
     if ((M % T_BM) == 0 && (N % T_BN) == 0 && !g_force_tile128) {
         a.tiles_n = N / T_BN;
         a.ntiles = (M / T_BM) * a.tiles_n;

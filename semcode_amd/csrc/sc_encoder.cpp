@@ -53,6 +53,7 @@ void sc_launch_bf16_to_f32(const void* in, float* out, int64_t n, hipStream_t s)
 void sc_gemm_set_debug(int v);
 void sc_gemm_set_order(int v);
 void sc_gemm_set_pp(int v);
+void sc_gemm_set_nt(int v);
 void sc_gemm_set_trace(unsigned long long* dev);
 void sc_gemm_force_tile128(bool on);
 
@@ -728,6 +729,7 @@ extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
     if (!strcmp(name, "coarse_workgroups")) sc_scan_set_coarse_workgroups(value);
     else if (!strcmp(name, "coarse_persistent")) sc_scan_set_coarse_persistent(value);
     else if (!strcmp(name, "gemm_pp")) sc_gemm_set_pp(value);
+    else if (!strcmp(name, "gemm_nt")) sc_gemm_set_nt(value);
     else if (!strcmp(name, "ivf_refresh_nomem")) sc_ivf_set_refresh_nomem(value);
     else if (!strcmp(name, "ivf_refine_cap")) sc_ivf_set_refine_cap(value);
     else if (!strcmp(name, "ivf_coarse_nomem")) sc_ivf_set_coarse_nomem(value);
@@ -911,4 +913,247 @@ extern "C" sc_status sc_diag_gemm_bench(sc_runtime* rt, int32_t epi, int32_t M, 
     if (he != hipSuccess) return sc_fail(SC_ERR_HIP, "diag gemm bench failed: %s", hipGetErrorString(he));
     *ms_per_launch = ms / iters;
     return SC_OK;
+}
+
+// ------------------------------------------------------------------ diagnostics: the LayerNorm-folded pipeline and the stand-alone kernels, one launch each
+// Same pattern as above: host f32 in (activations rounded to bf16 by f32_to_bf16_kernel), THE PRODUCT LAUNCHER, result widened to
+// f32 and copied back, synchronous.  Output buffers are pre-filled with 0xFF bytes (NaN as bf16 and as f32), so that an element a
+// kernel does not write shows in the result.
+namespace {
+sc_status upload_f32(const void* host, size_t bytes, DevBuf& out, hipStream_t s) {
+    if (out.alloc(bytes) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    if (host && bytes) SC_HIP(hipMemcpyAsync(out.p, host, bytes, hipMemcpyHostToDevice, s));
+    return SC_OK;
+}
+sc_status alloc_nan(DevBuf& out, size_t bytes, hipStream_t s) {
+    if (out.alloc(bytes) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    SC_HIP(hipMemsetAsync(out.p, 0xFF, bytes ? bytes : 16, s));
+    return SC_OK;
+}
+// device bf16 [n] -> host f32 [n]
+sc_status download_bf16(const void* dev, int64_t n, float* host, hipStream_t s) {
+    DevBuf fo;
+    if (fo.alloc((size_t)n * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    sc_launch_bf16_to_f32(dev, (float*)fo.p, n, s);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(host, fo.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+sc_status download_f32(const void* dev, size_t bytes, void* host, hipStream_t s) {
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+#define SC_TRY(expr)              \
+    do {                          \
+        sc_status st_ = (expr);   \
+        if (st_) return st_;      \
+    } while (0)
+}  // namespace
+
+// fold_ln_weights_kernel: W [N,K], gamma / beta [K], bias [N] or NULL (all f32) -> Wf [N,K] (the bf16 W', widened), c1 [N], c2 [N]
+extern "C" sc_status sc_diag_fold_ln(sc_runtime* rt, const float* W, const float* gamma, const float* beta, const float* bias, int32_t N, int32_t K,
+                                     float* Wf, float* c1, float* c2) {
+    if (!rt || !W || !gamma || !beta || !Wf || !c1 || !c2) return sc_fail(SC_ERR_INVALID, "sc_diag_fold_ln: NULL argument");
+    if (N < 1 || K < 4 || (K % 4)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_fold_ln: need N >= 1 and K a multiple of 4");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf dw, dg, db, dbias, dwf, dc1, dc2;
+    SC_TRY(upload_f32(W, (size_t)N * K * 4, dw, s));
+    SC_TRY(upload_f32(gamma, (size_t)K * 4, dg, s));
+    SC_TRY(upload_f32(beta, (size_t)K * 4, db, s));
+    if (bias) SC_TRY(upload_f32(bias, (size_t)N * 4, dbias, s));
+    SC_TRY(alloc_nan(dwf, (size_t)N * K * 2, s));
+    SC_TRY(alloc_nan(dc1, (size_t)N * 4, s));
+    SC_TRY(alloc_nan(dc2, (size_t)N * 4, s));
+    sc_launch_fold_ln_weights((const float*)dw.p, (const float*)dg.p, (const float*)db.p, bias ? (const float*)dbias.p : nullptr, N, K, dwf.p, (float*)dc1.p,
+                              (float*)dc2.p, s);
+    SC_TRY(download_f32(dc1.p, (size_t)N * 4, c1, s));
+    SC_TRY(download_f32(dc2.p, (size_t)N * 4, c2, s));
+    return download_bf16(dwf.p, (int64_t)N * K, Wf, s);
+}
+
+// EPI_LNA_BIAS / EPI_LNA_GELU / EPI_LNA_BIAS_ROPE through sc_launch_gemm_bf16_ln.  A [M,K] raw rows, Wf [N,K] / c1 / c2 [N] as
+// sc_diag_fold_ln returned them, stats_in [K/256][M][2] the caller's partial (sum, sum of squares).  flags bit 0: C in 64-column blocks
+// ([N/64][M][64], returned that way).  Rotary form: positions = row & (rope_S - 1), tables as sc_encoder_create builds them.
+extern "C" sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* Wf, const float* c1, const float* c2,
+                                      const float* stats_in, float eps, int32_t M, int32_t N, int32_t K, int32_t rope_S, float rope_theta,
+                                      int32_t rope_ncols, float* C, float* fin) {
+    if (!rt || !A || !Wf || !c1 || !c2 || !stats_in || !C || !fin) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: NULL argument");
+    if (epi != EPI_LNA_BIAS && epi != EPI_LNA_GELU && epi != EPI_LNA_BIAS_ROPE) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: epilogue must be 3, 4 or 6");
+    if ((flags & ~1) || !(eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: bad flags / eps");
+    if (!sc_gemm_ln_supported(M, N, K) || K > 4096) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_lna: need M%%256==0, N%%256==0, K%%256==0, K<=4096");
+    const bool rope = epi == EPI_LNA_BIAS_ROPE;
+    if (rope && (rope_S < 1 || rope_S > 65536 || (rope_S & (rope_S - 1)) || rope_ncols < 0 || rope_ncols > N || (rope_ncols % 64)))
+        return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: rope_S must be a power of two, rope_ncols a multiple of 64 within N");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fa, da, fw, dw, dc1, dc2, dst, dfin, dc, dt;
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(Wf, (int64_t)N * K, fw, dw, s));
+    SC_TRY(upload_f32(c1, (size_t)N * 4, dc1, s));
+    SC_TRY(upload_f32(c2, (size_t)N * 4, dc2, s));
+    SC_TRY(upload_f32(stats_in, (size_t)(K / 256) * M * 8, dst, s));
+    SC_TRY(alloc_nan(dfin, (size_t)M * 8, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
+    const float *cos_t = nullptr, *sin_t = nullptr;
+    std::vector<float> tab;
+    if (rope) {  // as sc_encoder_create builds it
+        const double theta = rope_theta > 0.f ? (double)rope_theta : 10000.0;
+        const size_t n = (size_t)rope_S * 32;
+        tab.resize(2 * n);
+        for (int i = 0; i < 32; ++i) {
+            const double f = std::pow(theta, -2.0 * i / 64.0);
+            for (int p = 0; p < rope_S; ++p) {
+                tab[(size_t)p * 32 + i] = (float)std::cos((double)p * f);
+                tab[n + (size_t)p * 32 + i] = (float)std::sin((double)p * f);
+            }
+        }
+        SC_TRY(upload_f32(tab.data(), tab.size() * 4, dt, s));
+        cos_t = (const float*)dt.p;
+        sin_t = cos_t + n;
+    }
+    sc_launch_gemm_bf16_ln(epi, da.p, K, dw.p, K, (const float*)dc2.p, nullptr, 0, dc.p, (flags & 1) ? SC_LDC_BLOCKED64 : N, M, N, K, s, (const float*)dc1.p,
+                           (const float*)dst.p, (float*)dfin.p, nullptr, nullptr, eps, cos_t, sin_t, rope ? rope_S : 0, rope ? rope_ncols : 0);
+    SC_TRY(download_f32(dfin.p, (size_t)M * 8, fin, s));  // synchronises: tab may go
+    return download_bf16(dc.p, (int64_t)M * N, C, s);
+}
+
+// EPI_RESLN_STATS through sc_launch_gemm_bf16_ln.  A [M,K] (flags bit 0: given as [K/64][M][64]), W [N,K], bias [N] (= b + beta), gam [N],
+// R [M,N] the raw residual, fin [M][2] its (mu, rs) -> C [M,N], stats_out [N/256][M][2].
+extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
+                                        const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out) {
+    if (!rt || !A || !W || !bias || !gam || !R || !fin || !C || !stats_out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_resln: NULL argument");
+    if ((flags & ~1) || !(eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_resln: bad flags / eps");
+    if (!sc_gemm_ln_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_resln: need M%%256==0, N%%256==0, K%%256==0");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fa, da, fw, dw, fr, dr, db, dg, dfin, dc, dso;
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(W, (int64_t)N * K, fw, dw, s));
+    SC_TRY(upload_bf16(R, (int64_t)M * N, fr, dr, s));
+    SC_TRY(upload_f32(bias, (size_t)N * 4, db, s));
+    SC_TRY(upload_f32(gam, (size_t)N * 4, dg, s));
+    SC_TRY(upload_f32(fin, (size_t)M * 8, dfin, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
+    SC_TRY(alloc_nan(dso, (size_t)(N / 256) * M * 8, s));
+    sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, da.p, (flags & 1) ? SC_LDC_BLOCKED64 : K, dw.p, K, (const float*)db.p, dr.p, N, dc.p, N, M, N, K, s, nullptr, nullptr,
+                           (float*)dfin.p, (const float*)dg.p, (float*)dso.p, eps);
+    SC_TRY(download_f32(dso.p, (size_t)(N / 256) * M * 8, stats_out, s));
+    return download_bf16(dc.p, (int64_t)M * N, C, s);
+}
+
+// sc_launch_attention as the pipelines call it.  blocked_rows == 0: qkv [B*S][3H] row-major; > 0: qkv [3 heads][blocked_rows][64], the layout
+// the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.
+extern "C" sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                                          const float* slopes, float* out) {
+    if (!rt || !qkv || !lens || !out || B < 1 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_ex: bad argument");
+    const int H = heads * 64;
+    if (!sc_attention_supported(S, H, heads)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_attention_ex: S must be one of 32,64,128,256,512,1024,2048");
+    const int64_t tokens = (int64_t)B * S;
+    if (blocked_rows && blocked_rows < tokens) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_ex: blocked_rows < B*S");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fq, dq, dl, dsl, dc;
+    SC_TRY(upload_bf16(qkv, (blocked_rows ? (int64_t)blocked_rows : tokens) * 3 * H, fq, dq, s));
+    SC_TRY(upload_f32(lens, (size_t)B * 4, dl, s));
+    if (slopes) SC_TRY(upload_f32(slopes, (size_t)heads * 4, dsl, s));
+    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
+    sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows);
+    return download_bf16(dc.p, tokens * H, out, s);
+}
+
+// layernorm_kernel<3|4|8>: x [tokens,H] -> out [tokens,H]
+extern "C" sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out) {
+    if (!rt || !x || !gamma || !beta || !out || tokens < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_layernorm: bad argument");
+    if (H < 8 || (H % 8) || H > 2048 || !(eps > 0.f)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_layernorm: H must be a multiple of 8, <= 2048");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fx, dx, dg, db, dc;
+    SC_TRY(upload_bf16(x, (int64_t)tokens * H, fx, dx, s));
+    SC_TRY(upload_f32(gamma, (size_t)H * 4, dg, s));
+    SC_TRY(upload_f32(beta, (size_t)H * 4, db, s));
+    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
+    sc_launch_layernorm(dx.p, tokens, H, (const float*)dg.p, (const float*)db.p, eps, dc.p, s);
+    return download_bf16(dc.p, (int64_t)tokens * H, out, s);
+}
+
+// sc_launch_mean_pool: normalize 0 = mean_pool_sliced_kernel, 1 = mean_pool_kernel with the L2 normalisation.  x [B*S,H] -> out [B,H] f32
+extern "C" sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out) {
+    if (!rt || !x || !lens || !out || B < 1 || S < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool: bad argument");
+    if (H < 8 || (H % 8)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_mean_pool: H must be a multiple of 8");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fx, dx, dl, dout;
+    SC_TRY(upload_bf16(x, (int64_t)B * S * H, fx, dx, s));
+    SC_TRY(upload_f32(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * H * 4, s));
+    sc_launch_mean_pool(dx.p, (const int32_t*)dl.p, B, S, H, normalize ? 1 : 0, (float*)dout.p, s);
+    return download_f32(dout.p, (size_t)B * H * 4, out, s);
+}
+
+// mean_pool_ln_kernel: y [tokens_pad,H] raw rows (the first B*S are read), stats [slots][tokens_pad][2] -> out [B,H] f32
+extern "C" sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,
+                                          const float* beta, float eps, const int32_t* lens, int32_t B, int32_t S, int32_t H, float* out) {
+    if (!rt || !y || !stats || !gamma || !beta || !lens || !out || B < 1 || S < 1 || slots < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool_ln: bad argument");
+    if (H < 8 || (H % 8) || !(eps > 0.f)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_mean_pool_ln: H must be a multiple of 8");
+    if ((int64_t)tokens_pad < (int64_t)B * S) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool_ln: tokens_pad < B*S");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fy, dy, dst, dg, db, dl, dout;
+    SC_TRY(upload_bf16(y, (int64_t)tokens_pad * H, fy, dy, s));
+    SC_TRY(upload_f32(stats, (size_t)slots * tokens_pad * 8, dst, s));
+    SC_TRY(upload_f32(gamma, (size_t)H * 4, dg, s));
+    SC_TRY(upload_f32(beta, (size_t)H * 4, db, s));
+    SC_TRY(upload_f32(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * H * 4, s));
+    sc_launch_mean_pool_ln(dy.p, (const float*)dst.p, slots, tokens_pad, (const float*)dg.p, (const float*)db.p, eps, (const int32_t*)dl.p, B, S, H, (float*)dout.p, s);
+    return download_f32(dout.p, (size_t)B * H * 4, out, s);
+}
+
+// glu_kernel<ActGelu>: h [rows, 2F] (gate | up) -> out [rows, F] = gelu(gate) * up
+extern "C" sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) {
+    if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "sc_diag_geglu: bad argument (F must be a multiple of 8)");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf fh, dh, dc;
+    SC_TRY(upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s));
+    SC_TRY(alloc_nan(dc, (size_t)rows * F * 2, s));
+    sc_launch_geglu(dh.p, rows, F, dc.p, s);
+    return download_bf16(dc.p, (int64_t)rows * F, out, s);
+}
+
+// The embedding kernels.  ln == 0: embed_raw_kernel -> rows [tokens_pad,H] + stats [slots][tokens_pad][2]; ln != 0: embed_ln_kernel ->
+// rows [tokens,H] (tokens_pad, slots, stats unused).  ids [tokens] (tokens = B*S, position = token % S), wemb [vocab,H], pemb [max_pos,H] or
+// NULL, temb [>= 1, H] (row 0 is used), all f32.
+extern "C" sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* ids, int32_t tokens, int32_t S, int32_t H, int32_t vocab, int32_t max_pos,
+                                   const float* wemb, const float* pemb, const float* temb, const float* gamma, const float* beta, float eps,
+                                   int32_t tokens_pad, int32_t slots, float* rows, float* stats) {
+    if (!rt || !ids || !wemb || !temb || !rows || tokens < 1 || S < 1 || vocab < 1 || max_pos < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: bad argument");
+    if (H < 4 || (H % 4) || H > 2048) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_embed: H must be a multiple of 4, <= 2048");
+    if (ln && (!gamma || !beta || !(eps > 0.f))) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: the LayerNorm form needs gamma, beta, eps");
+    if (!ln && (!stats || tokens_pad < tokens || slots < 1 || slots > 64)) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: the raw form needs stats, tokens_pad >= tokens, 1 <= slots <= 64");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    DevBuf di, dw, dp, dt, dg, db, dout, dst;
+    SC_TRY(upload_f32(ids, (size_t)tokens * 4, di, s));
+    SC_TRY(upload_f32(wemb, (size_t)vocab * H * 4, dw, s));
+    if (pemb) SC_TRY(upload_f32(pemb, (size_t)max_pos * H * 4, dp, s));
+    SC_TRY(upload_f32(temb, (size_t)H * 4, dt, s));
+    const int64_t nrows = ln ? tokens : tokens_pad;
+    SC_TRY(alloc_nan(dout, (size_t)nrows * H * 2, s));
+    if (ln) {
+        SC_TRY(upload_f32(gamma, (size_t)H * 4, dg, s));
+        SC_TRY(upload_f32(beta, (size_t)H * 4, db, s));
+        sc_launch_embed_ln((const int32_t*)di.p, tokens, S, H, vocab, max_pos, (const float*)dw.p, pemb ? (const float*)dp.p : nullptr, (const float*)dt.p,
+                           (const float*)dg.p, (const float*)db.p, eps, dout.p, s);
+    } else {
+        SC_TRY(alloc_nan(dst, (size_t)slots * tokens_pad * 8, s));
+        sc_launch_embed_raw((const int32_t*)di.p, tokens, tokens_pad, S, H, vocab, max_pos, (const float*)dw.p, pemb ? (const float*)dp.p : nullptr,
+                            (const float*)dt.p, dout.p, (float*)dst.p, slots, s);
+        SC_TRY(download_f32(dst.p, (size_t)slots * tokens_pad * 8, stats, s));
+    }
+    return download_bf16(dout.p, nrows * H, rows, s);
 }
