@@ -598,7 +598,7 @@ __global__ __launch_bounds__(512) void gemm256_bf16_kernel(GemmArgs a) {
     }
 }
 
-// ---- diagnostic: the int8 variant of the 256 tile main loop (scan_batched.hip's coarse stage) on its own, raw i32 accumulators out.
+// ---- diagnostic: the int8 variant of the 256 tile main loop (scan_coarse.hip's coarse stage) on its own, raw i32 accumulators out.
 // The A/B lane maps of v_mfma_i32_16x16x64_i8 are not documented in the guide ("check the map with exact integer data"): this
 // kernel is that check -- C[m][n] = sum_k A[m][k] * W[n][k] must hold exactly.
 __global__ __launch_bounds__(512) void gemm256_i8_diag_kernel(const int8_t* __restrict__ A, const int8_t* __restrict__ W, int32_t* __restrict__ C, int M, int N,

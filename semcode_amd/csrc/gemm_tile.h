@@ -1,5 +1,5 @@
 // gemm_tile.h -- the 128x128x64 bf16 MFMA tile machinery shared by gemm_bf16.hip (encoder GEMMs) and
-// scan_batched.hip (coarse distance GEMM).  See gemm_bf16.hip for the design notes.
+// scan_coarse.hip (coarse distance GEMM).  See gemm_bf16.hip for the design notes; bf16_t and its conversions: sc_common.h.
 #pragma once
 #include <type_traits>
 
@@ -12,8 +12,6 @@
 
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef const __attribute__((address_space(1))) void* gbl_vptr;
-typedef unsigned short bf16_t;
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
 typedef __bf16 hwbf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -56,15 +54,6 @@ static __device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
     q = __builtin_elementwise_fma(q, ah, (f32x2){9.69476332e-06f, 9.69476332e-06f});
     const f32x2 e = {__builtin_amdgcn_exp2f(q[0]), __builtin_amdgcn_exp2f(q[1])};
     return __builtin_elementwise_fma(-ah, e, h + ah);
-}
-
-static __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-static __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
-    // round to nearest even; NaN stays NaN
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (bf16_t)((u >> 16) | 0x40);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
 }
 
 
@@ -352,7 +341,7 @@ static __device__ __forceinline__ void gemm_tile256_mainloop(const bf16_t* __res
 //     s).  Same 2 pieces per wave and phase as the loop's own requests, in flight while the last 1.5 K-tiles multiply; the
 //     caller waits vmcnt(0) and passes ONE more barrier (all 8 waves) before reading, because every wave's pieces are in
 //     every slot.  The counted waits include the hook's pieces (vmcnt counts in issue order).
-//   * persistent use (PREF, scan_batched.hip).  A workgroup that walks several output tiles hands PPNextTileHook to the loop: its
+//   * persistent use (PREF, scan_coarse.hip).  A workgroup that walks several output tiles hands PPNextTileHook to the loop: its
 //     coop() requests half-tiles 0 .. 7 (the first TWO K-tiles) of the NEXT output tile into the falling-free slots, in ring order
 //     (they are the slots the next tile's loop expects when it starts with buffer parity par ^ (nk & 1)).  The next call (PREF)
 //     then has no prologue requests: it waits for half-tiles 0 and 1 (vmcnt(12): six younger half-tiles; anything the caller's

@@ -3,7 +3,7 @@
 // Replaces (reference): what Milvus does server-side for
 //   create_index(IVF_FLAT, nlist)  src/semcode/storage/milvus_store.py:76-84   (k-means + list build)
 //   search(params={nprobe})        src/semcode/storage/milvus_store.py:141-147 (probe + list scan)
-// The distance work itself reuses scan_exact.hip (segment mode) and scan_batched.hip (row assignment);
+// The distance work itself reuses scan_exact.hip (segment mode) and the batched scan, scan_batched.h (row assignment);
 // these kernels are bookkeeping and are bandwidth- or latency-bound.
 #include "sc_common.h"
 

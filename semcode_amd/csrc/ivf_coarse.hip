@@ -278,7 +278,7 @@ void sc_launch_ivf_slot_thr(const int32_t* slot_q, const float* slot_qnlb, const
 //   refine    S = {survA \ the 128 already done : lower bound <= T} + survB is re-scored exactly; exact top-k of (the 128 + S).
 // Every probed row outside S has exact distance >= lower bound > T >= d_k: the result is the exact probe's, bit for bit, with no
 // candidate count to exceed -- only |S| > IVFW_CAP or an overflowing survivor list send a query to the exact probe.
-// The allowance is the certificate's own (f32 rounding of the exact scores; scan_batched.hip certified<>).
+// The allowance is the certificate's own (f32 rounding of the exact scores; scan_rerank.hip certified<>).
 #define IVFW_CAP 4096
 int sc_ivf_widen_cap(void) { return IVFW_CAP; }
 
@@ -418,7 +418,7 @@ void sc_launch_ivf_refine_finalize(int metric, const uint64_t* ekeysA, int kpa, 
                                    float* out_dist, int64_t* out_rows, int Q, hipStream_t s) {
     hipLaunchKernelGGL(ivf_refine_finalize_kernel, dim3((unsigned)Q), dim3(256), 0, s, metric, ekeysA, kpa, ekeys, ncand, flags, k, row_base, out_dist, out_rows, IVFW_CAP);
 }
-// the same for the exhaustive path (collect pass, wide / compacted final step; scan_batched.hip): ekeys [Q][stride] (0: sc_ivf_widen_cap()), any metric, no pre-scored block
+// the same for the exhaustive path (collect pass, wide / compacted final step; scan_rerank.hip, scan_select.hip): ekeys [Q][stride] (0: sc_ivf_widen_cap()), any metric, no pre-scored block
 void sc_launch_refine_finalize(int metric, const uint64_t* ekeys, const int* ncand, const int* flags, int k, int64_t row_base, float* out_dist, int64_t* out_rows,
                                int Q, hipStream_t s, int stride) {
     hipLaunchKernelGGL(ivf_refine_finalize_kernel, dim3((unsigned)Q), dim3(256), 0, s, metric, (const uint64_t*)nullptr, 0, ekeys, ncand, flags, k, row_base, out_dist,

@@ -6,6 +6,7 @@
 #include "../../include/semcode_hip.h"
 
 #include <mutex>
+#include <type_traits>
 
 #define SC_WAVE 64
 #define SC_LD_ALIGN 64            // corpus row stride is a multiple of 64 floats (256 B)
@@ -18,6 +19,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short bf16_t;
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+
+static __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
+static __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
+    // round to nearest even; NaN stays NaN
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (bf16_t)((u >> 16) | 0x40);
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return (bf16_t)(u >> 16);
+}
 
 __host__ __device__ static inline uint64_t sc_mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -60,6 +72,16 @@ __host__ __device__ static inline float sc_key_score(int metric, uint64_t key) {
     u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
     float v = __builtin_bit_cast(float, u);
     return (metric == SC_METRIC_L2) ? v : -v;
+}
+
+// Calls f with the metric as a compile-time constant (std::integral_constant<int, SC_METRIC_...>): the one place where a launcher
+// turns its run-time `metric` into the METRIC template argument of a kernel.  Anything that is not L2 or COSINE is IP.
+//   sc_dispatch_metric(metric, [&](auto m) { hipLaunchKernelGGL(some_kernel<m.value>, grid, block, 0, s, ...); });
+template <class F>
+static inline void sc_dispatch_metric(int metric, F&& f) {
+    if (metric == SC_METRIC_L2) f(std::integral_constant<int, SC_METRIC_L2>{});
+    else if (metric == SC_METRIC_COSINE) f(std::integral_constant<int, SC_METRIC_COSINE>{});
+    else f(std::integral_constant<int, SC_METRIC_IP>{});
 }
 
 // One-time, PER-DEVICE setup at a launch site.  hipFuncSetAttribute (the dynamic-LDS limit of a kernel) applies to the calling
@@ -146,7 +168,8 @@ void sc_launch_topk_merge2(int metric, const float* d1, const int64_t* r1, const
 void sc_launch_topk_gather_merge(int metric, const uint64_t* partial, const int32_t* src, int lists_per_query, int Q, int k,
                                  int64_t row_base, float* out_dist, int64_t* out_rows, hipStream_t s);
 
-// scan_batched.hip: bf16 / int8 shadows, coarse GEMM + filter phases, selection, exact re-rank
+// scan_shadow.hip, scan_coarse.hip, scan_coarse64.hip, scan_select.hip, scan_rerank.hip (the batched scan, scan_batched.h): bf16 / int8
+// shadows, coarse GEMM + filter phases, selection, exact re-rank
 int sc_batched_kprime(void);   // candidates kept per query: bf16 stage
 int sc_batched_kprime8(void);  // int8 stage
 void sc_launch_shadow(const float* X, const float* xnorm, int64_t first, int64_t n, int ld, void* Xb, unsigned* res_bits, hipStream_t s);
@@ -161,6 +184,10 @@ void sc_launch_scan_coarse(int metric, const void* Xb, const float* xnorm, int64
                            int cap, hipStream_t s, bool i8 = false, const float* xscale = nullptr, const float* qscale = nullptr,
                            bool dense = false,  // dense: most scores of this row range are expected to survive (loose thresholds)
                            void* hit_scratch = nullptr, size_t hit_bytes = 0);  // per-wave hit lists of the narrow kernel (batches of <= 64 queries)
+// scan_coarse.hip, the coarse_workgroups / coarse_persistent options of sc_diag_set_option: workgroups of the persistent coarse kernels
+// (0 = one per CU); 0 = one workgroup per tile instead of the persistent 256-tile kernel
+void sc_scan_set_coarse_workgroups(int v);
+void sc_scan_set_coarse_persistent(int v);
 void sc_launch_scan_select(int metric, uint64_t* surv, unsigned* count, int cap, uint64_t* best, const float* qnorm, float* thr,
                            float* thr_fast, int* overflow, int Q, int kp, hipStream_t s);
 void sc_launch_scan_rerank(int metric, const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, const uint64_t* best,
@@ -168,7 +195,7 @@ void sc_launch_scan_rerank(int metric, const float* X, const float* xnorm, int l
                            int64_t row_base, const uint32_t* perm, float* out_dist, int64_t* out_rows, int* flags, hipStream_t s,
                            int kp, uint64_t* ekeys);
 
-// ivf_coarse.hip + scan_batched.hip: the int8 coarse stage of list-major IVF probing (L2)
+// ivf_coarse.hip + scan_coarse64.hip: the int8 coarse stage of list-major IVF probing (L2)
 void sc_launch_ivf_center_shadow(const float* X, int64_t rows, int ld, int ld8, const float* C, int ldc, const int64_t* list_off, int nlist, void* Xc8,
                                  float* xrow, unsigned* list_stats, hipStream_t s, const float* xnorm = nullptr, const float* cnorm = nullptr, const int64_t* only = nullptr);  // norms: COSINE
 void sc_launch_ivf_pair_query(const float* Qp, int ld, int ld8, const float* C, int ldc, const int32_t* slot_q, const int32_t* slot_l, int nslots,
@@ -180,19 +207,18 @@ void sc_launch_ivf_coarse(const void* Xc8, const float* xrow, int ld8, const voi
                           const float* slot_thr, const float* slot_qn, const float* slot_qs, const int32_t* slot_q, const float* slot_qb, const float* slot_qd,
                           uint64_t* surv, unsigned* count, int cap, void* hit_scratch, size_t hit_bytes, hipStream_t s,
                           const int32_t* slot_dst = nullptr, int metric = SC_METRIC_L2);  // non-null: dense phase (every row survives; count[] preset by the caller)
-void sc_launch_scan_rerank_keys_l2(const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, const uint64_t* cand, const int* ncand, int kp,
-                                   const uint32_t* perm, uint64_t* ekeys, int Q, hipStream_t s);
+// scan_rerank.hip
 void sc_launch_scan_rerank_keys(int metric, const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, const uint64_t* cand, const int* ncand, int kp,
                                 const uint32_t* perm, uint64_t* ekeys, int Q, hipStream_t s);
-// the collect pass of the exhaustive batched path (scan_batched.hip): thresholds from the k-th exact score of the failed pass; survivor counts -> candidate counts
+// the collect pass of the exhaustive batched path (scan_rerank.hip, scan_select.hip): thresholds from the k-th exact score of the failed pass; survivor counts -> candidate counts
 void sc_launch_scan_collect_bound(int metric, const float* prev_dist, int k, const float* qnorm, const float* qres, const unsigned* bits, int ld, float* thr,
                                   float* thr_fast, int* flags, int Q, hipStream_t s);
 void sc_launch_scan_collect_counts(const unsigned* count, int cap, int* ncand, int* flags, int Q, hipStream_t s);
-// thresholds from exact scores before the large phases (scan_batched.hip): ekeys [Q][kp <= 128] exact keys of the best coarse candidates
+// thresholds from exact scores before the large phases (scan_rerank.hip): ekeys [Q][kp <= 128] exact keys of the best coarse candidates
 void sc_launch_scan_tighten(int metric, const uint64_t* ekeys, int kp, int k, const float* qnorm, const float* qres, const unsigned* bits, int ld, float* thr,
                             float* thr_fast, float* thr_cut, int Q, hipStream_t s);
 void sc_launch_scan_thr_min(float* thr, const float* thr_cut, int Q, hipStream_t s);
-// the wide candidate set (scan_batched.hip): best [Q][kcap] with nbest[q] keys, every key within thr_cut kept
+// the wide candidate set (scan_select.hip, scan_rerank.hip): best [Q][kcap] with nbest[q] keys, every key within thr_cut kept
 void sc_launch_scan_select_wide(int metric, const uint64_t* surv, unsigned* count, int cap, uint64_t* best, unsigned* nbest, int kcap, int kp, const float* qnorm,
                                 float* thr, float* thr_fast, const float* thr_cut, int* overflow, int Q, hipStream_t s);
 void sc_launch_scan_wide_compact(int metric, const uint64_t* best, const unsigned* nbest, int kcap, const float* thr, uint64_t* cand, int* ncand, int Q, hipStream_t s);

@@ -714,8 +714,6 @@ extern "C" sc_status sc_diag_gemm_bf16(sc_runtime* rt, int32_t epi, const float*
 
 void sc_launch_gemm_i8_diag(const void* A, const void* W, void* C, int M, int N, int K, hipStream_t s);
 
-void sc_scan_set_coarse_workgroups(int v);
-void sc_scan_set_coarse_persistent(int v);
 void sc_ivf_set_refresh_nomem(int v);
 void sc_ivf_set_refine_cap(int v);
 void sc_ivf_set_coarse_nomem(int v);

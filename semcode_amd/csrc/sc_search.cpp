@@ -66,7 +66,7 @@ static sc_status search_exact_locked(sc_index* ix, const float* q_dev, int32_t Q
     return SC_OK;
 }
 
-// ---- batched path (scan_batched.hip): bf16 / int8 shadow + coarse GEMM phases + exact re-rank + certified fallback
+// ---- batched path (scan_batched.h): bf16 / int8 shadow + coarse GEMM phases + exact re-rank + certified fallback
 
 static const int BATCH_CAP = 4096;        // survivors kept per query and phase
 // first phase: every row of it survives (thresholds start at +inf), so it must stay well below BATCH_CAP; each next phase covers 4x
@@ -126,7 +126,7 @@ void sc_set_tighten(int v) { g_tighten = v; }
 static int g_collect_pass = 1;  // sc_diag_set_option("collect_pass", 0): uncertified queries go straight to the next stage (tests, A/B)
 void sc_set_collect_pass(int v) { g_collect_pass = v; }
 
-// The collect pass (scan_batched.hip, "the collect pass"): the sub-batch `fq` [R][dim] of queries a stage could not certify, with
+// The collect pass (scan_rerank.hip, "the collect pass"): the sub-batch `fq` [R][dim] of queries a stage could not certify, with
 // that stage's results in fd / fr [R][k] (fd's k-th column bounds the k-th score).  Resolved queries get their final results
 // written into fd / fr; `left` receives the sub-batch positions of those that still need the next stage (more than BATCH_CAP rows
 // within the bound, or no bound).  Uses the same scratch as the stage that called it (which is done with it).
@@ -191,7 +191,7 @@ static sc_status search_batched_stage_locked(sc_index* ix, const float* q_dev, i
     // 256-wide query tiles for batches above 64 queries (always for the int8 stage); 65 .. 128 queries used to take the 128-query tiles:
     // 1M x 768, 65 queries 2.02 ms there against 0.86 ms for 256 queries on the 256-wide tiles (profiles/r3z_q_rows.log)
     const int Qpad = (i8 || Q > 64) ? (Q + 255) / 256 * 256 : 128;
-    // the wide candidate set (scan_batched.hip): on corpora whose certificate fails at kp candidates the int8 stage keeps every key
+    // the wide candidate set (scan_select.hip): on corpora whose certificate fails at kp candidates the int8 stage keeps every key
     // within its exact-score cut -- needs the cuts (tightening: 2 k <= 128, a corpus beyond 2^17 rows) and 64 KiB of keys per query
     static const bool tighten_env = sc_env_flag("SC_TIGHTEN", true);  // A/B
     // (the cut needs the k-th exact score among re-scored candidates: the 128 best for k <= 64, all 512 of the int8 stage beyond)
@@ -238,7 +238,7 @@ static sc_status search_batched_stage_locked(sc_index* ix, const float* q_dev, i
     unsigned* nbest = (unsigned*)(b + o_nbest);
     if (wide) SC_HIP(hipMemsetAsync(nbest, 0, (size_t)Q * 4, s));
     ix->last_wide = wide ? 1 : 0;
-    // thresholds from exact scores before the large phases (scan_batched.hip, scan_tighten_kernel): from 2^17 rows seen on
+    // thresholds from exact scores before the large phases (scan_rerank.hip, scan_tighten_kernel): from 2^17 rows seen on
     // (10M x 768 x 1024, same box: from 2^19 8.45 ms per step, 2^17 8.38, 2^15 8.36; without 8.80)
     float* thr_cut = (float*)(b + o_cut);
     bool cut_used = false;

@@ -672,9 +672,7 @@ void sc_launch_scan_listgemm(int metric, int width, const float* X, const float*
     if (groups <= 0) return;
     ListGemmArgs a;
     a.X = X; a.xnorm = xnorm; a.ld = ld; a.Qp = Qp; a.qnorm = qnorm; a.k = k; a.partial = partial; a.perm = perm; a.seg_rows = seg_rows; a.qmap = qmap;
-    if (metric == SC_METRIC_L2) launch_scan_listgemm_m<SC_METRIC_L2>(a, width, groups, s);
-    else if (metric == SC_METRIC_COSINE) launch_scan_listgemm_m<SC_METRIC_COSINE>(a, width, groups, s);
-    else launch_scan_listgemm_m<SC_METRIC_IP>(a, width, groups, s);
+    sc_dispatch_metric(metric, [&](auto m) { launch_scan_listgemm_m<m.value>(a, width, groups, s); });
 }
 
 bool sc_scan_exact_plan(int ld, int Q, int k, int cus, ScanPlan* p, int force_qt, int nprobe, int64_t n_rows) {
@@ -734,12 +732,8 @@ void sc_launch_scan_exact(int metric, const float* X, const float* xnorm, int64_
     a.perm = perm; a.seg_base = seg_base; a.seg_rows = seg_rows; a.nprobe = nprobe; a.qmap = qmap; a.gstride = p.gstride;
     dim3 grid((unsigned)p.nwg, (unsigned)p.groups);
     if (p.qstream) {
-        if (metric == SC_METRIC_L2) launch_scan_exact<SC_METRIC_L2, 4>(a, grid, p.lds, s);
-        else if (metric == SC_METRIC_COSINE) launch_scan_exact<SC_METRIC_COSINE, 4>(a, grid, p.lds, s);
-        else launch_scan_exact<SC_METRIC_IP, 4>(a, grid, p.lds, s);
+        sc_dispatch_metric(metric, [&](auto m) { launch_scan_exact<m.value, 4>(a, grid, p.lds, s); });
     } else {
-        if (metric == SC_METRIC_L2) launch_scan_exact<SC_METRIC_L2, 0>(a, grid, p.lds, s);
-        else if (metric == SC_METRIC_COSINE) launch_scan_exact<SC_METRIC_COSINE, 0>(a, grid, p.lds, s);
-        else launch_scan_exact<SC_METRIC_IP, 0>(a, grid, p.lds, s);
+        sc_dispatch_metric(metric, [&](auto m) { launch_scan_exact<m.value, 0>(a, grid, p.lds, s); });
     }
 }
