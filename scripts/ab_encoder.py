@@ -1,0 +1,160 @@
+"""Same-box A/B of the encoder between two builds of the library (written for the split of sc_encoder.cpp:
+profiles/encoder_split_ab.log; scripts/ab_encoder.sh drives it).  One process per build:
+
+    python scripts/ab_encoder.py dump LIB.so OUT.txt        pooled vectors of synthetic-weight encoders and the diag_* results on
+                                                            seeded inputs, one line per array: name, shape, sha256 of its bytes
+    python scripts/ab_encoder.py compare A.txt B.txt        the two dumps line by line; VERDICT: pass only if every line is equal
+    python scripts/ab_encoder.py bench LIB.so ARGS...       bench.py ARGS... on that build (the library path is set, nothing is copied)
+    python scripts/ab_encoder.py speed DIR                  DIR/run_<i>_{new,base}.log + DIR/out_<i>_*/embed_pooled.npy of the bench runs:
+                                                            outputs bit for bit, medians; the new build passes if its median is not
+                                                            below the parent's by more than the parent's spread (max - min)
+
+Encoders: BERT, jina (ALiBi + GEGLU), nomic (rotary + SwiGLU, rope_fused 0 and 1) x {hidden 256 / ffn 512 (foldable), hidden 128 /
+ffn 384 (128-tile path)} x normalize {0, 1} x (B, S) {(2, 32), (5, 256)} (256 and 1 280 token rows: either side of the 1 024-row
+pipeline switch) x set_path {auto, batch, small}.
+"""
+import hashlib
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+
+def line(name, a):
+    a = np.ascontiguousarray(a)
+    return f"{name} {a.dtype}{list(a.shape)} {hashlib.sha256(a.tobytes()).hexdigest()}"
+
+
+def dump(lib_path, out_path):
+    from semcode_amd import _native as nv
+
+    nv.LIB_PATH = Path(lib_path).resolve()
+    rt = nv.Runtime()
+    out = []
+    rng = np.random.default_rng(2024)
+    families = {"bert": {}, "jina": dict(alibi=True, geglu=True), "nomic": dict(rotary=True, swiglu=True)}
+    shapes = {"h256": dict(hidden=256, heads=4, ffn=512), "h128": dict(hidden=128, heads=2, ffn=384)}
+    batches = {}
+    for B, S in ((2, 32), (5, 256)):
+        batches[(B, S)] = (rng.integers(1, 1000, size=(B, S)).astype(np.int32), rng.integers(1, S + 1, size=B).astype(np.int32))
+    for fam, switches in families.items():
+        for shape, dims in shapes.items():
+            for normalize in (0, 1):
+                cfg = dict(nv.BERT_BASE, vocab=1000, layers=2, max_pos=256, **dims, **switches)
+                enc = nv.Encoder(rt, cfg, weights=None, normalize=bool(normalize), synth_seed=5)
+                for fused in ((0, 1) if fam == "nomic" else (-1,)):
+                    nv.diag_set_option("rope_fused", fused)
+                    for (B, S), (ids, lens) in batches.items():
+                        for path in ("auto", "batch", "small"):
+                            enc.set_path(path)
+                            out.append(line(f"pooled {fam} {shape} norm={normalize} rope_fused={fused} B={B} S={S} path={path}", enc.embed_ids(ids, lens)))
+                nv.diag_set_option("rope_fused", -1)
+                enc.close()
+
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    M, N, K = 256, 256, 256
+    A, W, bias, R = f(M, K), 0.05 * f(N, K), f(N), f(M, N)
+    for epi in (0, 1, 2):
+        for sk in (0, 16):
+            out.append(line(f"gemm_bf16 epi={epi} splitk={sk}", nv.diag_gemm_bf16(rt, A, W, bias, R if epi == 2 else None, epi=epi | sk)))
+    out.append(line("gemm_bf16 128-tile", nv.diag_gemm_bf16(rt, f(128, 64), f(384, 64), f(384))))
+    out.append(line("gemm_i8", nv.diag_gemm_i8(rt, rng.integers(-127, 128, (256, 128)), rng.integers(-127, 128, (256, 128)))))
+    B, S, heads = 3, 64, 2
+    H = heads * 64
+    qkv, lens = f(B * S, 3 * H), np.array([64, 9, 1], np.int32)
+    out.append(line("attention", nv.diag_attention(rt, qkv, lens, B, S, heads)))
+    out.append(line("attention_ex blocked", nv.diag_attention_ex(rt, qkv, lens, B, S, heads, blocked_rows=256)))
+    out.append(line("attention_ex slopes", nv.diag_attention_ex(rt, qkv, lens, B, S, heads, slopes=np.array([0.25, 0.0625], np.float32))))
+    out.append(line("rope", nv.diag_rope(rt, f(200, 3 * 64), 64, 3, 10000.0)))
+    out.append(line("rope theta=1000", nv.diag_rope(rt, f(128, 64), 32, 1, 1000.0)))
+    h = f(70, 2 * 136)
+    out.append(line("swiglu", nv.diag_swiglu(rt, h)))
+    out.append(line("geglu", nv.diag_geglu(rt, h)))
+    gamma, beta = 1 + 0.1 * f(K), 0.1 * f(K)
+    Wf, c1, c2 = nv.diag_fold_ln(rt, W, gamma, beta, bias)
+    for name, a in (("Wf", Wf), ("c1", c1), ("c2", c2)):
+        out.append(line(f"fold_ln {name}", a))
+    stats = np.stack([A.sum(1), (A * A).sum(1)], axis=1).reshape(1, M, 2).astype(np.float32)
+    for epi, kw in ((3, {}), (4, dict(blocked=True)), (6, dict(blocked=True, rope_S=64, rope_theta=0.0, rope_ncols=128))):
+        Cc, fin = nv.diag_gemm_lna(rt, epi, A, Wf, c1, c2, stats, 1e-12, **kw)
+        out.append(line(f"gemm_lna epi={epi} C", Cc))
+        out.append(line(f"gemm_lna epi={epi} fin", fin))
+    for blocked in (False, True):
+        Cc, st = nv.diag_gemm_resln(rt, A, W, bias, gamma, R, fin, 1e-12, a_blocked=blocked)
+        out.append(line(f"gemm_resln blocked={blocked} C", Cc))
+        out.append(line(f"gemm_resln blocked={blocked} stats", st))
+    x = f(B * S, 256)
+    out.append(line("layernorm", nv.diag_layernorm(rt, x, gamma, beta, 1e-12)))
+    for normalize in (False, True):
+        out.append(line(f"mean_pool normalize={normalize}", nv.diag_mean_pool(rt, x, lens, S, normalize)))
+    y = f(256, 256)
+    ystats = np.stack([y.sum(1), (y * y).sum(1)], axis=1).reshape(1, 256, 2).astype(np.float32)
+    out.append(line("mean_pool_ln", nv.diag_mean_pool_ln(rt, y, ystats, gamma, beta, 1e-12, lens, S)))
+    ids = rng.integers(0, 50, size=(B, S)).astype(np.int32)
+    wemb, pemb, temb = f(50, 256), f(64, 256), f(2, 256)
+    rows, st = nv.diag_embed(rt, ids, wemb, pemb, temb, 64, tokens_pad=256, slots=1)
+    out.append(line("embed raw rows", rows))
+    out.append(line("embed raw stats", st))
+    out.append(line("embed ln", nv.diag_embed(rt, ids, wemb, None, temb, 64, ln=(gamma, beta, 1e-12))))
+    rt.close()
+    Path(out_path).write_text("\n".join(out) + "\n")
+    print(f"{len(out)} arrays -> {out_path}")
+
+
+def compare(a_path, b_path):
+    a, b = Path(a_path).read_text().splitlines(), Path(b_path).read_text().splitlines()
+    ok = len(a) == len(b) and len(a) > 0
+    for x, y in zip(a, b):
+        same = x == y
+        ok &= same
+        print(f"{x.rsplit(' ', 1)[0]}: {'equal' if same else 'DIFFERENT'}")
+    print(f"{len(a)} / {len(b)} arrays")
+    print("VERDICT:", "pass" if ok else "FAIL")
+    return 0 if ok else 1
+
+
+def bench(lib_path, argv):
+    import runpy
+
+    from semcode_amd import _native as nv
+
+    nv.LIB_PATH = Path(lib_path).resolve()
+    root = Path(__file__).resolve().parent.parent
+    sys.argv = [str(root / "bench.py"), *argv]
+    runpy.run_path(sys.argv[0], run_name="__main__")
+
+
+def speed(dirname):
+    import json
+
+    d = Path(dirname)
+    val, pooled = {"new": [], "base": []}, []
+    for log in sorted(d.glob("run_*.log")):
+        i, which = log.stem.split("_")[1:]
+        res = [json.loads(l) for l in log.read_text().splitlines() if l.startswith("{")][-1]
+        val[which].append(res["value"])
+        pooled.append(np.load(d / f"out_{i}_{which}" / "embed_pooled.npy"))
+        print(f"run {i} {which:4s} {res['value']:10.1f} chunks/s  {res['ms_per_step']:.3f} ms/step")
+    same = all(p.tobytes() == pooled[0].tobytes() for p in pooled)
+    print(f"embed_pooled.npy of the {len(pooled)} runs: {'byte-identical' if same else 'DIFFERENT'}")
+    nm, bm = float(np.median(val["new"])), float(np.median(val["base"]))
+    spread = max(val["base"]) - min(val["base"])
+    ok = same and len(val["new"]) == len(val["base"]) == 3 and nm >= bm - spread
+    print(f"median new {nm:.1f}  parent {bm:.1f}  new/parent {nm / bm:.4f}  parent spread {spread:.1f} ({100 * spread / bm:.2f} %)")
+    print("VERDICT:", "pass" if ok else "FAIL")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "dump":
+        dump(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    elif len(sys.argv) >= 3 and sys.argv[1] == "bench":
+        bench(sys.argv[2], sys.argv[3:])
+    elif len(sys.argv) == 3 and sys.argv[1] == "speed":
+        sys.exit(speed(sys.argv[2]))
+    else:
+        sys.exit(__doc__)

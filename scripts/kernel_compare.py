@@ -3,7 +3,9 @@ and whether the instruction text is identical (labels renumbered, comments dropp
 by stage (profiles/scan_split_kernels.log); `canon` maps the parent's template argument order of scan_coarse256_kernel to the new one.
 
     python -m semcode_amd.csrc.build --force --save-temps 2> BUILD.log     (in a checkout of each commit; keep csrc/_obj/*gfx950.s)
-    python scripts/kernel_compare.py PARENT_S_DIR PARENT_BUILD.log NEW_S_DIR NEW_BUILD.log
+    python scripts/kernel_compare.py PARENT_S_DIR PARENT_BUILD.log NEW_S_DIR NEW_BUILD.log [STEM,STEM...]
+
+With a list of stems (e.g. gemm_bf16,encoder_ops: profiles/encoder_split_kernels.log) the same files are compared in both builds.
 """
 import hashlib
 import re
@@ -75,11 +77,12 @@ def canon(d):
     return d
 
 
-def main(pdir, plog, ndir, nlog):
-    new_stems = ["scan_shadow", "scan_coarse", "scan_coarse64", "scan_select", "scan_rerank", "scan_exact"]
+def main(pdir, plog, ndir, nlog, stems=None):
+    new_stems = stems.split(",") if stems else ["scan_shadow", "scan_coarse", "scan_coarse64", "scan_select", "scan_rerank", "scan_exact"]
+    old_stems = new_stems if stems else ["scan_batched", "scan_exact"]
     pr, nr = remarks(plog), remarks(nlog)
-    pb, nb = bodies(pdir, ["scan_batched", "scan_exact"]), bodies(ndir, new_stems)
-    pr = {k: v for k, v in pr.items() if v["src"] in ("scan_batched.hip", "scan_exact.hip")}
+    pb, nb = bodies(pdir, old_stems), bodies(ndir, new_stems)
+    pr = {k: v for k, v in pr.items() if v["src"].split(".")[0] in old_stems}
     nr = {k: v for k, v in nr.items() if v["src"].split(".")[0] in new_stems}
     dm = demangle(list(pr) + list(nr))
     pk = {}
@@ -114,4 +117,4 @@ def main(pdir, plog, ndir, nlog):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:5])
+    main(*sys.argv[1:6])

@@ -1,0 +1,57 @@
+// encoder_ops.h -- the encoder's device entry points: what gemm_bf16.hip and encoder_ops.hip define and the encoder host files
+// (sc_encoder.cpp, sc_encoder_diag.cpp) call.  Defaults of optional arguments live here only; the .hip files include this header,
+// so a definition that drifts from its prototype does not compile.  All launchers enqueue on `s` and never synchronise.
+#pragma once
+#include <vector>
+
+#include "sc_common.h"
+
+// GEMM epilogues (gemm_bf16.hip describes the LayerNorm-folded ones)
+enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5, EPI_LNA_BIAS_ROPE = 6 };
+
+// ---- gemm_bf16.hip
+bool sc_gemm_bf16_supported(int M, int N, int K);
+// splitk_scratch (optional, f32): lets small-M GEMMs run as tile x K-slice workgroups + a reduce/epilogue kernel
+void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C,
+                         int ldc, int M, int N, int K, hipStream_t s, void* splitk_scratch = nullptr, size_t splitk_scratch_bytes = 0);
+int sc_gemm_splitk_factor(int M, int N, int K, int cus);
+// LayerNorm-folded batch pipeline (EPI_LNA_* / EPI_RESLN_STATS)
+bool sc_gemm_ln_supported(int M, int N, int K);
+void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C, int ldc, int M,
+                            int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps,
+                            const float* rope_cos = nullptr, const float* rope_sin = nullptr, int rope_S = 0, int rope_ncols = 0);
+void sc_launch_gemm_i8_diag(const void* A, const void* W, void* C, int M, int N, int K, hipStream_t s);
+// process-wide knobs of the launchers (sc_diag_set_option "gemm_pp" / "gemm_nt", sc_diag_gemm_trace, sc_diag_gemm_bench)
+void sc_gemm_set_debug(int v);
+void sc_gemm_set_order(int v);
+void sc_gemm_set_pp(int v);
+void sc_gemm_set_nt(int v);
+void sc_gemm_set_trace(unsigned long long* dev);
+void sc_gemm_force_tile128(bool on);
+
+// ---- encoder_ops.hip
+void sc_launch_embed_ln(const int32_t* ids, int tokens, int S, int H, int vocab, int max_pos, const float* wemb, const float* pemb,
+                        const float* temb, const float* g, const float* b, float eps, void* out, hipStream_t s);
+void sc_launch_layernorm(const void* in, int tokens, int H, const float* g, const float* b, float eps, void* out, hipStream_t s);
+bool sc_attention_supported(int S, int H, int heads);
+void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_geglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+// rotary positions: in-place rotation of the first `nblocks` 64-column blocks (Q and K heads) of a blocked buffer [blocks][M][64];
+// cos / sin [>= S][32] f32, row r is position r % S
+void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* cos_t, const float* sin_t, hipStream_t s);
+void sc_launch_embed_raw(const int32_t* ids, int tokens, int tokens_pad, int S, int H, int vocab, int max_pos, const float* wemb, const float* pemb,
+                         const float* temb, void* out, float* stats, int slots, hipStream_t s);
+void sc_launch_fold_ln_weights(const float* W, const float* gamma, const float* beta, const float* bias, int N, int K, void* Wf, float* c1, float* c2,
+                               hipStream_t s);
+void sc_launch_add_vectors(const float* a, const float* b, float* out, int n, hipStream_t s);
+void sc_launch_mean_pool_ln(const void* y, const float* stats, int slots, int tokens_pad, const float* gamma, const float* beta, float eps,
+                            const int32_t* lens, int B, int S, int H, float* out, hipStream_t s);
+void sc_launch_mean_pool(const void* x, const int32_t* lens, int B, int S, int H, int normalize, float* out, hipStream_t s);
+void sc_launch_f32_to_bf16(const float* in, void* out, int64_t n, hipStream_t s);
+void sc_launch_synth_scaled(float* out, int64_t n, uint64_t seed, float scale, float offset, hipStream_t s);
+void sc_launch_bf16_to_f32(const void* in, float* out, int64_t n, hipStream_t s);
+
+// ---- sc_encoder.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
+// angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000
+std::vector<float> sc_rope_table(int64_t positions, float theta);

@@ -19,17 +19,11 @@
 //   rope_qk_kernel    HBM-bound  : rotary position embedding of Q and K, in place on the blocked QKV buffer (nomic-bert)
 #include <cstdlib>
 
+#include "encoder_ops.h"
 #include "gemm_tile.h"  // bf16 helpers, LDS-DMA pointer types
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-static __device__ __forceinline__ float bf2f(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-static __device__ __forceinline__ bf16_t f2bf(float f) {
-    uint32_t u = __builtin_bit_cast(uint32_t, f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (bf16_t)((u >> 16) | 0x40);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
             const f32x4 b = *reinterpret_cast<const f32x4*>(beta + k0);
             u16x4 r;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) r[c] = f2bf((v[j][c] - mean) * rstd * g[c] + b[c]);
+            for (int c = 0; c < 4; ++c) r[c] = f32_to_bf16((v[j][c] - mean) * rstd * g[c] + b[c]);
             *reinterpret_cast<u16x4*>(o + k0) = r;
         }
     }
@@ -122,8 +116,8 @@ __global__ __launch_bounds__(256) void embed_raw_kernel(const int32_t* __restric
                 u16x4 r;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    r[c] = f2bf(v[c]);
-                    const float y = bf2f(r[c]);
+                    r[c] = f32_to_bf16(v[c]);
+                    const float y = bf16_to_f32(r[c]);
                     s1 += y;
                     s2 = fmaf(y, y, s2);
                 }
@@ -160,8 +154,8 @@ __global__ __launch_bounds__(256) void fold_ln_weights_kernel(const float* __res
         u16x4 r;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            r[c] = f2bf(w[c] * g[c]);
-            s1 += bf2f(r[c]);
+            r[c] = f32_to_bf16(w[c] * g[c]);
+            s1 += bf16_to_f32(r[c]);
             s2 = fmaf(b[c], w[c], s2);
         }
         *reinterpret_cast<u16x4*>(Wf + (size_t)n * K + k0) = r;
@@ -652,7 +646,7 @@ __global__ __launch_bounds__(256) void mean_pool_kernel(const bf16_t* __restrict
         for (int s = 0; s < len; ++s) {
             const u16x4 raw = *reinterpret_cast<const u16x4*>(p + (size_t)s * H);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] += bf2f(raw[c]);
+            for (int c = 0; c < 4; ++c) acc[c] += bf16_to_f32(raw[c]);
         }
         acc *= inv;
         *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0) = acc;
@@ -676,10 +670,10 @@ __global__ __launch_bounds__(256) void mean_pool_kernel(const bf16_t* __restrict
 
 // ------------------------------------------------------------------ f32 -> bf16 weight conversion, fills
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = f2bf(in[i]);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = f32_to_bf16(in[i]);
 }
 __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = bf2f(in[i]);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = bf16_to_f32(in[i]);
 }
 __global__ __launch_bounds__(256) void synth_scaled_kernel(float* __restrict__ out, int64_t n, uint64_t key, float scale, float offset) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -773,8 +767,8 @@ __global__ __launch_bounds__(256) void glu_kernel(const bf16_t* __restrict__ h, 
         u32x4 o;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const f32x2 gg = ACT::apply(f32x2{bf2f((bf16_t)g[2 * c]), bf2f((bf16_t)g[2 * c + 1])});
-            o[c] = pack_bf16x2(gg[0] * bf2f((bf16_t)u[2 * c]), gg[1] * bf2f((bf16_t)u[2 * c + 1]));
+            const f32x2 gg = ACT::apply(f32x2{bf16_to_f32((bf16_t)g[2 * c]), bf16_to_f32((bf16_t)g[2 * c + 1])});
+            o[c] = pack_bf16x2(gg[0] * bf16_to_f32((bf16_t)u[2 * c]), gg[1] * bf16_to_f32((bf16_t)u[2 * c + 1]));
         }
         *reinterpret_cast<u32x4*>(out + m * F + j) = o;
     }

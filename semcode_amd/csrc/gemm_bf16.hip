@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "encoder_ops.h"
 #include "gemm_tile.h"
 
 #ifndef SC_GEMM_PP_DEFAULT
@@ -34,7 +35,7 @@
 // row sums / sums of squares of THIS output (after its bf16 rounding) written per 256-column tile for the consumer's statistics.
 // EPI_LNA_BIAS_ROPE: EPI_LNA_BIAS of a QKV projection with the rotary position embedding (rotate-half) applied to the Q and K
 // columns in the accumulator registers, before the one rounding to bf16.
-enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES = 2, EPI_LNA_BIAS = 3, EPI_LNA_GELU = 4, EPI_RESLN_STATS = 5, EPI_LNA_BIAS_ROPE = 6 };
+// (the EPI_* codes: encoder_ops.h)
 
 struct GemmArgs {
     const bf16_t* A;   // [M, lda]

@@ -1,5 +1,5 @@
-// sc_api.cpp -- host side of the C ABI declared in include/semcode_hip.h: runtime + profiling, index create / destroy, rows in and
-// out, the getters of the last call's statistics.  Search: sc_search.cpp; delete: sc_delete.cpp; buffers and shadows: sc_index_state.cpp.
+// sc_api.cpp -- host side of the C ABI declared in include/semcode_hip.h: runtime + profiling, sc_diag_set_option, index create / destroy, rows in
+// and out, the getters of the last call's statistics.  Search: sc_search.cpp; delete: sc_delete.cpp; buffers and shadows: sc_index_state.cpp.
 //
 // Mirrors (reference): MilvusVectorStore's use of pymilvus -- connect / create collection + index /
 // upsert / search -- src/semcode/storage/milvus_store.py:39-148.  Error behaviour: every failure is
@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "encoder_ops.h"  // sc_gemm_set_*
 #include "sc_internal.h"
 
 static thread_local std::string g_err;
@@ -186,6 +187,26 @@ extern "C" sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows,
     sc_launch_synth_fill(out, rows, dim, ld, seed, first_row, nullptr, rt->stream);
     SC_HIP(hipGetLastError());
     return SC_OK;
+}
+
+// The process-wide switchboard of the tests and A/B scripts: every option forwards to a setter next to the code it steers.
+extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
+    if (!name) return sc_fail(SC_ERR_INVALID, "sc_diag_set_option: NULL name");
+    static const struct { const char* name; void (*set)(int); } options[] = {
+        {"coarse_workgroups", sc_scan_set_coarse_workgroups}, {"coarse_persistent", sc_scan_set_coarse_persistent},
+        {"gemm_pp", sc_gemm_set_pp},                          {"gemm_nt", sc_gemm_set_nt},
+        {"ivf_refresh_nomem", sc_ivf_set_refresh_nomem},      {"ivf_refine_cap", sc_ivf_set_refine_cap},
+        {"ivf_coarse_nomem", sc_ivf_set_coarse_nomem},        {"collect_pass", sc_set_collect_pass},
+        {"tighten", sc_set_tighten},                          {"wide_candidates", sc_set_wide_force},
+        {"ivf_tail_rows", sc_set_ivf_tail_rows},              {"delete_chunk_rows", sc_set_delete_chunk_rows},
+        {"rope_fused", sc_encoder_set_rope_fused},
+    };
+    for (const auto& o : options)
+        if (!strcmp(name, o.name)) {
+            o.set(value);
+            return SC_OK;
+        }
+    return sc_fail(SC_ERR_INVALID, "sc_diag_set_option: unknown option '%s'", name);
 }
 
 // ------------------------------------------------------------------ index

@@ -1,0 +1,423 @@
+// sc_encoder_diag.cpp -- sc_diag_*: one encoder kernel per call, for the single-kernel parity tests and the GEMM timing scripts.
+//
+// The pattern of every harness: host f32 in (activations rounded to bf16 by f32_to_bf16_kernel), THE PRODUCT LAUNCHER, result widened
+// to f32 and copied back, synchronous.  Output buffers are pre-filled with 0xFF bytes (NaN as bf16 and as f32), so that an element a
+// kernel does not write shows in the result.  (sc_diag_encoder_read, which needs the encoder handle, is in sc_encoder.cpp.)
+#include <cstring>
+#include <vector>
+
+#include "encoder_ops.h"
+#include "sc_internal.h"
+
+namespace {
+#define SC_TRY(expr)              \
+    do {                          \
+        sc_status st_ = (expr);   \
+        if (st_) return st_;      \
+    } while (0)
+
+sc_status dev_alloc(sc_devbuf& out, size_t bytes) {
+    if (out.alloc(bytes) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "diag: hipMalloc failed");
+    return SC_OK;
+}
+// host bytes -> device, as they are (f32 vectors, int32 ids / lens, int8 operands)
+sc_status upload(const void* host, size_t bytes, sc_devbuf& out, hipStream_t s) {
+    SC_TRY(dev_alloc(out, bytes));
+    if (host && bytes) SC_HIP(hipMemcpyAsync(out.p, host, bytes, hipMemcpyHostToDevice, s));
+    return SC_OK;
+}
+// host f32 [n] -> device bf16 (through a device f32 staging buffer)
+sc_status upload_bf16(const float* host, int64_t n, sc_devbuf& f32buf, sc_devbuf& out, hipStream_t s) {
+    SC_TRY(upload(host, (size_t)n * 4, f32buf, s));
+    SC_TRY(dev_alloc(out, (size_t)n * 2));
+    sc_launch_f32_to_bf16((const float*)f32buf.p, out.p, n, s);
+    return SC_OK;
+}
+sc_status alloc_nan(sc_devbuf& out, size_t bytes, hipStream_t s) {
+    SC_TRY(dev_alloc(out, bytes));
+    SC_HIP(hipMemsetAsync(out.p, 0xFF, bytes ? bytes : 16, s));
+    return SC_OK;
+}
+// device bytes -> host; synchronises
+sc_status download(const void* dev, size_t bytes, void* host, hipStream_t s) {
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+// device bf16 [n] -> host f32 [n]; synchronises
+sc_status download_bf16(const void* dev, int64_t n, float* host, hipStream_t s) {
+    sc_devbuf fo;
+    SC_TRY(dev_alloc(fo, (size_t)n * 4));
+    sc_launch_bf16_to_f32(dev, (float*)fo.p, n, s);
+    return download(fo.p, (size_t)n * 4, host, s);
+}
+}  // namespace
+
+// ------------------------------------------------------------------ the GEMMs
+
+extern "C" sc_status sc_diag_gemm_bf16(sc_runtime* rt, int32_t epi, const float* A, const float* W, const float* bias, const float* R,
+                                       int32_t M, int32_t N, int32_t K, float* out) {
+    if (!rt || !A || !W || !bias || !out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bf16: NULL argument");
+    const bool allow_splitk = epi >= 0 && (epi & 16);
+    if (epi >= 0) epi &= 15;
+    if (epi < 0 || epi > 2 || (epi == EPI_BIAS_RES && !R)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bf16: bad epilogue / missing residual");
+    if (!sc_gemm_bf16_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_bf16: need M%%128==0, N%%128==0, K%%64==0");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fa, fw, fr, da, dw, dr, db, dc, sk;
+    size_t sk_bytes = 0;
+    if (allow_splitk) {
+        sk_bytes = (size_t)sc_gemm_splitk_factor(M, N, K, rt->cus) * M * N * 4;
+        SC_TRY(dev_alloc(sk, sk_bytes));
+    }
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(W, (int64_t)N * K, fw, dw, s));
+    if (R) SC_TRY(upload_bf16(R, (int64_t)M * N, fr, dr, s));
+    SC_TRY(upload(bias, (size_t)N * 4, db, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
+    sc_launch_gemm_bf16(epi, da.p, K, dw.p, K, (const float*)db.p, dr.p, N, dc.p, N, M, N, K, s, sk.p, sk_bytes);
+    return download_bf16(dc.p, (int64_t)M * N, out, s);
+}
+
+extern "C" sc_status sc_diag_gemm_i8(sc_runtime* rt, const int8_t* A, const int8_t* W, int32_t M, int32_t N, int32_t K, int32_t* out) {
+    if (!rt || !A || !W || !out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_i8: NULL argument");
+    if (M <= 0 || N <= 0 || K <= 0 || (M % 256) || (N % 256) || (K % 128)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_i8: need M%%256==0, N%%256==0, K%%128==0");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf da, dw, dc;
+    SC_TRY(upload(A, (size_t)M * K, da, s));
+    SC_TRY(upload(W, (size_t)N * K, dw, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 4, s));
+    sc_launch_gemm_i8_diag(da.p, dw.p, dc.p, M, N, K, s);
+    return download(dc.p, (size_t)M * N * 4, out, s);
+}
+
+namespace {
+// device-resident synthetic operands of one GEMM shape (sc_diag_gemm_trace, sc_diag_gemm_bench): A ~ N(0,1), W ~ 0.05 N(0,1), both
+// bf16; bias and residual zero
+struct SynthGemm {
+    int epi, M, N, K;
+    sc_devbuf fa, da, fw, dw, db, dr, dc;
+    sc_status init(hipStream_t s) {
+        const int64_t na = (int64_t)M * K, nw = (int64_t)N * K, nc = (int64_t)M * N;
+        SC_TRY(dev_alloc(fa, na * 4));
+        SC_TRY(dev_alloc(da, na * 2));
+        SC_TRY(dev_alloc(fw, nw * 4));
+        SC_TRY(dev_alloc(dw, nw * 2));
+        SC_TRY(dev_alloc(db, (size_t)N * 4));
+        SC_TRY(dev_alloc(dr, nc * 2));
+        SC_TRY(dev_alloc(dc, nc * 2));
+        sc_launch_synth_scaled((float*)fa.p, na, 1, 1.0f, 0.0f, s);
+        sc_launch_synth_scaled((float*)fw.p, nw, 2, 0.05f, 0.0f, s);
+        sc_launch_f32_to_bf16((const float*)fa.p, da.p, na, s);
+        sc_launch_f32_to_bf16((const float*)fw.p, dw.p, nw, s);
+        SC_HIP(hipMemsetAsync(db.p, 0, (size_t)N * 4, s));
+        SC_HIP(hipMemsetAsync(dr.p, 0, (size_t)nc * 2, s));
+        return SC_OK;
+    }
+    void launch(hipStream_t s) const { sc_launch_gemm_bf16(epi, da.p, K, dw.p, K, (const float*)db.p, dr.p, N, dc.p, N, M, N, K, s); }
+};
+}  // namespace
+
+// Per-workgroup time stamps of the 256-tile kernel: out [launch][tile][8] words of back-to-back traced launches (as many as fit into
+// cap_words) on synthetic operands
+extern "C" sc_status sc_diag_gemm_trace(sc_runtime* rt, int32_t epi, int32_t M, int32_t N, int32_t K, uint64_t* out, int64_t cap_words) {
+    if (!rt || !out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_trace: bad argument");
+    if (M <= 0 || N <= 0 || K <= 0 || (M % 256) || (N % 256) || (K % 64)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_trace: need M%%256==0, N%%256==0, K%%64==0");
+    const int64_t ntiles = (int64_t)(M / 256) * (N / 256);
+    const int64_t launches = cap_words / (ntiles * 8);
+    if (launches < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_trace: out too small (need 8 words per tile)");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    SynthGemm g{epi, M, N, K};
+    sc_devbuf tr;
+    const size_t trace_bytes = (size_t)launches * ntiles * 64;
+    SC_TRY(dev_alloc(tr, trace_bytes));
+    SC_TRY(g.init(s));
+    SC_HIP(hipMemsetAsync(tr.p, 0, trace_bytes, s));
+    static const int dbg = (int)sc_env_i64("SC_GEMM_TRACE_DBG", 0);  // stamps around an ablated main loop (scripts/gemm_clock.py)
+    sc_gemm_set_debug(dbg);
+    for (int i = 0; i < 2; ++i) g.launch(s);
+    for (int64_t l = 0; l < launches; ++l) {
+        sc_gemm_set_trace((unsigned long long*)tr.p + l * ntiles * 8);
+        g.launch(s);
+    }
+    sc_gemm_set_trace(nullptr);
+    sc_gemm_set_debug(0);
+    hipError_t he = hipStreamSynchronize(s);
+    if (he != hipSuccess) return sc_fail(SC_ERR_HIP, "diag gemm trace failed: %s", hipGetErrorString(he));
+    SC_HIP(hipMemcpy(out, tr.p, trace_bytes, hipMemcpyDeviceToHost));
+    return SC_OK;
+}
+
+// Time `iters` launches of one GEMM shape on device-resident synthetic bf16 data (hipEvents on the
+// runtime's stream).  variant: 0 = product kernel; 1/2/4/5 = diagnostic ablations of the 256-tile kernel
+// (no in-loop LDS-DMA / no MFMA / no epilogue / no DMA + no epilogue); 128 = force the 128x128 tile.
+extern "C" sc_status sc_diag_gemm_bench(sc_runtime* rt, int32_t epi, int32_t M, int32_t N, int32_t K, int32_t iters, int32_t variant,
+                                        double* ms_per_launch) {
+    if (!rt || !ms_per_launch || iters < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bench: bad argument");
+    if (!sc_gemm_bf16_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_bench: need M%%128==0, N%%128==0, K%%64==0");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    SynthGemm g{epi, M, N, K};
+    SC_TRY(g.init(s));
+    // variant = 100000 * pp + v: pp = main loop of the 256-tile kernel (0 = as configured, 1 = one barrier per K-tile, 2..5 = ping-pong depth)
+    const int pp = variant / 100000;
+    variant %= 100000;
+    sc_gemm_set_pp(pp == 0 ? -1 : pp == 1 ? 0 : pp);
+    sc_gemm_force_tile128(variant == 128);
+    sc_gemm_set_debug((variant == 128 || variant >= 1000) ? 0 : variant);
+    sc_gemm_set_order(variant >= 1000 ? variant - 1000 : 16);  // variants 1000+o: tile order o with the real epilogue
+    hipEvent_t e0, e1;
+    SC_HIP(hipEventCreate(&e0));
+    SC_HIP(hipEventCreate(&e1));
+    for (int i = 0; i < 2; ++i) g.launch(s);
+    hipEventRecord(e0, s);
+    for (int i = 0; i < iters; ++i) g.launch(s);
+    hipEventRecord(e1, s);
+    hipError_t he = hipStreamSynchronize(s);
+    sc_gemm_force_tile128(false);
+    sc_gemm_set_debug(0);
+    sc_gemm_set_order(16);
+    sc_gemm_set_pp(-1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+    if (he != hipSuccess) return sc_fail(SC_ERR_HIP, "diag gemm bench failed: %s", hipGetErrorString(he));
+    *ms_per_launch = ms / iters;
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------ the LayerNorm-folded pipeline and the stand-alone kernels, one launch each
+
+// fold_ln_weights_kernel: W [N,K], gamma / beta [K], bias [N] or NULL (all f32) -> Wf [N,K] (the bf16 W', widened), c1 [N], c2 [N]
+extern "C" sc_status sc_diag_fold_ln(sc_runtime* rt, const float* W, const float* gamma, const float* beta, const float* bias, int32_t N, int32_t K,
+                                     float* Wf, float* c1, float* c2) {
+    if (!rt || !W || !gamma || !beta || !Wf || !c1 || !c2) return sc_fail(SC_ERR_INVALID, "sc_diag_fold_ln: NULL argument");
+    if (N < 1 || K < 4 || (K % 4)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_fold_ln: need N >= 1 and K a multiple of 4");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf dw, dg, db, dbias, dwf, dc1, dc2;
+    SC_TRY(upload(W, (size_t)N * K * 4, dw, s));
+    SC_TRY(upload(gamma, (size_t)K * 4, dg, s));
+    SC_TRY(upload(beta, (size_t)K * 4, db, s));
+    if (bias) SC_TRY(upload(bias, (size_t)N * 4, dbias, s));
+    SC_TRY(alloc_nan(dwf, (size_t)N * K * 2, s));
+    SC_TRY(alloc_nan(dc1, (size_t)N * 4, s));
+    SC_TRY(alloc_nan(dc2, (size_t)N * 4, s));
+    sc_launch_fold_ln_weights((const float*)dw.p, (const float*)dg.p, (const float*)db.p, bias ? (const float*)dbias.p : nullptr, N, K, dwf.p, (float*)dc1.p,
+                              (float*)dc2.p, s);
+    SC_TRY(download(dc1.p, (size_t)N * 4, c1, s));
+    SC_TRY(download(dc2.p, (size_t)N * 4, c2, s));
+    return download_bf16(dwf.p, (int64_t)N * K, Wf, s);
+}
+
+// EPI_LNA_BIAS / EPI_LNA_GELU / EPI_LNA_BIAS_ROPE through sc_launch_gemm_bf16_ln.  A [M,K] raw rows, Wf [N,K] / c1 / c2 [N] as
+// sc_diag_fold_ln returned them, stats_in [K/256][M][2] the caller's partial (sum, sum of squares).  flags bit 0: C in 64-column blocks
+// ([N/64][M][64], returned that way).  Rotary form: positions = row & (rope_S - 1), tables of sc_rope_table.
+extern "C" sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* Wf, const float* c1, const float* c2,
+                                      const float* stats_in, float eps, int32_t M, int32_t N, int32_t K, int32_t rope_S, float rope_theta,
+                                      int32_t rope_ncols, float* C, float* fin) {
+    if (!rt || !A || !Wf || !c1 || !c2 || !stats_in || !C || !fin) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: NULL argument");
+    if (epi != EPI_LNA_BIAS && epi != EPI_LNA_GELU && epi != EPI_LNA_BIAS_ROPE) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: epilogue must be 3, 4 or 6");
+    if ((flags & ~1) || !(eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: bad flags / eps");
+    if (!sc_gemm_ln_supported(M, N, K) || K > 4096) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_lna: need M%%256==0, N%%256==0, K%%256==0, K<=4096");
+    const bool rope = epi == EPI_LNA_BIAS_ROPE;
+    if (rope && (rope_S < 1 || rope_S > 65536 || (rope_S & (rope_S - 1)) || rope_ncols < 0 || rope_ncols > N || (rope_ncols % 64)))
+        return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_lna: rope_S must be a power of two, rope_ncols a multiple of 64 within N");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fa, da, fw, dw, dc1, dc2, dst, dfin, dc, dt;
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(Wf, (int64_t)N * K, fw, dw, s));
+    SC_TRY(upload(c1, (size_t)N * 4, dc1, s));
+    SC_TRY(upload(c2, (size_t)N * 4, dc2, s));
+    SC_TRY(upload(stats_in, (size_t)(K / 256) * M * 8, dst, s));
+    SC_TRY(alloc_nan(dfin, (size_t)M * 8, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
+    const float *cos_t = nullptr, *sin_t = nullptr;
+    std::vector<float> tab;
+    if (rope) {
+        tab = sc_rope_table(rope_S, rope_theta);
+        SC_TRY(upload(tab.data(), tab.size() * 4, dt, s));
+        cos_t = (const float*)dt.p;
+        sin_t = cos_t + tab.size() / 2;
+    }
+    sc_launch_gemm_bf16_ln(epi, da.p, K, dw.p, K, (const float*)dc2.p, nullptr, 0, dc.p, (flags & 1) ? SC_LDC_BLOCKED64 : N, M, N, K, s, (const float*)dc1.p,
+                           (const float*)dst.p, (float*)dfin.p, nullptr, nullptr, eps, cos_t, sin_t, rope ? rope_S : 0, rope ? rope_ncols : 0);
+    SC_TRY(download(dfin.p, (size_t)M * 8, fin, s));  // synchronises: tab may go
+    return download_bf16(dc.p, (int64_t)M * N, C, s);
+}
+
+// EPI_RESLN_STATS through sc_launch_gemm_bf16_ln.  A [M,K] (flags bit 0: given as [K/64][M][64]), W [N,K], bias [N] (= b + beta), gam [N],
+// R [M,N] the raw residual, fin [M][2] its (mu, rs) -> C [M,N], stats_out [N/256][M][2].
+extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
+                                        const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out) {
+    if (!rt || !A || !W || !bias || !gam || !R || !fin || !C || !stats_out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_resln: NULL argument");
+    if ((flags & ~1) || !(eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_resln: bad flags / eps");
+    if (!sc_gemm_ln_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_resln: need M%%256==0, N%%256==0, K%%256==0");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fa, da, fw, dw, fr, dr, db, dg, dfin, dc, dso;
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(W, (int64_t)N * K, fw, dw, s));
+    SC_TRY(upload_bf16(R, (int64_t)M * N, fr, dr, s));
+    SC_TRY(upload(bias, (size_t)N * 4, db, s));
+    SC_TRY(upload(gam, (size_t)N * 4, dg, s));
+    SC_TRY(upload(fin, (size_t)M * 8, dfin, s));
+    SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
+    SC_TRY(alloc_nan(dso, (size_t)(N / 256) * M * 8, s));
+    sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, da.p, (flags & 1) ? SC_LDC_BLOCKED64 : K, dw.p, K, (const float*)db.p, dr.p, N, dc.p, N, M, N, K, s, nullptr, nullptr,
+                           (float*)dfin.p, (const float*)dg.p, (float*)dso.p, eps);
+    SC_TRY(download(dso.p, (size_t)(N / 256) * M * 8, stats_out, s));
+    return download_bf16(dc.p, (int64_t)M * N, C, s);
+}
+
+// sc_launch_attention as the pipelines call it.  blocked_rows == 0: qkv [B*S][3H] row-major; > 0: qkv [3 heads][blocked_rows][64], the layout
+// the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.
+static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                                const float* slopes, float* out) {
+    if (!rt || !qkv || !lens || !out || B < 1 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    const int H = heads * 64;
+    if (!sc_attention_supported(S, H, heads)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
+    const int64_t tokens = (int64_t)B * S;
+    if (blocked_rows && blocked_rows < tokens) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fq, dq, dl, dsl, dc;
+    SC_TRY(upload_bf16(qkv, (blocked_rows ? (int64_t)blocked_rows : tokens) * 3 * H, fq, dq, s));
+    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
+    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
+    sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows);
+    return download_bf16(dc.p, tokens * H, out, s);
+}
+extern "C" sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                                          const float* slopes, float* out) {
+    return diag_attention("sc_diag_attention_ex", rt, qkv, lens, B, S, heads, blocked_rows, slopes, out);
+}
+extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out) {
+    return diag_attention("sc_diag_attention", rt, qkv, lens, B, S, heads, 0, nullptr, out);
+}
+
+// rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],
+// rotated in place, widened and laid out row-major again.
+extern "C" sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta) {
+    if (!rt || !qk || rows < 1 || heads < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_rope: bad argument");
+    if (S < 1 || S > 65536 || (S & (S - 1))) return sc_fail(SC_ERR_INVALID, "sc_diag_rope: S must be a power of two");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    const int64_t n = (int64_t)rows * heads * 64;
+    std::vector<float> blk((size_t)n);
+    const std::vector<float> tab = sc_rope_table(S, theta);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int h = 0; h < heads; ++h) memcpy(&blk[((size_t)h * rows + r) * 64], qk + ((size_t)r * heads + h) * 64, 256);
+    sc_devbuf fb, db, dt;
+    SC_TRY(upload_bf16(blk.data(), n, fb, db, s));
+    SC_TRY(upload(tab.data(), tab.size() * 4, dt, s));
+    sc_launch_rope_qk(db.p, rows, heads, S, (const float*)dt.p, (const float*)dt.p + tab.size() / 2, s);
+    SC_TRY(download_bf16(db.p, n, blk.data(), s));
+    for (int64_t r = 0; r < rows; ++r)
+        for (int h = 0; h < heads; ++h) memcpy(qk + ((size_t)r * heads + h) * 64, &blk[((size_t)h * rows + r) * 64], 256);
+    return SC_OK;
+}
+
+// layernorm_kernel<3|4|8>: x [tokens,H] -> out [tokens,H]
+extern "C" sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out) {
+    if (!rt || !x || !gamma || !beta || !out || tokens < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_layernorm: bad argument");
+    if (H < 8 || (H % 8) || H > 2048 || !(eps > 0.f)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_layernorm: H must be a multiple of 8, <= 2048");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fx, dx, dg, db, dc;
+    SC_TRY(upload_bf16(x, (int64_t)tokens * H, fx, dx, s));
+    SC_TRY(upload(gamma, (size_t)H * 4, dg, s));
+    SC_TRY(upload(beta, (size_t)H * 4, db, s));
+    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
+    sc_launch_layernorm(dx.p, tokens, H, (const float*)dg.p, (const float*)db.p, eps, dc.p, s);
+    return download_bf16(dc.p, (int64_t)tokens * H, out, s);
+}
+
+// sc_launch_mean_pool: normalize 0 = mean_pool_sliced_kernel, 1 = mean_pool_kernel with the L2 normalisation.  x [B*S,H] -> out [B,H] f32
+extern "C" sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out) {
+    if (!rt || !x || !lens || !out || B < 1 || S < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool: bad argument");
+    if (H < 8 || (H % 8)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_mean_pool: H must be a multiple of 8");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fx, dx, dl, dout;
+    SC_TRY(upload_bf16(x, (int64_t)B * S * H, fx, dx, s));
+    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * H * 4, s));
+    sc_launch_mean_pool(dx.p, (const int32_t*)dl.p, B, S, H, normalize ? 1 : 0, (float*)dout.p, s);
+    return download(dout.p, (size_t)B * H * 4, out, s);
+}
+
+// mean_pool_ln_kernel: y [tokens_pad,H] raw rows (the first B*S are read), stats [slots][tokens_pad][2] -> out [B,H] f32
+extern "C" sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,
+                                          const float* beta, float eps, const int32_t* lens, int32_t B, int32_t S, int32_t H, float* out) {
+    if (!rt || !y || !stats || !gamma || !beta || !lens || !out || B < 1 || S < 1 || slots < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool_ln: bad argument");
+    if (H < 8 || (H % 8) || !(eps > 0.f)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_mean_pool_ln: H must be a multiple of 8");
+    if ((int64_t)tokens_pad < (int64_t)B * S) return sc_fail(SC_ERR_INVALID, "sc_diag_mean_pool_ln: tokens_pad < B*S");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fy, dy, dst, dg, db, dl, dout;
+    SC_TRY(upload_bf16(y, (int64_t)tokens_pad * H, fy, dy, s));
+    SC_TRY(upload(stats, (size_t)slots * tokens_pad * 8, dst, s));
+    SC_TRY(upload(gamma, (size_t)H * 4, dg, s));
+    SC_TRY(upload(beta, (size_t)H * 4, db, s));
+    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * H * 4, s));
+    sc_launch_mean_pool_ln(dy.p, (const float*)dst.p, slots, tokens_pad, (const float*)dg.p, (const float*)db.p, eps, (const int32_t*)dl.p, B, S, H, (float*)dout.p, s);
+    return download(dout.p, (size_t)B * H * 4, out, s);
+}
+
+// The gate kernels between the two FFN GEMMs: h [rows, 2F] (gate | up) -> out [rows, F] = act(gate) * up
+static sc_status diag_gate(const char* who, bool swiglu, sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) {
+    if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "%s: bad argument (F must be a multiple of 8)", who);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fh, dh, dc;
+    SC_TRY(upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s));
+    SC_TRY(alloc_nan(dc, (size_t)rows * F * 2, s));
+    if (swiglu) sc_launch_swiglu(dh.p, rows, F, dc.p, s);
+    else sc_launch_geglu(dh.p, rows, F, dc.p, s);
+    return download_bf16(dc.p, (int64_t)rows * F, out, s);
+}
+// glu_kernel<ActGelu>: gelu(gate) * up
+extern "C" sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_geglu", false, rt, h, rows, F, out); }
+// swiglu_kernel: silu(gate) * up
+extern "C" sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_swiglu", true, rt, h, rows, F, out); }
+
+// The embedding kernels.  ln == 0: embed_raw_kernel -> rows [tokens_pad,H] + stats [slots][tokens_pad][2]; ln != 0: embed_ln_kernel ->
+// rows [tokens,H] (tokens_pad, slots, stats unused).  ids [tokens] (tokens = B*S, position = token % S), wemb [vocab,H], pemb [max_pos,H] or
+// NULL, temb [>= 1, H] (row 0 is used), all f32.
+extern "C" sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* ids, int32_t tokens, int32_t S, int32_t H, int32_t vocab, int32_t max_pos,
+                                   const float* wemb, const float* pemb, const float* temb, const float* gamma, const float* beta, float eps,
+                                   int32_t tokens_pad, int32_t slots, float* rows, float* stats) {
+    if (!rt || !ids || !wemb || !temb || !rows || tokens < 1 || S < 1 || vocab < 1 || max_pos < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: bad argument");
+    if (H < 4 || (H % 4) || H > 2048) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_embed: H must be a multiple of 4, <= 2048");
+    if (ln && (!gamma || !beta || !(eps > 0.f))) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: the LayerNorm form needs gamma, beta, eps");
+    if (!ln && (!stats || tokens_pad < tokens || slots < 1 || slots > 64)) return sc_fail(SC_ERR_INVALID, "sc_diag_embed: the raw form needs stats, tokens_pad >= tokens, 1 <= slots <= 64");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf di, dw, dp, dt, dg, db, dout, dst;
+    SC_TRY(upload(ids, (size_t)tokens * 4, di, s));
+    SC_TRY(upload(wemb, (size_t)vocab * H * 4, dw, s));
+    if (pemb) SC_TRY(upload(pemb, (size_t)max_pos * H * 4, dp, s));
+    SC_TRY(upload(temb, (size_t)H * 4, dt, s));
+    const int64_t nrows = ln ? tokens : tokens_pad;
+    SC_TRY(alloc_nan(dout, (size_t)nrows * H * 2, s));
+    if (ln) {
+        SC_TRY(upload(gamma, (size_t)H * 4, dg, s));
+        SC_TRY(upload(beta, (size_t)H * 4, db, s));
+        sc_launch_embed_ln((const int32_t*)di.p, tokens, S, H, vocab, max_pos, (const float*)dw.p, pemb ? (const float*)dp.p : nullptr, (const float*)dt.p,
+                           (const float*)dg.p, (const float*)db.p, eps, dout.p, s);
+    } else {
+        SC_TRY(alloc_nan(dst, (size_t)slots * tokens_pad * 8, s));
+        sc_launch_embed_raw((const int32_t*)di.p, tokens, tokens_pad, S, H, vocab, max_pos, (const float*)dw.p, pemb ? (const float*)dp.p : nullptr,
+                            (const float*)dt.p, dout.p, (float*)dst.p, slots, s);
+        SC_TRY(download(dst.p, (size_t)slots * tokens_pad * 8, stats, s));
+    }
+    return download_bf16(dout.p, nrows * H, rows, s);
+}

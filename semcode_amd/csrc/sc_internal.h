@@ -43,6 +43,14 @@ void sc_runtime_retain(sc_runtime* rt);
 void sc_runtime_release(sc_runtime* rt);  // frees the runtime when the last reference is dropped
 void sc_prof_begin(sc_runtime* rt, int which, hipEvent_t* a, hipEvent_t* b);
 void sc_prof_end(sc_runtime* rt, int which, hipEvent_t a, hipEvent_t b);
+// the pair around the launches that `launch` issues
+template <class F>
+static inline void sc_with_prof(sc_runtime* rt, int which, F&& launch) {
+    hipEvent_t a, b;
+    sc_prof_begin(rt, which, &a, &b);
+    launch();
+    sc_prof_end(rt, which, a, b);
+}
 
 // A growable device allocation: sc_grow makes room (contents lost), sc_buf_free returns it.
 struct sc_buf {
@@ -197,3 +205,14 @@ static inline int64_t sc_ivf_pos(const sc_index* ix, int64_t r) { return r < ix-
 // upsert body shared by sc_index_put_rows{,_dev} and sc_encoder_embed_ids_into; caller holds ix->mu and has set the device
 sc_status sc_index_put_rows_locked(sc_index* ix, const float* vecs, bool vecs_on_device, const int64_t* rows, int64_t n, const char* who);
 bool sc_ivf_applicable(const sc_index* ix, int Q, int nprobe);
+
+// process-wide test / A-B knobs behind sc_diag_set_option (sc_api.cpp), each defined next to the code it steers
+void sc_ivf_set_refresh_nomem(int v);  // sc_ivf.cpp
+void sc_ivf_set_refine_cap(int v);
+void sc_ivf_set_coarse_nomem(int v);
+void sc_set_collect_pass(int v);       // sc_search.cpp
+void sc_set_tighten(int v);
+void sc_set_wide_force(int v);
+void sc_set_ivf_tail_rows(int v);
+void sc_set_delete_chunk_rows(int v);  // sc_delete.cpp
+void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp

@@ -317,3 +317,54 @@ def test_jina_v2_base_shape(rt):
     lens = np.array([128, 77, 40], np.int32)
     check_pooled(enc.embed_ids(ids, lens), bo.forward(cfg, blob, ids, lens))
     enc.close()
+
+
+def test_embed_entry_points_agree(rt):
+    """The four embed entry points side by side on one ragged batch, per pipeline: embed_ids, embed_ids_dev, embed_ids_into and its
+    asynchronous form return / store the same bytes; three asynchronous batches before one wait() (the third re-uses the first pinned
+    slot, so it has to wait for the first batch) store their own rows; an index of another dimension is refused by name."""
+    import torch
+
+    cfg = dict(bo.BERT_BASE, vocab=1000, hidden=256, heads=4, ffn=512, layers=2, max_pos=64)  # smallest shape the folded pipeline takes
+    enc = _native.Encoder(rt, cfg, weights=None, synth_seed=3)
+    rng = np.random.default_rng(8)
+    B, S = 3, 32
+    batches = [rng.integers(1, 1000, size=(B, S)).astype(np.int32) for _ in range(3)]
+    ids, lens = batches[0], np.array([32, 7, 1], np.int32)
+    rows = np.arange(B, dtype=np.int64)
+    for path in ("small", "batch"):
+        enc.set_path(path)
+        want = enc.embed_ids(ids, lens)
+        assert np.isfinite(want).all()
+        ids_d, lens_d = torch.from_numpy(ids).to("cuda:0"), torch.from_numpy(lens).to("cuda:0")
+        out_d = torch.full((B, 256), float("nan"), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        enc.embed_ids_dev(ids_d.data_ptr(), lens_d.data_ptr(), B, S, out_d.data_ptr())
+        rt.synchronize()
+        assert out_d.cpu().numpy().tobytes() == want.tobytes(), path
+        ix = _native.Index(rt, 256, metric="IP", kind="FLAT")
+        got = enc.embed_ids_into(ids, lens, ix, rows, want_host=True)
+        assert got.tobytes() == want.tobytes(), path
+        assert len(ix) == B and ix.get_rows(0, B).tobytes() == want.tobytes(), path
+        ix.close()
+        ix = _native.Index(rt, 256, metric="IP", kind="FLAT")
+        assert enc.embed_ids_into(ids, lens, ix, rows, wait=False) is None
+        enc.wait()
+        assert len(ix) == B and ix.get_rows(0, B).tobytes() == want.tobytes(), path
+        ix.close()
+        each = [enc.embed_ids(b, lens) for b in batches]
+        assert not np.array_equal(each[0], each[2])
+        ix = _native.Index(rt, 256, metric="IP", kind="FLAT")
+        for i, b in enumerate(batches):
+            enc.embed_ids_into(b, lens, ix, rows + i * B, wait=False)
+        enc.wait()
+        assert len(ix) == 3 * B and ix.get_rows(0, 3 * B).tobytes() == np.concatenate(each).tobytes(), path
+        ix.close()
+    other = _native.Index(rt, 128, metric="IP", kind="FLAT")
+    for wait, name in ((True, "sc_encoder_embed_ids_into:"), (False, "sc_encoder_embed_ids_into_async:")):
+        with pytest.raises(_native.ScError) as err:
+            enc.embed_ids_into(ids, lens, other, rows, wait=wait)
+        assert err.value.status == -1 and name in str(err.value), str(err.value)  # SC_ERR_INVALID
+    assert len(other) == 0
+    other.close()
+    enc.close()
