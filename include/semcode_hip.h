@@ -336,6 +336,39 @@ sc_status sc_index_search(sc_index* ix, const float* q, int32_t Q, int32_t k, in
 sc_status sc_index_search_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe,
                               float* out_dist_dev, int64_t* out_rows_dev);
 
+/* Filtered search: Collection.search(..., expr=...) restricted to a set of rows the caller names.  (The reference has no such
+ * call: its front ends drop the hits of an unfiltered top-k that fail the user's repo / language filter, src/semcode/frontend/app.py:100-116,
+ * so a small repo in a large collection usually shows nothing.)  The index learns nothing about repos or languages: `allow` is a
+ * bitset over LOCAL row numbers, bit (r & 31) of 32-bit word (r >> 5) set = row r may be returned; allow_words >= ceil(rows / 32);
+ * bits at or beyond `rows` are ignored.  The result is, bit for bit, the exact exhaustive answer of an index that holds only the
+ * allowed rows: ids are the rows' own (row_base + local row), distances the canonical fmaf chain, best first, ties by lower row
+ * id, padded with -1 and +inf (L2) / -inf (IP, COSINE) when fewer than k rows are allowed.  All three metrics.  Always exact:
+ * there is no nprobe, and a trained IVF_FLAT index is scanned where its rows lie -- listed rows through the position map, rows
+ * appended since the layout behind the lists, overwritten rows in place -- without a refresh, a re-layout or k-means; a pending
+ * tail and pending overwritten rows stay pending.  Nothing about later unmasked searches changes.
+ * How: the bitset is compacted on the device into the ascending list of allowed stored positions (two deterministic passes, no
+ * atomics), and a gathered form of the exact scan streams only those rows -- its 16-row tiles are fed by per-lane source addresses
+ * from that list (HBM bytes = allowed * ld * 4 per pass of <= 16 queries; a larger batch runs ceil(Q / 16) passes in one launch).
+ * The queries of a pass are resident in LDS, so rows too long for 16 of them take more passes: 3 072 dimensions leave room for
+ * 6, i.e. 3 passes for 16 queries.  No allowed row, or an empty index: no scan is launched.  Every row allowed: the ordinary
+ * exhaustive planner answers (same bits, and the batched path for large batches).
+ * k outside 1 .. 1024, Q < 1, a NULL pointer or allow_words < ceil(rows / 32) give SC_ERR_INVALID before anything changes.
+ * Host pointers; synchronises.
+ * Out of scope: masks on the batched MFMA path and on the IVF probe paths (approximate filtered search), sharded collections
+ * (sc_index_search_sharded*), a `paths` filter, Milvus expr strings. */
+sc_status sc_index_search_masked(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint32_t* allow, int64_t allow_words,
+                                 float* out_dist, int64_t* out_rows);
+/* Same with DEVICE pointers (q row stride = dim), enqueued on the runtime's stream.  Synchronises the stream ONCE per call: the
+ * number of allowed rows is read back to size the scan's grid and to take the two shortcuts above (plus whatever the exhaustive
+ * planner waits for when every row is allowed, see sc_index_search_dev); the per-index mutex is held meanwhile.  Results are
+ * complete once the stream has passed the call. */
+sc_status sc_index_search_masked_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev,
+                                     int64_t allow_words, float* out_dist_dev, int64_t* out_rows_dev);
+/* After a masked search: rows its bitset allowed, rows the scan that answered read per pass (0: no scan was launched; allowed_rows:
+ * the gathered scan; all rows: the exhaustive planner) and whether the gathered kernel ran.  "mask_gather" of sc_diag_set_option
+ * (1) forces the gathered kernel even when every row is allowed (tests; results are identical; default 0). */
+sc_status sc_index_last_mask_stats(sc_index* ix, int64_t* allowed_rows, int64_t* scanned_rows, int32_t* gathered);
+
 /* Replaces Collection.create_index(IVF_FLAT, nlist) + load() (milvus_store.py:76-84) for an index created with
  * SC_INDEX_IVF_FLAT: deterministic k-means (niter Lloyd iterations on <= 256*nlist sampled rows), assignment of
  * every row to its nearest centroid, list-major re-ordering of the corpus in HBM.  Until it is called an IVF_FLAT index
@@ -366,7 +399,8 @@ sc_status sc_index_ivf_info(sc_index* ix, int32_t* nlist, float* centroids, int6
  * In mode 0 a trained IVF_FLAT index probes per query while Q * nprobe < nlist, list-major while that is estimated to be
  * cheaper than the exhaustive paths, and otherwise answers exhaustively (exact results). */
 sc_status sc_index_set_search_mode(sc_index* ix, int32_t mode);
-/* After a search: which path ran (1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major) and how many queries the batched path had to
+/* After a search: which path ran (1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 list-major behind the int8 coarse
+ * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner) and how many queries the batched path had to
  * re-run through the exact scan because their certificate failed. */
 sc_status sc_index_last_search_stats(sc_index* ix, int32_t* path, int32_t* uncertified);
 

@@ -109,6 +109,9 @@ SIGNATURES = {
     "sc_index_release_scratch": (C.c_int32, [C.c_void_p]),
     "sc_index_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_index_search_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_index_search_masked": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_search_masked_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_last_mask_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sc_index_train": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
     "sc_index_ivf_assignments": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "sc_index_set_ivf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -170,6 +173,22 @@ def _check(status: int) -> None:
         buf = C.create_string_buffer(512)
         lib().sc_last_error(buf, 512)
         raise ScError(status, buf.value.decode("utf-8", "replace"))
+
+
+def pack_allow(allow, rows: int) -> np.ndarray:
+    """The bitset of a masked search as uint32 words (bit r & 31 of word r >> 5 = row r may be returned): a uint32 array is taken as
+    the words themselves, a boolean array must have one entry per row and is packed."""
+    a = np.asarray(allow)
+    if a.dtype == np.bool_:
+        if a.shape != (rows,):
+            raise ValueError(f"a boolean mask must have one entry per row ({rows}), got shape {a.shape}")
+        bits = np.packbits(a, bitorder="little")
+        words = np.zeros((rows + 31) // 32 * 4, dtype=np.uint8)
+        words[: bits.size] = bits
+        return words.view("<u4")
+    if a.dtype != np.uint32 or a.ndim != 1:
+        raise ValueError("allow must be a 1-d uint32 word array or a boolean array with one entry per row")
+    return np.ascontiguousarray(a)
 
 
 def _as_f32(a, shape_last: int | None = None) -> np.ndarray:
@@ -357,6 +376,32 @@ class Index:
                                      dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
 
+    def search_masked(self, queries, allow, k: int = 10) -> tuple[np.ndarray, np.ndarray]:
+        """Exact search over the allowed rows only (sc_index_search_masked): allow = uint32 bitset words over local row numbers or a
+        boolean array of length len(index).  -> (dist [Q, k], rows [Q, k]) as search(); fewer than k allowed rows: padded with -1."""
+        q = _as_f32(queries, self.dim)
+        Q = q.shape[0]
+        words = pack_allow(allow, len(self))
+        if words.size == 0:  # an empty index: still a valid pointer
+            words = np.zeros(1, dtype=np.uint32)
+        dist = np.empty((Q, k), dtype=np.float32)
+        rows = np.empty((Q, k), dtype=np.int64)
+        _check(lib().sc_index_search_masked(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), words.ctypes.data_as(C.c_void_p), words.shape[0],
+                                            dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return dist, rows
+
+    def search_masked_dev(self, q_ptr: int, Q: int, k: int, allow_ptr: int, allow_words: int, dist_ptr: int, rows_ptr: int) -> None:
+        """Device-pointer variant (enqueued on the runtime's stream; synchronises it once: sc_index_search_masked_dev)."""
+        _check(lib().sc_index_search_masked_dev(self.handle, C.c_void_p(q_ptr), int(Q), int(k), C.c_void_p(allow_ptr), int(allow_words),
+                                                C.c_void_p(dist_ptr), C.c_void_p(rows_ptr)))
+
+    def last_mask_stats(self) -> dict:
+        """After a masked search: rows the bitset allowed, rows the answering scan read per pass (0: none launched), and whether the
+        gathered kernel ran (sc_index_last_mask_stats)."""
+        a, sc, g = C.c_int64(), C.c_int64(), C.c_int32()
+        _check(lib().sc_index_last_mask_stats(self.handle, C.byref(a), C.byref(sc), C.byref(g)))
+        return {"allowed_rows": int(a.value), "scanned_rows": int(sc.value), "gathered": bool(g.value)}
+
     def train(self, niter: int = 10, seed: int = 0) -> None:
         """IVF_FLAT: k-means + list build (sc_index_train)."""
         _check(lib().sc_index_train(self.handle, int(niter), int(seed)))
@@ -407,7 +452,7 @@ class Index:
         path, unc, bits, handed = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().sc_index_last_search_stats(self.handle, C.byref(path), C.byref(unc)))
         _check(lib().sc_index_last_coarse_stats(self.handle, C.byref(bits), C.byref(handed)))
-        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse"}[path.value], "uncertified": unc.value}
+        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked"}[path.value], "uncertified": unc.value}
         if path.value in (3, 4, 5):
             tail = C.c_int64()
             _check(lib().sc_index_last_tail_rows(self.handle, C.byref(tail)))

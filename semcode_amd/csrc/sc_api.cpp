@@ -199,7 +199,7 @@ extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
         {"ivf_coarse_nomem", sc_ivf_set_coarse_nomem},        {"collect_pass", sc_set_collect_pass},
         {"tighten", sc_set_tighten},                          {"wide_candidates", sc_set_wide_force},
         {"ivf_tail_rows", sc_set_ivf_tail_rows},              {"delete_chunk_rows", sc_set_delete_chunk_rows},
-        {"rope_fused", sc_encoder_set_rope_fused},
+        {"rope_fused", sc_encoder_set_rope_fused},            {"mask_gather", sc_set_mask_gather},
     };
     for (const auto& o : options)
         if (!strcmp(name, o.name)) {

@@ -154,6 +154,19 @@ void sc_launch_scan_exact(int metric, const float* X, const float* xnorm, int64_
 bool sc_scan_listgemm_supported(int ld, int k);
 void sc_launch_scan_listgemm(int metric, int width, const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, int k, int groups,
                              uint64_t* partial, const uint32_t* perm, const int64_t* seg_rows, const int32_t* qmap, hipStream_t s);
+// scan_masked.hip: the masked search (sc_index_search_masked*).
+// mask_compact: allow (bitset over row ids) -> sel[m], the ascending list of allowed stored positions among [0, n), padded to a
+// multiple of 16 entries; perm [perm_rows]: stored position -> row id (positions at or beyond perm_rows are row ids; NULL: all are).
+// Two launchers with the host's read of cnt[blocks] (= m) between them: ..._count fills flags [(n + 63) / 64] (bitset over
+// positions) and cnt [blocks + 1] (exclusive scan of the per-block popcounts, total last); ..._scatter writes sel.
+#define SC_MASK_BLOCK_ROWS 2048
+static inline int64_t sc_mask_blocks(int64_t n) { return (n + SC_MASK_BLOCK_ROWS - 1) / SC_MASK_BLOCK_ROWS; }
+void sc_launch_mask_count(const uint32_t* allow, int64_t n, const uint32_t* perm, int64_t perm_rows, uint64_t* flags, uint32_t* cnt, hipStream_t s);
+void sc_launch_mask_scatter(const uint64_t* flags, const uint32_t* cnt, int64_t n, uint32_t* sel, hipStream_t s);
+// the gathered exact scan: sc_launch_scan_exact (resident queries; plan from sc_scan_exact_plan with force_qt = 16 and n_rows = m) over
+// the m stored positions sel[] instead of a row range; reported ids = perm[position] below perm_rows, the position itself beyond
+void sc_launch_scan_gather(int metric, const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, int Q, int k, const ScanPlan& p,
+                           uint64_t* partial, const uint32_t* perm, int64_t perm_rows, const uint32_t* sel, int64_t m, hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

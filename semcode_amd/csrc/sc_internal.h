@@ -116,6 +116,11 @@ struct sc_index {
     sc_buf fb, fb2;                               // fallback staging (queries + results) of the first stage's uncertified queries; the same for the second stage (int8 -> bf16 -> exact)
     sc_buf tailbuf;                               // two [Q][k] result sets of a search that answers from the lists and from the tail (sc_search.cpp)
     int64_t last_tail_rows = 0;                   // rows the last search scanned behind the lists (0: none)
+    // masked search (sc_masked.cpp): the uploaded allow words of the host entry point; the bitset over stored positions + per-block counts
+    // and their scan; sel, the ascending allowed stored positions
+    sc_buf mask_words, mask_cnt, mask_sel;
+    int64_t last_mask_allowed = 0, last_mask_scanned = 0;  // sc_index_last_mask_stats
+    int last_mask_gathered = 0;
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -146,7 +151,7 @@ struct sc_index {
     int64_t last_unique_rows = 0, last_streamed_rows = 0;  // sc_index_last_probe_stats
     int last_groups = 0;
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
-    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major
+    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked
     int last_uncertified = 0;
     // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (sc_shadow::stat_bit) of the shadows kept / dropped
     int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
@@ -161,6 +166,7 @@ struct sc_index_buf { sc_buf sc_index::*buf; bool released; };
 inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
     {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
     {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
+    {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true},
     {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},
 };
 
@@ -215,4 +221,5 @@ void sc_set_tighten(int v);
 void sc_set_wide_force(int v);
 void sc_set_ivf_tail_rows(int v);
 void sc_set_delete_chunk_rows(int v);  // sc_delete.cpp
+void sc_set_mask_gather(int v);        // sc_masked.cpp
 void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp

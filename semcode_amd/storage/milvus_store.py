@@ -11,6 +11,7 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
                                                    settings.milvus_upsert_batch_size
     .search(vector, top_k=10)                   -> iterable of Hits; hit.entity.get(field), hit.distance,
                                                    hit.score, hit.id  (pymilvus SearchResult shape)
+    .search(..., repos=[..], languages=[..])    -> Collection.search(expr=...): only rows of these repos AND languages, exact
     .delete(ids) / .delete_where(repo=, path=, language=)
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
 
@@ -29,6 +30,7 @@ from typing import Any, Callable, Iterator, List, Optional, Sequence
 
 import numpy as np
 
+from .._native import pack_allow  # (numpy only: the library itself is loaded on first use, not on import)
 from ..embeddings.payload import EmbeddingPayload
 from ..settings import resolve as _resolve_settings
 
@@ -119,6 +121,13 @@ class MilvusVectorStore:
         self._paths: List[str] = []
         self._languages: List[str] = []
         self._row_of: dict[str, int] = {}
+        # filtered search: an integer code per row for repo and language (the device only sees row numbers: a filter becomes a bitset
+        # over rows, built with np.isin over these instead of a Python loop over the strings) and the packed bitsets built so far
+        self._repo_code: dict[str, int] = {}
+        self._lang_code: dict[str, int] = {}
+        self._repo_codes = np.zeros(0, dtype=np.int32)  # capacity >= len(self._ids); entries beyond it are unused
+        self._lang_codes = np.zeros(0, dtype=np.int32)
+        self._mask_cache: dict = {}  # (frozenset(repos) | None, frozenset(languages) | None) -> (words, every row passes); dropped on every mutation
         # IVF_FLAT lists are built lazily before a search (Milvus' background index build).  Once built they are kept across
         # upserts: the device index assigns upserted rows to the existing centroids at the next search (no k-means, like
         # Collection.upsert into an indexed collection, milvus_store.py:128).  k-means runs again only on build_index() or when
@@ -231,8 +240,10 @@ class MilvusVectorStore:
 
     def commit_rows(self, ids: Sequence[str], rows: np.ndarray, texts: Sequence[str], metadatas: Sequence[dict]) -> None:
         """Scalar columns + primary-key map for rows whose vectors have just been written (same mapping as _upsert_batch)."""
+        self._mask_cache.clear()
         for pk, row, text, meta in zip(ids, rows.tolist(), texts, metadatas):
             cols = (meta.get("repo", ""), meta.get("path", ""), meta.get("language", ""))
+            self._set_codes(row, cols[0], cols[2])
             if row == len(self._ids):
                 self._row_of[pk] = row
                 self._ids.append(pk)
@@ -246,6 +257,14 @@ class MilvusVectorStore:
                 self._texts[row] = text
                 self._metadata[row] = meta
         self._note_growth()
+
+    def _set_codes(self, row: int, repo: str, language: str) -> None:
+        if row >= self._repo_codes.size:
+            cap = max(1024, 2 * self._repo_codes.size, row + 1)
+            self._repo_codes = np.concatenate([self._repo_codes, np.zeros(cap - self._repo_codes.size, np.int32)])
+            self._lang_codes = np.concatenate([self._lang_codes, np.zeros(cap - self._lang_codes.size, np.int32)])
+        self._repo_codes[row] = self._repo_code.setdefault(repo, len(self._repo_code))
+        self._lang_codes[row] = self._lang_code.setdefault(language, len(self._lang_code))
 
     def _note_growth(self) -> None:
         n = len(self._ids)
@@ -344,28 +363,72 @@ class MilvusVectorStore:
             col = getattr(self, name)
             setattr(self, name, [col[r] for r in keep])
         self._row_of = {pk: r for r, pk in enumerate(self._ids)}
+        self._repo_codes = self._repo_codes[: gone.size][~gone]
+        self._lang_codes = self._lang_codes[: gone.size][~gone]
+        self._mask_cache.clear()
         if hasattr(ix, "__len__") and len(ix) != len(self._ids):
             raise RuntimeError(f"vector index holds {len(ix)} rows after the delete, the collection's columns expect {len(self._ids)}")
         return len(rows)
 
     # ------------------------------------------------------------------ search
-    def search(self, vector: "list[float]", top_k: int = 10) -> SearchResult:
-        """Run a raw vector search (one query), reference milvus_store.py:135-148."""
+    def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None) -> SearchResult:
+        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages: see search_batch."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
-        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k)
+        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages)
         return SearchResult([self._hits(dist[0], rows[0])])
 
-    def search_batch(self, queries: Any, top_k: int = 10) -> "tuple[np.ndarray, np.ndarray]":
-        """Batched search: queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64; -1 = no hit), best first."""
+    def search_batch(self, queries: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None) -> "tuple[np.ndarray, np.ndarray]":
+        """Batched search: queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64; -1 = no hit), best first.
+
+        repos / languages (Collection.search(expr=...) for the two filters of the reference front ends): None = no restriction, a
+        string or a collection of strings = only rows whose column value is one of them; both given = both must hold.  An empty
+        collection or unknown names match nothing: no hits.  A restricted search is always exact -- the exhaustive answer over the
+        rows that pass, never an IVF probe (Index.search_masked).  A filter that every row passes is today's unfiltered call."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"query dimension mismatch: collection dim={self.dim}, got shape {q.shape}")
         with self._lock:
-            self._maybe_train()
-            return self._collection.search(q, k=int(top_k), nprobe=self.nprobe)
+            flt = self._filter(repos, languages)
+            if flt is None or flt[1]:
+                self._maybe_train()
+                return self._collection.search(q, k=int(top_k), nprobe=self.nprobe)
+            ix = self._collection
+            if not hasattr(ix, "search_masked"):
+                raise NotImplementedError(f"{type(ix).__name__} has no search_masked(queries, allow, k): this vector index cannot filter")
+            return ix.search_masked(q, flt[0], k=int(top_k))
+
+    @staticmethod
+    def _name_set(names: Any) -> "Optional[frozenset]":
+        if names is None:
+            return None
+        return frozenset([names]) if isinstance(names, str) else frozenset(names)
+
+    def _filter(self, repos: Any, languages: Any) -> "Optional[tuple[np.ndarray, bool]]":
+        """(packed bitset over rows, every row passes) of a filter, cached until the next mutation; None without a filter.
+        Caller holds the lock."""
+        key = (self._name_set(repos), self._name_set(languages))
+        if key == (None, None):
+            return None
+        hit = self._mask_cache.get(key)
+        if hit is None:
+            n = len(self._ids)
+            ok = np.ones(n, dtype=bool)
+            for names, table, codes in ((key[0], self._repo_code, self._repo_codes), (key[1], self._lang_code, self._lang_codes)):
+                if names is not None:
+                    ok &= np.isin(codes[:n], np.asarray([table[x] for x in names if x in table], dtype=np.int32))
+            hit = self._mask_cache[key] = (pack_allow(ok, n), bool(ok.all()))
+        return hit
+
+    def row_filter(self, *, repos: Any = None, languages: Any = None) -> "Optional[np.ndarray]":
+        """The bitset search / search_batch hand to the device for this filter: uint32 words over row numbers (bit r & 31 of word
+        r >> 5 = row r passes), or None when neither argument is given.  Valid until the next upsert, delete or load -- row numbers
+        move; do not modify it (it is the cached array)."""
+        with self._lock:
+            flt = self._filter(repos, languages)
+            return None if flt is None else flt[0]
 
     def build_index(self, niter: int = 10) -> None:
         """(Re)build the IVF_FLAT lists now (create_index + load of the reference, milvus_store.py:76-84)."""
@@ -469,6 +532,9 @@ class MilvusVectorStore:
                     self._metadata.append(c["metadata"])
             if len(self._ids) != n:
                 raise ValueError(f"{path}: columns.jsonl holds {len(self._ids)} rows, manifest says {n}")
+            self._mask_cache.clear()
+            for row, (repo, language) in enumerate(zip(self._repos, self._languages)):
+                self._set_codes(row, repo, language)
             self._needs_train = True
             # the saved lists are reused as they are (no k-means) when they fit this collection's index parameters
             tn = int(manifest.get("ivf_trained_nlist", 0))
