@@ -162,6 +162,33 @@ sc_status sc_encoder_embed_ids_into_async(sc_encoder* enc, const int32_t* ids, c
 /* Block until every batch enqueued by sc_encoder_embed_ids_into_async has finished. */
 sc_status sc_encoder_wait(sc_encoder* enc);
 
+/* Packed variable-length batches: the same forward without padding every text to the longest one.  The caller passes the token
+ * ids of B texts one after another, unpadded: ids [offsets[B]] int32, offsets [B+1] with offsets[0] == 0, text i = ids[offsets[i] ..
+ * offsets[i+1]).  The library lays text i out on ceil32(len_i) token rows, one text after another, rounds the total up to 256 rows
+ * (the GEMM tile) and builds -- on the host, in pinned staging -- what the kernels need: the padded id array (alignment rows and the
+ * tail take token 0; their keys are masked, their outputs are finite and never pooled), a position per row, the first row and the
+ * length of every text, and the table of attention work items.  GEMMs, LayerNorm and the gate kernels run unchanged over those
+ * rows; embedding, rotary rotation, attention and pooling have packed forms (encoder_packed.hip).  Rotary models rotate Q and K with
+ * the stand-alone kernel in both pipelines: fusing the rotation into the QKV epilogue for packed rows is a follow-up.
+ * sc_encoder_set_path applies as for rectangles; the automatic rule (folded above 1 024 rows) looks at the packed row count.
+ * Packed and padded vectors of a text agree to bf16 rounding, not bit for bit.
+ * SC_ERR_INVALID, with nothing launched and nothing changed: a NULL pointer, B outside 1 .. 65536, offsets[0] != 0, a text shorter
+ * than 1 or longer than 2 048 tokens, or longer than max_pos for models with a position or rotary table.  SC_ERR_UNSUPPORTED: more
+ * than SC_ENCODER_PACKED_MAX_ROWS token rows -- 256 x 2 048, the largest rectangle sc_encoder_embed_ids is given by this project's
+ * callers; the workspace takes 17 KiB (BERT-base) to 29 KiB (nomic-bert) per row, i.e. up to 15 GiB at the bound. */
+#define SC_ENCODER_PACKED_MAX_ROWS 524288
+/* The token rows the packed forward runs for these offsets (a multiple of 256).  Validates as the embed calls do; no GPU work.
+ * Callers size their batches with it. */
+sc_status sc_encoder_packed_rows(sc_encoder* enc, const int64_t* offsets, int32_t B, int64_t* rows);
+/* sc_encoder_embed_ids on packed input: out [B,hidden] f32.  Host pointers; synchronises. */
+sc_status sc_encoder_embed_packed(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, float* out);
+/* sc_encoder_embed_ids_into / _into_async on packed input: same semantics, same in-flight rules (the two kinds share the two pinned
+ * slots: at most two batches of either kind are in flight, sc_encoder_wait covers both). */
+sc_status sc_encoder_embed_packed_into(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, sc_index* ix, const int64_t* rows,
+                                       float* out);
+sc_status sc_encoder_embed_packed_into_async(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, sc_index* ix,
+                                             const int64_t* rows);
+
 /* ----------------------------------------------------------------- tokenizer ---- */
 typedef struct sc_tokenizer sc_tokenizer;
 /* Host-side WordPiece tokenizer (BERT scheme), the step the reference leaves to its provider's library (raw strings
@@ -255,6 +282,12 @@ sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, cons
                              const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out);
 sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
                                const float* slopes, float* out);
+/* sc_diag_attention_packed: the packed attention kernel on its own, conventions of sc_diag_attention_ex.  Sequence b owns the rows
+ * starts[b] .. starts[b] + ceil32(lens[b]) (starts multiples of 32, lens 1 .. 2048); R = blocked_rows
+ * if > 0 (qkv is [3 heads][R][64]), else the end of the last sequence rounded up to 256 (qkv is [R][3*heads*64] row-major).
+ * out [R, heads*64]: rows of a sequence at or beyond its length are finite, rows outside every sequence stay NaN. */
+sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                   int32_t blocked_rows, const float* slopes, float* out);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,

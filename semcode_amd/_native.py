@@ -68,6 +68,10 @@ SIGNATURES = {
     "sc_encoder_embed_ids_into": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sc_encoder_embed_ids_into_async": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_encoder_wait": (C.c_int32, [C.c_void_p]),
+    "sc_encoder_packed_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    "sc_encoder_embed_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sc_encoder_embed_packed_into": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sc_encoder_embed_packed_into_async": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_tokenizer_create": (C.c_int32, [C.c_char_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]),
     "sc_tokenizer_destroy": (C.c_int32, [C.c_void_p]),
     "sc_tokenizer_info": (C.c_int32, [C.c_void_p] + [C.POINTER(C.c_int32)] * 5),
@@ -86,6 +90,7 @@ SIGNATURES = {
                                      C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_gemm_resln": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
@@ -643,6 +648,47 @@ class Encoder:
         """Block until every batch enqueued with embed_ids_into(..., wait=False) has finished."""
         _check(lib().sc_encoder_wait(self.handle))
 
+    # ---- packed variable-length batches: the ids of the texts one after another, unpadded, and offsets [B + 1] (offsets[0] == 0)
+    @staticmethod
+    def _packed_args(ids_flat, offsets) -> "tuple[np.ndarray, np.ndarray, int]":
+        ids_flat = np.ascontiguousarray(ids_flat, dtype=np.int32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if ids_flat.ndim != 1 or offsets.ndim != 1 or len(offsets) < 2:
+            raise ValueError("ids_flat must be [total] and offsets [B + 1]")
+        if int(offsets[-1]) != len(ids_flat) or (np.diff(offsets) < 0).any():
+            raise ValueError("offsets must ascend and end at len(ids_flat)")
+        return ids_flat, offsets, len(offsets) - 1
+
+    def packed_rows(self, offsets) -> int:
+        """Token rows the packed forward runs for these offsets (ceil32 per text, the total rounded up to 256); no GPU work."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        rows = C.c_int64()
+        _check(lib().sc_encoder_packed_rows(self.handle, offsets.ctypes.data_as(C.c_void_p), len(offsets) - 1, C.byref(rows)))
+        return rows.value
+
+    def embed_packed(self, ids_flat, offsets) -> np.ndarray:
+        """embed_ids without padding: text i = ids_flat[offsets[i]:offsets[i + 1]] -> [B, hidden] f32."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        out = np.empty((B, self.hidden), dtype=np.float32)
+        _check(lib().sc_encoder_embed_packed(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B,
+                                             out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def embed_packed_into(self, ids_flat, offsets, index: "Index", rows: np.ndarray, want_host: bool = False, wait: bool = True) -> "np.ndarray | None":
+        """embed_ids_into on packed input (same in-flight rules; wait() covers both kinds)."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.shape != (B,):
+            raise ValueError("rows must be [B]")
+        if not wait and not want_host:
+            _check(lib().sc_encoder_embed_packed_into_async(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B,
+                                                            index.handle, rows.ctypes.data_as(C.c_void_p)))
+            return None
+        out = np.empty((B, self.hidden), dtype=np.float32) if want_host else None
+        _check(lib().sc_encoder_embed_packed_into(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B, index.handle,
+                                                  rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p) if want_host else None))
+        return out
+
     def embed_ids_dev(self, ids_ptr: int, lens_ptr: int, B: int, S: int, out_ptr: int) -> None:
         _check(lib().sc_encoder_embed_ids_dev(self.handle, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), int(B), int(S), C.c_void_p(out_ptr)))
 
@@ -836,6 +882,24 @@ def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocke
     sl = None if slopes is None else _f32(slopes)
     out = np.empty((B * S, H), np.float32)
     _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    return out
+
+
+def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_rows: int = 0, slopes=None) -> np.ndarray:
+    """The packed attention kernel on its own: qkv [R, 3H] row-major, sequence b on the rows starts[b] .. starts[b] + ceil32(lens[b]);
+    R = blocked_rows (> 0: handed over as [3 heads][R][64]) or the last sequence's end rounded up to 256.  -> [R, H]."""
+    qkv = _f32(qkv)
+    starts = np.ascontiguousarray(starts, np.int32)
+    lens = np.ascontiguousarray(lens, np.int32)
+    H = heads * 64
+    R = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
+    if qkv.shape != (R, 3 * H) or starts.shape != lens.shape:
+        raise ValueError(f"diag_attention_packed: qkv must be [{R}, {3 * H}], starts and lens [B]")
+    if blocked_rows:
+        qkv = block64(qkv)
+    sl = None if slopes is None else _f32(slopes)
+    out = np.empty((R, H), np.float32)
+    _check(lib().sc_diag_attention_packed(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(blocked_rows), _ptr(sl), _ptr(out)))
     return out
 
 

@@ -52,6 +52,26 @@ void sc_launch_f32_to_bf16(const float* in, void* out, int64_t n, hipStream_t s)
 void sc_launch_synth_scaled(float* out, int64_t n, uint64_t seed, float scale, float offset, hipStream_t s);
 void sc_launch_bf16_to_f32(const void* in, float* out, int64_t n, hipStream_t s);
 
+// ---- encoder_packed.hip: the position-aware steps on packed variable-length rows.  pos [rows] = position of every token row inside
+// its sequence, starts / lens [B] = first row and real length of every sequence, items = the attention work-item table
+// sc_packed_items builds (4 int32 per item, sorted by launch class, nitems[3] per class).  All device pointers.
+void sc_launch_embed_ln_packed(const int32_t* ids, const int32_t* pos, int tokens, int H, int vocab, int max_pos, const float* wemb, const float* pemb,
+                               const float* temb, const float* g, const float* b, float eps, void* out, hipStream_t s);
+void sc_launch_embed_raw_packed(const int32_t* ids, const int32_t* pos, int tokens, int tokens_pad, int H, int vocab, int max_pos, const float* wemb,
+                                const float* pemb, const float* temb, void* out, float* stats, int slots, hipStream_t s);
+void sc_launch_rope_qk_packed(void* qkv, int64_t M, int nblocks, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t, hipStream_t s);
+int sc_packed_attention_class(int len);  // 0: longer than 256 tokens, 1: up to 256, 2: up to 128
+void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_mean_pool_packed(const void* x, const int32_t* starts, const int32_t* lens, int B, int H, int normalize, float* out, hipStream_t s);
+void sc_launch_mean_pool_ln_packed(const void* y, const float* stats, int slots, int tokens_pad, const float* gamma, const float* beta, float eps,
+                                   const int32_t* starts, const int32_t* lens, int B, int H, float* out, hipStream_t s);
+
+// ---- sc_encoder.cpp: the attention work items of packed sequences (host): per sequence one item for every 8 query blocks of 32 rows
+// (class 0) or one item (classes 1, 2), written as {start, len, first query block, 0} in class order.  items must hold
+// sc_packed_items_cap(rows, B) items.
+inline int64_t sc_packed_items_cap(int64_t rows, int64_t B) { return B + rows / 256; }
+void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int32_t* items, int nitems[3]);
+
 // ---- sc_encoder.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
 // angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000
 std::vector<float> sc_rope_table(int64_t positions, float theta);

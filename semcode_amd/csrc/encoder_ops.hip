@@ -19,72 +19,17 @@
 //   rope_qk_kernel    HBM-bound  : rotary position embedding of Q and K, in place on the blocked QKV buffer (nomic-bert)
 #include <cstdlib>
 
+#include "attention_core.h"  // AttnState, attention_qblock_core, attn_state_store
 #include "encoder_ops.h"
+#include "encoder_rows.h"   // the bodies of the embedding, rotary and pooling kernels, wave_sum
 #include "gemm_tile.h"  // bf16 helpers, LDS-DMA pointer types
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-static __device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-#define LN_MAXJ 8  // hidden <= 2048
 
 // ------------------------------------------------------------------ embeddings + LayerNorm
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids, int tokens, int S, int H, int vocab, int max_pos,
                                                         const float* __restrict__ wemb, const float* __restrict__ pemb,
                                                         const float* __restrict__ temb, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, bf16_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tok >= tokens) return;
-    int id = ids[tok];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    int pos = tok % S;
-    pos = pos >= max_pos ? max_pos - 1 : pos;
-    const float* we = wemb + (size_t)id * H;
-    const float* pe = pemb ? pemb + (size_t)pos * H : nullptr;  // NULL: no position table (ALiBi models)
-    f32x4 v[LN_MAXJ];
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int k0 = 4 * lane + 256 * j;
-        if (k0 < H) {
-            v[j] = *reinterpret_cast<const f32x4*>(we + k0);
-            if (pe) v[j] += *reinterpret_cast<const f32x4*>(pe + k0);
-            v[j] += *reinterpret_cast<const f32x4*>(temb + k0);
-            sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-        }
-    }
-    const float mean = wave_sum(sum) / (float)H;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int k0 = 4 * lane + 256 * j;
-        if (k0 < H) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float d = v[j][c] - mean;
-                sq = fmaf(d, d, sq);
-            }
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)H + eps);
-    bf16_t* o = out + (size_t)tok * H;
-#pragma unroll
-    for (int j = 0; j < LN_MAXJ; ++j) {
-        const int k0 = 4 * lane + 256 * j;
-        if (k0 < H) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + k0);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(beta + k0);
-            u16x4 r;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) r[c] = f32_to_bf16((v[j][c] - mean) * rstd * g[c] + b[c]);
-            *reinterpret_cast<u16x4*>(o + k0) = r;
-        }
-    }
+    embed_ln_rows(ids, tokens, PosInRect{S}, H, vocab, max_pos, wemb, pemb, temb, gamma, beta, eps, out);
 }
 
 // ------------------------------------------------------------------ LayerNorm-folded batch pipeline (sc_encoder.cpp, gemm_bf16.hip EPI_LNA_* / EPI_RESLN_STATS)
@@ -94,48 +39,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
 __global__ __launch_bounds__(256) void embed_raw_kernel(const int32_t* __restrict__ ids, int tokens, int tokens_pad, int S, int H, int vocab, int max_pos,
                                                          const float* __restrict__ wemb, const float* __restrict__ pemb,
                                                          const float* __restrict__ temb, bf16_t* __restrict__ out, float* __restrict__ stats, int slots) {
-    const int lane = threadIdx.x & 63;
-    const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tok >= tokens_pad) return;
-    float s1 = 0.f, s2 = 0.f;
-    if (tok < tokens) {
-        int id = ids[tok];
-        id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-        int pos = tok % S;
-        pos = pos >= max_pos ? max_pos - 1 : pos;
-        const float* we = wemb + (size_t)id * H;
-        const float* pe = pemb ? pemb + (size_t)pos * H : nullptr;
-        bf16_t* o = out + (size_t)tok * H;
-#pragma unroll
-        for (int j = 0; j < LN_MAXJ; ++j) {
-            const int k0 = 4 * lane + 256 * j;
-            if (k0 < H) {
-                f32x4 v = *reinterpret_cast<const f32x4*>(we + k0);
-                if (pe) v += *reinterpret_cast<const f32x4*>(pe + k0);
-                v += *reinterpret_cast<const f32x4*>(temb + k0);
-                u16x4 r;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    r[c] = f32_to_bf16(v[c]);
-                    const float y = bf16_to_f32(r[c]);
-                    s1 += y;
-                    s2 = fmaf(y, y, s2);
-                }
-                *reinterpret_cast<u16x4*>(o + k0) = r;
-            }
-        }
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-    } else {
-        // padding rows (tokens .. tokens_pad, never read by attention or pooling): zeros with statistics (0, 0), so that whatever the
-        // row-independent GEMMs compute for them stays finite (mu 0, rs 1/sqrt(eps), times zero)
-        for (int k0 = 4 * lane; k0 < H; k0 += 256) *reinterpret_cast<u16x4*>(out + (size_t)tok * H + k0) = u16x4{0, 0, 0, 0};
-    }
-    if (lane < slots) {
-        float* p = stats + ((size_t)lane * tokens_pad + tok) * 2;
-        p[0] = lane == 0 ? s1 : 0.f;
-        p[1] = lane == 0 ? s2 : 0.f;
-    }
+    embed_raw_rows(ids, tokens, tokens_pad, PosInRect{S}, H, vocab, max_pos, wemb, pemb, temb, out, stats, slots);
 }
 
 // W' = bf16(W diag(gamma)), c1[n] = sum_k W'[n,k] (of the ROUNDED values: it cancels what the MFMA accumulates),
@@ -177,56 +81,7 @@ __global__ __launch_bounds__(256) void add_vectors_kernel(const float* __restric
 __global__ __launch_bounds__(256) void mean_pool_ln_kernel(const bf16_t* __restrict__ y, const float* __restrict__ stats, int slots, int tokens_pad,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                             const int32_t* __restrict__ lens, int S, int H, float* __restrict__ out) {
-    __shared__ float part[8][32][9];
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const int b = blockIdx.y, cc = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int k0 = blockIdx.x * 256 + cc * 8;
-    int len = lens[b];
-    len = len < 1 ? 1 : (len > S ? S : len);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float accmu = 0.f;
-    const float inv_h = 1.0f / (float)H;
-    if (k0 < H) {
-        const bf16_t* p = y + (size_t)b * S * H + k0;
-#pragma unroll 2
-        for (int s0 = rg; s0 < len; s0 += 8) {
-            const size_t tok = (size_t)b * S + s0;
-            float s1 = 0.f, s2 = 0.f;
-            for (int t = 0; t < slots; ++t) {
-                s1 += stats[((size_t)t * tokens_pad + tok) * 2];
-                s2 += stats[((size_t)t * tokens_pad + tok) * 2 + 1];
-            }
-            const float mu = s1 * inv_h;
-            const float rs = 1.0f / sqrtf(fmaxf(s2 * inv_h - mu * mu, 0.f) + eps);
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(p + (size_t)s0 * H);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                acc[2 * c] = fmaf(rs, __builtin_bit_cast(float, raw[c] << 16), acc[2 * c]);
-                acc[2 * c + 1] = fmaf(rs, __builtin_bit_cast(float, raw[c] & 0xFFFF0000u), acc[2 * c + 1]);
-            }
-            accmu = fmaf(rs, mu, accmu);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) part[rg][cc][c] = acc[c];
-    part[rg][cc][8] = accmu;
-    __syncthreads();
-    if (rg == 0 && k0 < H) {
-        const float inv = 1.0f / (float)len;
-        float m = part[0][cc][8];
-#pragma unroll
-        for (int g = 1; g < 8; ++g) m += part[g][cc][8];
-        float o[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            float t = part[0][cc][c];
-#pragma unroll
-            for (int g = 1; g < 8; ++g) t += part[g][cc][c];
-            o[c] = fmaf((t - m) * inv, gamma[k0 + c], beta[k0 + c]);
-        }
-        *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0) = f32x4{o[0], o[1], o[2], o[3]};
-        *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0 + 4) = f32x4{o[4], o[5], o[6], o[7]};
-    }
+    mean_pool_ln_rows(y, stats, slots, tokens_pad, gamma, beta, eps, RectRows{lens, S}, blockIdx.y, blockIdx.x, H, out);
 }
 
 // ------------------------------------------------------------------ LayerNorm (input already holds x + sublayer(x))
@@ -331,170 +186,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
 // that only 64 score registers are live (S = 256 runs 2 workgroups per CU, S = 512 no longer spills).
 // FULL = every key of the padded sequence is real (len == S): no per-tile guards or masks.
 // ALIBI: scores get the symmetric linear bias -slope_head * |query - key| (jina-bert-v2 style encoders, no position table).
-// The online-softmax state of one 32-row query block: running maximum, running denominator, unnormalised output.  A sequence
-// longer than the 512 keys whose K and V fit the LDS is attended segment by segment (attention_long_kernel): the state is
-// carried from one segment of keys to the next.
-struct AttnState {
-    float m_run, l_run;
-    f32x16 o0, o1;
-};
-static __device__ __forceinline__ void attn_state_init(AttnState& a) {
-    a.m_run = -3.0e38f;
-    a.l_run = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { a.o0[r] = 0.f; a.o1[r] = 0.f; }
-}
-// One segment of keys (the KT tiles in Kl / Vl = keys key0 .. key0 + 32 KT of the sequence; len / nkt count inside the segment)
-// folded into the state.  first: the state is fresh (no rescale of O before the first group).
-template <int KT, bool FULL, bool ALIBI, int GKMAX = 4>
-static __device__ __forceinline__ void attention_qblock_core(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane,
-                                                             int qbase, float slope2, AttnState& S_, bool first, int key0) {
-    constexpr int GK = KT < GKMAX ? KT : GKMAX;   // key tiles per group
-    constexpr int NG = (KT + GK - 1) / GK;
-    const int l31 = lane & 31, hh = lane >> 5;
-    const float sl2 = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
-    const int tail = len & 31;                           // != 0: the last real key tile is partially masked
-    float m_run = S_.m_run, l_run = S_.l_run;
-    f32x16 o0 = S_.o0, o1 = S_.o1;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        if (!FULL && g * GK >= nkt) continue;  // wave-uniform: nothing real in this group
-        // S^T tiles of the group: st[i][r] = score(key = 32 t + (r&3) + 8 (r>>2) + 4 hh, query = l31), t = g*GK + i
-        f32x16 st[GK];
-#pragma unroll
-        for (int i = 0; i < GK; ++i) {
-            const int t = g * GK + i;
-            if (FULL || t < nkt) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                const int krow = 32 * t + l31;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const int c = 2 * ks + hh;
-                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
-                }
-                if (ALIBI) {  // work in the exp2 domain from here on: v = s * sl2 - slope2 * |q - key|
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float dist = (float)(key0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh - (qbase + l31));
-                        acc[r] = fmaf(acc[r], sl2, -slope2 * fabsf(dist));
-                    }
-                }
-                st[i] = acc;
-            }
-        }
-        const float sc2 = ALIBI ? 1.0f : sl2;  // scores already scaled when ALIBI
-        float mx = m_run;
-#pragma unroll
-        for (int i = 0; i < GK; ++i) {
-            const int t = g * GK + i;
-            if (FULL || t < nkt) {
-                if (!FULL && t == nkt - 1 && tail) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        if (32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh < len) mx = fmaxf(mx, st[i][r]);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[i][r]);
-                }
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mb = mx * sc2;
-        const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, sc2, -mb));  // first group: exp2(-huge) = 0, and O, l are 0 anyway
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < GK; ++i) {
-            const int t = g * GK + i;
-            if (FULL || t < nkt) {
-                const bool masked = !FULL && (t == nkt - 1) && tail;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float p = __builtin_amdgcn_exp2f(fmaf(st[i][r], sc2, -mb));
-                    if (masked && !(32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh < len)) p = 0.f;
-                    st[i][r] = p;
-                    sum += p;
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 32, 64);
-        l_run = fmaf(l_run, alpha, sum);
-        m_run = mx;
-        if (g > 0 || !first) {  // rescale O: its rows are queries (r&3) + 8 (r>>2) + 4 hh, alpha lives on lane q -> exchange through LDS
-            xch[l31] = alpha;
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const f32x4 al = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { o0[4 * g4 + c] *= al[c]; o1[4 * g4 + c] *= al[c]; }
-            }
-        }
-        // O += P V: A operand = P straight from the score registers (k order of step s:
-        // key = 32 t + 16 s + 8 (j>>2) + 4 hh + (j&3)), B operand = V by transposed LDS reads
-#pragma unroll
-        for (int i = 0; i < GK; ++i) {
-            const int t = g * GK + i;
-            if (FULL || t < nkt) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    u32x4 pp;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pp[j] = pack_bf16x2(st[i][8 * s + 2 * j], st[i][8 * s + 2 * j + 1]);
-                    const bf16x8 pf = __builtin_bit_cast(bf16x8, pp);
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        bf16x8 vf;
-#pragma unroll
-                        for (int piece = 0; piece < 2; ++piece) {
-                            const int row = 32 * t + 16 * s + 8 * piece + 4 * hh + ((lane & 15) >> 2);
-                            const int d0 = 32 * dt + 16 * ((lane >> 4) & 1);
-                            const int chunk = (d0 >> 3) + ((lane & 3) >> 1);
-                            const int sw = chunk ^ (((row >> 1) & 1) << 2);
-                            typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
-                            const s16x4 got = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(Vl + row * 128 + sw * 16 + 8 * (lane & 1)));
-                            vf[4 * piece + 0] = got[0];
-                            vf[4 * piece + 1] = got[1];
-                            vf[4 * piece + 2] = got[2];
-                            vf[4 * piece + 3] = got[3];
-                        }
-                        if (dt == 0) o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o0, 0, 0, 0);
-                        else o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o1, 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    S_.m_run = m_run;
-    S_.l_run = l_run;
-    S_.o0 = o0;
-    S_.o1 = o1;
-}
-// o[r] = O[q = (r&3) + 8 (r>>2) + 4 hh][d = 32 dt + l31]: normalise by 1/l[q], stage as bf16 [q][d] in LDS 8 query rows
-// at a time (1 KiB, wave-private; LDS runs a wave's instructions in order), then leave as whole 128-byte rows.
-static __device__ __forceinline__ void attn_state_store(const AttnState& S_, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
-    const int l31 = lane & 31, hh = lane >> 5;
-    const float l_run = S_.l_run;
-    const f32x16 o0 = S_.o0, o1 = S_.o1;
-    xch[l31] = 1.0f / l_run;
-    bf16_t* og = reinterpret_cast<bf16_t*>(ostg);
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-        const f32x4 il = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int ql = 4 * hh + c;  // row inside this block of 8
-            og[ql * 64 + l31] = (bf16_t)(pack_bf16x2(o0[4 * g4 + c] * il[c], 0.f) & 0xFFFFu);
-            og[ql * 64 + 32 + l31] = (bf16_t)(pack_bf16x2(o1[4 * g4 + c] * il[c], 0.f) & 0xFFFFu);
-        }
-        const int ql = lane >> 3, c8 = lane & 7;
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(ostg + ql * 128 + c8 * 16);
-        *reinterpret_cast<bf16x8*>(obase + (size_t)(8 * g4 + ql) * H + c8 * 8) = v;
-    }
-}
-
+// AttnState, attention_qblock_core and attn_state_store: attention_core.h.
 template <int KT, bool FULL, bool ALIBI, int GKMAX = 4>
 static __device__ __forceinline__ void attention_qblock(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, char* ostg,
                                                         bf16_t* obase, int H, int len, int nkt, int lane, int qbase, float slope2) {
@@ -634,38 +326,7 @@ __global__ __launch_bounds__(512, 1) void attention_long_kernel(const bf16_t* __
 // ------------------------------------------------------------------ masked mean pooling
 __global__ __launch_bounds__(256) void mean_pool_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ lens, int S, int H,
                                                          int normalize, float* __restrict__ out) {
-    __shared__ float red[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int len = lens[b];
-    len = len < 1 ? 1 : (len > S ? S : len);
-    const float inv = 1.0f / (float)len;
-    float ss = 0.f;
-    for (int k0 = 4 * tid; k0 < H; k0 += 1024) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const bf16_t* p = x + (size_t)b * S * H + k0;
-        for (int s = 0; s < len; ++s) {
-            const u16x4 raw = *reinterpret_cast<const u16x4*>(p + (size_t)s * H);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[c] += bf16_to_f32(raw[c]);
-        }
-        acc *= inv;
-        *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0) = acc;
-        ss += (acc[0] * acc[0] + acc[1] * acc[1]) + (acc[2] * acc[2] + acc[3] * acc[3]);
-    }
-    if (normalize) {
-        red[tid] = ss;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        const float scale = 1.0f / fmaxf(sqrtf(red[0]), 1e-12f);
-        for (int k0 = 4 * tid; k0 < H; k0 += 1024) {
-            f32x4 v = *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0);
-            v *= scale;
-            *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0) = v;
-        }
-    }
+    mean_pool_rows(x, RectRows{lens, S}, blockIdx.x, H, normalize, out);
 }
 
 // ------------------------------------------------------------------ f32 -> bf16 weight conversion, fills
@@ -791,29 +452,7 @@ void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream
 // of two, so that padding rows (>= the real tokens, content irrelevant) stay inside the table.  f32 math, one rounding back to bf16.
 __global__ __launch_bounds__(256) void rope_qk_kernel(bf16_t* __restrict__ qkv, int64_t M, int nblocks, int smask, const float* __restrict__ cos_t,
                                                        const float* __restrict__ sin_t) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const int64_t total = (int64_t)nblocks * M * 4;  // (block, row, quarter)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t vec = i >> 2;            // block * M + row
-        const int c = (int)(i & 3) * 8;
-        const int p = (int)((vec % M) & smask);
-        bf16_t* v = qkv + vec * 64 + c;
-        const u32x4 lo = *reinterpret_cast<const u32x4*>(v), hi = *reinterpret_cast<const u32x4*>(v + 32);
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cos_t + p * 32 + c), c1 = *reinterpret_cast<const f32x4*>(cos_t + p * 32 + c + 4);
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sin_t + p * 32 + c), s1 = *reinterpret_cast<const f32x4*>(sin_t + p * 32 + c + 4);
-        u32x4 olo, ohi;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float a0 = __builtin_bit_cast(float, lo[k] << 16), a1 = __builtin_bit_cast(float, lo[k] & 0xFFFF0000u);
-            const float b0 = __builtin_bit_cast(float, hi[k] << 16), b1 = __builtin_bit_cast(float, hi[k] & 0xFFFF0000u);
-            const float cc0 = k < 2 ? c0[2 * k] : c1[2 * k - 4], cc1 = k < 2 ? c0[2 * k + 1] : c1[2 * k - 3];
-            const float ss0 = k < 2 ? s0[2 * k] : s1[2 * k - 4], ss1 = k < 2 ? s0[2 * k + 1] : s1[2 * k - 3];
-            olo[k] = pack_bf16x2(fmaf(a0, cc0, -b0 * ss0), fmaf(a1, cc1, -b1 * ss1));
-            ohi[k] = pack_bf16x2(fmaf(b0, cc0, a0 * ss0), fmaf(b1, cc1, a1 * ss1));
-        }
-        *reinterpret_cast<u32x4*>(v) = olo;
-        *reinterpret_cast<u32x4*>(v + 32) = ohi;
-    }
+    rope_qk_rows(qkv, M, nblocks, PosMasked{smask}, cos_t, sin_t);
 }
 void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* cos_t, const float* sin_t, hipStream_t s) {
     int64_t blocks = ((int64_t)nblocks * M * 4 + 255) / 256;
@@ -825,42 +464,7 @@ void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* co
 // in a fixed order.
 __global__ __launch_bounds__(256) void mean_pool_sliced_kernel(const bf16_t* __restrict__ x, const int32_t* __restrict__ lens, int S, int H,
                                                                 float* __restrict__ out) {
-    __shared__ float part[8][32][8];
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const int b = blockIdx.y, cc = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int k0 = blockIdx.x * 256 + cc * 8;
-    int len = lens[b];
-    len = len < 1 ? 1 : (len > S ? S : len);
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (k0 < H) {
-        const bf16_t* p = x + (size_t)b * S * H + k0;
-#pragma unroll 4
-        for (int s0 = rg; s0 < len; s0 += 8) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(p + (size_t)s0 * H);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                acc[2 * c] += __builtin_bit_cast(float, raw[c] << 16);
-                acc[2 * c + 1] += __builtin_bit_cast(float, raw[c] & 0xFFFF0000u);
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) part[rg][cc][c] = acc[c];
-    __syncthreads();
-    if (rg == 0 && k0 < H) {
-        const float inv = 1.0f / (float)len;
-        f32x4 lo, hi;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            float t = part[0][cc][c];
-#pragma unroll
-            for (int g = 1; g < 8; ++g) t += part[g][cc][c];
-            if (c < 4) lo[c] = t * inv;
-            else hi[c - 4] = t * inv;
-        }
-        *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0) = lo;
-        *reinterpret_cast<f32x4*>(out + (size_t)b * H + k0 + 4) = hi;
-    }
+    mean_pool_sliced_rows(x, RectRows{lens, S}, blockIdx.y, blockIdx.x, H, out);
 }
 
 void sc_launch_mean_pool(const void* x, const int32_t* lens, int B, int S, int H, int normalize, float* out, hipStream_t s) {

@@ -51,6 +51,9 @@ struct sc_encoder {
     void *x = nullptr, *x1 = nullptr, *y = nullptr, *qkv = nullptr, *ctx = nullptr, *hm = nullptr, *hg = nullptr;
     int32_t* ids = nullptr;
     int32_t* lens = nullptr;
+    // packed batches: padded ids | positions | starts | lens | attention items (PlanOffsets), one upload per call.  Part of every
+    // workspace, rectangle callers' too: 8 bytes per token row + 24 per sequence next to the 17-29 KiB a row's activations take
+    char* plan = nullptr;
     float* pooled = nullptr;
     int64_t ws_batch = 0;
     float *stat_a = nullptr, *stat_b = nullptr;  // [slots][ws_tokens][2] partial row sums of the two pre-LayerNorm tensors (folded pipeline)
@@ -71,6 +74,44 @@ struct sc_encoder {
 };
 
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- packed variable-length batches (sc_encoder_embed_packed*): sequence i owns the token rows [starts[i], starts[i] + ceil32(len_i)),
+// one sequence after another; the GEMMs run on the total rounded up to 256 rows.
+static int64_t ceil32(int64_t v) { return (v + 31) & ~(int64_t)31; }
+// Where the sequences of a packed batch lie, for the four position-aware steps of the forward (device pointers into e->plan).
+// The forward takes it as a parameter: NULL = a [B, S] rectangle.
+struct PackedLayout {
+    const int32_t *pos, *starts, *items;
+    int nitems[3];
+    int rows;  // token rows in use = the sum of ceil32(len_i); rows .. M are the tail
+};
+// The plan of one packed call, laid out alike in pinned host staging and in e->plan (M token rows, B sequences): monotone in both, so
+// a call's plan fits the buffer of any larger workspace
+struct PlanOffsets {
+    size_t ids, pos, starts, lens, items, total;
+    PlanOffsets(size_t M, size_t B) {
+        size_t u = 0;
+        auto take = [&](size_t bytes) { const size_t at = u; u += align256(bytes); return at; };
+        ids = take(M * 4);
+        pos = take(M * 4);
+        starts = take(B * 4);
+        lens = take(B * 4);
+        items = take((size_t)sc_packed_items_cap((int64_t)M, (int64_t)B) * 16);
+        total = u;
+    }
+};
+void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int32_t* items, int nitems[3]) {
+    int32_t* w = items;
+    for (int cls = 0; cls < 3; ++cls) {
+        const int32_t* w0 = w;
+        for (int64_t i = 0; i < B; ++i) {
+            if (sc_packed_attention_class(lens[i]) != cls) continue;
+            const int nqb = (int)(ceil32(lens[i]) / 32);
+            for (int qb = 0; qb < (cls == 0 ? nqb : 1); qb += 8, w += 4) { w[0] = starts[i]; w[1] = lens[i]; w[2] = qb; w[3] = 0; }
+        }
+        nitems[cls] = (int)((w - w0) / 4);
+    }
+}
 
 // Lays the buffers of one device allocation out, each 256-byte aligned.  The layout code runs twice: over an arena without a base
 // it only measures (every buffer comes back NULL, `used` is the size to allocate), over the allocation it hands out the pointers.
@@ -319,6 +360,7 @@ static void layout_ws(sc_encoder* e, Arena& a, size_t tokens, size_t nb) {
     e->hg = ffn_gated(e->cfg) ? a.bf16(tokens * F) : nullptr;
     e->ids = (int32_t*)a.take(tokens * 4);
     e->lens = (int32_t*)a.take(nb * 4);
+    e->plan = (char*)a.take(PlanOffsets(tokens, nb).total);
     e->pooled = a.f32(nb * H);
     e->stat_a = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
     e->stat_b = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
@@ -326,8 +368,9 @@ static void layout_ws(sc_encoder* e, Arena& a, size_t tokens, size_t nb) {
     e->fin_b = e->foldable ? a.f32(tokens * 2) : nullptr;
 }
 
-static sc_status ensure_ws(sc_encoder* e, int64_t B, int64_t S) {
-    const int64_t tokens = (B * S + 255) / 256 * 256;  // GEMM tiles are 256 rows
+// ... for `rows` token rows (a rectangle's B * S, a packed batch's row count) of B sequences
+static sc_status ensure_ws(sc_encoder* e, int64_t rows, int64_t B) {
+    const int64_t tokens = (rows + 255) / 256 * 256;  // GEMM tiles are 256 rows
     if (tokens <= e->ws_tokens && B <= e->ws_batch) return SC_OK;
     SC_HIP(hipStreamSynchronize(e->rt->stream));
     hipFree(e->ws);
@@ -346,6 +389,21 @@ static sc_status ensure_ws(sc_encoder* e, int64_t B, int64_t S) {
     return SC_OK;
 }
 
+// The steps both pipelines launch in a rectangle form and a packed form (pk != NULL).  Packed rotary models always rotate with the
+// stand-alone kernel: the rotation fused into the QKV epilogue (EPI_LNA_BIAS_ROPE) takes its position from row & (S - 1).
+static void launch_rope(sc_encoder* e, int M, int S, const PackedLayout* pk, hipStream_t s) {
+    if (pk) sc_launch_rope_qk_packed(e->qkv, M, 2 * e->cfg.heads, pk->pos, e->cfg.max_pos, e->rope_cos, e->rope_sin, s);
+    else sc_launch_rope_qk(e->qkv, M, 2 * e->cfg.heads, S, e->rope_cos, e->rope_sin, s);
+}
+static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
+    if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M);
+    else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M);
+}
+static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
+    if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, e->cfg.normalize, out_dev, s);
+    else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, e->cfg.normalize, out_dev, s);
+}
+
 // The batch pipeline with every LayerNorm folded into its neighbours (no layernorm_kernel launch, no LayerNorm round trip
 // through HBM: 24 x 33 us and 24 x 200 MB per step at 256 x 256 tokens).  Activations between layers are the PRE-LayerNorm
 // tensors (raw bf16 rows) together with their row statistics:
@@ -357,20 +415,22 @@ static sc_status ensure_ws(sc_encoder* e, int64_t B, int64_t S) {
 //     x     = hm W2^T + b2 + LN_1(y)                                                         EPI_RESLN_STATS (fin_a -> stat_b)
 //   pooled = masked mean of LN_2(x) of the last layer, normalised on the fly (mean_pool_ln)
 // Statistics are taken of the bf16-ROUNDED rows, i.e. of exactly what the consumer reads; all reductions run in a fixed order.
-static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev) {
+static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
+                                       const PackedLayout* pk) {
     const sc_encoder_cfg& c = e->cfg;
     sc_runtime* rt = e->rt;
     hipStream_t s = rt->stream;
     const int H = c.hidden, F = c.ffn;
-    const int tokens = B * S;
+    const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     const int slots = H / 256;
     // statistics buffers are laid out for ws_tokens rows; this call uses the first M rows of every slot: slot stride must be M, so
     // they are addressed as [slots][M][2] inside the (larger or equal) allocation
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !gated && ffn_blocked_enabled();
-    const bool rope = c.pos_type == 2, rope_fused = rope && (g_rope_fused < 0 ? ROPE_FUSED_DEFAULT : g_rope_fused) != 0;
-    sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
+    const bool rope = c.pos_type == 2, rope_fused = rope && !pk && (g_rope_fused < 0 ? ROPE_FUSED_DEFAULT : g_rope_fused) != 0;
+    if (pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
+    else sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
         sc_with_prof(rt, SC_PROF_GEMM, [&] {
@@ -381,8 +441,8 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
                 sc_launch_gemm_bf16_ln(EPI_LNA_BIAS, e->x, H, w.wqkv_f, H, w.c2q, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, w.c1q, e->stat_b, e->fin_b, nullptr,
                                        nullptr, c.ln_eps);
         });
-        if (rope && !rope_fused) sc_launch_rope_qk(e->qkv, M, 2 * c.heads, S, e->rope_cos, e->rope_sin, s);
-        sc_with_prof(rt, SC_PROF_ATTN, [&] { sc_launch_attention(e->qkv, lens_dev, B, S, H, e->slopes, e->ctx, s, M); });
+        if (rope && !rope_fused) launch_rope(e, M, S, pk, s);
+        sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_attention(e, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] {
             sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, e->ctx, H, w.wo, H, w.bb_o, e->x, H, e->y, H, M, H, H, s, nullptr, nullptr, e->fin_b, w.g_prev, e->stat_a, c.ln_eps);
         });
@@ -406,7 +466,9 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     const LayerW& last = e->layers[c.layers - 1];
     if (c.normalize) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
         sc_launch_layernorm(e->x, tokens, H, last.ln2g, last.ln2b, c.ln_eps, e->x1, s);
-        sc_launch_mean_pool(e->x1, lens_dev, B, S, H, c.normalize, out_dev, s);
+        launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
+    } else if (pk) {
+        sc_launch_mean_pool_ln_packed(e->x, e->stat_b, slots, M, last.ln2g, last.ln2b, c.ln_eps, pk->starts, lens_dev, B, H, out_dev, s);
     } else {
         sc_launch_mean_pool_ln(e->x, e->stat_b, slots, M, last.ln2g, last.ln2b, c.ln_eps, lens_dev, B, S, H, out_dev, s);
     }
@@ -414,17 +476,19 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     return SC_OK;
 }
 
-// ids_dev [B,S], lens_dev [B] device pointers; out_dev [B,H] f32 device.  Caller holds e->mu.
-static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev) {
+// ids_dev [B,S], lens_dev [B] device pointers; out_dev [B,H] f32 device.  pk != NULL: a packed batch -- ids_dev holds one id per token
+// row of the layout (M of them), S is unused.  Caller holds e->mu.
+static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
+                                const PackedLayout* pk = nullptr) {
     const sc_encoder_cfg& c = e->cfg;
     sc_runtime* rt = e->rt;
     hipStream_t s = rt->stream;
     const int H = c.hidden, F = c.ffn;
-    const int tokens = B * S;
+    const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     // batches beyond 1024 token rows (or sc_encoder_set_path 1) take the LayerNorm-folded pipeline where the model's shapes allow it
     static const bool env_fold = sc_env_flag("SC_ENC_FOLD", true);  // SC_ENC_FOLD=0: same-box A/B against the stand-alone LayerNorm kernels
-    if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev);
+    if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
     void* sk = nullptr;
     if (M <= 1024 && e->path != 1) {  // a query or a few chunks: too few tiles for the chip, split K (gemm_bf16.hip)
         if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
@@ -437,15 +501,16 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     // in between), and only when F divides into 256-column tiles.
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !sk && !gated && (F % 256) == 0 && (H % 256) == 0 && ffn_blocked_enabled();
-    sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    else sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
         sc_with_prof(rt, SC_PROF_GEMM, [&] {
             // QKV in 64-column blocks, i.e. [3 heads][tokens][64]: attention reads each (chunk, head) operand as one contiguous block
             sc_launch_gemm_bf16(EPI_BIAS, e->x, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, sk, skb);
         });
-        if (c.pos_type == 2) sc_launch_rope_qk(e->qkv, M, 2 * c.heads, S, e->rope_cos, e->rope_sin, s);
-        sc_with_prof(rt, SC_PROF_ATTN, [&] { sc_launch_attention(e->qkv, lens_dev, B, S, H, e->slopes, e->ctx, s, M); });
+        if (c.pos_type == 2) launch_rope(e, M, S, pk, s);
+        sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_attention(e, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x, H, e->y, H, M, H, H, s, sk, skb); });
         sc_launch_layernorm(e->y, tokens, H, w.ln1g, w.ln1b, c.ln_eps, e->x1, s);
         const void* ffn_in = e->hm;
@@ -460,7 +525,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, ffn_blocked ? SC_LDC_BLOCKED64 : F, w.w2, F, w.b2, e->x1, H, e->y, H, M, H, F, s, sk, skb); });
         sc_launch_layernorm(e->y, tokens, H, w.ln2g, w.ln2b, c.ln_eps, e->x, s);
     }
-    sc_launch_mean_pool(e->x, lens_dev, B, S, H, c.normalize, out_dev, s);
+    launch_mean_pool(e, e->x, lens_dev, B, S, pk, out_dev, s);
     SC_HIP(hipGetLastError());
     return SC_OK;
 }
@@ -487,7 +552,7 @@ static sc_status check_into_args(sc_encoder* e, const void* ids, const void* len
 // Host ids [B,S] and lens [B] (pageable, or a pinned slot) into the workspace, forward into e->pooled.  Caller holds e->mu and has
 // set the device; nothing is synchronised.
 static sc_status embed_host_locked(sc_encoder* e, const void* ids, const void* lens, int32_t B, int32_t S) {
-    sc_status st = ensure_ws(e, B, S);
+    sc_status st = ensure_ws(e, (int64_t)B * S, B);
     if (st) return st;
     hipStream_t s = e->rt->stream;
     SC_HIP(hipMemcpyAsync(e->ids, ids, (size_t)B * S * 4, hipMemcpyHostToDevice, s));
@@ -507,7 +572,7 @@ extern "C" sc_status sc_encoder_embed_ids_dev(sc_encoder* e, const int32_t* ids_
     if (st) return st;
     std::lock_guard<std::mutex> g(e->mu);
     SC_HIP(hipSetDevice(e->rt->device));
-    st = ensure_ws(e, B, S);
+    st = ensure_ws(e, (int64_t)B * S, B);
     if (st) return st;
     return forward_locked(e, ids_dev, lens_dev, B, S, out_dev);
 }
@@ -553,6 +618,19 @@ static sc_status pin_slot_wait(sc_encoder::PinSlot& slot) {
     return SC_OK;
 }
 
+// an idle slot with at least `need` bytes of pinned memory and its event
+static sc_status pin_slot_reserve(sc_encoder::PinSlot& slot, size_t need) {
+    if (need > slot.cap) {
+        if (slot.host) hipHostFree(slot.host);
+        slot.host = nullptr;
+        slot.cap = 0;
+        SC_HIP(hipHostMalloc((void**)&slot.host, need, hipHostMallocDefault));
+        slot.cap = need;
+    }
+    if (!slot.done) SC_HIP(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    return SC_OK;
+}
+
 extern "C" sc_status sc_encoder_embed_ids_into_async(sc_encoder* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t S, sc_index* ix,
                                                      const int64_t* rows) {
     sc_status st = check_into_args(e, ids, lens, B, S, ix, rows, "sc_encoder_embed_ids_into_async");
@@ -563,14 +641,8 @@ extern "C" sc_status sc_encoder_embed_ids_into_async(sc_encoder* e, const int32_
     st = pin_slot_wait(slot);  // two batches may be in flight; the third waits for the first
     if (st) return st;
     const size_t ids_b = (size_t)B * S * 4, lens_b = align256((size_t)B * 4), rows_b = (size_t)B * 8, need = align256(ids_b) + lens_b + rows_b;
-    if (need > slot.cap) {
-        if (slot.host) hipHostFree(slot.host);
-        slot.host = nullptr;
-        slot.cap = 0;
-        SC_HIP(hipHostMalloc((void**)&slot.host, need, hipHostMallocDefault));
-        slot.cap = need;
-    }
-    if (!slot.done) SC_HIP(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
+    st = pin_slot_reserve(slot, need);
+    if (st) return st;
     char* h_ids = slot.host;
     char* h_lens = slot.host + align256(ids_b);
     int64_t* h_rows = (int64_t*)(h_lens + lens_b);
@@ -581,6 +653,156 @@ extern "C" sc_status sc_encoder_embed_ids_into_async(sc_encoder* e, const int32_
     if (st) return st;
     st = store_pooled_locked(e, ix, h_rows, B, "sc_encoder_embed_ids_into_async");
     if (st) return st;
+    SC_HIP(hipEventRecord(slot.done, e->rt->stream));
+    slot.busy = true;
+    e->pin_next ^= 1;
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------ packed variable-length batches
+// offsets [B + 1] of sc_encoder_embed_packed*: every rule of the header; *rows = the token rows in use (the sum of ceil32(len_i))
+static sc_status check_packed_offsets(sc_encoder* e, const int64_t* offsets, int32_t B, const char* who, int64_t* rows) {
+    if (!e || !offsets) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "%s: batch %d out of range", who, B);
+    if (offsets[0] != 0) return sc_fail(SC_ERR_INVALID, "%s: offsets[0] must be 0 (got %lld)", who, (long long)offsets[0]);
+    const int64_t max_len = e->cfg.pos_type != 1 && e->cfg.max_pos < 2048 ? e->cfg.max_pos : 2048;
+    int64_t used = 0;
+    for (int32_t i = 0; i < B; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (len < 1) return sc_fail(SC_ERR_INVALID, "%s: text %d has length %lld (every text needs at least one token)", who, i, (long long)len);
+        if (len > max_len)
+            return sc_fail(SC_ERR_INVALID, "%s: text %d has %lld tokens, more than %lld (the smaller of 2048 and the model's max_pos)", who, i, (long long)len, (long long)max_len);
+        used += ceil32(len);
+    }
+    if ((used + 255) / 256 * 256 > SC_ENCODER_PACKED_MAX_ROWS)
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: %lld token rows, more than SC_ENCODER_PACKED_MAX_ROWS = %d (split the batch)", who, (long long)used, SC_ENCODER_PACKED_MAX_ROWS);
+    *rows = used;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_packed_rows(sc_encoder* e, const int64_t* offsets, int32_t B, int64_t* rows) {
+    if (!rows) return sc_fail(SC_ERR_INVALID, "sc_encoder_packed_rows: NULL argument");
+    int64_t used = 0;
+    sc_status st = check_packed_offsets(e, offsets, B, "sc_encoder_packed_rows", &used);
+    if (st) return st;
+    *rows = (used + 255) / 256 * 256;
+    return SC_OK;
+}
+
+// Plans the layout of host ids / offsets into `slot` (idle, the caller waited for it), uploads it and runs the forward into e->pooled.
+// index_rows (NULL or [B]) are copied behind the plan: *rows_out points at the copy.  Caller holds e->mu and has validated the
+// offsets (`used` = check_packed_offsets' row count); nothing is synchronised.
+static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, int64_t used, sc_encoder::PinSlot& slot,
+                                     const int64_t* index_rows, const int64_t** rows_out) {
+    const int64_t M = (used + 255) / 256 * 256;
+    const PlanOffsets po((size_t)M, (size_t)B);
+    sc_status st = pin_slot_reserve(slot, po.total + (size_t)B * 8);
+    if (st) return st;
+    int32_t* h_ids = (int32_t*)(slot.host + po.ids);
+    int32_t* h_pos = (int32_t*)(slot.host + po.pos);
+    int32_t* h_starts = (int32_t*)(slot.host + po.starts);
+    int32_t* h_lens = (int32_t*)(slot.host + po.lens);
+    int32_t* h_items = (int32_t*)(slot.host + po.items);
+    memset(h_ids, 0, (size_t)M * 4);  // alignment rows and the tail take token 0 ...
+    memset(h_pos, 0, (size_t)M * 4);  // ... the tail position 0
+    int64_t row = 0;
+    for (int32_t i = 0; i < B; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i], span = ceil32(len);
+        h_starts[i] = (int32_t)row;
+        h_lens[i] = (int32_t)len;
+        memcpy(h_ids + row, ids + offsets[i], (size_t)len * 4);
+        for (int64_t j = 0; j < span; ++j) h_pos[row + j] = (int32_t)j;  // (the kernels clamp an alignment row's position into the table)
+        row += span;
+    }
+    PackedLayout pk{};
+    sc_packed_items(h_starts, h_lens, B, h_items, pk.nitems);
+    if (index_rows) {
+        int64_t* h_rows = (int64_t*)(slot.host + po.total);
+        memcpy(h_rows, index_rows, (size_t)B * 8);
+        *rows_out = h_rows;
+    }
+    st = ensure_ws(e, M, B);
+    if (st) return st;
+    SC_HIP(hipMemcpyAsync(e->plan, slot.host, po.total, hipMemcpyHostToDevice, e->rt->stream));
+    pk.pos = (const int32_t*)(e->plan + po.pos);
+    pk.starts = (const int32_t*)(e->plan + po.starts);
+    pk.items = (const int32_t*)(e->plan + po.items);
+    pk.rows = (int)used;
+    return forward_locked(e, (const int32_t*)(e->plan + po.ids), (const int32_t*)(e->plan + po.lens), B, 0, e->pooled, &pk);
+}
+
+static sc_status check_packed_into_args(sc_encoder* e, const void* ids, const int64_t* offsets, int32_t B, sc_index* ix, const int64_t* rows, const char* who,
+                                        int64_t* used) {
+    if (!ix || !rows || !ids) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    sc_status st = check_packed_offsets(e, offsets, B, who, used);
+    if (st) return st;
+    if (ix->rt != e->rt) return sc_fail(SC_ERR_INVALID, "%s: encoder and index belong to different runtimes", who);
+    if (ix->dim != e->cfg.hidden) return sc_fail(SC_ERR_INVALID, "%s: index dim %d != encoder hidden %d", who, ix->dim, e->cfg.hidden);
+    return SC_OK;
+}
+
+// The synchronous forms stage through the next pinned slot as well (after waiting for the batch that used it) and leave it idle.
+extern "C" sc_status sc_encoder_embed_packed(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, float* out) {
+    if (!ids || !out) return sc_fail(SC_ERR_INVALID, "sc_encoder_embed_packed: NULL argument");
+    int64_t used = 0;
+    sc_status st = check_packed_offsets(e, offsets, B, "sc_encoder_embed_packed", &used);
+    if (st) return st;
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);
+    if (st) return st;
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, nullptr, nullptr);
+    hipStream_t s = e->rt->stream;
+    if (st) {
+        hipStreamSynchronize(s);  // the slot's upload may be in flight
+        return st;
+    }
+    SC_HIP(hipMemcpyAsync(out, e->pooled, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_embed_packed_into(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, sc_index* ix, const int64_t* rows,
+                                                  float* out) {
+    int64_t used = 0;
+    sc_status st = check_packed_into_args(e, ids, offsets, B, ix, rows, "sc_encoder_embed_packed_into", &used);
+    if (st) return st;
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);
+    if (st) return st;
+    const int64_t* h_rows = nullptr;
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, rows, &h_rows);
+    hipStream_t s = e->rt->stream;
+    if (!st) st = store_pooled_locked(e, ix, h_rows, B, "sc_encoder_embed_packed_into");
+    if (st) {
+        hipStreamSynchronize(s);  // drain the stream before the error is reported
+        return st;
+    }
+    if (out) SC_HIP(hipMemcpyAsync(out, e->pooled, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_embed_packed_into_async(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, sc_index* ix,
+                                                        const int64_t* rows) {
+    int64_t used = 0;
+    sc_status st = check_packed_into_args(e, ids, offsets, B, ix, rows, "sc_encoder_embed_packed_into_async", &used);
+    if (st) return st;
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);  // two batches may be in flight; the third waits for the first
+    if (st) return st;
+    const int64_t* h_rows = nullptr;
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, rows, &h_rows);
+    if (!st) st = store_pooled_locked(e, ix, h_rows, B, "sc_encoder_embed_packed_into_async");
+    if (st) {
+        hipStreamSynchronize(e->rt->stream);  // the slot stays idle: nothing may still read it
+        return st;
+    }
     SC_HIP(hipEventRecord(slot.done, e->rt->stream));
     slot.busy = true;
     e->pin_next ^= 1;

@@ -302,6 +302,35 @@ extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const i
     return diag_attention("sc_diag_attention", rt, qkv, lens, B, S, heads, 0, nullptr, out);
 }
 
+// sc_launch_attention_packed as the packed forward calls it: the work items come from sc_packed_items, as there.
+extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                              int32_t blocked_rows, const float* slopes, float* out) {
+    const char* who = "sc_diag_attention_packed";
+    if (!rt || !qkv || !starts || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1 || heads > 32) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    const int H = heads * 64;
+    int64_t end = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
+            return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
+        const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
+        if (e > end) end = e;
+    }
+    const int64_t R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
+    if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    std::vector<int32_t> items((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
+    int nitems[3];
+    sc_packed_items(starts, lens, B, items.data(), nitems);
+    sc_devbuf fq, dq, di, dsl, dc;
+    SC_TRY(upload_bf16(qkv, R * 3 * H, fq, dq, s));
+    SC_TRY(upload(items.data(), items.size() * 4, di, s));
+    if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
+    SC_TRY(alloc_nan(dc, (size_t)R * H * 2, s));
+    sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows);
+    return download_bf16(dc.p, R * H, out, s);  // synchronises: items may go
+}
+
 // rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],
 // rotated in place, widened and laid out row-major again.
 extern "C" sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta) {

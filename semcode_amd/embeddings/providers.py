@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import logging
 from pathlib import Path
-from typing import Any, List, Optional, Sequence
+from typing import Any, Callable, List, Optional, Sequence
 
 import numpy as np
 
@@ -133,19 +133,52 @@ def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None
     raise ValueError(f"unsupported weight file {path} (use .npy blob, .safetensors or .gguf)")
 
 
+def cut_packed(lens: Sequence[int], budget: int, rows_of: "Callable[[np.ndarray], int]") -> "list[tuple[int, int]]":
+    """Cuts texts of `lens` tokens, in order, into consecutive groups [a, b) for packed encoder calls: a group takes as many texts as
+    rows_of(lens[a:b]) -- the token rows the encoder runs for them (Encoder.packed_rows) -- stays within `budget`; a text that alone
+    exceeds the budget is a group of its own.  rows_of must not decrease when a text is appended."""
+    lens = np.asarray(lens, dtype=np.int64)
+    groups, a, n = [], 0, len(lens)
+    while a < n:
+        lo, hi = a + 1, n  # the largest b in [a + 1, n] whose group fits; a + 1 is taken whatever it costs
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if rows_of(lens[a:mid]) <= budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        groups.append((a, lo))
+        a = lo
+    return groups
+
+
+def flatten_ids(ids: np.ndarray, lens: np.ndarray) -> "tuple[np.ndarray, np.ndarray]":
+    """Padded ids [n, S] + lens [n] -> (the real ids one text after another, offsets [n + 1]): the input of the packed encoder calls."""
+    lens = np.asarray(lens, dtype=np.int64)
+    offsets = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    keep = np.arange(ids.shape[1])[None, :] < lens[:, None]
+    return np.ascontiguousarray(ids[keep], dtype=np.int32), offsets
+
+
 class MI355XEmbeddings:
     """LangChain-Embeddings-shaped client whose forward runs in libsemcode_hip on the MI355X."""
 
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,
                  normalize: bool = False, batch_size: int = 256, runtime: Any = None, synth_seed: int = 0,
-                 allow_synthetic: Optional[bool] = None, document_prefix: Optional[str] = None, query_prefix: Optional[str] = None) -> None:
+                 allow_synthetic: Optional[bool] = None, document_prefix: Optional[str] = None, query_prefix: Optional[str] = None,
+                 packed: Optional[bool] = None, packed_rows_budget: int = 65536) -> None:
         from .. import _native  # raises loudly when libsemcode_hip.so is missing: there is no CPU fallback
 
         settings = _resolve_settings()
         self.model = model or getattr(settings, "embedding_model", None)
         self.max_tokens = int(max_tokens or getattr(settings, "mi355x_max_tokens", 512))
         self.batch_size = int(batch_size)
+        # packed=True: a batch runs on the token rows its texts need (32-row alignment per text) instead of batch x longest text.
+        # Off by default: packed and padded vectors agree to bf16 rounding, not bit for bit.
+        self.packed = bool(packed if packed is not None else getattr(settings, "mi355x_packed", False))
+        self.packed_rows_budget = int(packed_rows_budget)
         # task prefixes (nomic-embed-text expects "search_document: " / "search_query: "); llama.cpp behind LangChain adds none,
         # so none is the default
         self.document_prefix = str(document_prefix if document_prefix is not None else getattr(settings, "mi355x_document_prefix", "") or "")
@@ -245,8 +278,16 @@ class MI355XEmbeddings:
         out = np.empty((len(texts), self.dimension), dtype=np.float32)
         for start in range(0, len(texts), self.batch_size):
             ids, lens = self.tokenize(texts[start:start + self.batch_size], kind=kind)
-            out[start:start + len(lens)] = self._encoder.embed_ids(ids, lens)
+            if self.packed:
+                for a, b in self._packed_groups(lens):
+                    out[start + a:start + b] = self._encoder.embed_packed(*flatten_ids(ids[a:b], lens[a:b]))
+            else:
+                out[start:start + len(lens)] = self._encoder.embed_ids(ids, lens)
         return out
+
+    def _packed_groups(self, lens: np.ndarray) -> "list[tuple[int, int]]":
+        """Consecutive groups of one tokenised batch, each within packed_rows_budget token rows."""
+        return cut_packed(lens, self.packed_rows_budget, lambda l: self._encoder.packed_rows(np.concatenate(([0], np.cumsum(l)))))
 
     def tokenize(self, texts: Sequence[str], kind: str = "document") -> "tuple[np.ndarray, np.ndarray]":
         """texts -> (ids [n, S] int32 padded to the smallest sequence bucket that fits, lens [n]).  kind "document" | "query" picks
@@ -288,7 +329,12 @@ class MI355XEmbeddings:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
         if getattr(store, "_runtime", None) is not self._runtime:
             raise RuntimeError("embed_ids_into: the vector store and the embedding client use different runtimes")
-        return self._encoder.embed_ids_into(ids, lens, index, rows, want_host=want_host, wait=wait)
+        if not self.packed:
+            return self._encoder.embed_ids_into(ids, lens, index, rows, want_host=want_host, wait=wait)
+        rows = np.asarray(rows, dtype=np.int64)
+        got = [self._encoder.embed_packed_into(*flatten_ids(ids[a:b], lens[a:b]), index, rows[a:b], want_host=want_host, wait=wait)
+               for a, b in self._packed_groups(lens)]
+        return np.concatenate(got) if want_host else None
 
     def wait(self) -> None:
         """Block until every batch enqueued with embed_ids_into(..., wait=False) has finished."""
