@@ -464,6 +464,14 @@ sc_status sc_index_last_tail_rows(sc_index* ix, int64_t* rows);
  * config 5 = unique_rows * ld * 4), rows the scan kernel streamed (`streamed_rows`: list-major probing streams a list once per
  * group of <= 16 queries that want it; per-query probing once per query) and the number of (list part, query group) work items. */
 sc_status sc_index_last_probe_stats(sc_index* ix, int64_t* unique_rows, int64_t* streamed_rows, int32_t* groups);
+/* The host plan of a batched IVF probe, computed without a device (tests): path "listmajor" (the exact list-major probe) or "coarse"
+ * (the probe behind the int8 stage) for the probe table probes [Q, nprobe] (list ids; entries outside [0, nlist) are skipped), the
+ * list offsets list_off [nlist + 1], top-k k, row stride ld (floats) and cus compute units; wide 0 = no wide groups (as SC_IVF_WIDE=0).
+ * The scan parameters are derived exactly as the searches derive them.  out receives the plan's tables as records of
+ * {char name[16]; int32 kind (0 int32, 1 int64, 2 uint32, 3 {int64 row0; int32 rows; int32 slot_base}); int32 0; int64 count;
+ * count elements, padded to 8 bytes}; *need_bytes is their total size, and nothing is written when cap_bytes is smaller. */
+sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, int32_t Q, int32_t nprobe, const int64_t* list_off, int32_t nlist,
+                           int32_t k, int32_t ld, int32_t cus, int32_t wide, void* out, int64_t cap_bytes, int64_t* need_bytes);
 
 /* Multi-GPU final step (one process per GPU): merge `lists` per-shard results
  * dist [lists,Q,k] / rows [lists,Q,k] (as produced by sc_index_search* on each shard and

@@ -49,7 +49,7 @@ def gen_knn() -> None:
 
 
 def gen_ivf() -> None:
-    """IVF_FLAT build + probe of the deterministic build rule (oracle/ivf_oracle.py restates semcode_amd/csrc/sc_ivf.cpp) on the kNN
+    """IVF_FLAT build + probe of the deterministic build rule (oracle/ivf_oracle.py restates semcode_amd/csrc/sc_ivf_build.cpp) on the kNN
     fixture's rows.  There is nothing independent to generate these from (Milvus' k-means is random and absent): the file LOCKS
     the rule -- sampling, initialisation, Lloyd + re-seeding, assignment metric, probe order -- against silent change, and both the
     CPU restatement and the GPU build are checked against it."""

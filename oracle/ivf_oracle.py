@@ -3,7 +3,7 @@
 Parity status: "parity unpinned" -- the reference's IVF_FLAT lives in the Milvus 2.4.4 server
 (src/semcode/storage/milvus_store.py:76-84,141-147; docker-compose.yml:5), whose k-means uses random
 sampling/initialisation and is absent offline.  This restates the DETERMINISTIC build of
-semcode_amd/csrc/sc_ivf.cpp (sampling, initialisation, Lloyd iterations, assignment metric, probe
+semcode_amd/csrc/sc_ivf_build.cpp (sampling, initialisation, Lloyd iterations, assignment metric, probe
 rule), using the canonical scoring of sc_oracle.c, so that centroids, lists and results can be compared
 exactly; recall against the exhaustive oracle is the size-independent property used at full scale.
 """
@@ -38,7 +38,7 @@ def centroid_mean(S: np.ndarray, assign: np.ndarray, nlist: int, C_old: np.ndarr
 
 
 def reseed(Cent: np.ndarray, cnt: np.ndarray, ns: int) -> int:
-    """Between Lloyd iterations (sc_ivf.cpp sc_index_train): starved centroids (count < 0.75 average, smallest first, ties by
+    """Between Lloyd iterations (sc_ivf_plan.cpp sc_ivf_reseed_moves, called by sc_index_train): starved centroids (count < 0.75 average, smallest first, ties by
     id) are moved onto the largest ones (count > 2 average, largest first, ties by lower id; the size is halved on every
     split), the two copies pushed apart by the factors (1 +- 2^-10), sign alternating over the dimensions.  In place."""
     import heapq

@@ -130,6 +130,8 @@ SIGNATURES = {
     "sc_index_last_wide": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "sc_index_last_tail_rows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64)]),
     "sc_index_last_probe_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "sc_diag_ivf_plan": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_int64, C.POINTER(C.c_int64)]),
     "sc_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_size_t]),
     "sc_comm_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "sc_comm_destroy": (C.c_int32, [C.c_void_p]),
@@ -746,6 +748,31 @@ def diag_gemm_bf16(rt: Runtime, A, W, bias, R=None, epi: int = 0) -> np.ndarray:
         Rp = R.ctypes.data_as(C.c_void_p)
     _check(lib().sc_diag_gemm_bf16(rt.handle, epi, A.ctypes.data_as(C.c_void_p), W.ctypes.data_as(C.c_void_p),
                                    bias.ctypes.data_as(C.c_void_p), Rp, M, N, K, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+IVF_ITEM_DTYPE = np.dtype([("row0", "<i8"), ("rows", "<i4"), ("slot_base", "<i4")])
+
+
+def diag_ivf_plan(path: str, probes, list_off, k: int, ld: int, cus: int, wide: bool = True) -> "dict[str, np.ndarray]":
+    """The host plan of a batched IVF probe (sc_diag_ivf_plan; no device): path "listmajor" or "coarse", probes [Q, nprobe] list ids,
+    list_off [nlist + 1].  Every table the search would upload and every number it would report, by name; scalars as arrays of one."""
+    probes = np.ascontiguousarray(probes, np.int64)
+    list_off = np.ascontiguousarray(list_off, np.int64)
+    if probes.ndim != 2 or list_off.ndim != 1 or list_off.size < 2:
+        raise ValueError("diag_ivf_plan: probes must be [Q, nprobe], list_off [nlist + 1]")
+    need = C.c_int64()
+    args = (path.encode(), _ptr(probes), probes.shape[0], probes.shape[1], _ptr(list_off), list_off.size - 1, int(k), int(ld), int(cus), 1 if wide else 0)
+    _check(lib().sc_diag_ivf_plan(*args, None, 0, C.byref(need)))
+    blob = np.empty(need.value, np.uint8)
+    _check(lib().sc_diag_ivf_plan(*args, _ptr(blob), blob.size, C.byref(need)))
+    out, at, kinds = {}, 0, (np.dtype("<i4"), np.dtype("<i8"), np.dtype("<u4"), IVF_ITEM_DTYPE)
+    while at < blob.size:
+        name = blob[at:at + 16].tobytes().split(b"\0")[0].decode()
+        dt = kinds[int(blob[at + 16:at + 20].view("<i4")[0])]
+        n = int(blob[at + 24:at + 32].view("<i8")[0])
+        out[name] = blob[at + 32:at + 32 + n * dt.itemsize].view(dt).copy()
+        at += 32 + (n * dt.itemsize + 7) // 8 * 8
     return out
 
 

@@ -1,5 +1,5 @@
 // sc_api.cpp -- host side of the C ABI declared in include/semcode_hip.h: runtime + profiling, sc_diag_set_option, index create / destroy, rows in
-// and out, the getters of the last call's statistics.  Search: sc_search.cpp; delete: sc_delete.cpp; buffers and shadows: sc_index_state.cpp.
+// and out, the getters of the last call's statistics.  Search: sc_search.cpp; IVF build and probes: sc_ivf_*.cpp; delete: sc_delete.cpp; buffers and shadows: sc_index_state.cpp.
 //
 // Mirrors (reference): MilvusVectorStore's use of pymilvus -- connect / create collection + index /
 // upsert / search -- src/semcode/storage/milvus_store.py:39-148.  Error behaviour: every failure is

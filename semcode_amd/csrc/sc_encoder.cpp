@@ -73,8 +73,6 @@ struct sc_encoder {
     std::mutex mu;
 };
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---- packed variable-length batches (sc_encoder_embed_packed*): sequence i owns the token rows [starts[i], starts[i] + ceil32(len_i)),
 // one sequence after another; the GEMMs run on the total rounded up to 256 rows.
 static int64_t ceil32(int64_t v) { return (v + 31) & ~(int64_t)31; }
@@ -91,7 +89,7 @@ struct PlanOffsets {
     size_t ids, pos, starts, lens, items, total;
     PlanOffsets(size_t M, size_t B) {
         size_t u = 0;
-        auto take = [&](size_t bytes) { const size_t at = u; u += align256(bytes); return at; };
+        auto take = [&](size_t bytes) { const size_t at = u; u += sc_align256(bytes); return at; };
         ids = take(M * 4);
         pos = take(M * 4);
         starts = take(B * 4);
@@ -118,7 +116,7 @@ void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int3
 struct Arena {
     char* base = nullptr;
     size_t used = 0;
-    void* take(size_t bytes) { const size_t o = used; used += align256(bytes); return base ? base + o : nullptr; }
+    void* take(size_t bytes) { const size_t o = used; used += sc_align256(bytes); return base ? base + o : nullptr; }
     float* f32(size_t n) { return (float*)take(n * 4); }
     void* bf16(size_t n) { return take(n * 2); }
 };
@@ -640,11 +638,11 @@ extern "C" sc_status sc_encoder_embed_ids_into_async(sc_encoder* e, const int32_
     sc_encoder::PinSlot& slot = e->pin[e->pin_next];
     st = pin_slot_wait(slot);  // two batches may be in flight; the third waits for the first
     if (st) return st;
-    const size_t ids_b = (size_t)B * S * 4, lens_b = align256((size_t)B * 4), rows_b = (size_t)B * 8, need = align256(ids_b) + lens_b + rows_b;
+    const size_t ids_b = (size_t)B * S * 4, lens_b = sc_align256((size_t)B * 4), rows_b = (size_t)B * 8, need = sc_align256(ids_b) + lens_b + rows_b;
     st = pin_slot_reserve(slot, need);
     if (st) return st;
     char* h_ids = slot.host;
-    char* h_lens = slot.host + align256(ids_b);
+    char* h_lens = slot.host + sc_align256(ids_b);
     int64_t* h_rows = (int64_t*)(h_lens + lens_b);
     memcpy(h_ids, ids, ids_b);
     memcpy(h_lens, lens, (size_t)B * 4);

@@ -171,6 +171,21 @@ inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
 };
 
 static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
+// Offsets of the pieces of one scratch allocation, each 256-byte aligned: o = carve(bytes) ...; carve.off is the total to sc_grow.
+static inline size_t sc_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct sc_carver {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t o = off; off += sc_align256(bytes); return o; }
+};
+// A field set for the length of a scope (search_mode, coarse_mode, metric of an index under its lock): the old value returns on every way out.
+template <class T>
+struct sc_scoped_set {
+    T& ref;
+    const T saved;
+    sc_scoped_set(T& r, T v) : ref(r), saved(r) { r = v; }
+    ~sc_scoped_set() { ref = saved; }
+    sc_scoped_set(const sc_scoped_set&) = delete;
+};
 // A/B knobs of the environment; every call site keeps the value in a function-local static (read once per process).
 // sc_env_flag: a knob that is on by default goes off by a leading '0', one that is off by default goes on by a leading '1'.
 static inline int64_t sc_env_i64(const char* name, int64_t dflt) { const char* e = getenv(name); return e ? (int64_t)atoll(e) : dflt; }
@@ -193,7 +208,7 @@ struct sc_subbatch { float* q; float* d; int64_t* r; int32_t* idx; int R; };
 sc_status sc_subbatch_stage(sc_index* ix, sc_buf& buf, const float* q_dev, const std::vector<int>& which, int k, sc_subbatch* sb);
 sc_status sc_subbatch_scatter(sc_index* ix, const sc_subbatch& sb, int k, float* out_dist, int64_t* out_rows);  // results back to the batch's rows; synchronises
 
-// search and IVF internals shared between sc_search.cpp and sc_ivf.cpp (caller holds ix->mu)
+// search and IVF internals shared between sc_search.cpp and sc_ivf_{build,probe,coarse}.cpp (caller holds ix->mu)
 sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
 sc_status sc_search_flat_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, float* out_dist, int64_t* out_rows);
 sc_status sc_ivf_search_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
@@ -211,10 +226,21 @@ static inline int64_t sc_ivf_pos(const sc_index* ix, int64_t r) { return r < ix-
 // upsert body shared by sc_index_put_rows{,_dev} and sc_encoder_embed_ids_into; caller holds ix->mu and has set the device
 sc_status sc_index_put_rows_locked(sc_index* ix, const float* vecs, bool vecs_on_device, const int64_t* rows, int64_t n, const char* who);
 bool sc_ivf_applicable(const sc_index* ix, int Q, int nprobe);
+// sc_ivf_probe.cpp.  The nprobe nearest centroids of every query under the INDEX metric (the quantizer's own search; takes qz->mu):
+// distances and list ids at the head of ix->ivf_scratch, grown to hold `extra_bytes` more behind them; `host`: the ids there too
+// (synchronises).
+struct sc_ivf_probes { float* dist; int64_t* lists; char* extra; };
+sc_status sc_ivf_probe_quantizer_locked(sc_index* ix, const float* q_dev, int Q, int nprobe, size_t extra_bytes, sc_ivf_probes* out,
+                                        std::vector<int64_t>* host = nullptr);
+// What the host planners (sc_ivf_plan.h) read from the scan plans and the environment for (ld, k, nprobe) on `cus` compute units: the
+// one derivation shared by the searches and sc_diag_ivf_plan.  plan / plan_res (optional): the narrow scan's streamed / resident form.
+// false: the list-major probe cannot serve (ld, k, nprobe); pp->KP is valid either way.
+struct IvfPlanParams;
+bool sc_ivf_plan_params(int ld, int k, int nprobe, int cus, IvfPlanParams* pp, ScanPlan* plan = nullptr, ScanPlan* plan_res = nullptr);
 
 // process-wide test / A-B knobs behind sc_diag_set_option (sc_api.cpp), each defined next to the code it steers
-void sc_ivf_set_refresh_nomem(int v);  // sc_ivf.cpp
-void sc_ivf_set_refine_cap(int v);
+void sc_ivf_set_refresh_nomem(int v);  // sc_ivf_build.cpp
+void sc_ivf_set_refine_cap(int v);     // sc_ivf_coarse.cpp
 void sc_ivf_set_coarse_nomem(int v);
 void sc_set_collect_pass(int v);       // sc_search.cpp
 void sc_set_tighten(int v);

@@ -1,5 +1,5 @@
 // sc_search.cpp -- the flat-search planner and its stages (exact scan, batched coarse stages with their collect pass), the dispatch
-// between them and the IVF probes of sc_ivf.cpp, and the search entry points of the C ABI.  Caller holds ix->mu in every *_locked.
+// between them and the IVF probes of sc_ivf_probe.cpp / sc_ivf_coarse.cpp, and the search entry points of the C ABI.  Caller holds ix->mu in every *_locked.
 #include <algorithm>
 #include <chrono>
 #include <vector>
@@ -138,15 +138,14 @@ static sc_status search_collect_locked(sc_index* ix, const float* fq, int R, int
     const int Qpad = (i8 || R > 64) ? (R + 255) / 256 * 256 : 128;
     static_assert(BATCH_CAP == 4096, "the refine kernels' candidate stride (sc_ivf_widen_cap) is the survivor cap");
     if (sc_ivf_widen_cap() != BATCH_CAP) return sc_fail(SC_ERR_STATE, "collect pass: candidate stride mismatch");
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    sc_carver carve;
     const size_t o_qres = carve((size_t)R * 4), o_amax = carve(16);
     const size_t o_qb = carve(i8 ? (size_t)Qpad * ld8 : (size_t)Qpad * ld * 2), o_qs = carve((size_t)Qpad * 4), o_thr = carve((size_t)Qpad * 4),
                  o_tf = carve((size_t)Qpad * 4), o_cnt = carve((size_t)R * 4), o_ovf = carve((size_t)R * 4), o_flag = carve((size_t)R * 4), o_nc = carve((size_t)R * 4),
                  o_surv = carve((size_t)R * BATCH_CAP * 8), o_ek = carve((size_t)R * BATCH_CAP * 8);
     const size_t hit_bytes = (i8 && R <= 64) ? (size_t)2048 * (4 + 1024 * 16) + 256 : 0;
     const size_t o_hits = carve(hit_bytes ? hit_bytes : 16);
-    sc_status st = sc_grow(ix, ix->bscratch, off);
+    sc_status st = sc_grow(ix, ix->bscratch, carve.off);
     if (st) return st;
     char* b = ix->bscratch.as<char>();
     void* Qb = b + o_qb;
@@ -206,8 +205,7 @@ static sc_status search_batched_stage_locked(sc_index* ix, const float* q_dev, i
     sc_status st = i8 ? sc_ensure_shadow_i8(ix) : sc_ensure_shadow_b16(ix);
     if (st) return st;
     // scratch layout
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    sc_carver carve;
     const size_t o_qres = carve((size_t)Q * 4), o_amax = carve(16);
     const size_t o_qb = carve(i8 ? (size_t)Qpad * ld8 : (size_t)Qpad * ld * 2), o_qs = carve((size_t)Qpad * 4), o_thr = carve((size_t)Qpad * 4),
                  o_tf = carve((size_t)Qpad * 4), o_cnt = carve((size_t)Q * 4), o_ovf = carve((size_t)Q * 4), o_flag = carve((size_t)Q * 4),
@@ -219,7 +217,7 @@ static sc_status search_batched_stage_locked(sc_index* ix, const float* q_dev, i
     const size_t hit_bytes = (i8 && Q <= 64) ? (size_t)2048 * (4 + 1024 * 16) + 256 : 0;
     const size_t o_hits = carve(hit_bytes ? hit_bytes : 16);
     // the fallback sub-batch (depth 1) runs while the caller's scratch is no longer needed: one buffer serves both
-    st = sc_grow(ix, ix->bscratch, off);
+    st = sc_grow(ix, ix->bscratch, carve.off);
     if (st) return st;
     char* b = ix->bscratch.as<char>();
     void* Qb = b + o_qb;

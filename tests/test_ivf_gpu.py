@@ -647,3 +647,30 @@ def test_rows_overwritten_in_their_lists_refresh_their_shadow_rows_only(rt, metr
             assert (got["ivf"][1][:60, 0] == tgt).all() and (got["ivf"][1][60:80, 0] == 150_000 + np.arange(20)).all()
     finally:
         ix.close()
+
+
+def test_search_runs_the_plan_the_host_tests_check(rt):
+    """tests/test_ivf_plan_host.py checks the planners through sc_diag_ivf_plan; this ties that entry to the plan a search ran: fed the
+    probe table of the same batch (a FLAT search over the centroids under the index metric), the lists' sizes, ld and the CU count,
+    it predicts exactly the work the two batched probes report."""
+    X, centers = clustered(6000, 64, 24, seed=11)
+    rng = np.random.default_rng(12)
+    Q = (centers[rng.integers(0, 24, size=80)] + 0.3 * rng.standard_normal((80, 64))).astype(np.float32)
+    ix = _native.Index(rt, 64, metric="L2", kind="IVF_FLAT", nlist=32)
+    ix.add(X)
+    ix.train(niter=6)
+    info = ix.ivf_info()
+    qz = _native.Index(rt, 64, metric="L2")
+    qz.add(info["centroids"])
+    probes = qz.search(Q, k=4)[1]
+    qz.close()
+    list_off = np.concatenate([[0], np.cumsum(info["list_sizes"])])
+    for mode, path in (("ivf_listmajor", "listmajor"), ("ivf_coarse", "coarse")):
+        plan = _native.diag_ivf_plan(path, probes, list_off, 10, ix.info()["ld"], rt.device_info()["cus"])
+        ix.set_search_mode(mode)
+        ix.search(Q, k=10, nprobe=4)
+        stats = ix.last_search_stats()
+        assert stats["path"] == mode and stats["uncertified"] == 0, stats
+        want = {name: int(plan[name][0]) for name in ("unique_rows", "streamed_rows", "groups")}
+        assert ix.last_probe_stats() == want, (mode, ix.last_probe_stats(), want)
+    ix.close()
