@@ -402,6 +402,46 @@ sc_status sc_index_search_masked_dev(sc_index* ix, const float* q_dev, int32_t Q
  * (1) forces the gathered kernel even when every row is allowed (tests; results are identical; default 0). */
 sc_status sc_index_last_mask_stats(sc_index* ix, int64_t* allowed_rows, int64_t* scanned_rows, int32_t* gathered);
 
+/* Grouped search: Collection.search(..., group_by_field=...) -- at most ONE hit per group, exact.  (The reference has no such call:
+ * its RAG pipeline spends rag_max_context_sources on whatever the top-k holds, src/semcode/rag/pipeline.py:93-129, so the chunks of one
+ * large file crowd every other source out.)  The index learns nothing about files or repos: every local row carries an opaque int32
+ * LABEL, any value, compared for equality only.
+ * sc_index_set_groups installs labels[n] for the current rows (a device copy, 4 B per row; replaces any earlier set); n must equal the
+ * row count.  The labels are the caller's data parked on the device: the library does not persist, compact or interpret them, and
+ * they are not search scratch (sc_index_release_scratch keeps them).  They are valid while the index's row count equals the count
+ * they were installed for: an append outdates them, and sc_index_delete_rows drops them, because it renumbers the rows.  Host
+ * pointer; synchronises. */
+sc_status sc_index_set_groups(sc_index* ix, const int32_t* labels, int64_t n);
+/* The answer for a query: walk the allowed rows best first in the order of the keys (score, row) -- better score first, ties by
+ * lower row id -- keep a row if no earlier row had its label, stop after k rows.  out_rows = row_base + row, out_dist = the same bits
+ * the exact scan reports for that row, best first, padded with -1 and +inf (L2) / -inf (IP, COSINE) when the allowed rows hold
+ * fewer than k distinct labels.  All labels distinct: the plain exact search.  All labels equal: a single hit.
+ * allow == NULL (allow_words 0): every row; else the bitset of sc_index_search_masked (allow_words >= ceil(rows / 32)); a group whose
+ * best row is not allowed is represented by its best allowed row.  Always exact, all three metrics, no nprobe; a trained IVF_FLAT
+ * index is scanned as it lies, tail and overwritten rows included, without a refresh or a re-layout.
+ * How: round 0 takes every query through the exhaustive planner (the masked search, with a bitset) at a candidate width W0 >= k, and a
+ * selection kernel keeps the first row of every label of each best-first list, in list order.  A query is done with k labels, or when
+ * its list held padding (every allowed row was seen).  Each remaining query then goes on in rounds of its own: an exclusion kernel
+ * streams the labels (4 B per row) into a bitset of the allowed rows whose label is not among its hits, the masked search answers
+ * over that bitset at width W1, the selection kernel appends.  Every round finds a new label or ends the query: at most k rounds.
+ * The host reads the done flags once per round.  W0 = max(32, 4 k) within 64 (k <= 64) or 128, at least k; W1 = max(64, 4 k) within
+ * 256 in the first exclusion round and 256 in every further one (a masked scan gets slow with its width: 1 024 candidates cost
+ * seven times what 256 do); "group_width0" / "group_width1" of sc_diag_set_option set them (group_width1: every exclusion round; -1 =
+ * default; tests).  Results do not depend on either.
+ * Without valid labels: SC_ERR_INVALID naming both row counts, nothing launched.  k outside 1 .. 128, Q < 1, a NULL pointer or a
+ * short allow give SC_ERR_INVALID before anything changes.  Host pointers; synchronises.
+ * Out of scope: more than one hit per group, grouping on the IVF probe paths, sharded collections, labels that survive deletes. */
+sc_status sc_index_search_grouped(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint32_t* allow, int64_t allow_words,
+                                  float* out_dist, int64_t* out_rows);
+/* Same with DEVICE pointers (q row stride = dim; allow_dev may be NULL), enqueued on the runtime's stream.  Synchronises the stream
+ * once per round (the done flags) plus whatever the searches underneath wait for; the per-index mutex is held meanwhile.  Results
+ * are complete once the stream has passed the call. */
+sc_status sc_index_search_grouped_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev,
+                                      int64_t allow_words, float* out_dist_dev, int64_t* out_rows_dev);
+/* After a grouped search: the width of round 0, the queries that needed further rounds, the exclusion rounds run (summed over those
+ * queries; each is one masked search of one query) and the rows read by all scans of the call, per pass. */
+sc_status sc_index_last_group_stats(sc_index* ix, int32_t* first_width, int32_t* queries_continued, int32_t* rounds, int64_t* rows_scanned);
+
 /* Replaces Collection.create_index(IVF_FLAT, nlist) + load() (milvus_store.py:76-84) for an index created with
  * SC_INDEX_IVF_FLAT: deterministic k-means (niter Lloyd iterations on <= 256*nlist sampled rows), assignment of
  * every row to its nearest centroid, list-major re-ordering of the corpus in HBM.  Until it is called an IVF_FLAT index
@@ -433,7 +473,7 @@ sc_status sc_index_ivf_info(sc_index* ix, int32_t* nlist, float* centroids, int6
  * cheaper than the exhaustive paths, and otherwise answers exhaustively (exact results). */
 sc_status sc_index_set_search_mode(sc_index* ix, int32_t mode);
 /* After a search: which path ran (1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 list-major behind the int8 coarse
- * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner) and how many queries the batched path had to
+ * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner, 7 grouped: sc_index_search_grouped*) and how many queries the batched path had to
  * re-run through the exact scan because their certificate failed. */
 sc_status sc_index_last_search_stats(sc_index* ix, int32_t* path, int32_t* uncertified);
 

@@ -117,6 +117,10 @@ SIGNATURES = {
     "sc_index_search_masked": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sc_index_search_masked_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sc_index_last_mask_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "sc_index_set_groups": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sc_index_search_grouped": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_search_grouped_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_last_group_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "sc_index_train": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
     "sc_index_ivf_assignments": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "sc_index_set_ivf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -409,6 +413,42 @@ class Index:
         _check(lib().sc_index_last_mask_stats(self.handle, C.byref(a), C.byref(sc), C.byref(g)))
         return {"allowed_rows": int(a.value), "scanned_rows": int(sc.value), "gathered": bool(g.value)}
 
+    def set_groups(self, labels) -> None:
+        """Install one opaque int32 label per current row for search_grouped (sc_index_set_groups): a device copy that replaces any
+        earlier set; valid until the row count changes (an append) or delete_rows renumbers the rows."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        _check(lib().sc_index_set_groups(self.handle, lab.ctypes.data_as(C.c_void_p), lab.shape[0]))
+
+    def search_grouped(self, queries, k: int = 10, allow=None) -> tuple[np.ndarray, np.ndarray]:
+        """Exact search with at most one hit per label (sc_index_search_grouped): the best allowed row of each of the k best labels,
+        best first; allow = None (every row) or as for search_masked.  Fewer than k labels: padded with -1."""
+        q = _as_f32(queries, self.dim)
+        Q = q.shape[0]
+        dist = np.empty((Q, k), dtype=np.float32)
+        rows = np.empty((Q, k), dtype=np.int64)
+        allow_ptr, allow_words = None, 0
+        if allow is not None:
+            words = pack_allow(allow, len(self))
+            if words.size == 0:  # an empty index: still a valid pointer
+                words = np.zeros(1, dtype=np.uint32)
+            allow_ptr, allow_words = words.ctypes.data_as(C.c_void_p), words.shape[0]
+        _check(lib().sc_index_search_grouped(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), allow_ptr, allow_words,
+                                             dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return dist, rows
+
+    def search_grouped_dev(self, q_ptr: int, Q: int, k: int, allow_ptr: int, allow_words: int, dist_ptr: int, rows_ptr: int) -> None:
+        """Device-pointer variant (allow_ptr 0 with allow_words 0: every row; synchronises the stream once per round:
+        sc_index_search_grouped_dev)."""
+        _check(lib().sc_index_search_grouped_dev(self.handle, C.c_void_p(q_ptr), int(Q), int(k), C.c_void_p(allow_ptr) if allow_ptr else None, int(allow_words),
+                                                 C.c_void_p(dist_ptr), C.c_void_p(rows_ptr)))
+
+    def last_group_stats(self) -> dict:
+        """After a grouped search: width of round 0, queries that needed exclusion rounds, exclusion rounds run (summed over the
+        queries) and rows read by all scans of the call (sc_index_last_group_stats)."""
+        w, c, r, sc = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        _check(lib().sc_index_last_group_stats(self.handle, C.byref(w), C.byref(c), C.byref(r), C.byref(sc)))
+        return {"first_width": int(w.value), "queries_continued": int(c.value), "rounds": int(r.value), "rows_scanned": int(sc.value)}
+
     def train(self, niter: int = 10, seed: int = 0) -> None:
         """IVF_FLAT: k-means + list build (sc_index_train)."""
         _check(lib().sc_index_train(self.handle, int(niter), int(seed)))
@@ -459,7 +499,7 @@ class Index:
         path, unc, bits, handed = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().sc_index_last_search_stats(self.handle, C.byref(path), C.byref(unc)))
         _check(lib().sc_index_last_coarse_stats(self.handle, C.byref(bits), C.byref(handed)))
-        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked"}[path.value], "uncertified": unc.value}
+        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked", 7: "grouped"}[path.value], "uncertified": unc.value}
         if path.value in (3, 4, 5):
             tail = C.c_int64()
             _check(lib().sc_index_last_tail_rows(self.handle, C.byref(tail)))

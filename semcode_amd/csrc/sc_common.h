@@ -167,6 +167,15 @@ void sc_launch_mask_scatter(const uint64_t* flags, const uint32_t* cnt, int64_t 
 // the m stored positions sel[] instead of a row range; reported ids = perm[position] below perm_rows, the position itself beyond
 void sc_launch_scan_gather(int metric, const float* X, const float* xnorm, int ld, const float* Qp, const float* qnorm, int Q, int k, const ScanPlan& p,
                            uint64_t* partial, const uint32_t* perm, int64_t perm_rows, const uint32_t* sel, int64_t m, hipStream_t s);
+// scan_grouped.hip: the grouped search (sc_index_search_grouped*).
+// group_select: per query, the first occurrence of every label in its best-first candidate list cand_* [Q][W <= 1024] (ids; -1 =
+// padding) is appended, in list order, to out_* [Q][k <= 128] / found_labels [Q][k] at count[q]; count and done [Q] are updated (done:
+// k hits, or the list held padding).  first_round: count starts at 0 and the outputs are padded behind the hits.
+void sc_launch_group_select(int metric, const float* cand_dist, const int64_t* cand_rows, int W, int Q, const int32_t* labels, int64_t n, int64_t row_base, int k,
+                            bool first_round, float* out_dist, int64_t* out_rows, int32_t* found_labels, int32_t* count, int32_t* done, hipStream_t s);
+// group_exclude: out [ceil(n / 32)] = allow (NULL: every row) minus the rows whose label is one of ONE query's *count hit labels
+void sc_launch_group_exclude(const int32_t* labels, int64_t n, const uint32_t* allow, const int32_t* found_labels, const int32_t* count, uint32_t* out, int cus,
+                             hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

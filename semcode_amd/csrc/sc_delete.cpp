@@ -66,6 +66,7 @@ extern "C" sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int
         if (rows[i] < 0 || rows[i] >= ix->n) return sc_fail(SC_ERR_INVALID, "sc_index_delete_rows: rows[%lld] = %lld out of range [0,%lld)", (long long)i, (long long)rows[i], (long long)ix->n);
     std::vector<int64_t> ids(rows, rows + n);
     if (!sort_distinct(ids, ix->n)) return sc_fail(SC_ERR_INVALID, "sc_index_delete_rows: row numbers must be distinct");
+    ix->group_rows = -1;  // the rows are renumbered: the caller's group labels (sc_index_set_groups) no longer name them
     hipStream_t s = ix->rt->stream;
     const int64_t old_n = ix->n, ld = ix->ld;
     const bool listed = ix->perm != nullptr;  // trained layout installed: stored position != row id below ivf_rows

@@ -121,6 +121,12 @@ struct sc_index {
     sc_buf mask_words, mask_cnt, mask_sel;
     int64_t last_mask_allowed = 0, last_mask_scanned = 0;  // sc_index_last_mask_stats
     int last_mask_gathered = 0;
+    // grouped search (sc_grouped.cpp): the caller's label per row, valid while n == group_rows (-1: none installed) -- not scratch;
+    // the candidate lists, hit labels, counts, done flags and the exclusion bitset of a call
+    sc_buf groups, group_scratch;
+    int64_t group_rows = -1;
+    int last_group_width0 = 0, last_group_continued = 0, last_group_rounds = 0;  // sc_index_last_group_stats
+    int64_t last_group_scanned = 0;
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -151,7 +157,7 @@ struct sc_index {
     int64_t last_unique_rows = 0, last_streamed_rows = 0;  // sc_index_last_probe_stats
     int last_groups = 0;
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
-    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked
+    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked, 7 grouped
     int last_uncertified = 0;
     // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (sc_shadow::stat_bit) of the shadows kept / dropped
     int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
@@ -161,13 +167,13 @@ struct sc_index {
 };
 
 // The scratch buffers of an index (the shadows' arrays are reached through sc_index::shadows).  released: sc_index_release_scratch frees
-// it; the others are the small per-call query / result buffers, which stay.  sc_index_destroy frees all of them.
+// it; the others are the small per-call query / result buffers and the caller's group labels, which stay.  sc_index_destroy frees all of them.
 struct sc_index_buf { sc_buf sc_index::*buf; bool released; };
 inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
     {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
     {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
-    {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true},
-    {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},
+    {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true}, {&sc_index::group_scratch, true},
+    {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},          {&sc_index::groups, false},
 };
 
 static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
@@ -226,6 +232,9 @@ static inline int64_t sc_ivf_pos(const sc_index* ix, int64_t r) { return r < ix-
 // upsert body shared by sc_index_put_rows{,_dev} and sc_encoder_embed_ids_into; caller holds ix->mu and has set the device
 sc_status sc_index_put_rows_locked(sc_index* ix, const float* vecs, bool vecs_on_device, const int64_t* rows, int64_t n, const char* who);
 bool sc_ivf_applicable(const sc_index* ix, int Q, int nprobe);
+// sc_masked.cpp: the masked search under the lock.  q_dev tight [Q, dim], allow_dev >= ceil(n / 32) words, outputs [Q, k] (k <= 1024):
+// all device.  Synchronises the stream once (the allowed count).
+sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows);
 // sc_ivf_probe.cpp.  The nprobe nearest centroids of every query under the INDEX metric (the quantizer's own search; takes qz->mu):
 // distances and list ids at the head of ix->ivf_scratch, grown to hold `extra_bytes` more behind them; `host`: the ids there too
 // (synchronises).
@@ -248,4 +257,6 @@ void sc_set_wide_force(int v);
 void sc_set_ivf_tail_rows(int v);
 void sc_set_delete_chunk_rows(int v);  // sc_delete.cpp
 void sc_set_mask_gather(int v);        // sc_masked.cpp
+void sc_set_group_width0(int v);       // sc_grouped.cpp
+void sc_set_group_width1(int v);
 void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp

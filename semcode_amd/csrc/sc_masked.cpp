@@ -22,7 +22,7 @@ static sc_status check_allow_words(const sc_index* ix, int64_t allow_words) {
 }
 
 // q_dev tight [Q, dim], allow_dev >= ceil(n / 32) words, outputs [Q, k]: all device.  Synchronises the stream once (the allowed count).
-static sc_status search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows) {
+sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows) {
     sc_runtime* rt = ix->rt;
     hipStream_t s = rt->stream;
     const int64_t n = ix->n;
@@ -93,7 +93,7 @@ extern "C" sc_status sc_index_search_masked_dev(sc_index* ix, const float* q_dev
     st = check_allow_words(ix, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    return search_masked_locked(ix, q_dev, Q, k, allow_dev, out_dist_dev, out_rows_dev);
+    return sc_search_masked_locked(ix, q_dev, Q, k, allow_dev, out_dist_dev, out_rows_dev);
 }
 
 extern "C" sc_status sc_index_search_masked(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint32_t* allow, int64_t allow_words, float* out_dist,
@@ -118,7 +118,7 @@ extern "C" sc_status sc_index_search_masked(sc_index* ix, const float* q, int32_
     int64_t* dr = (int64_t*)(ix->io.as<char>() + qb + db);
     SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
     if (words) SC_HIP(hipMemcpyAsync(ix->mask_words.p, allow, words * 4, hipMemcpyHostToDevice, s));
-    st = search_masked_locked(ix, dq, Q, k, ix->mask_words.as<uint32_t>(), dd, dr);
+    st = sc_search_masked_locked(ix, dq, Q, k, ix->mask_words.as<uint32_t>(), dd, dr);
     if (st) return st;
     SC_HIP(hipMemcpyAsync(out_dist, dd, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
     SC_HIP(hipMemcpyAsync(out_rows, dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));

@@ -12,6 +12,7 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
     .search(vector, top_k=10)                   -> iterable of Hits; hit.entity.get(field), hit.distance,
                                                    hit.score, hit.id  (pymilvus SearchResult shape)
     .search(..., repos=[..], languages=[..])    -> Collection.search(expr=...): only rows of these repos AND languages, exact
+    .search(..., group_by="path" | "repo")      -> Collection.search(group_by_field=...): at most one hit per file / per repo, exact
     .delete(ids) / .delete_where(repo=, path=, language=)
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
 
@@ -128,6 +129,12 @@ class MilvusVectorStore:
         self._repo_codes = np.zeros(0, dtype=np.int32)  # capacity >= len(self._ids); entries beyond it are unused
         self._lang_codes = np.zeros(0, dtype=np.int32)
         self._mask_cache: dict = {}  # (frozenset(repos) | None, frozenset(languages) | None) -> (words, every row passes); dropped on every mutation
+        # grouped search: an integer code per row for the pair (repo, path) -- group_by="repo" reuses _repo_codes -- handed to the
+        # device index as opaque labels before a grouped search; _groups_installed names the column the index holds labels of for
+        # the rows as they are (None: none, or a mutation outdated them)
+        self._path_code: dict = {}
+        self._path_codes = np.zeros(0, dtype=np.int32)
+        self._groups_installed: Optional[str] = None
         # IVF_FLAT lists are built lazily before a search (Milvus' background index build).  Once built they are kept across
         # upserts: the device index assigns upserted rows to the existing centroids at the next search (no k-means, like
         # Collection.upsert into an indexed collection, milvus_store.py:128).  k-means runs again only on build_index() or when
@@ -241,9 +248,10 @@ class MilvusVectorStore:
     def commit_rows(self, ids: Sequence[str], rows: np.ndarray, texts: Sequence[str], metadatas: Sequence[dict]) -> None:
         """Scalar columns + primary-key map for rows whose vectors have just been written (same mapping as _upsert_batch)."""
         self._mask_cache.clear()
+        self._groups_installed = None
         for pk, row, text, meta in zip(ids, rows.tolist(), texts, metadatas):
             cols = (meta.get("repo", ""), meta.get("path", ""), meta.get("language", ""))
-            self._set_codes(row, cols[0], cols[2])
+            self._set_codes(row, cols[0], cols[2], cols[1])
             if row == len(self._ids):
                 self._row_of[pk] = row
                 self._ids.append(pk)
@@ -258,13 +266,15 @@ class MilvusVectorStore:
                 self._metadata[row] = meta
         self._note_growth()
 
-    def _set_codes(self, row: int, repo: str, language: str) -> None:
+    def _set_codes(self, row: int, repo: str, language: str, path: str = "") -> None:
         if row >= self._repo_codes.size:
             cap = max(1024, 2 * self._repo_codes.size, row + 1)
             self._repo_codes = np.concatenate([self._repo_codes, np.zeros(cap - self._repo_codes.size, np.int32)])
             self._lang_codes = np.concatenate([self._lang_codes, np.zeros(cap - self._lang_codes.size, np.int32)])
+            self._path_codes = np.concatenate([self._path_codes, np.zeros(cap - self._path_codes.size, np.int32)])
         self._repo_codes[row] = self._repo_code.setdefault(repo, len(self._repo_code))
         self._lang_codes[row] = self._lang_code.setdefault(language, len(self._lang_code))
+        self._path_codes[row] = self._path_code.setdefault((repo, path), len(self._path_code))
 
     def _note_growth(self) -> None:
         n = len(self._ids)
@@ -365,33 +375,46 @@ class MilvusVectorStore:
         self._row_of = {pk: r for r, pk in enumerate(self._ids)}
         self._repo_codes = self._repo_codes[: gone.size][~gone]
         self._lang_codes = self._lang_codes[: gone.size][~gone]
+        self._path_codes = self._path_codes[: gone.size][~gone]
         self._mask_cache.clear()
+        self._groups_installed = None
         if hasattr(ix, "__len__") and len(ix) != len(self._ids):
             raise RuntimeError(f"vector index holds {len(ix)} rows after the delete, the collection's columns expect {len(self._ids)}")
         return len(rows)
 
     # ------------------------------------------------------------------ search
-    def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None) -> SearchResult:
-        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages: see search_batch."""
+    def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None) -> SearchResult:
+        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages / group_by: see search_batch."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
-        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages)
+        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages, group_by=group_by)
         return SearchResult([self._hits(dist[0], rows[0])])
 
-    def search_batch(self, queries: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None) -> "tuple[np.ndarray, np.ndarray]":
+    GROUP_BY = ("path", "repo")
+
+    def search_batch(self, queries: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None,
+                     group_by: Optional[str] = None) -> "tuple[np.ndarray, np.ndarray]":
         """Batched search: queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64; -1 = no hit), best first.
 
         repos / languages (Collection.search(expr=...) for the two filters of the reference front ends): None = no restriction, a
         string or a collection of strings = only rows whose column value is one of them; both given = both must hold.  An empty
         collection or unknown names match nothing: no hits.  A restricted search is always exact -- the exhaustive answer over the
-        rows that pass, never an IVF probe (Index.search_masked).  A filter that every row passes is today's unfiltered call."""
+        rows that pass, never an IVF probe (Index.search_masked).  A filter that every row passes is today's unfiltered call.
+
+        group_by (Collection.search(group_by_field=...)): None = every chunk counts; "path" = at most one hit per file, i.e. per
+        pair (repo, path); "repo" = at most one hit per repo.  A group is represented by its best row among those the filter
+        passes; the hits are the top_k best groups, best first.  Always exact, top_k <= 128 (Index.search_grouped)."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
+        if group_by is not None and group_by not in self.GROUP_BY:
+            raise ValueError(f"group_by must be None or one of {self.GROUP_BY}, got {group_by!r}")
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"query dimension mismatch: collection dim={self.dim}, got shape {q.shape}")
         with self._lock:
             flt = self._filter(repos, languages)
+            if group_by is not None:
+                return self._search_grouped(q, int(top_k), flt, group_by)
             if flt is None or flt[1]:
                 self._maybe_train()
                 return self._collection.search(q, k=int(top_k), nprobe=self.nprobe)
@@ -399,6 +422,17 @@ class MilvusVectorStore:
             if not hasattr(ix, "search_masked"):
                 raise NotImplementedError(f"{type(ix).__name__} has no search_masked(queries, allow, k): this vector index cannot filter")
             return ix.search_masked(q, flt[0], k=int(top_k))
+
+    def _search_grouped(self, q: np.ndarray, top_k: int, flt: "Optional[tuple[np.ndarray, bool]]", group_by: str) -> "tuple[np.ndarray, np.ndarray]":
+        """The labels of `group_by` reach the index once per (mutation, column), then every grouped search reuses them.  Caller holds the lock."""
+        ix = self._collection
+        if not (hasattr(ix, "search_grouped") and hasattr(ix, "set_groups")):
+            raise NotImplementedError(f"{type(ix).__name__} has no set_groups(labels) / search_grouped(queries, k, allow): this vector index cannot group")
+        if self._groups_installed != group_by:
+            codes = self._path_codes if group_by == "path" else self._repo_codes
+            ix.set_groups(np.ascontiguousarray(codes[: len(self._ids)], dtype=np.int32))
+            self._groups_installed = group_by
+        return ix.search_grouped(q, k=top_k, allow=None if flt is None or flt[1] else flt[0])
 
     @staticmethod
     def _name_set(names: Any) -> "Optional[frozenset]":
@@ -533,8 +567,9 @@ class MilvusVectorStore:
             if len(self._ids) != n:
                 raise ValueError(f"{path}: columns.jsonl holds {len(self._ids)} rows, manifest says {n}")
             self._mask_cache.clear()
-            for row, (repo, language) in enumerate(zip(self._repos, self._languages)):
-                self._set_codes(row, repo, language)
+            self._groups_installed = None
+            for row, (repo, language, col_path) in enumerate(zip(self._repos, self._languages, self._paths)):
+                self._set_codes(row, repo, language, col_path)
             self._needs_train = True
             # the saved lists are reused as they are (no k-means) when they fit this collection's index parameters
             tn = int(manifest.get("ivf_trained_nlist", 0))
