@@ -442,6 +442,53 @@ sc_status sc_index_search_grouped_dev(sc_index* ix, const float* q_dev, int32_t 
  * queries; each is one masked search of one query) and the rows read by all scans of the call, per pass. */
 sc_status sc_index_last_group_stats(sc_index* ix, int32_t* first_width, int32_t* queries_continued, int32_t* rounds, int64_t* rows_scanned);
 
+/* MMR search: diversified top-k by maximal marginal relevance -- search_type="mmr" with fetch_k and lambda_mult of the LangChain vector
+ * stores, which download fetch_k embeddings and run numpy on them.  (The reference has no such call: vendored copies, generated code,
+ * license headers and forks are near-identical vectors under different paths and take every one of its rag_max_context_sources,
+ * src/semcode/rag/pipeline.py:93-129; grouping by file or repo does not touch them.)  Exact, all three metrics, bit for bit:
+ * 1. Candidates c_0 .. c_{C-1}: the exact top-fetch_k of the allowed rows in the order of the keys (better score first, ties by lower
+ *    row id) -- what sc_index_search / sc_index_search_masked return at k = fetch_k on an exhaustive scan.  C <= fetch_k is the number of
+ *    real hits (smaller when fewer rows are allowed).
+ * 2. Oriented score s(a, b): the index metric's score (IP: dot, COSINE: cosine, the canonical fmaf chain and the stored row norms),
+ *    negated for L2 so that larger is always better (the negation is exact).  rel_i = s(x_ci, q): the bits the search reported, negated
+ *    for L2.  red_ij = s(x_ci, x_cj): the dot in the canonical k order, both norms the stored row norms; red_ij and red_ji are the same bits.
+ * 3. Greedy selection: p_0 = 0; for t = 1 .. min(k, C) - 1 and every i not yet picked, m_i = max over the picked j of red_ij (an f32
+ *    max: exact) and v_i = fsub(fmul(lambda, rel_i), fmul(mu, m_i)) with mu = fsub(1, lambda) computed once -- three correctly rounded
+ *    f32 operations, never a fused multiply-add.  p_t is the i with the largest v_i; ties go to the smallest i.
+ * 4. Output in selection order: out_rows[t] = row_base + row(c_pt), out_dist[t] = the bits the exact scan reports for that row (the
+ *    distance: not v, not negated), padded with -1 and +inf (L2) / -inf (IP, COSINE) beyond min(k, C).
+ * So lambda = 1 gives the first k entries of the plain search, fetch_k = k a permutation of the plain top-k, k = 1 the best hit.
+ * allow == NULL (allow_words 0): every row; else the bitset of sc_index_search_masked (allow_words >= ceil(rows / 32)).
+ * 1 <= k <= fetch_k <= 128: the fast paths under the exhaustive planner take that width, and a 128 x 128 f32 score matrix is 64 KiB.
+ * Always exact and exhaustive, like the masked and the grouped search: no nprobe; a trained IVF_FLAT index is searched as it lies, tail
+ * and overwritten rows included, without a refresh or a re-layout.  Nothing about later searches changes.
+ * How: the candidate stage is the exhaustive planner (the masked search, with a bitset) at width fetch_k.  On a trained IVF_FLAT index a
+ * scatter kernel inverts the position map (4 B read + 4 B written per stored row) into the call's scratch: the candidates are row ids,
+ * the corpus is addressed by stored position.  mmr_gram_kernel computes the upper triangle of every query's candidate x candidate
+ * matrix in 16 x 16 tiles, one f32 MFMA chain per tile over rows gathered by position, and mirrors it; mmr_select_kernel runs the k - 1
+ * greedy steps, one workgroup per query, a butterfly arg-max per wave; no atomics decide anything.  Queries go through in chunks of
+ * 1 024 so that the matrices stay within 64 MiB; "mmr_chunk_q" of sc_diag_set_option shrinks the chunk (-1 = default; tests; results
+ * do not depend on it).  An empty index or no allowed row: no scan and no matrix kernel is launched, the selection kernel writes the
+ * padding alone.
+ * k < 1, k > fetch_k, fetch_k > 128, Q < 1, lambda outside [0, 1] or NaN, a NULL pointer or a short allow give SC_ERR_INVALID, naming
+ * the value, before anything changes.  Host pointers; synchronises.
+ * Out of scope: approximate candidates (nprobe, the IVF probe paths), fetch_k > 128, MMR together with grouping, sharded collections
+ * (sc_index_search_sharded*), a similarity for the redundancy term other than the index metric, caching the inverse position map
+ * (it would need invalidation hooks throughout the IVF code). */
+sc_status sc_index_search_mmr(sc_index* ix, const float* q, int32_t Q, int32_t k, int32_t fetch_k, float lambda, const uint32_t* allow,
+                              int64_t allow_words, float* out_dist, int64_t* out_rows);
+/* Same with DEVICE pointers (q row stride = dim; allow_dev may be NULL), enqueued on the runtime's stream.  Synchronises only where the
+ * searches underneath do (sc_index_search_dev, sc_index_search_masked_dev); the kernels added here need no host read.  The per-index
+ * mutex is held meanwhile.  Results are complete once the stream has passed the call. */
+sc_status sc_index_search_mmr_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t fetch_k, float lambda,
+                                  const uint32_t* allow_dev, int64_t allow_words, float* out_dist_dev, int64_t* out_rows_dev);
+/* After an MMR search: its fetch_k, the smallest candidate count C over the queries of the call (a device word read back here:
+ * synchronises the stream) and the rows read by the candidate scans of the call, per pass. */
+sc_status sc_index_last_mmr_stats(sc_index* ix, int32_t* fetch_k, int32_t* min_candidates, int64_t* rows_scanned);
+/* The selection rule (step 3) on the CPU, from the header the kernel compiles (tests on a machine without a GPU): rel [C], G [C rows of
+ * ldg >= C floats] = red_ij, picked [min(k, C)] receives candidate indices in selection order.  Nothing else of the search runs. */
+sc_status sc_diag_mmr_select_host(const float* rel, const float* G, int32_t C, int32_t ldg, int32_t k, float lambda, int32_t* picked);
+
 /* Replaces Collection.create_index(IVF_FLAT, nlist) + load() (milvus_store.py:76-84) for an index created with
  * SC_INDEX_IVF_FLAT: deterministic k-means (niter Lloyd iterations on <= 256*nlist sampled rows), assignment of
  * every row to its nearest centroid, list-major re-ordering of the corpus in HBM.  Until it is called an IVF_FLAT index
@@ -473,7 +520,7 @@ sc_status sc_index_ivf_info(sc_index* ix, int32_t* nlist, float* centroids, int6
  * cheaper than the exhaustive paths, and otherwise answers exhaustively (exact results). */
 sc_status sc_index_set_search_mode(sc_index* ix, int32_t mode);
 /* After a search: which path ran (1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 list-major behind the int8 coarse
- * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner, 7 grouped: sc_index_search_grouped*) and how many queries the batched path had to
+ * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner, 7 grouped: sc_index_search_grouped*, 8 mmr: sc_index_search_mmr*) and how many queries the batched path had to
  * re-run through the exact scan because their certificate failed. */
 sc_status sc_index_last_search_stats(sc_index* ix, int32_t* path, int32_t* uncertified);
 

@@ -121,6 +121,10 @@ SIGNATURES = {
     "sc_index_search_grouped": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sc_index_search_grouped_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sc_index_last_group_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "sc_index_search_mmr": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_search_mmr_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_last_mmr_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "sc_diag_mmr_select_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "sc_index_train": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
     "sc_index_ivf_assignments": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "sc_index_set_ivf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -449,6 +453,37 @@ class Index:
         _check(lib().sc_index_last_group_stats(self.handle, C.byref(w), C.byref(c), C.byref(r), C.byref(sc)))
         return {"first_width": int(w.value), "queries_continued": int(c.value), "rounds": int(r.value), "rows_scanned": int(sc.value)}
 
+    def search_mmr(self, queries, k: int = 10, fetch_k: int = 40, lam: float = 0.5, allow=None) -> tuple[np.ndarray, np.ndarray]:
+        """Diversified exact search by maximal marginal relevance (sc_index_search_mmr): the greedy selection of k out of the exact
+        top-fetch_k (k <= fetch_k <= 128) of the allowed rows, lam in [0, 1] weighing relevance against redundancy, in selection
+        order; allow = None (every row) or as for search_masked.  Fewer than k allowed rows: padded with -1."""
+        q = _as_f32(queries, self.dim)
+        Q = q.shape[0]
+        dist = np.empty((Q, k), dtype=np.float32)
+        rows = np.empty((Q, k), dtype=np.int64)
+        allow_ptr, allow_words = None, 0
+        if allow is not None:
+            words = pack_allow(allow, len(self))
+            if words.size == 0:  # an empty index: still a valid pointer
+                words = np.zeros(1, dtype=np.uint32)
+            allow_ptr, allow_words = words.ctypes.data_as(C.c_void_p), words.shape[0]
+        _check(lib().sc_index_search_mmr(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(fetch_k), float(lam), allow_ptr, allow_words,
+                                         dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return dist, rows
+
+    def search_mmr_dev(self, q_ptr: int, Q: int, k: int, fetch_k: int, lam: float, allow_ptr: int, allow_words: int, dist_ptr: int, rows_ptr: int) -> None:
+        """Device-pointer variant (allow_ptr 0 with allow_words 0: every row; synchronises only where the searches underneath do:
+        sc_index_search_mmr_dev)."""
+        _check(lib().sc_index_search_mmr_dev(self.handle, C.c_void_p(q_ptr), int(Q), int(k), int(fetch_k), float(lam), C.c_void_p(allow_ptr) if allow_ptr else None,
+                                             int(allow_words), C.c_void_p(dist_ptr), C.c_void_p(rows_ptr)))
+
+    def last_mmr_stats(self) -> dict:
+        """After an MMR search: its fetch_k, the smallest candidate count of the batch and the rows read by its candidate scans
+        (sc_index_last_mmr_stats)."""
+        f, c, sc = C.c_int32(), C.c_int32(), C.c_int64()
+        _check(lib().sc_index_last_mmr_stats(self.handle, C.byref(f), C.byref(c), C.byref(sc)))
+        return {"fetch_k": int(f.value), "min_candidates": int(c.value), "rows_scanned": int(sc.value)}
+
     def train(self, niter: int = 10, seed: int = 0) -> None:
         """IVF_FLAT: k-means + list build (sc_index_train)."""
         _check(lib().sc_index_train(self.handle, int(niter), int(seed)))
@@ -499,7 +534,7 @@ class Index:
         path, unc, bits, handed = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().sc_index_last_search_stats(self.handle, C.byref(path), C.byref(unc)))
         _check(lib().sc_index_last_coarse_stats(self.handle, C.byref(bits), C.byref(handed)))
-        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked", 7: "grouped"}[path.value], "uncertified": unc.value}
+        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked", 7: "grouped", 8: "mmr"}[path.value], "uncertified": unc.value}
         if path.value in (3, 4, 5):
             tail = C.c_int64()
             _check(lib().sc_index_last_tail_rows(self.handle, C.byref(tail)))

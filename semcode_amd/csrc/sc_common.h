@@ -176,6 +176,17 @@ void sc_launch_group_select(int metric, const float* cand_dist, const int64_t* c
 // group_exclude: out [ceil(n / 32)] = allow (NULL: every row) minus the rows whose label is one of ONE query's *count hit labels
 void sc_launch_group_exclude(const int32_t* labels, int64_t n, const uint32_t* allow, const int32_t* found_labels, const int32_t* count, uint32_t* out, int cus,
                              hipStream_t s);
+// scan_mmr.hip: the MMR search (sc_index_search_mmr*).
+// mmr_inverse: inv [n] = row -> stored position from perm [mapped] (stored position -> row; positions at or beyond mapped are rows).
+// mmr_gram: G [Q][Fp][Fp] (Fp = F rounded up to 16), G[q][i][j] = the oriented score (sc_score, negated for L2) of candidates i and j of
+// query q's best-first list cand_rows [Q][F <= 128] (ids; -1 = padding, last); inv NULL: the row is the position.  Entries of padding
+// slots are unspecified.  mmr_select: the greedy selection of mmr_rule.h over cand_* and G -> out_* [Q][k <= F] in selection order,
+// padded; cand_rows NULL: padding only.  *min_count = min(*min_count, candidates of every query).
+void sc_launch_mmr_inverse(const uint32_t* perm, int64_t mapped, int64_t n, uint32_t* inv, hipStream_t s);
+void sc_launch_mmr_gram(int metric, const float* X, const float* xnorm, int ld, int64_t n, int64_t row_base, const uint32_t* inv, const int64_t* cand_rows, int F, int Q,
+                        float* G, hipStream_t s);
+void sc_launch_mmr_select(int metric, const float* cand_dist, const int64_t* cand_rows, int F, const float* G, int Q, int k, float lambda, float* out_dist,
+                          int64_t* out_rows, int32_t* min_count, hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

@@ -127,6 +127,12 @@ struct sc_index {
     int64_t group_rows = -1;
     int last_group_width0 = 0, last_group_continued = 0, last_group_rounds = 0;  // sc_index_last_group_stats
     int64_t last_group_scanned = 0;
+    // MMR search (sc_mmr.cpp): the candidate lists, the candidate x candidate score matrices and the row -> position map of a call;
+    // the smallest candidate count of the last call, a device word that sc_index_last_mmr_stats reads when asked (not scratch)
+    sc_buf mmr_scratch, mmr_stat;
+    int last_mmr_fetch = 0;
+    bool mmr_stat_pending = false;                // the device word holds the last call's count
+    int64_t last_mmr_scanned = 0;
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -157,7 +163,7 @@ struct sc_index {
     int64_t last_unique_rows = 0, last_streamed_rows = 0;  // sc_index_last_probe_stats
     int last_groups = 0;
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
-    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked, 7 grouped
+    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked, 7 grouped, 8 mmr
     int last_uncertified = 0;
     // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (sc_shadow::stat_bit) of the shadows kept / dropped
     int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
@@ -173,7 +179,9 @@ inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
     {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
     {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
     {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true}, {&sc_index::group_scratch, true},
+    {&sc_index::mmr_scratch, true},
     {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},          {&sc_index::groups, false},
+    {&sc_index::mmr_stat, false},
 };
 
 static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
@@ -259,4 +267,5 @@ void sc_set_delete_chunk_rows(int v);  // sc_delete.cpp
 void sc_set_mask_gather(int v);        // sc_masked.cpp
 void sc_set_group_width0(int v);       // sc_grouped.cpp
 void sc_set_group_width1(int v);
+void sc_set_mmr_chunk_q(int v);        // sc_mmr.cpp
 void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp

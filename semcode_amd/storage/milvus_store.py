@@ -13,6 +13,7 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
                                                    hit.score, hit.id  (pymilvus SearchResult shape)
     .search(..., repos=[..], languages=[..])    -> Collection.search(expr=...): only rows of these repos AND languages, exact
     .search(..., group_by="path" | "repo")      -> Collection.search(group_by_field=...): at most one hit per file / per repo, exact
+    .search(..., mmr=0.5, fetch_k=40)           -> search_type="mmr" (lambda_mult, fetch_k) of the LangChain stores: diversified top_k, exact, on device
     .delete(ids) / .delete_where(repo=, path=, language=)
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
 
@@ -383,17 +384,20 @@ class MilvusVectorStore:
         return len(rows)
 
     # ------------------------------------------------------------------ search
-    def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None) -> SearchResult:
-        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages / group_by: see search_batch."""
+    def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
+               mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> SearchResult:
+        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages / group_by / mmr / fetch_k: see
+        search_batch."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
-        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages, group_by=group_by)
+        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages, group_by=group_by, mmr=mmr, fetch_k=fetch_k)
         return SearchResult([self._hits(dist[0], rows[0])])
 
     GROUP_BY = ("path", "repo")
+    MMR_MAX_FETCH = 128  # the widest candidate list of Index.search_mmr
 
     def search_batch(self, queries: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None,
-                     group_by: Optional[str] = None) -> "tuple[np.ndarray, np.ndarray]":
+                     group_by: Optional[str] = None, mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> "tuple[np.ndarray, np.ndarray]":
         """Batched search: queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64; -1 = no hit), best first.
 
         repos / languages (Collection.search(expr=...) for the two filters of the reference front ends): None = no restriction, a
@@ -403,11 +407,34 @@ class MilvusVectorStore:
 
         group_by (Collection.search(group_by_field=...)): None = every chunk counts; "path" = at most one hit per file, i.e. per
         pair (repo, path); "repo" = at most one hit per repo.  A group is represented by its best row among those the filter
-        passes; the hits are the top_k best groups, best first.  Always exact, top_k <= 128 (Index.search_grouped)."""
+        passes; the hits are the top_k best groups, best first.  Always exact, top_k <= 128 (Index.search_grouped).
+
+        mmr (search_type="mmr" of the LangChain vector stores; the value is their lambda_mult): None = today's behaviour; a number
+        in [0, 1] = maximal marginal relevance over the exact top-fetch_k of the rows the filter passes: the best hit first, then
+        greedily the candidate with the largest mmr * relevance - (1 - mmr) * (largest similarity to a hit already taken), both in
+        the collection's metric.  1 = the plain order, 0 = diversity alone.  The hits come in selection order, not best first.
+        fetch_k defaults to min(128, max(20, 4 top_k)); top_k <= fetch_k <= 128.  Always exact (Index.search_mmr); not combined
+        with group_by."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
         if group_by is not None and group_by not in self.GROUP_BY:
             raise ValueError(f"group_by must be None or one of {self.GROUP_BY}, got {group_by!r}")
+        if mmr is None and fetch_k is not None:
+            raise ValueError("fetch_k is the candidate width of an mmr search: give mmr as well")
+        if mmr is not None:
+            if group_by is not None:
+                raise ValueError("mmr together with group_by is not supported")
+            lam = float(mmr)
+            if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError(f"mmr must be within [0, 1], got {mmr!r}")
+            top_k = int(top_k)
+            if top_k > self.MMR_MAX_FETCH:
+                raise ValueError(f"an mmr search takes top_k <= {self.MMR_MAX_FETCH}, got {top_k}")
+            fetch_k = min(self.MMR_MAX_FETCH, max(20, 4 * top_k)) if fetch_k is None else int(fetch_k)
+            if fetch_k > self.MMR_MAX_FETCH:
+                raise ValueError(f"an mmr search takes fetch_k <= {self.MMR_MAX_FETCH}, got {fetch_k}")
+            if fetch_k < top_k:
+                raise ValueError(f"fetch_k={fetch_k} is smaller than top_k={top_k}")
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"query dimension mismatch: collection dim={self.dim}, got shape {q.shape}")
@@ -415,6 +442,11 @@ class MilvusVectorStore:
             flt = self._filter(repos, languages)
             if group_by is not None:
                 return self._search_grouped(q, int(top_k), flt, group_by)
+            if mmr is not None:
+                ix = self._collection
+                if not hasattr(ix, "search_mmr"):
+                    raise NotImplementedError(f"{type(ix).__name__} has no search_mmr(queries, k, fetch_k, lam, allow): this vector index cannot diversify")
+                return ix.search_mmr(q, k=top_k, fetch_k=fetch_k, lam=lam, allow=None if flt is None or flt[1] else flt[0])
             if flt is None or flt[1]:
                 self._maybe_train()
                 return self._collection.search(q, k=int(top_k), nprobe=self.nprobe)
