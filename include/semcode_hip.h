@@ -254,6 +254,9 @@ sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* len
  * result widened to f32; synchronous; outputs are pre-filled with NaN so that an element the kernel leaves unwritten shows.
  * "gemm_nt" of sc_diag_set_option: C stores of the 256-tile GEMMs (-1 = default: non-temporal from 64 MiB of output, or the SC_GEMM_NT
  * environment variable; 0 = never; 1 = always) -- lets a small shape take the non-temporal store path; results are identical.
+ * "gemm_strip": the EPI_LNA_* GEMMs as strips of consecutive column tiles of one row panel per workgroup (-1 = default: by shape, or
+ * the SC_GEMM_STRIP environment variable; 0 = one workgroup per tile; L >= 1 = L tiles per strip, clamped to the tiles of a panel);
+ * "gemm_strip_n": N > 0 applies a forced "gemm_strip" to the launches with that N only, the others run per tile (scripts/strip_sweep.py).
  * sc_diag_fold_ln: W [N,K], gamma / beta [K], bias [N] or NULL -> Wf [N,K] = bf16(W diag(gamma)) widened, c1 [N] = row sums of Wf,
  *   c2 [N] = bias + W beta (K a multiple of 4).
  * sc_diag_gemm_lna: epi 3 (EPI_LNA_BIAS), 4 (EPI_LNA_GELU) or 6 (EPI_LNA_BIAS_ROPE): C [M,N] = LN(A) W^T + b computed as
@@ -278,6 +281,10 @@ sc_status sc_diag_fold_ln(sc_runtime* rt, const float* W, const float* gamma, co
 sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* Wf, const float* c1, const float* c2,
                            const float* stats_in, float eps, int32_t M, int32_t N, int32_t K, int32_t rope_S, float rope_theta,
                            int32_t rope_ncols, float* C, float* fin);
+/* Strip selection of the EPI_LNA_* GEMM launcher.  M > 0: tiles per strip an [M,K] x [N,K] launch would get under the current options
+ * ("gemm_strip", "gemm_strip_n", "gemm_pp", SC_GEMM_STRIP) on a device with `cus` compute units (cus <= 0: the current device's),
+ * 0 = one workgroup per tile; host arithmetic only.  M == 0: what the most recent EPI_LNA_* launch of this process used. */
+int32_t sc_diag_gemm_strip(int32_t M, int32_t N, int32_t K, int32_t cus);
 sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
                              const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out);
 sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,

@@ -22,15 +22,34 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
+def use_library(lib_path):
+    """Points semcode_amd._native at that build.  A build of the parent commit does not export entry points added since: the binding
+    drops those (named on stderr) instead of refusing the whole library; nothing this script calls may be among them."""
+    import ctypes
+
+    from semcode_amd import _native as nv
+
+    try:
+        import torch  # noqa: F401  (before the library, as _native.lib() loads it)
+    except Exception:
+        pass
+    nv.LIB_PATH = Path(lib_path).resolve()
+    handle = ctypes.CDLL(str(nv.LIB_PATH))
+    missing = [name for name in nv.SIGNATURES if not hasattr(handle, name)]
+    for name in missing:
+        del nv.SIGNATURES[name]
+    if missing:
+        print(f"{nv.LIB_PATH.name} lacks {missing}: not bound", file=sys.stderr)
+    return nv
+
+
 def line(name, a):
     a = np.ascontiguousarray(a)
     return f"{name} {a.dtype}{list(a.shape)} {hashlib.sha256(a.tobytes()).hexdigest()}"
 
 
 def dump(lib_path, out_path):
-    from semcode_amd import _native as nv
-
-    nv.LIB_PATH = Path(lib_path).resolve()
+    nv = use_library(lib_path)
     rt = nv.Runtime()
     out = []
     rng = np.random.default_rng(2024)
@@ -118,9 +137,7 @@ def compare(a_path, b_path):
 def bench(lib_path, argv):
     import runpy
 
-    from semcode_amd import _native as nv
-
-    nv.LIB_PATH = Path(lib_path).resolve()
+    use_library(lib_path)
     root = Path(__file__).resolve().parent.parent
     sys.argv = [str(root / "bench.py"), *argv]
     runpy.run_path(sys.argv[0], run_name="__main__")

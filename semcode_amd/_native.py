@@ -86,6 +86,7 @@ SIGNATURES = {
     "sc_diag_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     "sc_diag_swiglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_fold_ln": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "sc_diag_gemm_strip": (C.c_int32, [C.c_int32] * 4),
     "sc_diag_gemm_lna": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_gemm_resln": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -955,6 +956,12 @@ def diag_gemm_lna(rt: Runtime, epi: int, A, Wf, c1, c2, stats_in, eps: float, bl
     _check(lib().sc_diag_gemm_lna(rt.handle, epi, 1 if blocked else 0, _ptr(A), _ptr(Wf), _ptr(c1), _ptr(c2), _ptr(stats_in), float(eps), M, N, K,
                                   int(rope_S), float(rope_theta), int(rope_ncols), _ptr(Cc), _ptr(fin)))
     return (unblock64(Cc, M, N) if blocked else Cc), fin
+
+
+def diag_gemm_strip(M: int = 0, N: int = 0, K: int = 0, cus: int = 0) -> int:
+    """Tiles per strip the EPI_LNA_* launcher picks for this shape under the current options (0 = per-tile kernel); no launch, and
+    no device when cus > 0.  M == 0: what the most recent EPI_LNA_* launch of this process used."""
+    return int(lib().sc_diag_gemm_strip(int(M), int(N), int(K), int(cus)))
 
 
 def diag_gemm_resln(rt: Runtime, A, W, bias, gam, R, fin, eps: float, a_blocked: bool = False):

@@ -21,11 +21,17 @@ void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int 
                             int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps,
                             const float* rope_cos = nullptr, const float* rope_sin = nullptr, int rope_S = 0, int rope_ncols = 0);
 void sc_launch_gemm_i8_diag(const void* A, const void* W, void* C, int M, int N, int K, hipStream_t s);
-// process-wide knobs of the launchers (sc_diag_set_option "gemm_pp" / "gemm_nt", sc_diag_gemm_trace, sc_diag_gemm_bench)
+// process-wide knobs of the launchers (sc_diag_set_option "gemm_pp" / "gemm_nt" / "gemm_strip" / "gemm_strip_n", sc_diag_gemm_trace,
+// sc_diag_gemm_bench)
 void sc_gemm_set_debug(int v);
 void sc_gemm_set_order(int v);
 void sc_gemm_set_pp(int v);
 void sc_gemm_set_nt(int v);
+void sc_gemm_set_strip(int v);
+void sc_gemm_set_strip_n(int v);
+int sc_gemm_strip_rule(int M, int N, int K, int cus);                       // the shape rule alone (host arithmetic)
+int sc_gemm_strip_tiles(int M, int N, int K, int cus, bool a_blocked = false);  // ... under the current options: tiles per strip, 0 = per-tile
+int sc_gemm_last_strip(void);                                                // tiles per strip of the last EPI_LNA_* launch (0 = per-tile kernel)
 void sc_gemm_set_trace(unsigned long long* dev);
 void sc_gemm_force_tile128(bool on);
 

@@ -48,6 +48,7 @@ struct GemmArgs {
     int ntiles;        // (M/128) * tiles_n
     int order;         // 256-tile kernels: tile walk (see gemm256_tile)
     int splitk;        // split-K kernels: number of K slices (grid = ntiles * splitk)
+    int strip;         // strip kernel: column tiles per workgroup (grid = (M / 256) * ceil(tiles_n / strip))
     float* partial;    // split-K kernels: [splitk][M][N] f32 partial products
     unsigned long long* trace;  // diagnostic: per-workgroup time stamps [ntiles][8] (sc_diag_gemm_trace), else nullptr
     int nt;            // 256-tile kernel: write C with non-temporal stores (outputs far larger than L2)
@@ -328,8 +329,20 @@ static __device__ __forceinline__ void gemm256_epilogue(const GemmArgs& a, int m
 // EPI_LNA_BIAS / EPI_LNA_GELU: out = rs_m (acc - mu_m c1[n]) + c2[n] (+ GELU).  (mu, rs) of a row come from the partial sums the
 // producing GEMM left per 256-column tile of the A tensor (LnaTailHook put this wave's 128 rows x slots into its pipeline slice);
 // the column tile n0 == 0 also publishes them finalised ([M][2]) for the residual epilogue of the next GEMM.
-template <int EPI>
-static __device__ __forceinline__ void gemm256_epilogue_lna(const GemmArgs& a, int m0, int n0, char* smem, int w, int lane, f32x4 (&acc)[4][8]) {
+// (mu, rs) of two rows from their summed {sum, sumsq | sum, sumsq}: v_rsq_f32 (1 ulp) is ample in front of a bf16 rounding
+static __device__ __forceinline__ f32x4 lna_finalise(const GemmArgs& a, const f32x4& sacc) {
+    const float inv_k = 1.0f / (float)a.K;
+    const float mu0 = sacc[0] * inv_k, mu1 = sacc[2] * inv_k;
+    const float rs0 = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mu0, mu0, sacc[1] * inv_k), 0.f) + a.ln_eps);
+    const float rs1 = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mu1, mu1, sacc[3] * inv_k), 0.f) + a.ln_eps);
+    return f32x4{mu0, rs0, mu1, rs1};
+}
+
+// mrs: where the finalised (mu, rs) of this wave's 128 rows live in LDS (1 KiB).  Per-tile kernel: the wave's pipeline slice -- the
+// statistics slots arrive there and are finalised in place.  STRIP (gemm256_strip_kernel): behind the staging area, finalised once
+// by the caller -- the pipeline ring already holds the next tile and is not touched here.
+template <int EPI, bool STRIP = false>
+static __device__ __forceinline__ void gemm256_epilogue_lna(const GemmArgs& a, int m0, int n0, char* smem, int w, int lane, f32x4 (&acc)[4][8], char* mrs) {
     const int wm = w >> 2, wn = w & 3;
     int ln = lane;
     asm volatile("" : "+v"(ln));
@@ -346,23 +359,18 @@ static __device__ __forceinline__ void gemm256_epilogue_lna(const GemmArgs& a, i
         c1v[ni] = *reinterpret_cast<const f32x4*>(a.c1 + n0 + wn * 64 + ni * 16 + 4 * fq);
         c2v[ni] = *reinterpret_cast<const f32x4*>(a.bias + n0 + wn * 64 + ni * 16 + 4 * fq);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's statistics DMA has landed
-    // (mu, rs) of the wave's 128 rows: lane ln finalises rows 2 ln and 2 ln + 1 ONCE (every lane doing its own 8 rows cost 8 divide
-    // + square-root sequences per lane: +29 / +52 us per QKV / FFN1 launch, gpurun_out/prof_fold1) and parks them in place of
-    // slot 0; v_rsq_f32 (1 ulp) is ample in front of a bf16 rounding.
-    char* slice = smem + w * 16384;
-    {
+    if constexpr (!STRIP) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's statistics DMA has landed
+        // (mu, rs) of the wave's 128 rows: lane ln finalises rows 2 ln and 2 ln + 1 ONCE (every lane doing its own 8 rows cost 8 divide
+        // + square-root sequences per lane: +29 / +52 us per QKV / FFN1 launch, gpurun_out/prof_fold1) and parks them in place of
+        // slot 0.
         f32x4 sacc = {0.f, 0.f, 0.f, 0.f};  // {sum, sumsq} of row 2 ln | of row 2 ln + 1
-        for (int t = 0; t < a.stat_slots; ++t) sacc += *reinterpret_cast<const f32x4*>(slice + t * 1024 + ln * 16);
-        const float inv_k = 1.0f / (float)a.K;
-        const float mu0 = sacc[0] * inv_k, mu1 = sacc[2] * inv_k;
-        const float rs0 = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mu0, mu0, sacc[1] * inv_k), 0.f) + a.ln_eps);
-        const float rs1 = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mu1, mu1, sacc[3] * inv_k), 0.f) + a.ln_eps);
-        const f32x4 fin4 = {mu0, rs0, mu1, rs1};
-        *reinterpret_cast<f32x4*>(slice + ln * 16) = fin4;
+        for (int t = 0; t < a.stat_slots; ++t) sacc += *reinterpret_cast<const f32x4*>(mrs + t * 1024 + ln * 16);
+        const f32x4 fin4 = lna_finalise(a, sacc);
+        *reinterpret_cast<f32x4*>(mrs + ln * 16) = fin4;
         if (n0 == 0 && wn == 0) *reinterpret_cast<f32x4*>(a.fin + (size_t)(m0 + wm * 128) * 2 + ln * 4) = fin4;  // for the residual epilogue of the next GEMM
     }
-    const char* sl = slice + fr * 8;
+    const char* sl = mrs + fr * 8;
     const size_t crs = a.cblock ? 64 : (size_t)a.ldc;
     bf16_t* cp = a.C + c_index(a, m0 + wm * 128 + prow, n0 + wn * 64) + c8;
 #pragma unroll
@@ -590,12 +598,78 @@ __global__ __launch_bounds__(512) void gemm256_bf16_kernel(GemmArgs a) {
         return;
     }
     if (EPI == EPI_RESLN_STATS) gemm256_epilogue_resln<COOP>(a, m0, n0, smem, w, lane, acc);
-    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU || EPI == EPI_LNA_BIAS_ROPE) gemm256_epilogue_lna<EPI>(a, m0, n0, smem, w, lane, acc);
+    else if (EPI == EPI_LNA_BIAS || EPI == EPI_LNA_GELU || EPI == EPI_LNA_BIAS_ROPE) gemm256_epilogue_lna<EPI>(a, m0, n0, smem, w, lane, acc, smem + w * 16384);
     else gemm256_epilogue<EPI, COOP && !(DBG & 31)>(a, m0, n0, smem, w, lane, acc);
     if (a.trace) {
         gemm256_stamp(a, blockIdx.x, 4);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         gemm256_stamp(a, blockIdx.x, 5);
+    }
+}
+
+// ---- strip walk of the EPI_LNA_* GEMMs: one workgroup takes `strip` consecutive column tiles of ONE row panel, in order, and the
+// LDS ring never drains between them (scan_coarse.hip's persistent form, gemm_tile.h "persistent use"): every tile but the last hands
+// PPNextTileHook to the loop, which requests the first two K-tiles of the next tile (same A rows, W rows n0 + 256 ...) into the
+// slots that fall free, and every tile but the first starts behind that prefetch (PREF).  K is a multiple of 256, so a tile is a
+// multiple of 4 K-tiles and the ring parity stays 0.
+// All tiles of a strip have the same rows: the row statistics are loaded and finalised ONCE, before the first tile, and parked in
+// 1 KiB per wave behind the epilogue staging area.  The epilogue then neither fetches (no LnaTailHook: the tail phases belong to the
+// prefetch) nor waits nor finalises, and it never touches the ring, which holds the next tile by then.  Its C stores are younger
+// than the prefetched pieces, which only makes the next tile's first wait conservative (gemm_tile.h).
+// A is row-major [M][lda] (no caller hands blocked A to an EPI_LNA_* GEMM; the launcher keeps such a launch on the per-tile kernel).
+// No per-lane value lives across tiles (the hook is all scalars; everything else is re-derived per tile from the lane id).
+#define T_STRIP_LDS_BYTES (T_LDS_BYTES + 8 * 1024)
+template <int EPI, int PP>
+__global__ __launch_bounds__(512) void gemm256_strip_kernel(GemmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // 128 KiB ring + epilogue staging + 8 x 1 KiB (mu, rs)
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // strips of one row panel are consecutive logical ids: they share the A panel in one XCD's L2 (xcd_remap)
+    const int spp = (a.tiles_n + a.strip - 1) / a.strip;
+    const int sid = xcd_remap(blockIdx.x, gridDim.x);
+    const int mt = sid / spp;
+    const int m0 = __builtin_amdgcn_readfirstlane(mt * T_BM);
+    const int t0 = __builtin_amdgcn_readfirstlane((sid - mt * spp) * a.strip);
+    const int t1 = t0 + a.strip < a.tiles_n ? t0 + a.strip : a.tiles_n;
+    char* mrs = smem + T_LDS_BYTES + w * 1024;
+    {   // lane ln: rows 2 ln, 2 ln + 1 of the wave's 128; slots summed in order t = 0, 1, ... as the per-tile epilogue does
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const float* st = a.stats_in + (size_t)(m0 + (w >> 2) * 128) * 2 + ln * 4;
+        f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < a.stat_slots; ++t) sacc += *reinterpret_cast<const f32x4*>(st + (size_t)t * a.M * 2);
+        const f32x4 fin4 = lna_finalise(a, sacc);
+        *reinterpret_cast<f32x4*>(mrs + ln * 16) = fin4;
+        if (t0 == 0 && (w & 3) == 0) *reinterpret_cast<f32x4*>(a.fin + (size_t)(m0 + (w >> 2) * 128) * 2 + ln * 4) = fin4;
+    }
+    const int lda = a.lda;  // A is row-major here (the launcher keeps blocked A on the per-tile kernel)
+    const size_t a_kstep = G_BK;
+    PPNextTileHook hook;
+    hook.a_kbytes = (uint32_t)(G_BK * 2); hook.a1_off = (uint32_t)(64 * lda * 2); hook.w1_off = (uint32_t)(32 * a.ldw * 2);
+    hook.w = w; hook.smem = smem;
+    hook.ra = __builtin_amdgcn_make_buffer_rsrc((void*)(a.A + (size_t)m0 * lda), 0, -1, 0x00020000);
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        const int n0 = __builtin_amdgcn_readfirstlane(t * T_BN);
+        const bool first = t == t0, last = t + 1 == t1;
+        int ln = lane;
+        asm volatile("" : "+v"(ln));  // the loop's per-lane addresses are derived again for every tile instead of living across the epilogue
+        hook.rw = __builtin_amdgcn_make_buffer_rsrc((void*)(a.W + (size_t)(last ? n0 : n0 + T_BN) * a.ldw), 0, -1, 0x00020000);
+        f32x4 acc[4][8];  // [ni][mi]
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (first) {
+            if (last) gemm_tile256_mainloop_pp<PP, 0, NoTailHook, false, false>(a.A, lda, m0, a.W, a.ldw, n0, a.K, smem, acc, w, ln, NoTailHook{}, a_kstep);
+            else gemm_tile256_mainloop_pp<PP, 0, PPNextTileHook, false, false>(a.A, lda, m0, a.W, a.ldw, n0, a.K, smem, acc, w, ln, hook, a_kstep);
+        } else {
+            if (last) gemm_tile256_mainloop_pp<PP, 0, NoTailHook, false, true>(a.A, lda, m0, a.W, a.ldw, n0, a.K, smem, acc, w, ln, NoTailHook{}, a_kstep);
+            else gemm_tile256_mainloop_pp<PP, 0, PPNextTileHook, false, true>(a.A, lda, m0, a.W, a.ldw, n0, a.K, smem, acc, w, ln, hook, a_kstep);
+        }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        gemm256_epilogue_lna<EPI, true>(a, m0, n0, smem, w, lane, acc, mrs);
     }
 }
 
@@ -721,6 +795,45 @@ static int gemm_nt(int M, int N) {
     static const char* env_nt = getenv("SC_GEMM_NT");
     return g_gemm_nt >= 0 ? g_gemm_nt : env_nt ? atoi(env_nt) : ((size_t)M * (size_t)N * 2 >= ((size_t)64 << 20));
 }
+// Strip walk of the EPI_LNA_* GEMMs ("gemm_strip" of sc_diag_set_option, SC_GEMM_STRIP): -1 = by shape, 0 = one workgroup per tile,
+// L >= 1 = L column tiles per workgroup (clamped to the tiles of a row panel).  "gemm_strip_n" (scripts/strip_sweep.py) restricts a
+// forced value to the launches with that N; the others then run one workgroup per tile, so that a sweep measures one shape alone.  A strip needs the ping-pong loop, a row-major A and
+// no trace / ablation mode (the strip kernel has neither stamps nor DBG forms).
+static int g_gemm_strip = -1, g_gemm_strip_n = 0, g_gemm_strip_last = 0;
+void sc_gemm_set_strip(int v) { g_gemm_strip = v < 0 ? -1 : v; }
+void sc_gemm_set_strip_n(int v) { g_gemm_strip_n = v > 0 ? v : 0; }
+int sc_gemm_last_strip(void) { return g_gemm_strip_last; }
+// The shape rule (host arithmetic only: tests/test_gemm_strip_host.py).  Lengths that won a same-box A/B of the encoder step
+// (profiles/strip_ab.log): QKV (9 tiles, K = 768) 3, FFN1 (12 tiles, K = 768) 6; no other shape has been measured.  A strip makes
+// the scheduling quantum L tiles instead of one, so the rule also counts rounds: with `cus` workgroups side by side the strips
+// take ceil(strips / cus) * L tile-times and the per-tile kernel ceil(tiles / cus); a strip is chosen only where it needs no more
+// (M = 32768: QKV would need 6 tile-times against 5 and measured 1 % slower -> per-tile; FFN1 needs 6 against 6 and measured
+// 1.7 % faster), and only with at least one strip per CU.
+int sc_gemm_strip_rule(int M, int N, int K, int cus) {
+    if (M <= 0 || (M % T_BM) || N <= 0 || (N % T_BN) || K != 768 || cus <= 0) return 0;
+    const int tiles_n = N / T_BN, L = tiles_n == 9 ? 3 : tiles_n == 12 ? 6 : 0;
+    if (!L) return 0;
+    const int64_t panels = M / T_BM, strips = panels * (tiles_n / L), tiles = panels * tiles_n;
+    if (strips < (int64_t)cus) return 0;
+    return ((strips + cus - 1) / cus) * L <= (tiles + cus - 1) / cus ? L : 0;
+}
+// what sc_launch_gemm_bf16_ln does with an EPI_LNA_* launch of this shape under the current options: tiles per strip, 0 = per-tile
+int sc_gemm_strip_tiles(int M, int N, int K, int cus, bool a_blocked) {
+    static const char* env = getenv("SC_GEMM_STRIP");
+    if (K < 256 || gemm_pp() == 0 || a_blocked || g_gemm_trace || g_gemm_dbg) return 0;
+    int v = g_gemm_strip >= 0 ? g_gemm_strip : env ? atoi(env) : -1;
+    if (v >= 0 && g_gemm_strip_n && N != g_gemm_strip_n) v = 0;
+    if (v < 0) v = sc_gemm_strip_rule(M, N, K, cus);
+    return std::min(v, N / T_BN);
+}
+template <int EPI>
+static void launch256_strip(GemmArgs a, int strip, hipStream_t s) {
+    static ScDeviceOnce once;
+    sc_device_once(once, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_strip_kernel<EPI, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T_STRIP_LDS_BYTES); });
+    a.strip = strip;
+    const unsigned grid = (unsigned)((a.M / T_BM) * ((a.tiles_n + strip - 1) / strip));
+    hipLaunchKernelGGL((gemm256_strip_kernel<EPI, 4>), dim3(grid), dim3(512), T_STRIP_LDS_BYTES, s, a);
+}
 template <int EPI, int DBG, int PP>
 static void launch256_pp(const GemmArgs& a, dim3 grid, dim3 block, hipStream_t s) {
     static ScDeviceOnce once;  // one per instantiation (and device)
@@ -766,6 +879,16 @@ void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int 
     a.partial = nullptr;
     a.c1 = c1; a.stats_in = stats_in; a.stat_slots = K / 256; a.fin = fin; a.gam = gam; a.stats_out = stats_out; a.ln_eps = eps;
     dim3 grid((unsigned)a.ntiles), block(512);
+    a.strip = 0;
+    if (epi != EPI_RESLN_STATS) {
+        g_gemm_strip_last = sc_gemm_strip_tiles(M, N, K, sc_device_cus(), a.ablock != 0);
+        if (const int strip = g_gemm_strip_last) {
+            if (epi == EPI_LNA_BIAS) launch256_strip<EPI_LNA_BIAS>(a, strip, s);
+            else if (epi == EPI_LNA_BIAS_ROPE) launch256_strip<EPI_LNA_BIAS_ROPE>(a, strip, s);
+            else launch256_strip<EPI_LNA_GELU>(a, strip, s);
+            return;
+        }
+    }
     if (epi == EPI_LNA_BIAS) launch256<EPI_LNA_BIAS, 0>(a, grid, block, s);
     else if (epi == EPI_LNA_BIAS_ROPE) launch256<EPI_LNA_BIAS_ROPE, 0>(a, grid, block, s);
     else if (epi == EPI_LNA_GELU) launch256<EPI_LNA_GELU, 0>(a, grid, block, s);
@@ -790,6 +913,7 @@ void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw
         a.ntiles = (M / T_BM) * a.tiles_n;
         dim3 grid((unsigned)a.ntiles), block(512);
         a.splitk = 1;
+        a.strip = 0;
         a.partial = nullptr;
         if (splitk_scratch && !g_gemm_dbg && !g_gemm_trace) {
             const int d = sc_gemm_splitk_factor(M, N, K, sc_device_cus());

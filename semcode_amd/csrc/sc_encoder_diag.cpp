@@ -251,6 +251,12 @@ extern "C" sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags
     return download_bf16(dc.p, (int64_t)M * N, C, s);
 }
 
+// Strip selection of the EPI_LNA_* launcher, without a launch and without a device when cus > 0 (include/semcode_hip.h)
+extern "C" int32_t sc_diag_gemm_strip(int32_t M, int32_t N, int32_t K, int32_t cus) {
+    if (M == 0) return sc_gemm_last_strip();
+    return sc_gemm_strip_tiles(M, N, K, cus > 0 ? cus : sc_device_cus());
+}
+
 // EPI_RESLN_STATS through sc_launch_gemm_bf16_ln.  A [M,K] (flags bit 0: given as [K/64][M][64]), W [N,K], bias [N] (= b + beta), gam [N],
 // R [M,N] the raw residual, fin [M][2] its (mu, rs) -> C [M,N], stats_out [N/256][M][2].
 extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
