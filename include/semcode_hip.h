@@ -496,6 +496,80 @@ sc_status sc_index_last_mmr_stats(sc_index* ix, int32_t* fetch_k, int32_t* min_c
  * ldg >= C floats] = red_ij, picked [min(k, C)] receives candidate indices in selection order.  Nothing else of the search runs. */
 sc_status sc_diag_mmr_select_host(const float* rel, const float* G, int32_t C, int32_t ldg, int32_t k, float lambda, int32_t* picked);
 
+/* Hybrid search: a lexical BM25 leg over hashed code terms, on device, fused with the dense leg by weighted reciprocal rank
+ * (Milvus: hybrid_search + RRFRanker; the LangChain ensemble retrievers).  Off unless asked for: no other call changes.  The rules
+ * live once, in semcode_amd/csrc/lex_rule.h, for the kernels and for the two sc_diag_*_host functions below.
+ * Term row: T uint16 slots, T one of 32, 64, 128, 256 and fixed per index by the first install; slots sorted ascending, repeats kept
+ * (tf of a term = the length of its run), padded with 0xFFFF; dl = the number of slots that are not padding.
+ * sc_lex_terms: the extractor, plain C++ (no runtime, no device).  Text i is bytes[offsets[i] .. offsets[i + 1]) (offsets [n + 1],
+ * ascending); out_terms [n][T] receives its term row, out_counts [n] (may be NULL) its dl.  A term run is a maximal run of bytes in
+ * [A-Za-z0-9_] or >= 0x80.  It has a split point at every '_' (part of no token) and between a lower-case ASCII letter and an upper-
+ * case one that follows it, a letter and a digit, a digit and a letter (bytes >= 0x80 are letters without case).  A run emits itself
+ * and then, when it has a split point, every part between split points.  Tokens have their ASCII letters lower-cased, are cut to
+ * their first 64 bytes and dropped when shorter than 2 bytes; the hash is 32-bit FNV-1a over the bytes, folded as
+ * (h ^ (h >> 16)) & 0xFFFF, with 0xFFFF mapped to 0xFFFE.  The first T tokens in text order are kept, then sorted.  No vocabulary, no
+ * stemming: collisions are accepted and deterministic. */
+sc_status sc_lex_terms(const uint8_t* bytes, const int64_t* offsets, int64_t n, int32_t T, uint16_t* out_terms, int32_t* out_counts);
+/* Term rows are caller data parked on the device in LOCAL ROW-NUMBER order, wherever an IVF layout put the vectors; they are handled
+ * as the labels of sc_index_set_groups are: not persisted, not search scratch (sc_index_release_scratch keeps them), dropped by
+ * sc_index_delete_rows, valid only while their row count equals the index's.  sc_index_set_terms installs or overwrites rows
+ * [first_row, first_row + n) from terms [n][T] (host): first_row must not exceed the term rows already held, first_row + n not the
+ * index's rows, and T must be the T of the rows held -- an append costs only its own bytes (the device array grows geometrically,
+ * contents kept).  Synchronises.  sc_index_drop_terms removes them and frees the array. */
+sc_status sc_index_set_terms(sc_index* ix, int64_t first_row, int64_t n, int32_t T, const uint16_t* terms);
+sc_status sc_index_drop_terms(sc_index* ix);
+/* rows = the term rows held, sum_dl = the sum of their dl, df [65536] (host; may be NULL): df[t] = the number of rows that hold term
+ * t.  A statistics kernel recomputes them only when the term rows changed since the last call (integer atomics: the result does not
+ * depend on any order); otherwise the call is a 256 KiB copy.  The library never computes an IDF: the caller turns df into the query
+ * weights, which keeps log() out of the parity question.  Term rows not valid: SC_ERR_INVALID naming both counts.  Synchronises. */
+sc_status sc_index_lex_stats(sc_index* ix, int64_t* rows, int64_t* sum_dl, uint32_t* df);
+/* The lexical search.  Query q has m = nterms[q] <= 32 terms qterms[q * 32 ..] = t_0 < ... < t_{m-1}, STRICTLY ascending and none
+ * 0xFFFF, with weights qweights[q * 32 ..] finite and > 0 -- anything else is SC_ERR_INVALID (the _dev form cannot see them
+ * before it launches: its kernels treat such a query as one without terms and the call returns SC_ERR_INVALID after its one host read).
+ * Score of a row, every step one correctly rounded f32 operation, never fused:
+ *   K = k1 * ((1 - b) + (b * (float)dl) / avgdl);  c_j = (w_j * ((float)tf_j * (k1 + 1))) / ((float)tf_j + K);
+ *   score = ((0 + c_j0) + c_j1) + ... over the j with tf_j > 0, ascending.  A row with no matching term is never a hit.
+ * Larger score first, ties to the lower row; out_rows = row_base + row; padded with -1 and -inf.  1 <= k <= 128.  allow == NULL
+ * (allow_words 0): every row; else the bitset of sc_index_search_masked over local row numbers: the bit is tested before a row's
+ * slots are read.  Exact and exhaustive on FLAT and IVF_FLAT alike: bit-identical to the rule run on the CPU.
+ * How: one pass over the rows * 2 T bytes of term rows serves 16 queries: their terms form a 65 536-bit set in LDS, every slot is
+ * one LDS bit test, only rows with a member slot compute tf (integer sums over the row's lanes) and the score; per-wave sorted key lists,
+ * sc_topk_merge's tree merge finishes.  Q queries take ceil(Q / 16) passes, in chunks of 1 024 queries ("lex_chunk_q" of
+ * sc_diag_set_option shrinks the chunk; -1 = default; results do not depend on it).
+ * Term rows not valid: SC_ERR_INVALID naming both counts, nothing launched.  k outside 1 .. 128, Q < 1, k1 / b not finite, avgdl not
+ * finite or <= 0, a NULL pointer or a short allow: SC_ERR_INVALID before anything changes.  Host pointers; synchronises. */
+sc_status sc_index_search_lexical(sc_index* ix, int32_t Q, int32_t k, const uint16_t* qterms, const float* qweights, const int32_t* nterms, float k1, float b,
+                                  float avgdl, const uint32_t* allow, int64_t allow_words, float* out_score, int64_t* out_rows);
+/* Same with DEVICE pointers, enqueued on the runtime's stream; synchronises it once at the end (the flag of the query check). */
+sc_status sc_index_search_lexical_dev(sc_index* ix, int32_t Q, int32_t k, const uint16_t* qterms_dev, const float* qweights_dev, const int32_t* nterms_dev,
+                                      float k1, float b, float avgdl, const uint32_t* allow_dev, int64_t allow_words, float* out_score_dev,
+                                      int64_t* out_rows_dev);
+/* The hybrid search: q [Q, dim] dense queries plus the lexical arguments above; 1 <= k <= fetch_k <= 128.  The dense leg is the
+ * exhaustive planner at width fetch_k (the masked search when a bitset is given; exact, a trained IVF_FLAT index is searched as it
+ * lies, as sc_index_search_mmr does); the lexical leg runs at width fetch_k.  Fusion, ranks from 0 in the two best-first lists:
+ *   f(row) = wd / (float)(c + rank_dense) + wl / (float)(c + rank_lex), a row missing from one list gets 0 for that term, the dense
+ * term is added first; c an int32 >= 1 (60 is customary), wd and wl finite and >= 0.  Output best first by f, ties to the lower row,
+ * out_score = f, padded with -1 and -inf.  One fusion kernel, one workgroup per query, no atomics deciding an order.  With wl = 0 and
+ * fetch_k = k the rows come in the dense order.  Errors as for the lexical search, plus k > fetch_k, fetch_k > 128, c < 1, a weight
+ * negative or not finite.  Host pointers; synchronises.  Out of scope: sharded collections, grouping or MMR on top, approximate (IVF
+ * probe) candidates. */
+sc_status sc_index_search_hybrid(sc_index* ix, const float* q, int32_t Q, int32_t k, int32_t fetch_k, const uint16_t* qterms, const float* qweights,
+                                 const int32_t* nterms, float k1, float b, float avgdl, int32_t c, float wd, float wl, const uint32_t* allow,
+                                 int64_t allow_words, float* out_score, int64_t* out_rows);
+/* Same with DEVICE pointers; synchronises where the dense searches underneath do and once at the end (the flag of the query check). */
+sc_status sc_index_search_hybrid_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t fetch_k, const uint16_t* qterms_dev,
+                                     const float* qweights_dev, const int32_t* nterms_dev, float k1, float b, float avgdl, int32_t c, float wd, float wl,
+                                     const uint32_t* allow_dev, int64_t allow_words, float* out_score_dev, int64_t* out_rows_dev);
+/* After a lexical or hybrid search: term rows a pass streams, their bytes (rows * 2 T) and the passes the call ran (16 queries each). */
+sc_status sc_index_last_lex_stats(sc_index* ix, int64_t* rows_scanned, int64_t* bytes_per_pass, int32_t* passes);
+/* The two rules on the CPU, from the header the kernels compile (tests on a machine without a GPU).  sc_diag_lex_score_host: terms
+ * [n][T] rows, one query of m terms -> out_score [n], out_hit [n] (1: the row holds a query term; else score 0).
+ * sc_diag_rrf_host: one query's best-first lists dense_rows / lex_rows [F] (-1 = padding) -> the k best fused hits, padded. */
+sc_status sc_diag_lex_score_host(const uint16_t* terms, int64_t n, int32_t T, const uint16_t* qterms, const float* qweights, int32_t m, float k1, float b,
+                                 float avgdl, float* out_score, uint8_t* out_hit);
+sc_status sc_diag_rrf_host(const int64_t* dense_rows, const int64_t* lex_rows, int32_t F, int32_t k, int32_t c, float wd, float wl, float* out_score,
+                           int64_t* out_rows);
+
 /* Replaces Collection.create_index(IVF_FLAT, nlist) + load() (milvus_store.py:76-84) for an index created with
  * SC_INDEX_IVF_FLAT: deterministic k-means (niter Lloyd iterations on <= 256*nlist sampled rows), assignment of
  * every row to its nearest centroid, list-major re-ordering of the corpus in HBM.  Until it is called an IVF_FLAT index
@@ -527,7 +601,7 @@ sc_status sc_index_ivf_info(sc_index* ix, int32_t* nlist, float* centroids, int6
  * cheaper than the exhaustive paths, and otherwise answers exhaustively (exact results). */
 sc_status sc_index_set_search_mode(sc_index* ix, int32_t mode);
 /* After a search: which path ran (1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 list-major behind the int8 coarse
- * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner, 7 grouped: sc_index_search_grouped*, 8 mmr: sc_index_search_mmr*) and how many queries the batched path had to
+ * stage, 6 masked: sc_index_search_masked* answered without the exhaustive planner, 7 grouped: sc_index_search_grouped*, 8 mmr: sc_index_search_mmr*, 9 lexical: sc_index_search_lexical*, 10 hybrid: sc_index_search_hybrid*) and how many queries the batched path had to
  * re-run through the exact scan because their certificate failed. */
 sc_status sc_index_last_search_stats(sc_index* ix, int32_t* path, int32_t* uncertified);
 

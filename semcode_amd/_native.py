@@ -126,6 +126,21 @@ SIGNATURES = {
     "sc_index_search_mmr_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sc_index_last_mmr_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "sc_diag_mmr_select_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "sc_lex_terms": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_index_set_terms": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "sc_index_drop_terms": (C.c_int32, [C.c_void_p]),
+    "sc_index_lex_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
+    "sc_index_search_lexical": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p]),
+    "sc_index_search_lexical_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p]),
+    "sc_index_search_hybrid": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                           C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_search_hybrid_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                               C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_index_last_lex_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "sc_diag_lex_score_host": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "sc_diag_rrf_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "sc_index_train": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
     "sc_index_ivf_assignments": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "sc_index_set_ivf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -205,6 +220,51 @@ def pack_allow(allow, rows: int) -> np.ndarray:
     if a.dtype != np.uint32 or a.ndim != 1:
         raise ValueError("allow must be a 1-d uint32 word array or a boolean array with one entry per row")
     return np.ascontiguousarray(a)
+
+
+LEX_MAX_QTERMS = 32   # terms of one lexical query (csrc/lex_rule.h)
+LEX_DF_SIZE = 65536   # entries of the df table
+LEX_PAD = 0xFFFF      # the padding slot of a term row
+
+
+def lex_terms(texts, T: int = 128) -> "tuple[np.ndarray, np.ndarray]":
+    """The term rows of these texts (sc_lex_terms; no GPU): (terms [n, T] uint16 sorted ascending and padded with 0xFFFF, dl [n] int32).
+    str entries are taken as UTF-8, bytes as they are."""
+    raw = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in texts]
+    n = len(raw)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in raw], out=offsets[1:])
+    blob = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+    terms = np.empty((n, int(T)), dtype=np.uint16)
+    counts = np.empty(n, dtype=np.int32)
+    _check(lib().sc_lex_terms(blob.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), n, int(T), terms.ctypes.data_as(C.c_void_p),
+                              counts.ctypes.data_as(C.c_void_p)))
+    return terms, counts
+
+
+def diag_lex_score_host(terms, qterms, qweights, k1: float, b: float, avgdl: float) -> "tuple[np.ndarray, np.ndarray]":
+    """The score rule of csrc/lex_rule.h on the CPU (sc_diag_lex_score_host): terms [n, T], one query -> (score [n] f32, hit [n] bool)."""
+    t = np.ascontiguousarray(terms, dtype=np.uint16)
+    qt = np.ascontiguousarray(qterms, dtype=np.uint16).reshape(-1)
+    qw = np.ascontiguousarray(qweights, dtype=np.float32).reshape(-1)
+    score = np.empty(t.shape[0], dtype=np.float32)
+    hit = np.empty(t.shape[0], dtype=np.uint8)
+    _check(lib().sc_diag_lex_score_host(t.ctypes.data_as(C.c_void_p), t.shape[0], t.shape[1], qt.ctypes.data_as(C.c_void_p), qw.ctypes.data_as(C.c_void_p), qt.shape[0],
+                                        float(k1), float(b), float(avgdl), score.ctypes.data_as(C.c_void_p), hit.ctypes.data_as(C.c_void_p)))
+    return score, hit.astype(bool)
+
+
+def diag_rrf_host(dense_rows, lex_rows, k: int, c: int = 60, dense_weight: float = 1.0, lexical_weight: float = 1.0) -> "tuple[np.ndarray, np.ndarray]":
+    """The fusion rule of csrc/lex_rule.h on the CPU (sc_diag_rrf_host): two best-first row lists [F] (-1 = padding) -> (score [k], rows [k])."""
+    d = np.ascontiguousarray(dense_rows, dtype=np.int64).reshape(-1)
+    l = np.ascontiguousarray(lex_rows, dtype=np.int64).reshape(-1)
+    if d.shape != l.shape:
+        raise ValueError("the two lists must have one length")
+    score = np.empty(k, dtype=np.float32)
+    rows = np.empty(k, dtype=np.int64)
+    _check(lib().sc_diag_rrf_host(d.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p), d.shape[0], int(k), int(c), float(dense_weight), float(lexical_weight),
+                                  score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+    return score, rows
 
 
 def _as_f32(a, shape_last: int | None = None) -> np.ndarray:
@@ -485,6 +545,94 @@ class Index:
         _check(lib().sc_index_last_mmr_stats(self.handle, C.byref(f), C.byref(c), C.byref(sc)))
         return {"fetch_k": int(f.value), "min_candidates": int(c.value), "rows_scanned": int(sc.value)}
 
+    def set_terms(self, terms, first_row: int = 0) -> None:
+        """Install or overwrite the term rows [first_row, first_row + len(terms)) of the lexical search (sc_index_set_terms): terms
+        [n, T] uint16 as lex_terms() makes them, T fixed by the first install; first_row at most the term rows held.  Valid while
+        the index has exactly as many rows; delete_rows drops them."""
+        t = np.ascontiguousarray(terms, dtype=np.uint16)
+        if t.ndim != 2:
+            raise ValueError(f"terms must be a [n, T] uint16 array, got shape {t.shape}")
+        _check(lib().sc_index_set_terms(self.handle, int(first_row), t.shape[0], t.shape[1], t.ctypes.data_as(C.c_void_p)))
+
+    def drop_terms(self) -> None:
+        """Remove the term rows and free their device array (sc_index_drop_terms)."""
+        _check(lib().sc_index_drop_terms(self.handle))
+
+    def lex_stats(self) -> dict:
+        """rows, sum_dl and df [65536] uint32 (rows holding each term) of the term rows (sc_index_lex_stats); the caller derives avgdl
+        and the IDF weights from them."""
+        rows, total = C.c_int64(), C.c_int64()
+        df = np.empty(LEX_DF_SIZE, dtype=np.uint32)
+        _check(lib().sc_index_lex_stats(self.handle, C.byref(rows), C.byref(total), df.ctypes.data_as(C.c_void_p)))
+        return {"rows": int(rows.value), "sum_dl": int(total.value), "df": df}
+
+    @staticmethod
+    def _lex_query_args(qterms, qweights, nterms) -> "tuple[np.ndarray, np.ndarray, np.ndarray]":
+        qt = np.ascontiguousarray(qterms, dtype=np.uint16)
+        qw = np.ascontiguousarray(qweights, dtype=np.float32)
+        nt = np.ascontiguousarray(nterms, dtype=np.int32).reshape(-1)
+        if qt.ndim != 2 or qt.shape[1] != LEX_MAX_QTERMS or qw.shape != qt.shape or nt.shape[0] != qt.shape[0]:
+            raise ValueError(f"expected qterms / qweights [Q, {LEX_MAX_QTERMS}] and nterms [Q], got {qt.shape}, {qw.shape}, {nt.shape}")
+        return qt, qw, nt
+
+    def _allow_args(self, allow):
+        if allow is None:
+            return None, 0, None
+        words = pack_allow(allow, len(self))
+        if words.size == 0:  # an empty index: still a valid pointer
+            words = np.zeros(1, dtype=np.uint32)
+        return words.ctypes.data_as(C.c_void_p), words.shape[0], words
+
+    def search_lexical(self, qterms, qweights, nterms, k: int = 10, k1: float = 1.2, b: float = 0.75, avgdl: float = 1.0, allow=None) -> tuple[np.ndarray, np.ndarray]:
+        """BM25 over the term rows (sc_index_search_lexical): qterms [Q, 32] uint16 strictly ascending per query, qweights [Q, 32] f32
+        finite and > 0, nterms [Q] -> (score [Q, k] f32, rows [Q, k] i64), larger score first, ties to the lower row, padded with
+        -1 / -inf; rows without a query term are never hits.  allow as for search_masked, or None."""
+        qt, qw, nt = self._lex_query_args(qterms, qweights, nterms)
+        Q = qt.shape[0]
+        score = np.empty((Q, k), dtype=np.float32)
+        rows = np.empty((Q, k), dtype=np.int64)
+        allow_ptr, allow_words, _keep = self._allow_args(allow)
+        _check(lib().sc_index_search_lexical(self.handle, Q, int(k), qt.ctypes.data_as(C.c_void_p), qw.ctypes.data_as(C.c_void_p), nt.ctypes.data_as(C.c_void_p),
+                                             float(k1), float(b), float(avgdl), allow_ptr, allow_words, score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return score, rows
+
+    def search_lexical_dev(self, Q: int, k: int, qterms_ptr: int, qweights_ptr: int, nterms_ptr: int, k1: float, b: float, avgdl: float, allow_ptr: int,
+                           allow_words: int, score_ptr: int, rows_ptr: int) -> None:
+        """Device-pointer variant (allow_ptr 0 with allow_words 0: every row; synchronises the stream once: sc_index_search_lexical_dev)."""
+        _check(lib().sc_index_search_lexical_dev(self.handle, int(Q), int(k), C.c_void_p(qterms_ptr), C.c_void_p(qweights_ptr), C.c_void_p(nterms_ptr), float(k1), float(b),
+                                                 float(avgdl), C.c_void_p(allow_ptr) if allow_ptr else None, int(allow_words), C.c_void_p(score_ptr), C.c_void_p(rows_ptr)))
+
+    def search_hybrid(self, queries, qterms, qweights, nterms, k: int = 10, fetch_k: int = 40, k1: float = 1.2, b: float = 0.75, avgdl: float = 1.0, c: int = 60,
+                      dense_weight: float = 1.0, lexical_weight: float = 1.0, allow=None) -> tuple[np.ndarray, np.ndarray]:
+        """Dense top-fetch_k and lexical top-fetch_k fused by weighted reciprocal rank (sc_index_search_hybrid): score of a row =
+        dense_weight / (c + its dense rank) + lexical_weight / (c + its lexical rank), ranks from 0, a missing rank contributing 0;
+        -> (fused score [Q, k], rows [Q, k]) best first, ties to the lower row, padded with -1 / -inf.  k <= fetch_k <= 128."""
+        q = _as_f32(queries, self.dim)
+        qt, qw, nt = self._lex_query_args(qterms, qweights, nterms)
+        Q = q.shape[0]
+        if qt.shape[0] != Q:
+            raise ValueError(f"{Q} query vectors but {qt.shape[0]} term lists")
+        score = np.empty((Q, k), dtype=np.float32)
+        rows = np.empty((Q, k), dtype=np.int64)
+        allow_ptr, allow_words, _keep = self._allow_args(allow)
+        _check(lib().sc_index_search_hybrid(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(fetch_k), qt.ctypes.data_as(C.c_void_p),
+                                            qw.ctypes.data_as(C.c_void_p), nt.ctypes.data_as(C.c_void_p), float(k1), float(b), float(avgdl), int(c), float(dense_weight),
+                                            float(lexical_weight), allow_ptr, allow_words, score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return score, rows
+
+    def search_hybrid_dev(self, q_ptr: int, Q: int, k: int, fetch_k: int, qterms_ptr: int, qweights_ptr: int, nterms_ptr: int, k1: float, b: float, avgdl: float, c: int,
+                          dense_weight: float, lexical_weight: float, allow_ptr: int, allow_words: int, score_ptr: int, rows_ptr: int) -> None:
+        """Device-pointer variant (sc_index_search_hybrid_dev)."""
+        _check(lib().sc_index_search_hybrid_dev(self.handle, C.c_void_p(q_ptr), int(Q), int(k), int(fetch_k), C.c_void_p(qterms_ptr), C.c_void_p(qweights_ptr),
+                                                C.c_void_p(nterms_ptr), float(k1), float(b), float(avgdl), int(c), float(dense_weight), float(lexical_weight),
+                                                C.c_void_p(allow_ptr) if allow_ptr else None, int(allow_words), C.c_void_p(score_ptr), C.c_void_p(rows_ptr)))
+
+    def last_lex_stats(self) -> dict:
+        """After a lexical or hybrid search: term rows a pass streams, their bytes, passes run (sc_index_last_lex_stats)."""
+        r, by, p = C.c_int64(), C.c_int64(), C.c_int32()
+        _check(lib().sc_index_last_lex_stats(self.handle, C.byref(r), C.byref(by), C.byref(p)))
+        return {"rows_scanned": int(r.value), "bytes_per_pass": int(by.value), "passes": int(p.value)}
+
     def train(self, niter: int = 10, seed: int = 0) -> None:
         """IVF_FLAT: k-means + list build (sc_index_train)."""
         _check(lib().sc_index_train(self.handle, int(niter), int(seed)))
@@ -535,7 +683,7 @@ class Index:
         path, unc, bits, handed = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().sc_index_last_search_stats(self.handle, C.byref(path), C.byref(unc)))
         _check(lib().sc_index_last_coarse_stats(self.handle, C.byref(bits), C.byref(handed)))
-        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked", 7: "grouped", 8: "mmr"}[path.value], "uncertified": unc.value}
+        out = {"path": {0: "none", 1: "exact", 2: "batched", 3: "ivf", 4: "ivf_listmajor", 5: "ivf_coarse", 6: "masked", 7: "grouped", 8: "mmr", 9: "lexical", 10: "hybrid"}[path.value], "uncertified": unc.value}
         if path.value in (3, 4, 5):
             tail = C.c_int64()
             _check(lib().sc_index_last_tail_rows(self.handle, C.byref(tail)))

@@ -201,8 +201,8 @@ extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
         {"ivf_tail_rows", sc_set_ivf_tail_rows},              {"delete_chunk_rows", sc_set_delete_chunk_rows},
         {"rope_fused", sc_encoder_set_rope_fused},            {"mask_gather", sc_set_mask_gather},
         {"group_width0", sc_set_group_width0},                {"group_width1", sc_set_group_width1},
-        {"mmr_chunk_q", sc_set_mmr_chunk_q},                  {"gemm_strip", sc_gemm_set_strip},
-        {"gemm_strip_n", sc_gemm_set_strip_n},
+        {"mmr_chunk_q", sc_set_mmr_chunk_q},                  {"lex_chunk_q", sc_set_lex_chunk_q},
+        {"gemm_strip", sc_gemm_set_strip},                    {"gemm_strip_n", sc_gemm_set_strip_n},
     };
     for (const auto& o : options)
         if (!strcmp(name, o.name)) {

@@ -187,6 +187,22 @@ void sc_launch_mmr_gram(int metric, const float* X, const float* xnorm, int ld, 
                         float* G, hipStream_t s);
 void sc_launch_mmr_select(int metric, const float* cand_dist, const int64_t* cand_rows, int F, const float* G, int Q, int k, float lambda, float* out_dist,
                           int64_t* out_rows, int32_t* min_count, hipStream_t s);
+// scan_lexical.hip: the lexical and the hybrid search (sc_index_search_lexical*, sc_index_search_hybrid*; rules: lex_rule.h).
+// lex_prep: qterms / qweights [Q][32], nterms [Q] -> memb [ceil(Q / qp)][2048] (the membership set of every pass of qp =
+// sc_lex_queries_per_pass() queries), nt_eff [Q] (nterms; 0 for a query that breaks the rules, which also sets *bad).
+// lex_scan: one pass -- nq <= qp queries (the pass's slice of qterms / qweights / nt_eff and its memb) over terms [n][T], allow NULL or a
+// bitset over rows -> partial [nwg * 4][qp][k] sorted IP keys for sc_launch_topk_merge (groups 1, lists nwg * 4, qt qp); nwg from
+// sc_lex_scan_workgroups.  lex_stats: df [65536] += rows holding each term, *sum_dl += slots that are not padding (both zeroed by
+// the caller).  lex_fuse: dense_rows / lex_rows [Q][F <= 128] best first (-1 = padding) -> out_* [Q][k <= F] by lex_rrf, padded;
+// dense_rows NULL: padding only.
+int sc_lex_queries_per_pass(void);
+int sc_lex_scan_workgroups(int64_t n, int T, int k, int cus);
+void sc_launch_lex_prep(const uint16_t* qterms, const float* qweights, const int32_t* nterms, int Q, uint32_t* memb, int32_t* nt_eff, int32_t* bad, hipStream_t s);
+void sc_launch_lex_scan(const uint16_t* terms, int64_t n, int T, const uint32_t* allow, const uint32_t* memb, const uint16_t* qterms, const float* qweights,
+                        const int32_t* nt_eff, int nq, int k, float k1, float b, float avgdl, int nwg, uint64_t* partial, hipStream_t s);
+void sc_launch_lex_stats(const uint16_t* terms, int64_t n, int T, uint32_t* df, unsigned long long* sum_dl, hipStream_t s);
+void sc_launch_lex_fuse(const int64_t* dense_rows, const int64_t* lex_rows, int F, int Q, int k, int32_t c, float wd, float wl, float* out_score, int64_t* out_rows,
+                        hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

@@ -67,6 +67,7 @@ extern "C" sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int
     std::vector<int64_t> ids(rows, rows + n);
     if (!sort_distinct(ids, ix->n)) return sc_fail(SC_ERR_INVALID, "sc_index_delete_rows: row numbers must be distinct");
     ix->group_rows = -1;  // the rows are renumbered: the caller's group labels (sc_index_set_groups) no longer name them
+    sc_lex_drop_locked(ix);  // ... and neither do its term rows (sc_index_set_terms)
     hipStream_t s = ix->rt->stream;
     const int64_t old_n = ix->n, ld = ix->ld;
     const bool listed = ix->perm != nullptr;  // trained layout installed: stored position != row id below ivf_rows

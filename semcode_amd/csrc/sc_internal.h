@@ -133,6 +133,15 @@ struct sc_index {
     int last_mmr_fetch = 0;
     bool mmr_stat_pending = false;                // the device word holds the last call's count
     int64_t last_mmr_scanned = 0;
+    // lexical / hybrid search (sc_lexical.cpp): the caller's term rows [term_cap][term_T] uint16 in local row-number order, valid while
+    // n == term_rows (-1: none installed) -- not scratch, grown with its contents kept; df [65536] + sum_dl behind it, recomputed when
+    // lex_stat_dirty; the membership sets, partial lists, candidate lists and the bad-query flag of a call
+    sc_buf terms, lex_stat, lex_scratch;
+    int64_t term_rows = -1, term_cap = 0;
+    int term_T = 0;
+    bool lex_stat_dirty = true;
+    int64_t last_lex_rows = 0, last_lex_bytes = 0;  // sc_index_last_lex_stats
+    int last_lex_passes = 0;
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -163,7 +172,7 @@ struct sc_index {
     int64_t last_unique_rows = 0, last_streamed_rows = 0;  // sc_index_last_probe_stats
     int last_groups = 0;
     int search_mode = 0;                          // 0 auto, 1 exact only, 2 batched whenever supported, 3 / 4 IVF probe per query / list-major whenever trained
-    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked, 7 grouped, 8 mmr
+    int last_path = 0;                            // 1 exact, 2 batched, 3 ivf probe per query, 4 ivf probe list-major, 5 behind the int8 coarse stage, 6 masked, 7 grouped, 8 mmr, 9 lexical, 10 hybrid
     int last_uncertified = 0;
     // sc_index_last_delete_stats: what the last sc_index_delete_rows moved; bit sets (sc_shadow::stat_bit) of the shadows kept / dropped
     int64_t last_del_rows_moved = 0, last_del_bytes_moved = 0;
@@ -179,9 +188,9 @@ inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
     {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
     {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
     {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true}, {&sc_index::group_scratch, true},
-    {&sc_index::mmr_scratch, true},
+    {&sc_index::mmr_scratch, true}, {&sc_index::lex_scratch, true},
     {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},          {&sc_index::groups, false},
-    {&sc_index::mmr_stat, false},
+    {&sc_index::mmr_stat, false},   {&sc_index::terms, false},      {&sc_index::lex_stat, false},
 };
 
 static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
@@ -243,6 +252,8 @@ bool sc_ivf_applicable(const sc_index* ix, int Q, int nprobe);
 // sc_masked.cpp: the masked search under the lock.  q_dev tight [Q, dim], allow_dev >= ceil(n / 32) words, outputs [Q, k] (k <= 1024):
 // all device.  Synchronises the stream once (the allowed count).
 sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows);
+// sc_lexical.cpp: forget the term rows (sc_index_delete_rows renumbers the rows; sc_index_drop_terms)
+void sc_lex_drop_locked(sc_index* ix);
 // sc_ivf_probe.cpp.  The nprobe nearest centroids of every query under the INDEX metric (the quantizer's own search; takes qz->mu):
 // distances and list ids at the head of ix->ivf_scratch, grown to hold `extra_bytes` more behind them; `host`: the ids there too
 // (synchronises).
@@ -268,4 +279,5 @@ void sc_set_mask_gather(int v);        // sc_masked.cpp
 void sc_set_group_width0(int v);       // sc_grouped.cpp
 void sc_set_group_width1(int v);
 void sc_set_mmr_chunk_q(int v);        // sc_mmr.cpp
+void sc_set_lex_chunk_q(int v);        // sc_lexical.cpp
 void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp

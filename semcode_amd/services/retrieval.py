@@ -79,22 +79,28 @@ class Retriever:
         return True
 
     @staticmethod
-    def _filter_kwargs(repos: Any, languages: Any, group_by: Any = None, mmr: Any = None, fetch_k: Any = None) -> Dict[str, Any]:
-        # only what was given: a call without a filter reaches the store exactly as before (any store with the reference's surface)
+    def _filter_kwargs(repos: Any, languages: Any, group_by: Any = None, mmr: Any = None, fetch_k: Any = None, hybrid: Any = None, **text: Any) -> Dict[str, Any]:
+        # only what was given: a call without a filter reaches the store exactly as before (any store with the reference's surface);
+        # text = query_text / query_texts, the question(s) themselves, handed on only with hybrid
         given = (("repos", repos), ("languages", languages), ("group_by", group_by), ("mmr", mmr), ("fetch_k", fetch_k))
-        return {name: value for name, value in given if value is not None}
+        out = {name: value for name, value in given if value is not None}
+        if hybrid is not None and hybrid is not False:
+            out.update(hybrid=hybrid, **text)
+        return out
 
     def retrieve(self, question: str, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                 mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
+                 mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None) -> List[Dict[str, Any]]:
         """pipeline.py:93-129, one question.  repos / languages restrict the search itself (MilvusVectorStore.search), where the
         reference front ends drop hits from an unfiltered top-k afterwards.  group_by ("path" | "repo"): at most one document per
         file / per repo, so rag_max_context_sources buys that many different sources.  mmr (in [0, 1]) / fetch_k: maximal marginal
-        relevance over the best fetch_k chunks, so near-identical chunks under different paths do not take every slot."""
+        relevance over the best fetch_k chunks, so near-identical chunks under different paths do not take every slot.  hybrid (True
+        or {c, dense_weight, lexical_weight}): the question text goes along and its BM25 hits over the chunks' code terms are fused
+        with the dense ones, so a question that names an identifier finds the chunk that defines it."""
         if not self._ensure_connected():
             return []
         vector = embed_query(self.embedding_client, question)
         try:
-            results = self.vector_store.search(vector, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k))
+            results = self.vector_store.search(vector, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k, hybrid, query_text=question))
         except Exception as exc:
             log.error("milvus_search_failed error=%s", exc)
             self.last_error = exc
@@ -114,22 +120,22 @@ class Retriever:
         return documents
 
     def retrieve_batch(self, questions: Sequence[str], *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                       mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> List[List[Dict[str, Any]]]:
+                       mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None) -> List[List[Dict[str, Any]]]:
         """Many questions at once: one encoder batch (`embed_documents_array`) and one batched search (`search_batch`) when the
         seams offer them, else `retrieve` per question.  Per question the result is what `retrieve` returns for it (a store
-        that returns no hit for a question yields [] for that question).  repos / languages / group_by / mmr / fetch_k: one setting for the
-        whole batch, as in `retrieve`."""
+        that returns no hit for a question yields [] for that question).  repos / languages / group_by / mmr / fetch_k / hybrid: one setting
+        for the whole batch, as in `retrieve`."""
         questions = list(questions)
         if not questions:
             return []
         fast = hasattr(self.embedding_client, "embed_documents_array") and hasattr(self.vector_store, "search_batch") and hasattr(self.vector_store, "hits_for")
         if not fast:
-            return [self.retrieve(q, **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k)) for q in questions]
+            return [self.retrieve(q, repos=repos, languages=languages, group_by=group_by, mmr=mmr, fetch_k=fetch_k, hybrid=hybrid) for q in questions]
         if not self._ensure_connected():
             return [[] for _ in questions]
         try:
             vectors = np.asarray(self.embedding_client.embed_documents_array(questions), dtype=np.float32)
-            dist, rows = self.vector_store.search_batch(vectors, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k))
+            dist, rows = self.vector_store.search_batch(vectors, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k, hybrid, query_texts=questions))
             results = self.vector_store.hits_for(dist, rows)
         except Exception as exc:
             log.error("milvus_search_failed error=%s", exc)

@@ -14,6 +14,8 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
     .search(..., repos=[..], languages=[..])    -> Collection.search(expr=...): only rows of these repos AND languages, exact
     .search(..., group_by="path" | "repo")      -> Collection.search(group_by_field=...): at most one hit per file / per repo, exact
     .search(..., mmr=0.5, fetch_k=40)           -> search_type="mmr" (lambda_mult, fetch_k) of the LangChain stores: diversified top_k, exact, on device
+    .search(..., query_text=q, hybrid=True)     -> Collection.hybrid_search(..., RRFRanker()): dense top-fetch_k fused with a BM25 top-fetch_k over
+                                                   hashed code terms, on device (needs MilvusVectorStore(lexical=True))
     .delete(ids) / .delete_where(repo=, path=, language=)
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
 
@@ -101,7 +103,8 @@ class MilvusVectorStore:
 
     def __init__(self, collection_name: str = "semcode_chunks", dim: Optional[int] = None, *, metric: Optional[str] = None,
                  index_type: Optional[str] = None, nlist: Optional[int] = None, nprobe: Optional[int] = None,
-                 device: Optional[int] = None, runtime: Any = None, index_factory: Optional[Callable[..., Any]] = None) -> None:
+                 device: Optional[int] = None, runtime: Any = None, index_factory: Optional[Callable[..., Any]] = None,
+                 lexical: Optional[bool] = None, lex_slots: int = 128) -> None:
         settings = _resolve_settings()
         self.collection_name = collection_name
         self.dim = dim or settings.embedding_dimension
@@ -142,6 +145,16 @@ class MilvusVectorStore:
         # the collection has grown to RETRAIN_GROWTH x the row count the centroids were trained on.
         self._needs_train = False
         self._trained_rows = 0
+        # hybrid search (lexical=True, or SEMCODE_MI355X_LEXICAL): one term row of lex_slots hashed terms per chunk, extracted from its
+        # text at commit time into a host matrix (capacity >= len(self._ids)) and uploaded to the device index by row range;
+        # _terms_on_device = the rows the index holds valid term rows for (-1: none); the df table is fetched once per mutation
+        self.lexical = bool(getattr(settings, "mi355x_lexical", False) if lexical is None else lexical)
+        self.lex_slots = int(lex_slots)
+        if self.lex_slots not in (32, 64, 128, 256):
+            raise ValueError(f"lex_slots must be 32, 64, 128 or 256, got {lex_slots!r}")
+        self._terms = np.zeros((0, self.lex_slots), dtype=np.uint16)
+        self._terms_on_device = -1
+        self._lex_stats: Optional[tuple] = None  # (idf [65536] f32, avgdl f32)
 
     # ------------------------------------------------------------------ lifecycle
     def connect(self) -> None:
@@ -265,7 +278,49 @@ class MilvusVectorStore:
                 self._repos[row], self._paths[row], self._languages[row] = cols
                 self._texts[row] = text
                 self._metadata[row] = meta
+        if self.lexical and len(rows):
+            self._commit_terms(rows, texts)
         self._note_growth()
+
+    # ------------------------------------------------------------------ term rows of the hybrid search
+    @staticmethod
+    def _lex_terms(texts: Sequence[str], slots: int) -> np.ndarray:
+        from .. import _native
+
+        return _native.lex_terms(texts, slots)[0]
+
+    def _commit_terms(self, rows: np.ndarray, texts: Sequence[str]) -> None:
+        """Term rows of the rows just committed: into the host matrix, then the range [lowest, highest] of them to the device -- an append
+        uploads its own rows only.  An index that holds no valid term rows (first use, after a delete) gets the whole matrix."""
+        n = len(self._ids)
+        if n > self._terms.shape[0]:
+            grown = np.full((max(1024, 2 * self._terms.shape[0], n), self.lex_slots), 0xFFFF, dtype=np.uint16)
+            grown[: self._terms.shape[0]] = self._terms
+            self._terms = grown
+        rows = np.asarray(rows, dtype=np.int64)
+        self._terms[rows] = self._lex_terms(list(texts), self.lex_slots)
+        self._lex_stats = None
+        ix = self._collection
+        if not hasattr(ix, "set_terms"):
+            self._terms_on_device = -1  # (a search with hybrid= names what is missing)
+            return
+        lo, hi = int(rows.min()), int(rows.max()) + 1
+        if self._terms_on_device < 0 or lo > self._terms_on_device:
+            self._upload_all_terms()
+            return
+        ix.set_terms(self._terms[lo:hi], first_row=lo)
+        self._terms_on_device = max(hi, self._terms_on_device)
+
+    def _upload_all_terms(self) -> None:
+        """The whole host matrix to the device index (after a delete dropped its term rows, after load).  Caller holds the lock."""
+        ix = self._collection
+        self._lex_stats = None
+        self._terms_on_device = -1
+        if hasattr(ix, "set_terms"):
+            if hasattr(ix, "drop_terms"):
+                ix.drop_terms()
+            ix.set_terms(self._terms[: len(self._ids)], first_row=0)
+            self._terms_on_device = len(self._ids)
 
     def _set_codes(self, row: int, repo: str, language: str, path: str = "") -> None:
         if row >= self._repo_codes.size:
@@ -360,7 +415,9 @@ class MilvusVectorStore:
 
     def _delete_rows(self, rows: "list[int]") -> int:
         """rows: ascending, distinct.  One native call, then the columns: committed only after the call has succeeded, so a
-        failure leaves the vectors and the columns as they were (caller holds the lock)."""
+        failure leaves the vectors and the columns as they were (caller holds the lock).  With lexical=True the host term matrix is
+        compacted with the same renumbering and uploaded again WHOLE (2 * lex_slots bytes per surviving row over the host link): the
+        device index drops its term rows on a delete and does not compact them in place."""
         ix = self._collection
         if not hasattr(ix, "delete_rows"):
             raise NotImplementedError(f"{type(ix).__name__} has no delete_rows(rows): this vector index cannot delete")
@@ -379,25 +436,33 @@ class MilvusVectorStore:
         self._path_codes = self._path_codes[: gone.size][~gone]
         self._mask_cache.clear()
         self._groups_installed = None
+        if self.lexical:
+            self._terms = self._terms[: gone.size][~gone]
+            self._upload_all_terms()
         if hasattr(ix, "__len__") and len(ix) != len(self._ids):
             raise RuntimeError(f"vector index holds {len(ix)} rows after the delete, the collection's columns expect {len(self._ids)}")
         return len(rows)
 
     # ------------------------------------------------------------------ search
     def search(self, vector: "list[float]", top_k: int = 10, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-               mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> SearchResult:
-        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages / group_by / mmr / fetch_k: see
-        search_batch."""
+               mmr: Optional[float] = None, fetch_k: Optional[int] = None, query_text: Optional[str] = None, hybrid: Any = None) -> SearchResult:
+        """Run a raw vector search (one query), reference milvus_store.py:135-148.  repos / languages / group_by / mmr / fetch_k /
+        query_text (query_texts there) / hybrid: see search_batch."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
-        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages, group_by=group_by, mmr=mmr, fetch_k=fetch_k)
+        dist, rows = self.search_batch(np.asarray([vector], dtype=np.float32), top_k, repos=repos, languages=languages, group_by=group_by, mmr=mmr, fetch_k=fetch_k,
+                                       query_texts=None if query_text is None else [query_text], hybrid=hybrid)
         return SearchResult([self._hits(dist[0], rows[0])])
 
     GROUP_BY = ("path", "repo")
     MMR_MAX_FETCH = 128  # the widest candidate list of Index.search_mmr
+    HYBRID_MAX_FETCH = 128  # ... and of Index.search_hybrid
+    HYBRID_DEFAULTS = {"c": 60, "dense_weight": 1.0, "lexical_weight": 1.0}
+    BM25_K1, BM25_B = 1.2, 0.75
 
     def search_batch(self, queries: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None,
-                     group_by: Optional[str] = None, mmr: Optional[float] = None, fetch_k: Optional[int] = None) -> "tuple[np.ndarray, np.ndarray]":
+                     group_by: Optional[str] = None, mmr: Optional[float] = None, fetch_k: Optional[int] = None,
+                     query_texts: Optional[Sequence[str]] = None, hybrid: Any = None) -> "tuple[np.ndarray, np.ndarray]":
         """Batched search: queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64; -1 = no hit), best first.
 
         repos / languages (Collection.search(expr=...) for the two filters of the reference front ends): None = no restriction, a
@@ -414,13 +479,33 @@ class MilvusVectorStore:
         greedily the candidate with the largest mmr * relevance - (1 - mmr) * (largest similarity to a hit already taken), both in
         the collection's metric.  1 = the plain order, 0 = diversity alone.  The hits come in selection order, not best first.
         fetch_k defaults to min(128, max(20, 4 top_k)); top_k <= fetch_k <= 128.  Always exact (Index.search_mmr); not combined
-        with group_by."""
+        with group_by.
+
+        hybrid (Collection.hybrid_search with an RRFRanker; the LangChain ensemble retrievers): None / False = today's behaviour; True
+        or a dict with any of c (default 60), dense_weight, lexical_weight (default 1) = the exact dense top-fetch_k and the BM25
+        top-fetch_k of query_texts (one text per query) over the chunks' hashed code terms, fused by weighted reciprocal rank:
+        score = dense_weight / (c + dense rank) + lexical_weight / (c + lexical rank), ranks from 0, a chunk missing from one list
+        getting 0 for it.  The returned distances are these fused scores, best first.  A question that names an identifier finds the
+        chunks that contain it even where the embedding does not.  The text goes through the extractor of the chunks and is reduced
+        to its at most 32 distinct terms of highest IDF = ln(1 + (N - df + 0.5) / (df + 0.5)) (ties to the lower term); k1 = 1.2,
+        b = 0.75, avgdl = sum_dl / N.  fetch_k defaults as for mmr; top_k <= fetch_k <= 128.  Needs lexical=True at construction (or
+        SEMCODE_MI355X_LEXICAL); always exact (Index.search_hybrid); not combined with group_by or mmr."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
         if group_by is not None and group_by not in self.GROUP_BY:
             raise ValueError(f"group_by must be None or one of {self.GROUP_BY}, got {group_by!r}")
-        if mmr is None and fetch_k is not None:
+        fuse = self._hybrid_options(hybrid, query_texts, group_by, mmr)
+        if mmr is None and fuse is None and fetch_k is not None:
             raise ValueError("fetch_k is the candidate width of an mmr search: give mmr as well")
+        if fuse is not None:
+            top_k = int(top_k)
+            if top_k > self.HYBRID_MAX_FETCH:
+                raise ValueError(f"a hybrid search takes top_k <= {self.HYBRID_MAX_FETCH}, got {top_k}")
+            fetch_k = min(self.HYBRID_MAX_FETCH, max(20, 4 * top_k)) if fetch_k is None else int(fetch_k)
+            if fetch_k > self.HYBRID_MAX_FETCH:
+                raise ValueError(f"a hybrid search takes fetch_k <= {self.HYBRID_MAX_FETCH}, got {fetch_k}")
+            if fetch_k < top_k:
+                raise ValueError(f"fetch_k={fetch_k} is smaller than top_k={top_k}")
         if mmr is not None:
             if group_by is not None:
                 raise ValueError("mmr together with group_by is not supported")
@@ -438,8 +523,12 @@ class MilvusVectorStore:
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"query dimension mismatch: collection dim={self.dim}, got shape {q.shape}")
+        if fuse is not None and len(query_texts) != q.shape[0]:
+            raise ValueError(f"hybrid: {q.shape[0]} query vectors but {len(query_texts)} query texts")
         with self._lock:
             flt = self._filter(repos, languages)
+            if fuse is not None:
+                return self._search_hybrid(q, top_k, fetch_k, list(query_texts), fuse, flt)
             if group_by is not None:
                 return self._search_grouped(q, int(top_k), flt, group_by)
             if mmr is not None:
@@ -465,6 +554,72 @@ class MilvusVectorStore:
             ix.set_groups(np.ascontiguousarray(codes[: len(self._ids)], dtype=np.int32))
             self._groups_installed = group_by
         return ix.search_grouped(q, k=top_k, allow=None if flt is None or flt[1] else flt[0])
+
+    def _hybrid_options(self, hybrid: Any, query_texts: Any, group_by: Any, mmr: Any) -> "Optional[dict]":
+        """None when no hybrid search is asked for, else {c, dense_weight, lexical_weight}; names every conflict."""
+        if hybrid is None or hybrid is False:
+            return None
+        if hybrid is True:
+            opts = dict(self.HYBRID_DEFAULTS)
+        elif isinstance(hybrid, dict):
+            unknown = sorted(set(hybrid) - set(self.HYBRID_DEFAULTS))
+            if unknown:
+                raise ValueError(f"hybrid: unknown keys {unknown}; known: {sorted(self.HYBRID_DEFAULTS)}")
+            opts = {**self.HYBRID_DEFAULTS, **hybrid}
+        else:
+            raise ValueError(f"hybrid must be None, a bool or a dict with any of {sorted(self.HYBRID_DEFAULTS)}, got {hybrid!r}")
+        if not self.lexical:
+            raise ValueError("hybrid search needs the lexical leg: construct the store with lexical=True (or set SEMCODE_MI355X_LEXICAL)")
+        if query_texts is None:
+            raise ValueError("hybrid search needs the query text: give query_text (search) / query_texts (search_batch)")
+        if group_by is not None:
+            raise ValueError("hybrid together with group_by is not supported")
+        if mmr is not None:
+            raise ValueError("hybrid together with mmr is not supported")
+        c = opts["c"]
+        if isinstance(c, bool) or int(c) != c or int(c) < 1:
+            raise ValueError(f"hybrid: c must be an integer >= 1, got {c!r}")
+        opts["c"] = int(c)
+        for name in ("dense_weight", "lexical_weight"):
+            w = float(opts[name])
+            if not (0.0 <= w < float("inf")):
+                raise ValueError(f"hybrid: {name} must be finite and >= 0, got {opts[name]!r}")
+            opts[name] = w
+        return opts
+
+    def lex_query(self, text: str, idf: np.ndarray) -> "tuple[np.ndarray, np.ndarray, int]":
+        """(qterms [32] uint16 ascending, qweights [32] f32, m) of a query text: its distinct terms through the chunks' extractor, the at
+        most 32 of highest idf kept (ties to the lower term), weighted by that idf."""
+        ts = np.unique(self._lex_terms([text], self.lex_slots)[0])
+        ts = ts[ts != 0xFFFF]
+        ts = ts[np.lexsort((ts, -idf[ts].astype(np.float64)))][:32]
+        ts.sort()
+        qt = np.full(32, 0xFFFF, dtype=np.uint16)
+        qw = np.zeros(32, dtype=np.float32)
+        qt[: ts.size] = ts
+        qw[: ts.size] = idf[ts]
+        return qt, qw, int(ts.size)
+
+    def _search_hybrid(self, q: np.ndarray, top_k: int, fetch_k: int, texts: "list[str]", fuse: dict, flt: "Optional[tuple[np.ndarray, bool]]") -> "tuple[np.ndarray, np.ndarray]":
+        """Caller holds the lock.  The df table comes from the device once per mutation."""
+        ix = self._collection
+        if not (hasattr(ix, "search_hybrid") and hasattr(ix, "set_terms") and hasattr(ix, "lex_stats")):
+            raise NotImplementedError(f"{type(ix).__name__} has no set_terms / lex_stats / search_hybrid: this vector index cannot run a hybrid search")
+        if self._terms_on_device != len(self._ids):
+            self._upload_all_terms()
+        if self._lex_stats is None:
+            st = ix.lex_stats()
+            n = int(st["rows"])
+            df = np.asarray(st["df"], dtype=np.float64)
+            idf = np.log(1.0 + (n - df + 0.5) / (df + 0.5)).astype(np.float32)
+            self._lex_stats = (idf, np.float32(st["sum_dl"] / n) if n > 0 and st["sum_dl"] > 0 else np.float32(1.0))
+        idf, avgdl = self._lex_stats
+        terms = [self.lex_query(t, idf) for t in texts]
+        qt = np.stack([t[0] for t in terms])
+        qw = np.stack([t[1] for t in terms])
+        nt = np.asarray([t[2] for t in terms], dtype=np.int32)
+        return ix.search_hybrid(q, qt, qw, nt, k=top_k, fetch_k=fetch_k, k1=self.BM25_K1, b=self.BM25_B, avgdl=float(avgdl), c=fuse["c"],
+                                dense_weight=fuse["dense_weight"], lexical_weight=fuse["lexical_weight"], allow=None if flt is None or flt[1] else flt[0])
 
     @staticmethod
     def _name_set(names: Any) -> "Optional[frozenset]":
@@ -602,6 +757,9 @@ class MilvusVectorStore:
             self._groups_installed = None
             for row, (repo, language, col_path) in enumerate(zip(self._repos, self._languages, self._paths)):
                 self._set_codes(row, repo, language, col_path)
+            if self.lexical:  # (the term rows are not persisted: rebuilt from the saved texts)
+                self._terms = self._lex_terms(self._texts, self.lex_slots) if n else np.zeros((0, self.lex_slots), dtype=np.uint16)
+                self._upload_all_terms()
             self._needs_train = True
             # the saved lists are reused as they are (no k-means) when they fit this collection's index parameters
             tn = int(manifest.get("ivf_trained_nlist", 0))
