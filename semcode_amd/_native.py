@@ -222,6 +222,11 @@ def pack_allow(allow, rows: int) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def _result_arrays(Q: int, k: int) -> "tuple[np.ndarray, np.ndarray]":
+    """The (dist [Q, k] f32, rows [Q, k] i64) a host-pointer search writes."""
+    return np.empty((Q, k), dtype=np.float32), np.empty((Q, k), dtype=np.int64)
+
+
 LEX_MAX_QTERMS = 32   # terms of one lexical query (csrc/lex_rule.h)
 LEX_DF_SIZE = 65536   # entries of the df table
 LEX_PAD = 0xFFFF      # the padding slot of a term row
@@ -446,8 +451,7 @@ class Index:
         """queries [Q, dim] -> (dist [Q, k] f32, rows [Q, k] i64), best first."""
         q = _as_f32(queries, self.dim)
         Q = q.shape[0]
-        dist = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
+        dist, rows = _result_arrays(Q, k)
         _check(lib().sc_index_search(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(nprobe),
                                      dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
@@ -457,12 +461,9 @@ class Index:
         boolean array of length len(index).  -> (dist [Q, k], rows [Q, k]) as search(); fewer than k allowed rows: padded with -1."""
         q = _as_f32(queries, self.dim)
         Q = q.shape[0]
-        words = pack_allow(allow, len(self))
-        if words.size == 0:  # an empty index: still a valid pointer
-            words = np.zeros(1, dtype=np.uint32)
-        dist = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
-        _check(lib().sc_index_search_masked(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), words.ctypes.data_as(C.c_void_p), words.shape[0],
+        allow_ptr, allow_words, _keep = self._allow_args(pack_allow(allow, len(self)))  # (packed here: the bitset is required, None is refused)
+        dist, rows = _result_arrays(Q, k)
+        _check(lib().sc_index_search_masked(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), allow_ptr, allow_words,
                                             dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
 
@@ -489,14 +490,8 @@ class Index:
         best first; allow = None (every row) or as for search_masked.  Fewer than k labels: padded with -1."""
         q = _as_f32(queries, self.dim)
         Q = q.shape[0]
-        dist = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
-        allow_ptr, allow_words = None, 0
-        if allow is not None:
-            words = pack_allow(allow, len(self))
-            if words.size == 0:  # an empty index: still a valid pointer
-                words = np.zeros(1, dtype=np.uint32)
-            allow_ptr, allow_words = words.ctypes.data_as(C.c_void_p), words.shape[0]
+        dist, rows = _result_arrays(Q, k)
+        allow_ptr, allow_words, _keep = self._allow_args(allow)
         _check(lib().sc_index_search_grouped(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), allow_ptr, allow_words,
                                              dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
@@ -520,14 +515,8 @@ class Index:
         order; allow = None (every row) or as for search_masked.  Fewer than k allowed rows: padded with -1."""
         q = _as_f32(queries, self.dim)
         Q = q.shape[0]
-        dist = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
-        allow_ptr, allow_words = None, 0
-        if allow is not None:
-            words = pack_allow(allow, len(self))
-            if words.size == 0:  # an empty index: still a valid pointer
-                words = np.zeros(1, dtype=np.uint32)
-            allow_ptr, allow_words = words.ctypes.data_as(C.c_void_p), words.shape[0]
+        dist, rows = _result_arrays(Q, k)
+        allow_ptr, allow_words, _keep = self._allow_args(allow)
         _check(lib().sc_index_search_mmr(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(fetch_k), float(lam), allow_ptr, allow_words,
                                          dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
@@ -589,8 +578,7 @@ class Index:
         -1 / -inf; rows without a query term are never hits.  allow as for search_masked, or None."""
         qt, qw, nt = self._lex_query_args(qterms, qweights, nterms)
         Q = qt.shape[0]
-        score = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
+        score, rows = _result_arrays(Q, k)
         allow_ptr, allow_words, _keep = self._allow_args(allow)
         _check(lib().sc_index_search_lexical(self.handle, Q, int(k), qt.ctypes.data_as(C.c_void_p), qw.ctypes.data_as(C.c_void_p), nt.ctypes.data_as(C.c_void_p),
                                              float(k1), float(b), float(avgdl), allow_ptr, allow_words, score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
@@ -612,8 +600,7 @@ class Index:
         Q = q.shape[0]
         if qt.shape[0] != Q:
             raise ValueError(f"{Q} query vectors but {qt.shape[0]} term lists")
-        score = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
+        score, rows = _result_arrays(Q, k)
         allow_ptr, allow_words, _keep = self._allow_args(allow)
         _check(lib().sc_index_search_hybrid(self.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(fetch_k), qt.ctypes.data_as(C.c_void_p),
                                             qw.ctypes.data_as(C.c_void_p), nt.ctypes.data_as(C.c_void_p), float(k1), float(b), float(avgdl), int(c), float(dense_weight),
@@ -700,8 +687,7 @@ class Index:
         """Row-sharded search (every rank calls it with the same queries): -> the merged global (dist, rows) [Q, k]."""
         q = _as_f32(queries, self.dim)
         Q = q.shape[0]
-        dist = np.empty((Q, k), dtype=np.float32)
-        rows = np.empty((Q, k), dtype=np.int64)
+        dist, rows = _result_arrays(Q, k)
         _check(lib().sc_index_search_sharded(self.handle, comm.handle, q.ctypes.data_as(C.c_void_p), Q, int(k), int(nprobe),
                                              dist.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
         return dist, rows
@@ -1227,8 +1213,7 @@ def topk_merge_host(metric: str, dist: np.ndarray, rows: np.ndarray) -> tuple[np
     if d.ndim != 3 or d.shape != r.shape:
         raise ValueError("dist and rows must both be [lists, Q, k]")
     lists, Q, k = d.shape
-    od = np.empty((Q, k), dtype=np.float32)
-    orow = np.empty((Q, k), dtype=np.int64)
+    od, orow = _result_arrays(Q, k)
     _check(lib().sc_topk_merge_host(METRICS[metric], lists, Q, k, d.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
                                     od.ctypes.data_as(C.c_void_p), orow.ctypes.data_as(C.c_void_p)))
     return od, orow

@@ -120,7 +120,7 @@ extern "C" sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int
 
     // the per-row arrays, each valid (and moved) below its own extent of stored positions
     struct Arr { void* base; size_t row_bytes; int64_t extent; };
-    const int64_t perm_have = listed ? (ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0;
+    const int64_t perm_have = sc_perm_entries(ix);
     std::vector<Arr> arrs;
     arrs.push_back({ix->X, (size_t)ld * 4, old_n});
     arrs.push_back({ix->xnorm, 4, old_n});

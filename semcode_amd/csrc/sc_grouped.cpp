@@ -1,6 +1,6 @@
 // sc_grouped.cpp -- the grouped search of the C ABI (sc_index_set_groups, sc_index_search_grouped*, include/semcode_hip.h): at most one
-// hit per label, exact.  The scores come from the existing searches -- the exhaustive planner or the masked search at a candidate
-// width -- and scan_grouped.hip picks the first row of every label out of their best-first lists.  Queries whose list ran out before
+// hit per label, exact.  The scores come from the existing searches -- sc_candidates_locked at a candidate width -- and
+// scan_grouped.hip picks the first row of every label out of their best-first lists.  Queries whose list ran out before
 // k labels go on in rounds: their hit labels are excluded by a bitset and the masked search answers over what is left.
 // The labels are the caller's data parked on the device: never interpreted, never persisted, dropped by sc_index_delete_rows.
 #include <algorithm>
@@ -30,21 +30,18 @@ static int width1(int k, int round) {
     return round > 1 ? 256 : std::min(256, std::max(64, 4 * k));
 }
 
+static const char* const WHO = "grouped search";
+
 static sc_status check_grouped_args(sc_index* ix, const void* q, int32_t Q, int32_t k, const void* allow, int64_t allow_words, const void* od, const void* orow) {
-    if (!ix || !q || !od || !orow) return sc_fail(SC_ERR_INVALID, "grouped search: NULL argument");
-    if (Q < 1 || Q > (1 << 20)) return sc_fail(SC_ERR_INVALID, "grouped search: Q=%d out of range", Q);
-    if (k < 1 || k > GROUP_MAX_K) return sc_fail(SC_ERR_INVALID, "grouped search: top_k must be 1..%d (got %d)", GROUP_MAX_K, k);
-    if (!allow && allow_words != 0) return sc_fail(SC_ERR_INVALID, "grouped search: allow is NULL but allow_words=%lld", (long long)allow_words);
-    return SC_OK;
+    const sc_status st = sc_check_query_args(WHO, !ix || !q || !od || !orow, Q, k, GROUP_MAX_K);
+    return st ? st : sc_check_allow_null(WHO, allow, allow_words);
 }
 // (under the lock: the row count is the index's)
 static sc_status check_grouped_state(const sc_index* ix, const void* allow, int64_t allow_words) {
     if (ix->group_rows != ix->n)
         return sc_fail(SC_ERR_INVALID, "grouped search: no valid labels -- installed for %lld rows (-1: none), the index has %lld; call sc_index_set_groups",
                        (long long)ix->group_rows, (long long)ix->n);
-    if (allow && allow_words < (ix->n + 31) / 32)
-        return sc_fail(SC_ERR_INVALID, "grouped search: allow_words=%lld, %lld rows need %lld", (long long)allow_words, (long long)ix->n, (long long)((ix->n + 31) / 32));
-    return SC_OK;
+    return sc_check_allow_words(WHO, ix, allow, allow_words);
 }
 
 // One pass of <= GROUP_CHUNK_Q queries.  q_dev tight [Q, dim], allow_dev NULL or >= ceil(n / 32) words, outputs [Q, k]: all device.
@@ -66,22 +63,11 @@ static sc_status grouped_chunk_locked(sc_index* ix, const float* q_dev, int32_t 
     int32_t *found = (int32_t*)(b + o_lab), *cnt = (int32_t*)(b + o_cnt), *done = (int32_t*)(b + o_done);
     uint32_t* excl = (uint32_t*)(b + o_excl);
 
-    // ---- round 0: every query through the existing searches at width W0
-    if (allow_dev) {
-        st = sc_search_masked_locked(ix, q_dev, Q, W0, allow_dev, cd, cr);
-        if (st) return st;
-        ix->last_group_scanned += ix->last_mask_scanned;
-    } else {
-        // the exhaustive planner; a trained index is scanned as it lies (the masked search's every-row-allowed shortcut)
-        const int64_t mapped = ix->perm ? std::min<int64_t>(n, ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0;
-        if (ix->perm && mapped < n) {
-            st = sc_ivf_cover_tail_locked(ix);
-            if (st) return st;
-        }
-        st = sc_search_flat_locked(ix, q_dev, Q, W0, cd, cr);
-        if (st) return st;
-        ix->last_group_scanned += n;
-    }
+    // ---- round 0: the candidate stage at width W0 (run on an empty index too: the selection reads the padding it writes)
+    int64_t scanned = 0;
+    st = sc_candidates_locked(ix, q_dev, Q, W0, allow_dev, cd, cr, &scanned, nullptr);
+    if (st) return st;
+    ix->last_group_scanned += scanned;
     sc_with_prof(rt, SC_PROF_MERGE, [&] { sc_launch_group_select(metric, cd, cr, W0, Q, labels, n, ix->row_base, k, true, out_dist, out_rows, found, cnt, done, s); });
     SC_HIP(hipGetLastError());
     // the host's one read per round: the done flags
@@ -166,30 +152,12 @@ extern "C" sc_status sc_index_search_grouped(sc_index* ix, const float* q, int32
     st = check_grouped_state(ix, allow, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    hipStream_t s = ix->rt->stream;
-    const size_t qb = ((size_t)Q * ix->dim * 4 + 15) & ~(size_t)15;
-    const size_t db = ((size_t)Q * k * 4 + 15) & ~(size_t)15;
-    const size_t rb = (size_t)Q * k * 8;
-    st = sc_grow(ix, ix->io, qb + db + rb);
+    sc_host_io io;
+    st = sc_stage_host_locked(ix, q, Q, k, allow, 0, &io);
     if (st) return st;
-    float* dq = ix->io.as<float>();
-    float* dd = (float*)(ix->io.as<char>() + qb);
-    int64_t* dr = (int64_t*)(ix->io.as<char>() + qb + db);
-    SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
-    const uint32_t* dallow = nullptr;
-    if (allow) {
-        const size_t words = (size_t)((ix->n + 31) / 32);  // bits beyond the rows are never read
-        st = sc_grow(ix, ix->mask_words, std::max<size_t>(words * 4, 16));
-        if (st) return st;
-        if (words) SC_HIP(hipMemcpyAsync(ix->mask_words.p, allow, words * 4, hipMemcpyHostToDevice, s));
-        dallow = ix->mask_words.as<uint32_t>();
-    }
-    st = search_grouped_locked(ix, dq, Q, k, dallow, dd, dr);
+    st = search_grouped_locked(ix, io.q, Q, k, io.allow, io.dist, io.rows);
     if (st) return st;
-    SC_HIP(hipMemcpyAsync(out_dist, dd, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(out_rows, dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    return SC_OK;
+    return sc_fetch_host_locked(ix, io, Q, k, out_dist, out_rows);
 }
 
 extern "C" sc_status sc_index_last_group_stats(sc_index* ix, int32_t* first_width, int32_t* queries_continued, int32_t* rounds, int64_t* rows_scanned) {

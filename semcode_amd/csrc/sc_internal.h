@@ -116,8 +116,8 @@ struct sc_index {
     sc_buf fb, fb2;                               // fallback staging (queries + results) of the first stage's uncertified queries; the same for the second stage (int8 -> bf16 -> exact)
     sc_buf tailbuf;                               // two [Q][k] result sets of a search that answers from the lists and from the tail (sc_search.cpp)
     int64_t last_tail_rows = 0;                   // rows the last search scanned behind the lists (0: none)
-    // masked search (sc_masked.cpp): the uploaded allow words of the host entry point; the bitset over stored positions + per-block counts
-    // and their scan; sel, the ascending allowed stored positions
+    // the uploaded allow words of a host-pointer search (sc_stage_host_locked); masked search (sc_masked.cpp): the bitset over stored
+    // positions + per-block counts and their scan; sel, the ascending allowed stored positions
     sc_buf mask_words, mask_cnt, mask_sel;
     int64_t last_mask_allowed = 0, last_mask_scanned = 0;  // sc_index_last_mask_stats
     int last_mask_gathered = 0;
@@ -231,6 +231,29 @@ struct sc_subbatch { float* q; float* d; int64_t* r; int32_t* idx; int R; };
 sc_status sc_subbatch_stage(sc_index* ix, sc_buf& buf, const float* q_dev, const std::vector<int>& which, int k, sc_subbatch* sb);
 sc_status sc_subbatch_scatter(sc_index* ix, const sc_subbatch& sb, int k, float* out_dist, int64_t* out_rows);  // results back to the batch's rows; synchronises
 
+// sc_search_entry.cpp: what the search entry points share.
+// The checks every one of them starts with, `who` being the prefix of the message ("masked search").  any_null: one of the call's
+// pointers is NULL; k_max: the widest top_k (0: no upper bound).  Then the two checks of an optional bitset: before the lock that a
+// word count comes with words, under it (the row count is the index's) that the words cover the rows.
+sc_status sc_check_query_args(const char* who, bool any_null, int32_t Q, int32_t k, int32_t k_max);
+sc_status sc_check_allow_null(const char* who, const void* allow, int64_t allow_words);
+sc_status sc_check_allow_words(const char* who, const sc_index* ix, const void* allow, int64_t allow_words);
+// Staging of a host-pointer search (caller holds ix->mu and has set the device): the device copies of the queries [Q, dim] (q may be
+// NULL: none) and of the ceil(n / 32) allow words (allow may be NULL: io->allow is too), room for the [Q, k] results and `extra_bytes`
+// more at a 256-byte boundary for the caller's own uploads.  Valid until the next staging on the index.  sc_fetch_host_locked copies
+// the results to the caller and synchronises.
+struct sc_host_io { float* q; float* dist; int64_t* rows; const uint32_t* allow; char* extra; };
+sc_status sc_stage_host_locked(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint32_t* allow, size_t extra_bytes, sc_host_io* io);
+sc_status sc_fetch_host_locked(sc_index* ix, const sc_host_io& io, int32_t Q, int32_t k, float* out_dist, int64_t* out_rows);
+// The exact top-k over every row through the exhaustive planner, whatever the layout: rows behind the lists of a trained index are
+// scanned where they lie (nothing is folded in).
+sc_status sc_search_exhaustive_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, float* out_dist, int64_t* out_rows);
+// The candidate stage of the grouped, MMR and hybrid searches: the exact best-first top-W of every query over the allowed rows
+// (allow_dev >= ceil(n / 32) device words: the masked search) or over all rows (NULL: the exhaustive search), lists [Q, W] on the
+// device.  scanned / allowed (optional): rows the answering scan read per pass / rows that were eligible.
+sc_status sc_candidates_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t W, const uint32_t* allow_dev, float* cand_dist, int64_t* cand_rows, int64_t* scanned,
+                               int64_t* allowed);
+
 // search and IVF internals shared between sc_search.cpp and sc_ivf_{build,probe,coarse}.cpp (caller holds ix->mu)
 sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
 sc_status sc_search_flat_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, float* out_dist, int64_t* out_rows);
@@ -244,6 +267,8 @@ void sc_ivf_drop_lists_locked(sc_index* ix);    // drop lists without restoring 
 sc_status sc_ivf_cover_tail_locked(sc_index* ix);  // extend perm over rows appended since the build (identity): exhaustive search only
 sc_status sc_ivf_refresh_locked(sc_index* ix, bool keep_tail = false);  // fold rows upserted since the lists were built into them (no k-means);
                                                                         // keep_tail: only settle the overwritten rows -- if none left its list, appended rows stay a tail
+// entries of ix->perm (0: no trained layout): a stored position below it reports perm[position], one at or beyond it is its own row id
+static inline int64_t sc_perm_entries(const sc_index* ix) { return ix->perm ? (ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0; }
 // stored position of row `r` (trained layout installed: ix->perm != nullptr)
 static inline int64_t sc_ivf_pos(const sc_index* ix, int64_t r) { return r < ix->ivf_rows ? (int64_t)ix->inv_h[(size_t)r] : r; }
 // upsert body shared by sc_index_put_rows{,_dev} and sc_encoder_embed_ids_into; caller holds ix->mu and has set the device

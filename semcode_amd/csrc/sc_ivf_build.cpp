@@ -154,9 +154,8 @@ static int g_ivf_refresh_nomem = 0;  // sc_diag_set_option("ivf_refresh_nomem", 
 void sc_ivf_set_refresh_nomem(int v) { g_ivf_refresh_nomem = v; }
 
 sc_status sc_ivf_cover_tail_locked(sc_index* ix) {
-    if (!ix->perm) return SC_OK;
-    const int64_t have = ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows;
-    if (have >= ix->n) return SC_OK;
+    const int64_t have = sc_perm_entries(ix);
+    if (!ix->perm || have >= ix->n) return SC_OK;  // (no trained layout, or every position mapped already)
     hipStream_t s = ix->rt->stream;
     sc_devbuf d_new;
     if (d_new.alloc((size_t)ix->n * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "ivf: hipMalloc of the extended row map failed");

@@ -113,21 +113,16 @@ struct LexParams {
 
 static sc_status check_lex_args(sc_index* ix, int32_t Q, int32_t k, const void* qt, const void* qw, const void* nt, const LexParams& p, const void* allow,
                                 int64_t allow_words, const void* od, const void* orow, const char* who) {
-    if (!ix || !qt || !qw || !nt || !od || !orow) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
-    if (Q < 1 || Q > (1 << 20)) return sc_fail(SC_ERR_INVALID, "%s: Q=%d out of range", who, Q);
-    if (k < 1 || k > LEX_MAX_K) return sc_fail(SC_ERR_INVALID, "%s: top_k must be 1..%d (got %d)", who, LEX_MAX_K, k);
+    const sc_status st = sc_check_query_args(who, !ix || !qt || !qw || !nt || !od || !orow, Q, k, LEX_MAX_K);
+    if (st) return st;
     if (!std::isfinite(p.k1) || !std::isfinite(p.b) || !std::isfinite(p.avgdl) || !(p.avgdl > 0.0f))
         return sc_fail(SC_ERR_INVALID, "%s: k1=%g, b=%g must be finite and avgdl=%g finite and > 0", who, (double)p.k1, (double)p.b, (double)p.avgdl);
-    if (!allow && allow_words != 0) return sc_fail(SC_ERR_INVALID, "%s: allow is NULL but allow_words=%lld", who, (long long)allow_words);
-    return SC_OK;
+    return sc_check_allow_null(who, allow, allow_words);
 }
 // (under the lock: the row counts are the index's)
 static sc_status check_lex_state(const sc_index* ix, const void* allow, int64_t allow_words, const char* who) {
     const sc_status st = check_terms_state(ix, who);
-    if (st) return st;
-    if (allow && allow_words < (ix->n + 31) / 32)
-        return sc_fail(SC_ERR_INVALID, "%s: allow_words=%lld, %lld rows need %lld", who, (long long)allow_words, (long long)ix->n, (long long)((ix->n + 31) / 32));
-    return SC_OK;
+    return st ? st : sc_check_allow_words(who, ix, allow, allow_words);
 }
 // the rules of a query's terms, checked on the host where the host holds them (the _dev forms leave it to lex_prep_kernel)
 static sc_status check_queries_host(const uint16_t* qt, const float* qw, const int32_t* nt, int32_t Q, const char* who) {
@@ -247,21 +242,11 @@ static sc_status search_hybrid_locked(sc_index* ix, const float* q_dev, int32_t 
     for (int32_t q0 = 0; q0 < Q; q0 += QC) {
         const int32_t nq = std::min<int32_t>(QC, Q - q0);
         const float* qc = q_dev + (size_t)q0 * ix->dim;
-        // ---- the dense leg: the existing searches at width fetch_k (sc_mmr.cpp's candidate stage)
-        if (n > 0 && allow_dev) {
-            st = sc_search_masked_locked(ix, qc, nq, F, allow_dev, sc.cd, sc.cr);
-            if (st) return st;
-        } else if (n > 0) {
-            const int64_t mapped = ix->perm ? std::min<int64_t>(n, ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0;
-            if (ix->perm && mapped < n) {
-                st = sc_ivf_cover_tail_locked(ix);
-                if (st) return st;
-            }
-            st = sc_search_flat_locked(ix, qc, nq, F, sc.cd, sc.cr);
-            if (st) return st;
-        }
-        // ---- the lexical leg at the same width, then the fusion (an empty index: it writes the padding alone)
+        // ---- the dense leg (the candidate stage) and the lexical leg at width fetch_k, then the fusion (an empty index: it writes the
+        // padding alone)
         if (n > 0) {
+            st = sc_candidates_locked(ix, qc, nq, F, allow_dev, sc.cd, sc.cr, nullptr, nullptr);
+            if (st) return st;
             st = lexical_chunk_locked(ix, sc, nq, F, qt + (size_t)q0 * LEX_MAX_QTERMS, qw + (size_t)q0 * LEX_MAX_QTERMS, nt + q0, p, allow_dev, sc.ld, sc.lr);
             if (st) return st;
         }
@@ -292,50 +277,27 @@ extern "C" sc_status sc_index_search_lexical_dev(sc_index* ix, int32_t Q, int32_
     return lex_check_bad(ix, bad, who);
 }
 
-// host staging shared by the two host-pointer forms: [queries (hybrid) | qterms | qweights | nterms | scores | rows] in ix->io, allow in ix->mask_words
-struct LexIo {
-    float* dq;
+// The staging of the two host-pointer forms (q: the hybrid search's query vectors, or NULL), with the queries' terms uploaded into
+// its extra region as [qterms | qweights | nterms].
+struct LexQueries {
     uint16_t* qt;
     float* qw;
     int32_t* nt;
-    float* ds;
-    int64_t* dr;
-    const uint32_t* allow;
 };
-static sc_status lex_stage_host(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint16_t* qterms, const float* qweights, const int32_t* nterms,
-                                const uint32_t* allow, LexIo* io) {
+static sc_status lex_stage_queries(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint16_t* qterms, const float* qweights, const int32_t* nterms,
+                                   const uint32_t* allow, sc_host_io* io, LexQueries* lq) {
     hipStream_t s = ix->rt->stream;
+    const size_t qt_bytes = (size_t)Q * LEX_MAX_QTERMS * 2, qw_bytes = (size_t)Q * LEX_MAX_QTERMS * 4, nt_bytes = (size_t)Q * 4;
     sc_carver carve;
-    const size_t o_q = carve(q ? (size_t)Q * ix->dim * 4 : 16), o_qt = carve((size_t)Q * LEX_MAX_QTERMS * 2), o_qw = carve((size_t)Q * LEX_MAX_QTERMS * 4),
-                 o_nt = carve((size_t)Q * 4), o_ds = carve((size_t)Q * k * 4), o_dr = carve((size_t)Q * k * 8);
-    sc_status st = sc_grow(ix, ix->io, carve.off);
+    const size_t o_qt = carve(qt_bytes), o_qw = carve(qw_bytes), o_nt = carve(nt_bytes);
+    const sc_status st = sc_stage_host_locked(ix, q, Q, k, allow, carve.off, io);
     if (st) return st;
-    char* b = ix->io.as<char>();
-    io->dq = (float*)(b + o_q);
-    io->qt = (uint16_t*)(b + o_qt);
-    io->qw = (float*)(b + o_qw);
-    io->nt = (int32_t*)(b + o_nt);
-    io->ds = (float*)(b + o_ds);
-    io->dr = (int64_t*)(b + o_dr);
-    io->allow = nullptr;
-    if (q) SC_HIP(hipMemcpyAsync(io->dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(io->qt, qterms, (size_t)Q * LEX_MAX_QTERMS * 2, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(io->qw, qweights, (size_t)Q * LEX_MAX_QTERMS * 4, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(io->nt, nterms, (size_t)Q * 4, hipMemcpyHostToDevice, s));
-    if (allow) {
-        const size_t words = (size_t)((ix->n + 31) / 32);  // bits beyond the rows are never read
-        st = sc_grow(ix, ix->mask_words, std::max<size_t>(words * 4, 16));
-        if (st) return st;
-        if (words) SC_HIP(hipMemcpyAsync(ix->mask_words.p, allow, words * 4, hipMemcpyHostToDevice, s));
-        io->allow = ix->mask_words.as<uint32_t>();
-    }
-    return SC_OK;
-}
-static sc_status lex_results_host(sc_index* ix, const LexIo& io, int32_t Q, int32_t k, float* out_score, int64_t* out_rows) {
-    hipStream_t s = ix->rt->stream;
-    SC_HIP(hipMemcpyAsync(out_score, io.ds, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(out_rows, io.dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
+    lq->qt = (uint16_t*)(io->extra + o_qt);
+    lq->qw = (float*)(io->extra + o_qw);
+    lq->nt = (int32_t*)(io->extra + o_nt);
+    SC_HIP(hipMemcpyAsync(lq->qt, qterms, qt_bytes, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(lq->qw, qweights, qw_bytes, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(lq->nt, nterms, nt_bytes, hipMemcpyHostToDevice, s));
     return SC_OK;
 }
 
@@ -351,13 +313,14 @@ extern "C" sc_status sc_index_search_lexical(sc_index* ix, int32_t Q, int32_t k,
     st = check_lex_state(ix, allow, allow_words, who);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    LexIo io;
-    st = lex_stage_host(ix, nullptr, Q, k, qterms, qweights, nterms, allow, &io);
+    sc_host_io io;
+    LexQueries lq;
+    st = lex_stage_queries(ix, nullptr, Q, k, qterms, qweights, nterms, allow, &io, &lq);
     if (st) return st;
     const int32_t* bad = nullptr;
-    st = search_lexical_locked(ix, Q, k, io.qt, io.qw, io.nt, p, io.allow, io.ds, io.dr, &bad);
+    st = search_lexical_locked(ix, Q, k, lq.qt, lq.qw, lq.nt, p, io.allow, io.dist, io.rows, &bad);
     if (st) return st;
-    return lex_results_host(ix, io, Q, k, out_score, out_rows);
+    return sc_fetch_host_locked(ix, io, Q, k, out_score, out_rows);
 }
 
 static sc_status check_hybrid_args(const void* q, int32_t k, int32_t fetch_k, int32_t c, float wd, float wl) {
@@ -405,13 +368,14 @@ extern "C" sc_status sc_index_search_hybrid(sc_index* ix, const float* q, int32_
     st = check_lex_state(ix, allow, allow_words, who);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    LexIo io;
-    st = lex_stage_host(ix, q, Q, k, qterms, qweights, nterms, allow, &io);
+    sc_host_io io;
+    LexQueries lq;
+    st = lex_stage_queries(ix, q, Q, k, qterms, qweights, nterms, allow, &io, &lq);
     if (st) return st;
     const int32_t* bad = nullptr;
-    st = search_hybrid_locked(ix, io.dq, Q, k, fetch_k, io.qt, io.qw, io.nt, p, c, wd, wl, io.allow, io.ds, io.dr, &bad);
+    st = search_hybrid_locked(ix, io.q, Q, k, fetch_k, lq.qt, lq.qw, lq.nt, p, c, wd, wl, io.allow, io.dist, io.rows, &bad);
     if (st) return st;
-    return lex_results_host(ix, io, Q, k, out_score, out_rows);
+    return sc_fetch_host_locked(ix, io, Q, k, out_score, out_rows);
 }
 
 extern "C" sc_status sc_index_last_lex_stats(sc_index* ix, int64_t* rows_scanned, int64_t* bytes_per_pass, int32_t* passes) {

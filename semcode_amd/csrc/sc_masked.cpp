@@ -8,18 +8,8 @@
 static int g_mask_gather = 0;  // sc_diag_set_option("mask_gather", 1): the gathered kernel answers even when every row is allowed (tests)
 void sc_set_mask_gather(int v) { g_mask_gather = v; }
 
-static sc_status check_masked_args(sc_index* ix, const void* q, int32_t Q, int32_t k, const void* allow, const void* od, const void* orow) {
-    if (!ix || !q || !allow || !od || !orow) return sc_fail(SC_ERR_INVALID, "masked search: NULL argument");
-    if (Q < 1 || Q > (1 << 20)) return sc_fail(SC_ERR_INVALID, "masked search: Q=%d out of range", Q);
-    if (k < 1 || k > 1024) return sc_fail(SC_ERR_INVALID, "masked search: top_k must be 1..1024 (got %d)", k);
-    return SC_OK;
-}
-// (under the lock: the row count is the index's)
-static sc_status check_allow_words(const sc_index* ix, int64_t allow_words) {
-    if (allow_words < (ix->n + 31) / 32)
-        return sc_fail(SC_ERR_INVALID, "masked search: allow_words=%lld, %lld rows need %lld", (long long)allow_words, (long long)ix->n, (long long)((ix->n + 31) / 32));
-    return SC_OK;
-}
+static const char* const WHO = "masked search";
+static const int MASK_MAX_K = 1024;  // the widest list of the exact scan
 
 // q_dev tight [Q, dim], allow_dev >= ceil(n / 32) words, outputs [Q, k]: all device.  Synchronises the stream once (the allowed count).
 sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows) {
@@ -30,7 +20,7 @@ sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, i
     ix->last_mask_gathered = 0;
     // stored position -> row id is valid below `mapped` (the lists of a trained IVF_FLAT index; further where a search extended it over
     // the tail with the identity, which is what positions beyond it mean anyway)
-    const int64_t mapped = ix->perm ? std::min<int64_t>(n, ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0;
+    const int64_t mapped = std::min(n, sc_perm_entries(ix));
     int64_t m = 0;
     if (n > 0) {
         const int64_t nb = sc_mask_blocks(n);
@@ -49,14 +39,9 @@ sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, i
     }
     ix->last_mask_allowed = m;
     if (m == n && n > 0 && !g_mask_gather) {
-        // every row allowed: the exhaustive planner (same bits; the batched path for large batches).  A trained index is scanned as it
-        // lies: its position map is extended over the tail with the identity, the tail itself stays a tail.
-        if (ix->perm && mapped < n) {
-            const sc_status cst = sc_ivf_cover_tail_locked(ix);
-            if (cst) return cst;
-        }
+        // every row allowed: the exhaustive planner (same bits; the batched path for large batches)
         ix->last_mask_scanned = n;
-        return sc_search_flat_locked(ix, q_dev, Q, k, out_dist, out_rows);
+        return sc_search_exhaustive_locked(ix, q_dev, Q, k, out_dist, out_rows);
     }
     ScanPlan plan;
     // force_qt = 16: the resident-query variant whatever the row length
@@ -87,10 +72,10 @@ sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, i
 
 extern "C" sc_status sc_index_search_masked_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, int64_t allow_words,
                                                 float* out_dist_dev, int64_t* out_rows_dev) {
-    sc_status st = check_masked_args(ix, q_dev, Q, k, allow_dev, out_dist_dev, out_rows_dev);
+    sc_status st = sc_check_query_args(WHO, !ix || !q_dev || !allow_dev || !out_dist_dev || !out_rows_dev, Q, k, MASK_MAX_K);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
-    st = check_allow_words(ix, allow_words);
+    st = sc_check_allow_words(WHO, ix, allow_dev, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
     return sc_search_masked_locked(ix, q_dev, Q, k, allow_dev, out_dist_dev, out_rows_dev);
@@ -98,32 +83,18 @@ extern "C" sc_status sc_index_search_masked_dev(sc_index* ix, const float* q_dev
 
 extern "C" sc_status sc_index_search_masked(sc_index* ix, const float* q, int32_t Q, int32_t k, const uint32_t* allow, int64_t allow_words, float* out_dist,
                                             int64_t* out_rows) {
-    sc_status st = check_masked_args(ix, q, Q, k, allow, out_dist, out_rows);
+    sc_status st = sc_check_query_args(WHO, !ix || !q || !allow || !out_dist || !out_rows, Q, k, MASK_MAX_K);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
-    st = check_allow_words(ix, allow_words);
+    st = sc_check_allow_words(WHO, ix, allow, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    hipStream_t s = ix->rt->stream;
-    const size_t qb = ((size_t)Q * ix->dim * 4 + 15) & ~(size_t)15;
-    const size_t db = ((size_t)Q * k * 4 + 15) & ~(size_t)15;
-    const size_t rb = (size_t)Q * k * 8;
-    st = sc_grow(ix, ix->io, qb + db + rb);
+    sc_host_io io;
+    st = sc_stage_host_locked(ix, q, Q, k, allow, 0, &io);
     if (st) return st;
-    const size_t words = (size_t)((ix->n + 31) / 32);  // bits beyond the rows are never read
-    st = sc_grow(ix, ix->mask_words, std::max<size_t>(words * 4, 16));
+    st = sc_search_masked_locked(ix, io.q, Q, k, io.allow, io.dist, io.rows);
     if (st) return st;
-    float* dq = ix->io.as<float>();
-    float* dd = (float*)(ix->io.as<char>() + qb);
-    int64_t* dr = (int64_t*)(ix->io.as<char>() + qb + db);
-    SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
-    if (words) SC_HIP(hipMemcpyAsync(ix->mask_words.p, allow, words * 4, hipMemcpyHostToDevice, s));
-    st = sc_search_masked_locked(ix, dq, Q, k, ix->mask_words.as<uint32_t>(), dd, dr);
-    if (st) return st;
-    SC_HIP(hipMemcpyAsync(out_dist, dd, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(out_rows, dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    return SC_OK;
+    return sc_fetch_host_locked(ix, io, Q, k, out_dist, out_rows);
 }
 
 extern "C" sc_status sc_index_last_mask_stats(sc_index* ix, int64_t* allowed_rows, int64_t* scanned_rows, int32_t* gathered) {

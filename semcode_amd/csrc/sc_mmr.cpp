@@ -1,6 +1,6 @@
 // sc_mmr.cpp -- the MMR search of the C ABI (sc_index_search_mmr*, include/semcode_hip.h): diversified top-k by maximal marginal
-// relevance, exact.  The candidates come from the existing searches -- the exhaustive planner or the masked search at width fetch_k
-// -- and scan_mmr.hip scores them against each other and runs the greedy selection of mmr_rule.h.  Nothing is kept between calls:
+// relevance, exact.  The candidates come from the existing searches -- sc_candidates_locked at width fetch_k -- and scan_mmr.hip
+// scores them against each other and runs the greedy selection of mmr_rule.h.  Nothing is kept between calls:
 // the row -> position map of a trained index is rebuilt per call into the scratch.
 #include <algorithm>
 #include <cmath>
@@ -15,24 +15,18 @@ void sc_set_mmr_chunk_q(int v) { g_mmr_chunk_q = v; }
 static const int MMR_MAX_FETCH = 128;  // the widest candidate list: the planner's fast paths take it, and its score matrix is 64 KiB
 static const int MMR_CHUNK_Q = 1024;   // queries per pass: bounds the score matrices (64 KiB per query at fetch_k = 128)
 
+static const char* const WHO = "mmr search";
+
 static int chunk_q() { return g_mmr_chunk_q > 0 ? g_mmr_chunk_q : MMR_CHUNK_Q; }
 
 static sc_status check_mmr_args(sc_index* ix, const void* q, int32_t Q, int32_t k, int32_t fetch_k, float lambda, const void* allow, int64_t allow_words, const void* od,
                                 const void* orow) {
-    if (!ix || !q || !od || !orow) return sc_fail(SC_ERR_INVALID, "mmr search: NULL argument");
-    if (Q < 1 || Q > (1 << 20)) return sc_fail(SC_ERR_INVALID, "mmr search: Q=%d out of range", Q);
-    if (k < 1) return sc_fail(SC_ERR_INVALID, "mmr search: top_k must be >= 1 (got %d)", k);
+    const sc_status st = sc_check_query_args(WHO, !ix || !q || !od || !orow, Q, k, 0);
+    if (st) return st;
     if (fetch_k > MMR_MAX_FETCH) return sc_fail(SC_ERR_INVALID, "mmr search: fetch_k must be <= %d (got %d)", MMR_MAX_FETCH, fetch_k);
     if (k > fetch_k) return sc_fail(SC_ERR_INVALID, "mmr search: top_k=%d exceeds fetch_k=%d", k, fetch_k);
     if (!(lambda >= 0.0f && lambda <= 1.0f)) return sc_fail(SC_ERR_INVALID, "mmr search: lambda must be within [0, 1] (got %g)", (double)lambda);
-    if (!allow && allow_words != 0) return sc_fail(SC_ERR_INVALID, "mmr search: allow is NULL but allow_words=%lld", (long long)allow_words);
-    return SC_OK;
-}
-// (under the lock: the row count is the index's)
-static sc_status check_mmr_state(const sc_index* ix, const void* allow, int64_t allow_words) {
-    if (allow && allow_words < (ix->n + 31) / 32)
-        return sc_fail(SC_ERR_INVALID, "mmr search: allow_words=%lld, %lld rows need %lld", (long long)allow_words, (long long)ix->n, (long long)((ix->n + 31) / 32));
-    return SC_OK;
+    return sc_check_allow_null(WHO, allow, allow_words);
 }
 
 // q_dev tight [Q, dim], allow_dev NULL or >= ceil(n / 32) words, outputs [Q, k]: all device.
@@ -68,29 +62,17 @@ static sc_status search_mmr_locked(sc_index* ix, const float* q_dev, int32_t Q, 
         const float* qc = q_dev + (size_t)q0 * ix->dim;
         float* od = out_dist + (size_t)q0 * k;
         int64_t* orow = out_rows + (size_t)q0 * k;
-        // ---- candidates: every query through the existing searches at width fetch_k (sc_grouped.cpp round 0)
-        bool any = n > 0;
-        if (n > 0 && allow_dev) {
-            st = sc_search_masked_locked(ix, qc, nq, F, allow_dev, cd, cr);
+        // ---- candidates: the candidate stage at width fetch_k
+        int64_t scanned = 0, allowed = 0;
+        if (n > 0) {
+            st = sc_candidates_locked(ix, qc, nq, F, allow_dev, cd, cr, &scanned, &allowed);
             if (st) return st;
-            ix->last_mmr_scanned += ix->last_mask_scanned;
-            any = ix->last_mask_allowed > 0;
-        } else if (n > 0) {
-            // the exhaustive planner; a trained index is scanned as it lies (the masked search's every-row-allowed shortcut)
-            const int64_t mapped = ix->perm ? std::min<int64_t>(n, ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows) : 0;
-            if (ix->perm && mapped < n) {
-                st = sc_ivf_cover_tail_locked(ix);
-                if (st) return st;
-            }
-            st = sc_search_flat_locked(ix, qc, nq, F, cd, cr);
-            if (st) return st;
-            ix->last_mmr_scanned += n;
+            ix->last_mmr_scanned += scanned;
         }
-        if (any) {
+        if (allowed > 0) {
             // ---- candidate rows -> stored positions (list-major storage only; once per call, after a search may have extended perm)
             if (ix->perm && !have_inv) {
-                const int64_t mapped = std::min<int64_t>(n, ix->perm_rows > 0 ? ix->perm_rows : ix->ivf_rows);
-                sc_with_prof(rt, SC_PROF_MERGE, [&] { sc_launch_mmr_inverse(ix->perm, mapped, n, inv, s); });
+                sc_with_prof(rt, SC_PROF_MERGE, [&] { sc_launch_mmr_inverse(ix->perm, std::min(n, sc_perm_entries(ix)), n, inv, s); });
                 have_inv = true;
             }
             sc_with_prof(rt, SC_PROF_SCAN, [&] { sc_launch_mmr_gram(metric, ix->X, ix->xnorm, ix->ld, n, ix->row_base, ix->perm ? inv : nullptr, cr, F, nq, G, s); });
@@ -109,7 +91,7 @@ extern "C" sc_status sc_index_search_mmr_dev(sc_index* ix, const float* q_dev, i
     sc_status st = check_mmr_args(ix, q_dev, Q, k, fetch_k, lambda, allow_dev, allow_words, out_dist_dev, out_rows_dev);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
-    st = check_mmr_state(ix, allow_dev, allow_words);
+    st = sc_check_allow_words(WHO, ix, allow_dev, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
     return search_mmr_locked(ix, q_dev, Q, k, fetch_k, lambda, allow_dev, out_dist_dev, out_rows_dev);
@@ -120,33 +102,15 @@ extern "C" sc_status sc_index_search_mmr(sc_index* ix, const float* q, int32_t Q
     sc_status st = check_mmr_args(ix, q, Q, k, fetch_k, lambda, allow, allow_words, out_dist, out_rows);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
-    st = check_mmr_state(ix, allow, allow_words);
+    st = sc_check_allow_words(WHO, ix, allow, allow_words);
     if (st) return st;
     SC_HIP(hipSetDevice(ix->rt->device));
-    hipStream_t s = ix->rt->stream;
-    const size_t qb = ((size_t)Q * ix->dim * 4 + 15) & ~(size_t)15;
-    const size_t db = ((size_t)Q * k * 4 + 15) & ~(size_t)15;
-    const size_t rb = (size_t)Q * k * 8;
-    st = sc_grow(ix, ix->io, qb + db + rb);
+    sc_host_io io;
+    st = sc_stage_host_locked(ix, q, Q, k, allow, 0, &io);
     if (st) return st;
-    float* dq = ix->io.as<float>();
-    float* dd = (float*)(ix->io.as<char>() + qb);
-    int64_t* dr = (int64_t*)(ix->io.as<char>() + qb + db);
-    SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
-    const uint32_t* dallow = nullptr;
-    if (allow) {
-        const size_t words = (size_t)((ix->n + 31) / 32);  // bits beyond the rows are never read
-        st = sc_grow(ix, ix->mask_words, std::max<size_t>(words * 4, 16));
-        if (st) return st;
-        if (words) SC_HIP(hipMemcpyAsync(ix->mask_words.p, allow, words * 4, hipMemcpyHostToDevice, s));
-        dallow = ix->mask_words.as<uint32_t>();
-    }
-    st = search_mmr_locked(ix, dq, Q, k, fetch_k, lambda, dallow, dd, dr);
+    st = search_mmr_locked(ix, io.q, Q, k, fetch_k, lambda, io.allow, io.dist, io.rows);
     if (st) return st;
-    SC_HIP(hipMemcpyAsync(out_dist, dd, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(out_rows, dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    return SC_OK;
+    return sc_fetch_host_locked(ix, io, Q, k, out_dist, out_rows);
 }
 
 extern "C" sc_status sc_index_last_mmr_stats(sc_index* ix, int32_t* fetch_k, int32_t* min_candidates, int64_t* rows_scanned) {

@@ -472,9 +472,7 @@ sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
             // The re-layout needs a second copy of the corpus (246 GB at 10M x 3072).  Without it the rows upserted since the build
             // cannot join their lists -- but they can still be FOUND: extend the position -> row id map over the tail (positions
             // == row ids there, 4 B per row) and answer exhaustively (exact results) until a refresh or a rebuild succeeds.
-            rst = sc_ivf_cover_tail_locked(ix);
-            if (rst) return rst;
-            return sc_search_flat_locked(ix, q_dev, Q, k, out_dist, out_rows);
+            return sc_search_exhaustive_locked(ix, q_dev, Q, k, out_dist, out_rows);
         }
         if (rst) return rst;
     }
@@ -518,23 +516,12 @@ static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t
 exact_probe:
     if (sc_ivf_listmajor_applicable(ix, Q, k, nprobe, batched_applicable(ix, Q, k)))
         return sc_ivf_search_listmajor_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
-    if (ix->perm && ix->perm_rows < ix->n && ix->n > ix->ivf_rows) {  // (a tail behind the lists: the exhaustive paths need every position mapped)
-        const sc_status cst = sc_ivf_cover_tail_locked(ix);
-        if (cst) return cst;
-    }
-    return sc_search_flat_locked(ix, q_dev, Q, k, out_dist, out_rows);
-}
-
-static sc_status check_search_args(sc_index* ix, const void* q, int32_t Q, int32_t k, const void* od, const void* orow) {
-    if (!ix || !q || !od || !orow) return sc_fail(SC_ERR_INVALID, "search: NULL argument");
-    if (Q < 1 || Q > (1 << 20)) return sc_fail(SC_ERR_INVALID, "search: Q=%d out of range", Q);
-    if (k < 1) return sc_fail(SC_ERR_INVALID, "search: top_k must be >= 1 (got %d)", k);
-    return SC_OK;
+    return sc_search_exhaustive_locked(ix, q_dev, Q, k, out_dist, out_rows);  // (a tail behind the lists is scanned as one)
 }
 
 extern "C" sc_status sc_index_search_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist_dev,
                                          int64_t* out_rows_dev) {
-    sc_status st = check_search_args(ix, q_dev, Q, k, out_dist_dev, out_rows_dev);
+    const sc_status st = sc_check_query_args("search", !ix || !q_dev || !out_dist_dev || !out_rows_dev, Q, k, 0);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
     SC_HIP(hipSetDevice(ix->rt->device));
@@ -543,24 +530,14 @@ extern "C" sc_status sc_index_search_dev(sc_index* ix, const float* q_dev, int32
 
 extern "C" sc_status sc_index_search(sc_index* ix, const float* q, int32_t Q, int32_t k, int32_t nprobe, float* out_dist,
                                      int64_t* out_rows) {
-    sc_status st = check_search_args(ix, q, Q, k, out_dist, out_rows);
+    sc_status st = sc_check_query_args("search", !ix || !q || !out_dist || !out_rows, Q, k, 0);
     if (st) return st;
     std::lock_guard<std::mutex> g(ix->mu);
     SC_HIP(hipSetDevice(ix->rt->device));
-    hipStream_t s = ix->rt->stream;
-    const size_t qb = ((size_t)Q * ix->dim * 4 + 15) & ~(size_t)15;
-    const size_t db = ((size_t)Q * k * 4 + 15) & ~(size_t)15;
-    const size_t rb = (size_t)Q * k * 8;
-    st = sc_grow(ix, ix->io, qb + db + rb);
+    sc_host_io io;
+    st = sc_stage_host_locked(ix, q, Q, k, nullptr, 0, &io);
     if (st) return st;
-    float* dq = ix->io.as<float>();
-    float* dd = (float*)(ix->io.as<char>() + qb);
-    int64_t* dr = (int64_t*)(ix->io.as<char>() + qb + db);
-    SC_HIP(hipMemcpyAsync(dq, q, (size_t)Q * ix->dim * 4, hipMemcpyHostToDevice, s));
-    st = sc_search_dev_locked(ix, dq, Q, k, nprobe, dd, dr);
+    st = sc_search_dev_locked(ix, io.q, Q, k, nprobe, io.dist, io.rows);
     if (st) return st;
-    SC_HIP(hipMemcpyAsync(out_dist, dd, (size_t)Q * k * 4, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(out_rows, dr, (size_t)Q * k * 8, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    return SC_OK;
+    return sc_fetch_host_locked(ix, io, Q, k, out_dist, out_rows);
 }

@@ -498,28 +498,14 @@ class MilvusVectorStore:
         if mmr is None and fuse is None and fetch_k is not None:
             raise ValueError("fetch_k is the candidate width of an mmr search: give mmr as well")
         if fuse is not None:
-            top_k = int(top_k)
-            if top_k > self.HYBRID_MAX_FETCH:
-                raise ValueError(f"a hybrid search takes top_k <= {self.HYBRID_MAX_FETCH}, got {top_k}")
-            fetch_k = min(self.HYBRID_MAX_FETCH, max(20, 4 * top_k)) if fetch_k is None else int(fetch_k)
-            if fetch_k > self.HYBRID_MAX_FETCH:
-                raise ValueError(f"a hybrid search takes fetch_k <= {self.HYBRID_MAX_FETCH}, got {fetch_k}")
-            if fetch_k < top_k:
-                raise ValueError(f"fetch_k={fetch_k} is smaller than top_k={top_k}")
+            top_k, fetch_k = self._candidate_widths("a hybrid", top_k, fetch_k, self.HYBRID_MAX_FETCH)
         if mmr is not None:
             if group_by is not None:
                 raise ValueError("mmr together with group_by is not supported")
             lam = float(mmr)
             if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
                 raise ValueError(f"mmr must be within [0, 1], got {mmr!r}")
-            top_k = int(top_k)
-            if top_k > self.MMR_MAX_FETCH:
-                raise ValueError(f"an mmr search takes top_k <= {self.MMR_MAX_FETCH}, got {top_k}")
-            fetch_k = min(self.MMR_MAX_FETCH, max(20, 4 * top_k)) if fetch_k is None else int(fetch_k)
-            if fetch_k > self.MMR_MAX_FETCH:
-                raise ValueError(f"an mmr search takes fetch_k <= {self.MMR_MAX_FETCH}, got {fetch_k}")
-            if fetch_k < top_k:
-                raise ValueError(f"fetch_k={fetch_k} is smaller than top_k={top_k}")
+            top_k, fetch_k = self._candidate_widths("an mmr", top_k, fetch_k, self.MMR_MAX_FETCH)
         q = np.asarray(queries, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.dim:
             raise ValueError(f"query dimension mismatch: collection dim={self.dim}, got shape {q.shape}")
@@ -527,24 +513,38 @@ class MilvusVectorStore:
             raise ValueError(f"hybrid: {q.shape[0]} query vectors but {len(query_texts)} query texts")
         with self._lock:
             flt = self._filter(repos, languages)
+            allow = None if flt is None or flt[1] else flt[0]  # the bitset handed down: none where every row passes
             if fuse is not None:
-                return self._search_hybrid(q, top_k, fetch_k, list(query_texts), fuse, flt)
+                return self._search_hybrid(q, top_k, fetch_k, list(query_texts), fuse, allow)
             if group_by is not None:
-                return self._search_grouped(q, int(top_k), flt, group_by)
+                return self._search_grouped(q, int(top_k), allow, group_by)
             if mmr is not None:
                 ix = self._collection
                 if not hasattr(ix, "search_mmr"):
                     raise NotImplementedError(f"{type(ix).__name__} has no search_mmr(queries, k, fetch_k, lam, allow): this vector index cannot diversify")
-                return ix.search_mmr(q, k=top_k, fetch_k=fetch_k, lam=lam, allow=None if flt is None or flt[1] else flt[0])
-            if flt is None or flt[1]:
+                return ix.search_mmr(q, k=top_k, fetch_k=fetch_k, lam=lam, allow=allow)
+            if allow is None:
                 self._maybe_train()
                 return self._collection.search(q, k=int(top_k), nprobe=self.nprobe)
             ix = self._collection
             if not hasattr(ix, "search_masked"):
                 raise NotImplementedError(f"{type(ix).__name__} has no search_masked(queries, allow, k): this vector index cannot filter")
-            return ix.search_masked(q, flt[0], k=int(top_k))
+            return ix.search_masked(q, allow, k=int(top_k))
 
-    def _search_grouped(self, q: np.ndarray, top_k: int, flt: "Optional[tuple[np.ndarray, bool]]", group_by: str) -> "tuple[np.ndarray, np.ndarray]":
+    @staticmethod
+    def _candidate_widths(what: str, top_k: Any, fetch_k: Any, widest: int) -> "tuple[int, int]":
+        """(top_k, fetch_k) of `what` ("an mmr" / "a hybrid") search as integers, fetch_k defaulted: top_k <= fetch_k <= widest."""
+        top_k = int(top_k)
+        if top_k > widest:
+            raise ValueError(f"{what} search takes top_k <= {widest}, got {top_k}")
+        fetch_k = min(widest, max(20, 4 * top_k)) if fetch_k is None else int(fetch_k)
+        if fetch_k > widest:
+            raise ValueError(f"{what} search takes fetch_k <= {widest}, got {fetch_k}")
+        if fetch_k < top_k:
+            raise ValueError(f"fetch_k={fetch_k} is smaller than top_k={top_k}")
+        return top_k, fetch_k
+
+    def _search_grouped(self, q: np.ndarray, top_k: int, allow: "Optional[np.ndarray]", group_by: str) -> "tuple[np.ndarray, np.ndarray]":
         """The labels of `group_by` reach the index once per (mutation, column), then every grouped search reuses them.  Caller holds the lock."""
         ix = self._collection
         if not (hasattr(ix, "search_grouped") and hasattr(ix, "set_groups")):
@@ -553,7 +553,7 @@ class MilvusVectorStore:
             codes = self._path_codes if group_by == "path" else self._repo_codes
             ix.set_groups(np.ascontiguousarray(codes[: len(self._ids)], dtype=np.int32))
             self._groups_installed = group_by
-        return ix.search_grouped(q, k=top_k, allow=None if flt is None or flt[1] else flt[0])
+        return ix.search_grouped(q, k=top_k, allow=allow)
 
     def _hybrid_options(self, hybrid: Any, query_texts: Any, group_by: Any, mmr: Any) -> "Optional[dict]":
         """None when no hybrid search is asked for, else {c, dense_weight, lexical_weight}; names every conflict."""
@@ -600,7 +600,7 @@ class MilvusVectorStore:
         qw[: ts.size] = idf[ts]
         return qt, qw, int(ts.size)
 
-    def _search_hybrid(self, q: np.ndarray, top_k: int, fetch_k: int, texts: "list[str]", fuse: dict, flt: "Optional[tuple[np.ndarray, bool]]") -> "tuple[np.ndarray, np.ndarray]":
+    def _search_hybrid(self, q: np.ndarray, top_k: int, fetch_k: int, texts: "list[str]", fuse: dict, allow: "Optional[np.ndarray]") -> "tuple[np.ndarray, np.ndarray]":
         """Caller holds the lock.  The df table comes from the device once per mutation."""
         ix = self._collection
         if not (hasattr(ix, "search_hybrid") and hasattr(ix, "set_terms") and hasattr(ix, "lex_stats")):
@@ -619,7 +619,7 @@ class MilvusVectorStore:
         qw = np.stack([t[1] for t in terms])
         nt = np.asarray([t[2] for t in terms], dtype=np.int32)
         return ix.search_hybrid(q, qt, qw, nt, k=top_k, fetch_k=fetch_k, k1=self.BM25_K1, b=self.BM25_B, avgdl=float(avgdl), c=fuse["c"],
-                                dense_weight=fuse["dense_weight"], lexical_weight=fuse["lexical_weight"], allow=None if flt is None or flt[1] else flt[0])
+                                dense_weight=fuse["dense_weight"], lexical_weight=fuse["lexical_weight"], allow=allow)
 
     @staticmethod
     def _name_set(names: Any) -> "Optional[frozenset]":

@@ -291,6 +291,52 @@ def test_hybrid_search(rt, data, X, metric):
     empty.close()
 
 
+@pytest.mark.parametrize("metric", ["IP", "L2"])
+def test_hybrid_on_a_trained_index_with_a_tail(rt, data, X, metric):
+    """A trained IVF_FLAT index with 300 rows appended behind its lists: the hybrid search answers as the reference fusion and as a
+    FLAT twin, host and device pointers alike, and leaves the tail a tail (the probe that follows still reports it)."""
+    import torch
+
+    T, trained, n, k, F = 128, 1000, 1300, 10, 40
+    terms, _, (qt, qw, nt), _ = data[T]
+    avgdl = avgdl_of(terms[:n])
+    Q = orc.synth(NQ, DIM, seed=78)
+    ivf = _native.Index(rt, DIM, metric=metric, kind="IVF_FLAT", nlist=16)
+    ivf.add(X[:trained])
+    ivf.train(niter=3)
+    ivf.add(X[trained:n])
+    ivf.set_terms(terms[:n])
+    twin = index_with_terms(rt, X, terms, n, metric=metric)
+    some = np.random.default_rng(14).random(n) < 0.4
+    some[-5:] = True
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    tq, tt, tw, tn = dev(Q), dev(qt.view(np.int16)), dev(qw), dev(nt)
+    for name, allow in (("none", None), ("40 %", some)):
+        dense = dense_reference(X[:n], Q, F, metric, allow)
+        lex = reference(data, T, n, allow, None if allow is None else "tail " + name)[1][:, :F]
+        want = [lex_ref.rrf(dense[i], lex[i], k, 60, 1.0, 1.0) for i in range(NQ)]
+        want = (np.stack([w[0] for w in want]), np.stack([w[1] for w in want]))
+        words = None if allow is None else dev(_native.pack_allow(allow, n).view(np.int32))
+        for nq in (NQ, 1):
+            what = f"{metric} mask={name} Q={nq}"
+            got = ivf.search_hybrid(Q[:nq], qt[:nq], qw[:nq], nt[:nq], k=k, fetch_k=F, k1=K1, b=B, avgdl=avgdl, allow=allow)
+            check(got, (want[0][:nq], want[1][:nq]), what)
+            assert ivf.last_search_stats()["path"] == "hybrid"
+            check(got, twin.search_hybrid(Q[:nq], qt[:nq], qw[:nq], nt[:nq], k=k, fetch_k=F, k1=K1, b=B, avgdl=avgdl, allow=allow), what + ", the FLAT twin")
+            score = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+            rows = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            ivf.search_hybrid_dev(tq.data_ptr(), nq, k, F, tt.data_ptr(), tw.data_ptr(), tn.data_ptr(), K1, B, avgdl, 60, 1.0, 1.0,
+                                  0 if words is None else words.data_ptr(), 0 if words is None else words.numel(), score.data_ptr(), rows.data_ptr())
+            rt.synchronize()
+            check((score.cpu().numpy(), rows.cpu().numpy()), got, what + ", device pointers")
+    ivf.search(Q[:1], k=k, nprobe=4)  # a probe next: it answers from the lists AND the tail, which the hybrid searches left pending
+    stats = ivf.last_search_stats()
+    assert stats["path"].startswith("ivf") and stats["tail_rows"] == n - trained, stats
+    ivf.close()
+    twin.close()
+
+
 def test_hybrid_dev_pointers_report_a_bad_query(rt, data, X):
     import torch
 
