@@ -189,6 +189,31 @@ sc_status sc_encoder_embed_packed_into(sc_encoder* enc, const int32_t* ids, cons
 sc_status sc_encoder_embed_packed_into_async(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, sc_index* ix,
                                              const int64_t* rows);
 
+/* Pairs (cross-encoder / reranker): the stage after retrieval.  A pair is ONE packed sequence [CLS] question [SEP] passage [SEP]; the
+ * first first_lens[i] tokens of pair i take segment id 0 (type_emb row 0), the rest segment id 1.  The forward is the packed one --
+ * same plan, same GEMMs, same attention over the pair's real length, both pipelines (sc_encoder_set_path applies as for packed
+ * embeds) -- with three differences: the embedding kernels read a per-row segment id that the plan carries next to the positions
+ * (alignment rows and the tail take 0), the output is the last hidden state (after its LayerNorm) of each pair's FIRST row instead
+ * of a mean (the packed pooling kernels with a length of one), and it is never L2-normalised, whatever cfg.normalize says.  The
+ * head then computes, in f32 from f32 weights kept on the device, p = tanh(pooler_w cls + pooler_b) -- or p = cls without a pooler --
+ * and logits = cls_w p + cls_b (pair_head_kernel: 16 pairs per workgroup, f32 MFMA, fixed reduction orders; tanh saturates to +-1
+ * and is finite for every input).  What the logits mean is the model's business: a caller scores with logit[0] (1 label) or
+ * logit[1] - logit[0] (2 labels).
+ * sc_encoder_set_pair_head installs, replaces or (cls_w == NULL) removes the head; pooler_w == NULL = no pooler; the arrays are
+ * copied before it returns.  Embedding calls on the same encoder are not affected by a head.
+ * sc_encoder_score_pairs: ids / offsets as sc_encoder_embed_packed; out_logits [B,num_labels]; out_cls [B,hidden] (the [CLS] rows the
+ * head read) or NULL.  Host pointers; synchronises; shares the two pinned slots and the in-flight rules of the packed embed calls.
+ * SC_ERR_INVALID, with nothing launched and nothing changed: no head installed, a NULL pointer, B outside 1 .. 65536, offsets[0] != 0,
+ * a pair shorter than 2 or longer than 2 048 tokens, or longer than max_pos for models with a position or rotary table,
+ * first_lens[i] outside 1 .. len_i, a second segment (first_lens[i] < len_i) on a model with type_vocab < 2, num_labels outside
+ * 1 .. 2.  SC_ERR_UNSUPPORTED: more than SC_ENCODER_PACKED_MAX_ROWS token rows (size batches with sc_encoder_packed_rows).
+ * Out of scope: CLS-pooled embedding models, heads other than pooler + linear (Electra), more than 2 labels, an asynchronous or
+ * device-pointer form.  ALiBi and rotary models with type_vocab >= 2 run, but no reference pins their result. */
+sc_status sc_encoder_set_pair_head(sc_encoder* enc, const float* pooler_w /*[H,H]*/, const float* pooler_b /*[H]*/,
+                                   const float* cls_w /*[num_labels,H]*/, const float* cls_b /*[num_labels]*/, int32_t num_labels);
+sc_status sc_encoder_score_pairs(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, const int32_t* first_lens, int32_t B,
+                                 float* out_logits, float* out_cls);
+
 /* ----------------------------------------------------------------- tokenizer ---- */
 typedef struct sc_tokenizer sc_tokenizer;
 /* Host-side WordPiece tokenizer (BERT scheme), the step the reference leaves to its provider's library (raw strings
@@ -303,6 +328,15 @@ sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F,
 sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* ids, int32_t tokens, int32_t S, int32_t H, int32_t vocab, int32_t max_pos,
                         const float* wemb, const float* pemb, const float* temb, const float* gamma, const float* beta, float eps,
                         int32_t tokens_pad, int32_t slots, float* rows, float* stats);
+/* The kernels of the pair path on their own (tests/test_rerank_gpu.py).  sc_diag_embed_pairs: sc_diag_embed with a position and a
+ * segment id per row -- pos / types [tokens] int32, clamped into the tables, temb [type_vocab,H]; rows and stats as there.
+ * sc_diag_pair_head: pair_head_kernel on f32 data as they are: cls [B,H], pooler_w [H,H] / pooler_b [H] (both NULL: no pooler),
+ * cls_w [num_labels,H], cls_b [num_labels] -> out_logits [B,num_labels].  B 1 .. 65536, H a multiple of 16 up to 2 048, num_labels 1 or 2. */
+sc_status sc_diag_embed_pairs(sc_runtime* rt, int32_t ln, const int32_t* ids, const int32_t* pos, const int32_t* types, int32_t tokens, int32_t H,
+                              int32_t vocab, int32_t max_pos, int32_t type_vocab, const float* wemb, const float* pemb, const float* temb,
+                              const float* gamma, const float* beta, float eps, int32_t tokens_pad, int32_t slots, float* rows, float* stats);
+sc_status sc_diag_pair_head(sc_runtime* rt, const float* cls, int32_t B, int32_t H, const float* pooler_w, const float* pooler_b,
+                            const float* cls_w, const float* cls_b, int32_t num_labels, float* out_logits);
 
 /* -------------------------------------------------------------- vector index ---- */
 

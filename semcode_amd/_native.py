@@ -70,6 +70,11 @@ SIGNATURES = {
     "sc_encoder_wait": (C.c_int32, [C.c_void_p]),
     "sc_encoder_packed_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "sc_encoder_embed_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sc_encoder_set_pair_head": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32]),
+    "sc_encoder_score_pairs": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_embed_pairs": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32,
+                                                                                                                       C.c_void_p, C.c_void_p]),
+    "sc_diag_pair_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "sc_encoder_embed_packed_into": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sc_encoder_embed_packed_into_async": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_tokenizer_create": (C.c_int32, [C.c_char_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -792,6 +797,7 @@ class Encoder:
         self.rt = rt
         self.hidden = c["hidden"]
         self.max_pos = c["max_pos"]
+        self.num_labels = 0  # of the installed pair head (set_pair_head)
         self._h = C.c_void_p()
         need = C.c_int64()
         _check(lib().sc_encoder_blob_bytes(C.byref(self.cfg), C.byref(need)))
@@ -900,6 +906,37 @@ class Encoder:
         _check(lib().sc_encoder_embed_packed_into(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B, index.handle,
                                                   rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p) if want_host else None))
         return out
+
+    # ---- pairs (cross-encoder): [CLS] question [SEP] passage [SEP] as one packed sequence, segment ids from first_lens
+    def set_pair_head(self, cls_w, cls_b, pooler_w=None, pooler_b=None) -> None:
+        """Install (or replace) the classification head: cls_w [num_labels, H], cls_b [num_labels], optionally the pooler
+        (pooler_w [H, H], pooler_b [H]; tanh).  cls_w None removes the head."""
+        if cls_w is None:
+            _check(lib().sc_encoder_set_pair_head(self.handle, None, None, None, None, 0))
+            self.num_labels = 0
+            return
+        cls_w, cls_b = _f32(cls_w).reshape(-1, self.hidden), _f32(cls_b).reshape(-1)
+        if cls_b.shape[0] != cls_w.shape[0]:
+            raise ValueError("cls_w must be [num_labels, hidden] and cls_b [num_labels]")
+        if pooler_w is not None:
+            pooler_w, pooler_b = _f32(pooler_w), _f32(pooler_b)
+            if pooler_w.shape != (self.hidden, self.hidden) or pooler_b.shape != (self.hidden,):
+                raise ValueError("pooler_w must be [hidden, hidden] and pooler_b [hidden]")
+        _check(lib().sc_encoder_set_pair_head(self.handle, _ptr(pooler_w), _ptr(pooler_b) if pooler_w is not None else None, _ptr(cls_w), _ptr(cls_b),
+                                              int(cls_w.shape[0])))
+        self.num_labels = int(cls_w.shape[0])
+
+    def score_pairs(self, ids_flat, offsets, first_lens, want_cls: bool = False):
+        """Packed pairs -> logits [B, num_labels] (and the [CLS] rows [B, hidden] the head read, with want_cls).  first_lens [B]: the
+        tokens of each pair that take segment id 0."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        first_lens = np.ascontiguousarray(first_lens, dtype=np.int32)
+        if first_lens.shape != (B,):
+            raise ValueError("first_lens must be [B]")
+        logits = np.empty((B, max(1, self.num_labels)), dtype=np.float32)
+        cls = np.empty((B, self.hidden), dtype=np.float32) if want_cls else None
+        _check(lib().sc_encoder_score_pairs(self.handle, _ptr(ids_flat), _ptr(offsets), _ptr(first_lens), B, _ptr(logits), _ptr(cls)))
+        return (logits, cls) if want_cls else logits
 
     def embed_ids_dev(self, ids_ptr: int, lens_ptr: int, B: int, S: int, out_ptr: int) -> None:
         _check(lib().sc_encoder_embed_ids_dev(self.handle, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), int(B), int(S), C.c_void_p(out_ptr)))
@@ -1217,3 +1254,35 @@ def topk_merge_host(metric: str, dist: np.ndarray, rows: np.ndarray) -> tuple[np
     _check(lib().sc_topk_merge_host(METRICS[metric], lists, Q, k, d.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p),
                                     od.ctypes.data_as(C.c_void_p), orow.ctypes.data_as(C.c_void_p)))
     return od, orow
+
+
+def diag_embed_pairs(rt: Runtime, ids, pos, types, wemb, pemb, temb, max_pos: int, ln=None, tokens_pad: int = 0, slots: int = 1):
+    """The typed embedding kernels on ids / pos / types [tokens]: diag_embed with a position and a segment id per row; temb [type_vocab, H]."""
+    ids, pos, types = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (ids, pos, types))
+    tokens = ids.size
+    wemb, temb = _f32(wemb), _f32(temb)
+    pemb = None if pemb is None else _f32(pemb)
+    vocab, H = wemb.shape
+    if ln is None:
+        tp = max(int(tokens_pad), tokens)
+        rows, stats = np.empty((tp, H), np.float32), np.empty((slots, tp, 2), np.float32)
+        _check(lib().sc_diag_embed_pairs(rt.handle, 0, _ptr(ids), _ptr(pos), _ptr(types), tokens, H, vocab, int(max_pos), temb.shape[0], _ptr(wemb), _ptr(pemb),
+                                         _ptr(temb), None, None, 0.0, tp, int(slots), _ptr(rows), _ptr(stats)))
+        return rows, stats
+    gamma, beta = _f32(ln[0]), _f32(ln[1])
+    rows = np.empty((tokens, H), np.float32)
+    _check(lib().sc_diag_embed_pairs(rt.handle, 1, _ptr(ids), _ptr(pos), _ptr(types), tokens, H, vocab, int(max_pos), temb.shape[0], _ptr(wemb), _ptr(pemb),
+                                     _ptr(temb), _ptr(gamma), _ptr(beta), float(ln[2]), 0, 0, _ptr(rows), None))
+    return rows
+
+
+def diag_pair_head(rt: Runtime, cls, cls_w, cls_b, pooler_w=None, pooler_b=None) -> np.ndarray:
+    """pair_head_kernel on cls [B, H]: logits [B, num_labels] = cls_w p + cls_b, p = tanh(pooler_w cls + pooler_b) or cls."""
+    cls, cls_w, cls_b = _f32(cls), _f32(cls_w), _f32(cls_b)
+    B, H = cls.shape
+    nl = cls_w.shape[0]
+    pooler_w = None if pooler_w is None else _f32(pooler_w)
+    pooler_b = None if pooler_w is None else _f32(pooler_b)
+    out = np.empty((B, nl), np.float32)
+    _check(lib().sc_diag_pair_head(rt.handle, _ptr(cls), B, H, _ptr(pooler_w), _ptr(pooler_b), _ptr(cls_w), _ptr(cls_b), nl, _ptr(out)))
+    return out

@@ -72,6 +72,17 @@ void sc_launch_mean_pool_packed(const void* x, const int32_t* starts, const int3
 void sc_launch_mean_pool_ln_packed(const void* y, const float* stats, int slots, int tokens_pad, const float* gamma, const float* beta, float eps,
                                    const int32_t* starts, const int32_t* lens, int B, int H, float* out, hipStream_t s);
 
+// ---- encoder_pairs.hip: the packed embedding with a per-row segment id (types [rows], clamped into type_emb's type_vocab rows), and
+// the classification head of a cross-encoder: cls [B,H] f32 -> logits [B,num_labels] = Wc p + bc, p = tanh(Wp cls + bp), or p = cls when
+// Wp is NULL.  Wp [H,H], bp [H], Wc [num_labels,H], bc [num_labels] f32 on the device; H a multiple of 16, <= 2048; num_labels 1 or 2.
+void sc_launch_embed_ln_pairs(const int32_t* ids, const int32_t* pos, const int32_t* types, int tokens, int H, int vocab, int max_pos, int type_vocab,
+                              const float* wemb, const float* pemb, const float* temb, const float* g, const float* b, float eps, void* out, hipStream_t s);
+void sc_launch_embed_raw_pairs(const int32_t* ids, const int32_t* pos, const int32_t* types, int tokens, int tokens_pad, int H, int vocab, int max_pos,
+                               int type_vocab, const float* wemb, const float* pemb, const float* temb, void* out, float* stats, int slots, hipStream_t s);
+bool sc_pair_head_supported(int H, int num_labels);
+void sc_launch_pair_head(const float* cls, int B, int H, const float* Wp, const float* bp, const float* Wc, const float* bc, int num_labels, float* logits,
+                         hipStream_t s);
+
 // ---- sc_encoder.cpp: the attention work items of packed sequences (host): per sequence one item for every 8 query blocks of 32 rows
 // (class 0) or one item (classes 1, 2), written as {start, len, first query block, 0} in class order.  items must hold
 // sc_packed_items_cap(rows, B) items.

@@ -31,6 +31,19 @@ struct PosArray {
         return p >= max_pos ? max_pos - 1 : p;
     }
 };
+// type_emb row of token row r: TypeZero -- row 0 (every embedding model); TypeArray -- a per-row segment id, clamped into the table
+// (encoder_pairs.hip: the two halves of a cross-encoder's pair)
+struct TypeZero {
+    __device__ __forceinline__ int operator()(int64_t) const { return 0; }
+};
+struct TypeArray {
+    const int32_t* types;
+    int type_vocab;
+    __device__ __forceinline__ int operator()(int64_t r) const {
+        const int t = types[r];
+        return t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+    }
+};
 // the rows of sequence b: rectangles -- b * S .., lens clamped to 1 .. S; packed -- starts[b] ..
 struct RectRows {
     const int32_t* lens;
@@ -50,10 +63,11 @@ struct PackedRows {
     __device__ __forceinline__ size_t first(int b) const { return (size_t)starts[b]; }
 };
 
-template <class POS>
+template <class POS, class TYPE = TypeZero>
 static __device__ __forceinline__ void embed_ln_rows(const int32_t* __restrict__ ids, int tokens, POS pos_of, int H, int vocab, int max_pos,
                                                      const float* __restrict__ wemb, const float* __restrict__ pemb, const float* __restrict__ temb,
-                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, bf16_t* __restrict__ out) {
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, bf16_t* __restrict__ out,
+                                                     TYPE type_of = TYPE()) {
     const int lane = threadIdx.x & 63;
     const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tok >= tokens) return;
@@ -63,6 +77,7 @@ static __device__ __forceinline__ void embed_ln_rows(const int32_t* __restrict__
     pos = pos >= max_pos ? max_pos - 1 : pos;
     const float* we = wemb + (size_t)id * H;
     const float* pe = pemb ? pemb + (size_t)pos * H : nullptr;  // NULL: no position table (ALiBi models)
+    const float* te = temb + (size_t)type_of(tok) * H;
     f32x4 v[LN_MAXJ];
     float sum = 0.f;
 #pragma unroll
@@ -71,7 +86,7 @@ static __device__ __forceinline__ void embed_ln_rows(const int32_t* __restrict__
         if (k0 < H) {
             v[j] = *reinterpret_cast<const f32x4*>(we + k0);
             if (pe) v[j] += *reinterpret_cast<const f32x4*>(pe + k0);
-            v[j] += *reinterpret_cast<const f32x4*>(temb + k0);
+            v[j] += *reinterpret_cast<const f32x4*>(te + k0);
             sum += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
         }
     }
@@ -104,10 +119,10 @@ static __device__ __forceinline__ void embed_ln_rows(const int32_t* __restrict__
     }
 }
 
-template <class POS>
+template <class POS, class TYPE = TypeZero>
 static __device__ __forceinline__ void embed_raw_rows(const int32_t* __restrict__ ids, int tokens, int tokens_pad, POS pos_of, int H, int vocab, int max_pos,
                                                       const float* __restrict__ wemb, const float* __restrict__ pemb, const float* __restrict__ temb,
-                                                      bf16_t* __restrict__ out, float* __restrict__ stats, int slots) {
+                                                      bf16_t* __restrict__ out, float* __restrict__ stats, int slots, TYPE type_of = TYPE()) {
     const int lane = threadIdx.x & 63;
     const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tok >= tokens_pad) return;
@@ -119,6 +134,7 @@ static __device__ __forceinline__ void embed_raw_rows(const int32_t* __restrict_
         pos = pos >= max_pos ? max_pos - 1 : pos;
         const float* we = wemb + (size_t)id * H;
         const float* pe = pemb ? pemb + (size_t)pos * H : nullptr;
+        const float* te = temb + (size_t)type_of(tok) * H;
         bf16_t* o = out + (size_t)tok * H;
 #pragma unroll
         for (int j = 0; j < LN_MAXJ; ++j) {
@@ -126,7 +142,7 @@ static __device__ __forceinline__ void embed_raw_rows(const int32_t* __restrict_
             if (k0 < H) {
                 f32x4 v = *reinterpret_cast<const f32x4*>(we + k0);
                 if (pe) v += *reinterpret_cast<const f32x4*>(pe + k0);
-                v += *reinterpret_cast<const f32x4*>(temb + k0);
+                v += *reinterpret_cast<const f32x4*>(te + k0);
                 u16x4 r;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {

@@ -9,6 +9,8 @@
 //   -> X1 = LN(Y) -> Hm = gelu(X1 W1^T + b1) -> Y2 = Hm W2^T + b2 + X1 -> X = LN(Y2); pooled = masked mean.
 // Activations bf16 in HBM ([tokens, H] row-major, tokens padded to 128), weights bf16 [out, in],
 // biases / LayerNorm parameters / embedding tables f32.
+// Pairs of a cross-encoder (sc_encoder_set_pair_head / sc_encoder_score_pairs) run the packed forward with a segment id per row and
+// take each pair's [CLS] row instead of a mean; the head on those rows is encoder_pairs.hip's.
 // The single-kernel harnesses (sc_diag_*) are in sc_encoder_diag.cpp, the device entry points in encoder_ops.h.
 #include <cmath>
 #include <cstring>
@@ -70,6 +72,12 @@ struct sc_encoder {
         bool busy = false;
     } pin[2];
     int pin_next = 0;
+    // the pair head of a cross-encoder (sc_encoder_set_pair_head): one device allocation Wp [H,H] | bp [H] | Wc [labels,H] | bc [labels],
+    // all f32; head_wp NULL = no pooler, head_wc NULL = no head installed
+    char* head = nullptr;
+    float *head_wp = nullptr, *head_bp = nullptr, *head_wc = nullptr, *head_bc = nullptr;
+    int head_labels = 0;
+    float* logits = nullptr;  // [ws_batch][2] (workspace)
     std::mutex mu;
 };
 
@@ -82,12 +90,17 @@ struct PackedLayout {
     const int32_t *pos, *starts, *items;
     int nitems[3];
     int rows;  // token rows in use = the sum of ceil32(len_i); rows .. M are the tail
+    // pairs of a cross-encoder (sc_encoder_score_pairs): the segment id of every row.  Such a batch is embedded with its types, the
+    // lens the forward gets are ones (pooling then returns the [CLS] row; attention reads the real lengths from its items) and
+    // the output is never L2-normalised.  NULL: texts to embed.
+    const int32_t* types = nullptr;
 };
 // The plan of one packed call, laid out alike in pinned host staging and in e->plan (M token rows, B sequences): monotone in both, so
 // a call's plan fits the buffer of any larger workspace
+// (pairs: the segment id of every row and a length of one per pair come behind the rest, so that a plan without them lies as before).
 struct PlanOffsets {
-    size_t ids, pos, starts, lens, items, total;
-    PlanOffsets(size_t M, size_t B) {
+    size_t ids, pos, starts, lens, items, types = 0, ones = 0, total;
+    PlanOffsets(size_t M, size_t B, bool pairs = false) {
         size_t u = 0;
         auto take = [&](size_t bytes) { const size_t at = u; u += sc_align256(bytes); return at; };
         ids = take(M * 4);
@@ -95,6 +108,10 @@ struct PlanOffsets {
         starts = take(B * 4);
         lens = take(B * 4);
         items = take((size_t)sc_packed_items_cap((int64_t)M, (int64_t)B) * 16);
+        if (pairs) {
+            types = take(M * 4);
+            ones = take(B * 4);
+        }
         total = u;
     }
 };
@@ -336,6 +353,7 @@ extern "C" sc_status sc_encoder_destroy(sc_encoder* e) {
     hipFree(e->params);
     hipFree(e->ws);
     hipFree(e->splitk);
+    hipFree(e->head);
     for (auto& slot : e->pin) {
         if (slot.host) hipHostFree(slot.host);
         if (slot.done) hipEventDestroy(slot.done);
@@ -358,8 +376,9 @@ static void layout_ws(sc_encoder* e, Arena& a, size_t tokens, size_t nb) {
     e->hg = ffn_gated(e->cfg) ? a.bf16(tokens * F) : nullptr;
     e->ids = (int32_t*)a.take(tokens * 4);
     e->lens = (int32_t*)a.take(nb * 4);
-    e->plan = (char*)a.take(PlanOffsets(tokens, nb).total);
+    e->plan = (char*)a.take(PlanOffsets(tokens, nb, true).total);
     e->pooled = a.f32(nb * H);
+    e->logits = a.f32(nb * 2);
     e->stat_a = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
     e->stat_b = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
     e->fin_a = e->foldable ? a.f32(tokens * 2) : nullptr;
@@ -398,7 +417,7 @@ static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int 
     else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M);
 }
 static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
-    if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, e->cfg.normalize, out_dev, s);
+    if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, pk->types ? 0 : e->cfg.normalize, out_dev, s);
     else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, e->cfg.normalize, out_dev, s);
 }
 
@@ -427,7 +446,9 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !gated && ffn_blocked_enabled();
     const bool rope = c.pos_type == 2, rope_fused = rope && !pk && (g_rope_fused < 0 ? ROPE_FUSED_DEFAULT : g_rope_fused) != 0;
-    if (pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
+    if (pk && pk->types)
+        sc_launch_embed_raw_pairs(ids_dev, pk->pos, pk->types, tokens, M, H, c.vocab, c.max_pos, c.type_vocab, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
+    else if (pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
     else sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
@@ -462,7 +483,7 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
         });
     }
     const LayerW& last = e->layers[c.layers - 1];
-    if (c.normalize) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
+    if (c.normalize && !(pk && pk->types)) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
         sc_launch_layernorm(e->x, tokens, H, last.ln2g, last.ln2b, c.ln_eps, e->x1, s);
         launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
     } else if (pk) {
@@ -499,7 +520,9 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     // in between), and only when F divides into 256-column tiles.
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !sk && !gated && (F % 256) == 0 && (H % 256) == 0 && ffn_blocked_enabled();
-    if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    if (pk && pk->types)
+        sc_launch_embed_ln_pairs(ids_dev, pk->pos, pk->types, tokens, H, c.vocab, c.max_pos, c.type_vocab, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    else if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     else sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
@@ -690,10 +713,12 @@ extern "C" sc_status sc_encoder_packed_rows(sc_encoder* e, const int64_t* offset
 // Plans the layout of host ids / offsets into `slot` (idle, the caller waited for it), uploads it and runs the forward into e->pooled.
 // index_rows (NULL or [B]) are copied behind the plan: *rows_out points at the copy.  Caller holds e->mu and has validated the
 // offsets (`used` = check_packed_offsets' row count); nothing is synchronised.
+// first_lens (NULL or [B], validated): the batch holds the pairs of a cross-encoder -- the first first_lens[i] rows of pair i take segment
+// id 0, the rest of the pair 1, and e->pooled receives the last hidden state of every pair's first row.
 static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, int64_t used, sc_encoder::PinSlot& slot,
-                                     const int64_t* index_rows, const int64_t** rows_out) {
+                                     const int64_t* index_rows, const int64_t** rows_out, const int32_t* first_lens = nullptr) {
     const int64_t M = (used + 255) / 256 * 256;
-    const PlanOffsets po((size_t)M, (size_t)B);
+    const PlanOffsets po((size_t)M, (size_t)B, first_lens != nullptr);
     sc_status st = pin_slot_reserve(slot, po.total + (size_t)B * 8);
     if (st) return st;
     int32_t* h_ids = (int32_t*)(slot.host + po.ids);
@@ -712,6 +737,15 @@ static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const in
         for (int64_t j = 0; j < span; ++j) h_pos[row + j] = (int32_t)j;  // (the kernels clamp an alignment row's position into the table)
         row += span;
     }
+    if (first_lens) {
+        int32_t* h_types = (int32_t*)(slot.host + po.types);
+        int32_t* h_ones = (int32_t*)(slot.host + po.ones);
+        memset(h_types, 0, (size_t)M * 4);  // alignment rows and the tail take type 0
+        for (int32_t i = 0; i < B; ++i) {
+            for (int32_t j = first_lens[i]; j < h_lens[i]; ++j) h_types[h_starts[i] + j] = 1;
+            h_ones[i] = 1;
+        }
+    }
     PackedLayout pk{};
     sc_packed_items(h_starts, h_lens, B, h_items, pk.nitems);
     if (index_rows) {
@@ -726,7 +760,8 @@ static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const in
     pk.starts = (const int32_t*)(e->plan + po.starts);
     pk.items = (const int32_t*)(e->plan + po.items);
     pk.rows = (int)used;
-    return forward_locked(e, (const int32_t*)(e->plan + po.ids), (const int32_t*)(e->plan + po.lens), B, 0, e->pooled, &pk);
+    if (first_lens) pk.types = (const int32_t*)(e->plan + po.types);
+    return forward_locked(e, (const int32_t*)(e->plan + po.ids), (const int32_t*)(e->plan + (first_lens ? po.ones : po.lens)), B, 0, e->pooled, &pk);
 }
 
 static sc_status check_packed_into_args(sc_encoder* e, const void* ids, const int64_t* offsets, int32_t B, sc_index* ix, const int64_t* rows, const char* who,
@@ -804,6 +839,99 @@ extern "C" sc_status sc_encoder_embed_packed_into_async(sc_encoder* e, const int
     SC_HIP(hipEventRecord(slot.done, e->rt->stream));
     slot.busy = true;
     e->pin_next ^= 1;
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------ pairs (cross-encoder / reranker)
+extern "C" sc_status sc_encoder_set_pair_head(sc_encoder* e, const float* pooler_w, const float* pooler_b, const float* cls_w, const float* cls_b,
+                                              int32_t num_labels) {
+    if (!e) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pair_head: NULL encoder");
+    const size_t H = (size_t)e->cfg.hidden;
+    if (cls_w) {
+        if (num_labels < 1 || num_labels > 2) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pair_head: num_labels %d outside 1 .. 2", num_labels);
+        if (!cls_b) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pair_head: cls_b is NULL");
+        if (pooler_w && !pooler_b) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pair_head: pooler_b is NULL");
+        if (!sc_pair_head_supported((int)H, num_labels)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_set_pair_head: hidden %d must be a multiple of 16, at most 2048", (int)H);
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    hipStream_t s = e->rt->stream;
+    char* fresh = nullptr;
+    Arena a;
+    float *wp = nullptr, *bp = nullptr, *wc = nullptr, *bc = nullptr;
+    auto lay = [&] {
+        wp = pooler_w ? a.f32(H * H) : nullptr;
+        bp = pooler_w ? a.f32(H) : nullptr;
+        wc = a.f32((size_t)num_labels * H);
+        bc = a.f32((size_t)num_labels);
+    };
+    if (cls_w) {
+        lay();  // measure
+        hipError_t he = hipMalloc((void**)&fresh, a.used);
+        if (he != hipSuccess) return sc_fail(SC_ERR_NOMEM, "hipMalloc pair head (%zu B) failed: %s", a.used, hipGetErrorString(he));
+        a = Arena{fresh};
+        lay();  // place
+        hipError_t up = hipSuccess;
+        auto put = [&](float* d, const float* src, size_t n) {
+            if (up == hipSuccess) up = hipMemcpyAsync(d, src, n * 4, hipMemcpyHostToDevice, s);
+        };
+        if (pooler_w) {
+            put(wp, pooler_w, H * H);
+            put(bp, pooler_b, H);
+        }
+        put(wc, cls_w, (size_t)num_labels * H);
+        put(bc, cls_b, (size_t)num_labels);
+        if (up == hipSuccess) up = hipStreamSynchronize(s);  // the caller's arrays are free on return
+        if (up != hipSuccess) {
+            hipFree(fresh);
+            return sc_fail(SC_ERR_HIP, "pair head upload failed: %s", hipGetErrorString(up));
+        }
+    } else {
+        SC_HIP(hipStreamSynchronize(s));  // nothing may still read the head that goes
+    }
+    hipFree(e->head);
+    e->head = fresh;
+    e->head_wp = wp;
+    e->head_bp = bp;
+    e->head_wc = cls_w ? wc : nullptr;
+    e->head_bc = cls_w ? bc : nullptr;
+    e->head_labels = cls_w ? num_labels : 0;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, const int64_t* offsets, const int32_t* first_lens, int32_t B,
+                                            float* out_logits, float* out_cls) {
+    const char* who = "sc_encoder_score_pairs";
+    if (!e || !ids || !offsets || !first_lens || !out_logits) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    int64_t used = 0;
+    sc_status st = check_packed_offsets(e, offsets, B, who, &used);
+    if (st) return st;
+    for (int32_t i = 0; i < B; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (len < 2) return sc_fail(SC_ERR_INVALID, "%s: pair %d has %lld token(s) (a pair needs at least 2)", who, i, (long long)len);
+        if (first_lens[i] < 1 || first_lens[i] > len)
+            return sc_fail(SC_ERR_INVALID, "%s: first_lens[%d] = %d outside 1 .. %lld (the pair's length)", who, i, first_lens[i], (long long)len);
+        if (first_lens[i] < len && e->cfg.type_vocab < 2)
+            return sc_fail(SC_ERR_INVALID, "%s: pair %d has a second segment, the model's type_vocab is %d (needs 2)", who, i, e->cfg.type_vocab);
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->head_wc) return sc_fail(SC_ERR_INVALID, "%s: no pair head installed (sc_encoder_set_pair_head)", who);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);
+    if (st) return st;
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, nullptr, nullptr, first_lens);
+    hipStream_t s = e->rt->stream;
+    if (st) {
+        hipStreamSynchronize(s);  // the slot's upload may be in flight
+        return st;
+    }
+    const int H = e->cfg.hidden, nl = e->head_labels;
+    sc_launch_pair_head(e->pooled, B, H, e->head_wp, e->head_bp, e->head_wc, e->head_bc, nl, e->logits, s);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(out_logits, e->logits, (size_t)B * nl * 4, hipMemcpyDeviceToHost, s));
+    if (out_cls) SC_HIP(hipMemcpyAsync(out_cls, e->pooled, (size_t)B * H * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }
 

@@ -456,3 +456,63 @@ extern "C" sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* id
     }
     return download_bf16(dout.p, nrows * H, rows, s);
 }
+
+// The typed embedding kernels of encoder_pairs.hip: sc_diag_embed with a position and a segment id per row (pos / types [tokens]) instead
+// of token % S and type 0; temb [type_vocab, H].
+extern "C" sc_status sc_diag_embed_pairs(sc_runtime* rt, int32_t ln, const int32_t* ids, const int32_t* pos, const int32_t* types, int32_t tokens, int32_t H,
+                                         int32_t vocab, int32_t max_pos, int32_t type_vocab, const float* wemb, const float* pemb, const float* temb,
+                                         const float* gamma, const float* beta, float eps, int32_t tokens_pad, int32_t slots, float* rows, float* stats) {
+    if (!rt || !ids || !pos || !types || !wemb || !temb || !rows || tokens < 1 || vocab < 1 || max_pos < 1 || type_vocab < 1)
+        return sc_fail(SC_ERR_INVALID, "sc_diag_embed_pairs: bad argument");
+    if (H < 4 || (H % 4) || H > 2048) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_embed_pairs: H must be a multiple of 4, <= 2048");
+    if (ln && (!gamma || !beta || !(eps > 0.f))) return sc_fail(SC_ERR_INVALID, "sc_diag_embed_pairs: the LayerNorm form needs gamma, beta, eps");
+    if (!ln && (!stats || tokens_pad < tokens || slots < 1 || slots > 64))
+        return sc_fail(SC_ERR_INVALID, "sc_diag_embed_pairs: the raw form needs stats, tokens_pad >= tokens, 1 <= slots <= 64");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf di, dpo, dty, dw, dp, dt, dg, db, dout, dst;
+    SC_TRY(upload(ids, (size_t)tokens * 4, di, s));
+    SC_TRY(upload(pos, (size_t)tokens * 4, dpo, s));
+    SC_TRY(upload(types, (size_t)tokens * 4, dty, s));
+    SC_TRY(upload(wemb, (size_t)vocab * H * 4, dw, s));
+    if (pemb) SC_TRY(upload(pemb, (size_t)max_pos * H * 4, dp, s));
+    SC_TRY(upload(temb, (size_t)type_vocab * H * 4, dt, s));
+    const int64_t nrows = ln ? tokens : tokens_pad;
+    SC_TRY(alloc_nan(dout, (size_t)nrows * H * 2, s));
+    if (ln) {
+        SC_TRY(upload(gamma, (size_t)H * 4, dg, s));
+        SC_TRY(upload(beta, (size_t)H * 4, db, s));
+        sc_launch_embed_ln_pairs((const int32_t*)di.p, (const int32_t*)dpo.p, (const int32_t*)dty.p, tokens, H, vocab, max_pos, type_vocab, (const float*)dw.p,
+                                 pemb ? (const float*)dp.p : nullptr, (const float*)dt.p, (const float*)dg.p, (const float*)db.p, eps, dout.p, s);
+    } else {
+        SC_TRY(alloc_nan(dst, (size_t)slots * tokens_pad * 8, s));
+        sc_launch_embed_raw_pairs((const int32_t*)di.p, (const int32_t*)dpo.p, (const int32_t*)dty.p, tokens, tokens_pad, H, vocab, max_pos, type_vocab,
+                                  (const float*)dw.p, pemb ? (const float*)dp.p : nullptr, (const float*)dt.p, dout.p, (float*)dst.p, slots, s);
+        SC_TRY(download(dst.p, (size_t)slots * tokens_pad * 8, stats, s));
+    }
+    return download_bf16(dout.p, nrows * H, rows, s);
+}
+
+// pair_head_kernel on host f32 data, as they are (nothing is rounded): cls [B,H], pooler_w [H,H] / pooler_b [H] or both NULL,
+// cls_w [num_labels,H], cls_b [num_labels] -> out_logits [B,num_labels].
+extern "C" sc_status sc_diag_pair_head(sc_runtime* rt, const float* cls, int32_t B, int32_t H, const float* pooler_w, const float* pooler_b, const float* cls_w,
+                                       const float* cls_b, int32_t num_labels, float* out_logits) {
+    if (!rt || !cls || !cls_w || !cls_b || !out_logits || (pooler_w && !pooler_b)) return sc_fail(SC_ERR_INVALID, "sc_diag_pair_head: NULL argument");
+    if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "sc_diag_pair_head: batch %d out of range", B);
+    if (num_labels < 1 || num_labels > 2) return sc_fail(SC_ERR_INVALID, "sc_diag_pair_head: num_labels %d outside 1 .. 2", num_labels);
+    if (!sc_pair_head_supported(H, num_labels)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_pair_head: H must be a multiple of 16, <= 2048 (got %d)", H);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf dx, dwp, dbp, dwc, dbc, dout;
+    SC_TRY(upload(cls, (size_t)B * H * 4, dx, s));
+    if (pooler_w) {
+        SC_TRY(upload(pooler_w, (size_t)H * H * 4, dwp, s));
+        SC_TRY(upload(pooler_b, (size_t)H * 4, dbp, s));
+    }
+    SC_TRY(upload(cls_w, (size_t)num_labels * H * 4, dwc, s));
+    SC_TRY(upload(cls_b, (size_t)num_labels * 4, dbc, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * num_labels * 4, s));
+    sc_launch_pair_head((const float*)dx.p, B, H, pooler_w ? (const float*)dwp.p : nullptr, pooler_w ? (const float*)dbp.p : nullptr, (const float*)dwc.p,
+                        (const float*)dbc.p, num_labels, (float*)dout.p, s);
+    return download(dout.p, (size_t)B * num_labels * 4, out_logits, s);
+}

@@ -26,7 +26,7 @@ from .tokenizer import HashTokenizer, WordPieceTokenizer, pack
 
 log = logging.getLogger(__name__)
 
-__all__ = ["EmbeddingPayload", "EmbeddingProviderFactory", "MI355XEmbeddings"]
+__all__ = ["EmbeddingPayload", "EmbeddingProviderFactory", "MI355XEmbeddings", "create_reranker"]
 
 MI355X_PROVIDER_NAMES = {"mi355x", "hip", "rocm"}
 
@@ -402,3 +402,15 @@ class EmbeddingProviderFactory:
             return LlamaCppEmbeddings(**llama_kwargs)
 
         raise NotImplementedError(f"Embedding provider not yet supported: {provider_name}")
+
+
+def create_reranker(model: "str | None" = None, **kwargs: Any) -> Any:
+    """The cross-encoder for `Retriever(reranker=...)`: an MI355XReranker on settings.mi355x_reranker_path (or `model`), None when
+    neither is set -- reranking is opt-in, the reference's pipeline has no such stage."""
+    path = model or getattr(_resolve_settings(), "mi355x_reranker_path", None)
+    if not path:
+        return None
+    from .reranker import MI355XReranker
+
+    log.info("initializing_mi355x_reranker model=%s", path)
+    return MI355XReranker(path, **kwargs)

@@ -56,13 +56,28 @@ def _top_k() -> int:
     return max(1, int(getattr(_resolve_settings(), "rag_max_context_sources", 5)))
 
 
+def _rerank_fetch_k(fetch_k: Optional[int], top_k: int) -> int:
+    """Hits the store is asked for when a reranker re-orders them: fetch_k or settings.mi355x_rerank_fetch_k, at least top_k."""
+    k = fetch_k if fetch_k is not None else getattr(_resolve_settings(), "mi355x_rerank_fetch_k", 40)
+    return max(int(k), top_k)
+
+
+def _apply_scores(documents: List[Dict[str, Any]], scores: Any, top_k: int) -> List[Dict[str, Any]]:
+    """Documents in retrieval order + one reranker score each -> the top_k by score, ties by retrieval rank; `score` becomes the
+    reranker's, `retrieval_score` keeps the store's."""
+    order = sorted(range(len(documents)), key=lambda i: (-float(scores[i]), i))[:top_k]
+    return [dict(documents[i], retrieval_score=documents[i]["score"], score=float(scores[i])) for i in order]
+
+
 class Retriever:
     """question -> documents, with the reference's error protocol: every failure yields [] and is kept in `last_error`
-    (`_last_retrieval_error` there); a successful retrieval clears it."""
+    (`_last_retrieval_error` there); a successful retrieval clears it.  reranker (optional): an object with
+    score_pairs(questions, passages) -> scores (embeddings.reranker.MI355XReranker), used by calls that pass rerank=True."""
 
-    def __init__(self, embedding_client: Any, vector_store: Any) -> None:
+    def __init__(self, embedding_client: Any, vector_store: Any, reranker: Any = None) -> None:
         self.embedding_client = embedding_client
         self.vector_store = vector_store
+        self.reranker = reranker
         self.last_error: Optional[BaseException] = None
         self._connected = False
 
@@ -88,19 +103,46 @@ class Retriever:
             out.update(hybrid=hybrid, **text)
         return out
 
+    def _check_rerank(self, rerank: Any, mmr: Any) -> bool:
+        """Argument errors of rerank=, raised before anything runs."""
+        if not rerank:
+            return False
+        if mmr is not None:
+            raise ValueError("rerank together with mmr is not supported: pick one way of re-ordering the candidates")
+        if self.reranker is None:
+            raise ValueError("rerank=True needs a reranker: Retriever(embedding_client, vector_store, reranker=...)")
+        return True
+
+    def _rerank(self, questions: Sequence[str], per_question: List[List[Dict[str, Any]]], top_k: int) -> List[List[Dict[str, Any]]]:
+        """All (question, snippet) pairs of all questions in one score_pairs call (shared packed batches), then _apply_scores each."""
+        qs = [q for q, docs in zip(questions, per_question) for _ in docs]
+        ps = [doc["snippet"] for docs in per_question for doc in docs]
+        scores = self.reranker.score_pairs(qs, ps) if qs else []
+        out, at = [], 0
+        for docs in per_question:
+            out.append(_apply_scores(docs, scores[at:at + len(docs)], top_k))
+            at += len(docs)
+        return out
+
     def retrieve(self, question: str, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                 mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None) -> List[Dict[str, Any]]:
+                 mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None) -> List[Dict[str, Any]]:
         """pipeline.py:93-129, one question.  repos / languages restrict the search itself (MilvusVectorStore.search), where the
         reference front ends drop hits from an unfiltered top-k afterwards.  group_by ("path" | "repo"): at most one document per
         file / per repo, so rag_max_context_sources buys that many different sources.  mmr (in [0, 1]) / fetch_k: maximal marginal
         relevance over the best fetch_k chunks, so near-identical chunks under different paths do not take every slot.  hybrid (True
         or {c, dense_weight, lexical_weight}): the question text goes along and its BM25 hits over the chunks' code terms are fused
-        with the dense ones, so a question that names an identifier finds the chunk that defines it."""
+        with the dense ones, so a question that names an identifier finds the chunk that defines it.  rerank=True: the store is asked
+        for fetch_k hits (default settings.mi355x_rerank_fetch_k, at least top_k; filters, group_by and hybrid apply to that search), the
+        reranker scores every (question, snippet) pair, and the top_k by that score come back -- ties by retrieval rank, `score` the
+        reranker's, `retrieval_score` the store's.  Not together with mmr (ValueError); a reranker failure yields [] and last_error."""
+        reranking = self._check_rerank(rerank, mmr)
         if not self._ensure_connected():
             return []
         vector = embed_query(self.embedding_client, question)
+        top_k = _top_k()
+        ask_k, store_fetch_k = (_rerank_fetch_k(fetch_k, top_k), None) if reranking else (top_k, fetch_k)
         try:
-            results = self.vector_store.search(vector, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k, hybrid, query_text=question))
+            results = self.vector_store.search(vector, top_k=ask_k, **self._filter_kwargs(repos, languages, group_by, mmr, store_fetch_k, hybrid, query_text=question))
         except Exception as exc:
             log.error("milvus_search_failed error=%s", exc)
             self.last_error = exc
@@ -116,32 +158,52 @@ class Retriever:
         except TypeError:  # not iterable: taken as the hits themselves, as the reference does
             hits = results
         documents = [doc for doc in (hit_to_document(hit) for hit in hits) if doc]
+        if reranking:
+            try:
+                documents = self._rerank([question], [documents], top_k)[0]
+            except Exception as exc:
+                log.error("rerank_failed error=%s", exc)
+                self.last_error = exc
+                return []
         self.last_error = None
         return documents
 
     def retrieve_batch(self, questions: Sequence[str], *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                       mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None) -> List[List[Dict[str, Any]]]:
+                       mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None) -> List[List[Dict[str, Any]]]:
         """Many questions at once: one encoder batch (`embed_documents_array`) and one batched search (`search_batch`) when the
         seams offer them, else `retrieve` per question.  Per question the result is what `retrieve` returns for it (a store
         that returns no hit for a question yields [] for that question).  repos / languages / group_by / mmr / fetch_k / hybrid: one setting
-        for the whole batch, as in `retrieve`."""
+        for the whole batch, as in `retrieve`.  rerank=True: as in `retrieve`, with the pairs of ALL questions scored in shared
+        packed batches."""
         questions = list(questions)
+        reranking = self._check_rerank(rerank, mmr)
         if not questions:
             return []
         fast = hasattr(self.embedding_client, "embed_documents_array") and hasattr(self.vector_store, "search_batch") and hasattr(self.vector_store, "hits_for")
         if not fast:
+            if reranking:
+                return [self.retrieve(q, repos=repos, languages=languages, group_by=group_by, fetch_k=fetch_k, hybrid=hybrid, rerank=True) for q in questions]
             return [self.retrieve(q, repos=repos, languages=languages, group_by=group_by, mmr=mmr, fetch_k=fetch_k, hybrid=hybrid) for q in questions]
         if not self._ensure_connected():
             return [[] for _ in questions]
+        top_k = _top_k()
+        ask_k, store_fetch_k = (_rerank_fetch_k(fetch_k, top_k), None) if reranking else (top_k, fetch_k)
         try:
             vectors = np.asarray(self.embedding_client.embed_documents_array(questions), dtype=np.float32)
-            dist, rows = self.vector_store.search_batch(vectors, top_k=_top_k(), **self._filter_kwargs(repos, languages, group_by, mmr, fetch_k, hybrid, query_texts=questions))
+            dist, rows = self.vector_store.search_batch(vectors, top_k=ask_k, **self._filter_kwargs(repos, languages, group_by, mmr, store_fetch_k, hybrid, query_texts=questions))
             results = self.vector_store.hits_for(dist, rows)
         except Exception as exc:
             log.error("milvus_search_failed error=%s", exc)
             self.last_error = exc
             return [[] for _ in questions]
         out = [[doc for doc in (hit_to_document(hit) for hit in hits) if doc] for hits in results]
+        if reranking:
+            try:
+                out = self._rerank(questions, out, top_k)
+            except Exception as exc:
+                log.error("rerank_failed error=%s", exc)
+                self.last_error = exc
+                return [[] for _ in questions]
         # as retrieve() (pipeline.py:112-122): "no_results" only when the store's result container itself is falsy; a
         # non-empty container whose hit lists hold nothing usable clears the error
         self.last_error = None if results else ValueError("no_results")
