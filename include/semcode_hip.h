@@ -102,7 +102,8 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
 /* ------------------------------------------------------------------- encoder ---- */
 
 /* BERT-family post-LN transformer encoder (the "transformer-encoder forward" of BASELINE.json;
- * BERT-base shape = 30522 / 768 / 12 / 12 / 3072 / 512 / 2, eps 1e-12).  Head dimension must be 64. */
+ * BERT-base shape = 30522 / 768 / 12 / 12 / 3072 / 512 / 2, eps 1e-12).  Head dimension hidden / heads must be 64, or 32 with
+ * pos_type 0 (MiniLM-L6 shape = 30522 / 384 / 6 / 12 / 1536 / 512 / 2); 32 with ALiBi or rotary positions is SC_ERR_UNSUPPORTED. */
 typedef struct sc_encoder_cfg {
     int32_t vocab, hidden, layers, heads, ffn, max_pos, type_vocab;
     float ln_eps;
@@ -320,6 +321,13 @@ sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* 
  * out [R, heads*64]: rows of a sequence at or beyond its length are finite, rows outside every sequence stay NaN. */
 sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
                                    int32_t blocked_rows, const float* slopes, float* out);
+/* sc_diag_attention_hd / sc_diag_attention_packed_hd: sc_diag_attention_ex / sc_diag_attention_packed for a head dimension of 64 or 32:
+ * qkv is [rows][3*heads*head_dim] row-major, or -- blocked -- [3*heads*head_dim/64][blocked_rows][64]; out [rows, heads*head_dim].
+ * head_dim 32 needs an even number of heads (a 64-column block holds heads 2j and 2j+1) and slopes == NULL. */
+sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                               int32_t blocked_rows, const float* slopes, float* out);
+sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                      int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,

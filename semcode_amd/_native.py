@@ -97,6 +97,8 @@ SIGNATURES = {
     "sc_diag_gemm_resln": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
@@ -1054,7 +1056,9 @@ def diag_gemm_i8(rt: Runtime, A, W) -> np.ndarray:
     return out
 
 
-def diag_attention(rt: Runtime, qkv, lens, B: int, S: int, heads: int) -> np.ndarray:
+def diag_attention(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, blocked_rows: int = 0) -> np.ndarray:
+    if head_dim != 64 or blocked_rows:
+        return diag_attention_ex(rt, qkv, lens, B, S, heads, blocked_rows=blocked_rows, head_dim=head_dim)
     qkv = np.ascontiguousarray(qkv, np.float32)
     lens = np.ascontiguousarray(lens, np.int32)
     out = np.empty((B * S, heads * 64), np.float32)
@@ -1149,29 +1153,32 @@ def diag_gemm_resln(rt: Runtime, A, W, bias, gam, R, fin, eps: float, a_blocked:
     return Cc, st
 
 
-def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocked_rows: int = 0, slopes=None) -> np.ndarray:
-    """sc_launch_attention as the pipelines call it: blocked_rows > 0 lays qkv [B*S, 3H] out as [3 heads][blocked_rows][64] (rows beyond
-    B*S zero); slopes [heads] = ALiBi."""
+def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
+    """sc_launch_attention as the pipelines call it: blocked_rows > 0 lays qkv [B*S, 3H] out as [3H/64][blocked_rows][64] (rows beyond
+    B*S zero); slopes [heads] = ALiBi; head_dim 64 or 32 (H = heads * head_dim)."""
     qkv = _f32(qkv)
     lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * 64
+    H = heads * head_dim
     if blocked_rows:
         pad = np.zeros((blocked_rows, 3 * H), np.float32)
         pad[: B * S] = qkv
         qkv = block64(pad)
     sl = None if slopes is None else _f32(slopes)
     out = np.empty((B * S, H), np.float32)
-    _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    if head_dim != 64:
+        _check(lib().sc_diag_attention_hd(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(head_dim), int(blocked_rows), _ptr(sl), _ptr(out)))
+    else:
+        _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
     return out
 
 
-def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_rows: int = 0, slopes=None) -> np.ndarray:
+def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
     """The packed attention kernel on its own: qkv [R, 3H] row-major, sequence b on the rows starts[b] .. starts[b] + ceil32(lens[b]);
-    R = blocked_rows (> 0: handed over as [3 heads][R][64]) or the last sequence's end rounded up to 256.  -> [R, H]."""
+    R = blocked_rows (> 0: handed over as [3H/64][R][64]) or the last sequence's end rounded up to 256.  -> [R, H], H = heads * head_dim."""
     qkv = _f32(qkv)
     starts = np.ascontiguousarray(starts, np.int32)
     lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * 64
+    H = heads * head_dim
     R = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
     if qkv.shape != (R, 3 * H) or starts.shape != lens.shape:
         raise ValueError(f"diag_attention_packed: qkv must be [{R}, {3 * H}], starts and lens [B]")
@@ -1179,7 +1186,11 @@ def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_ro
         qkv = block64(qkv)
     sl = None if slopes is None else _f32(slopes)
     out = np.empty((R, H), np.float32)
-    _check(lib().sc_diag_attention_packed(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    if head_dim != 64:
+        _check(lib().sc_diag_attention_packed_hd(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(head_dim), int(blocked_rows), _ptr(sl),
+                                                 _ptr(out)))
+    else:
+        _check(lib().sc_diag_attention_packed(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(blocked_rows), _ptr(sl), _ptr(out)))
     return out
 
 

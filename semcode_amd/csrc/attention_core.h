@@ -1,6 +1,8 @@
 // attention_core.h -- the device code the attention kernels share (encoder_ops.hip: rectangles, encoder_packed.hip: packed
 // variable-length rows): the online-softmax state of one 32-row query block, the fold of one segment of keys into it, the store.
 // LDS images: K [keys][64] with chunk ^= (row>>1)&7, V [keys][64] with chunk ^= ((row>>1)&1)<<2 (encoder_ops.hip describes them).
+// Head dimension 32 (encoder_attn32.hip): the same images hold a PAIR of heads, AttnState32 / attention_qblock_core32 / attn_state32_store
+// at the end of this file run the softmax once per head of the pair.
 #pragma once
 #include "gemm_tile.h"  // bf16 helpers, vector types
 
@@ -163,6 +165,182 @@ static __device__ __forceinline__ void attn_state_store(const AttnState& S_, flo
             const int ql = 4 * hh + c;  // row inside this block of 8
             og[ql * 64 + l31] = (bf16_t)(pack_bf16x2(o0[4 * g4 + c] * il[c], 0.f) & 0xFFFFu);
             og[ql * 64 + 32 + l31] = (bf16_t)(pack_bf16x2(o1[4 * g4 + c] * il[c], 0.f) & 0xFFFFu);
+        }
+        const int ql = lane >> 3, c8 = lane & 7;
+        const bf16x8 v = *reinterpret_cast<const bf16x8*>(ostg + ql * 128 + c8 * 16);
+        *reinterpret_cast<bf16x8*>(obase + (size_t)(8 * g4 + ql) * H + c8 * 8) = v;
+    }
+}
+
+// ------------------------------------------------------------------ head dimension 32: a pair of heads per 64-column block
+// The 64 columns of a staged K / V row, of a wave's four Q fragments and of an output row hold heads 2j (columns 0..31) and 2j + 1
+// (columns 32..63) of block j.  The state is one (m, l, O tile) per head of the pair: 36 registers against AttnState's 34.
+struct AttnState32 {
+    float m_run[2], l_run[2];
+    f32x16 o[2];
+};
+static __device__ __forceinline__ void attn_state32_init(AttnState32& a) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        a.m_run[e] = -3.0e38f;
+        a.l_run[e] = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a.o[e][r] = 0.f;
+    }
+}
+// attention_qblock_core for a pair of 32-wide heads, plain attention only.  Per group of key tiles and per head e of the pair: the
+// score tile is the two MFMA steps ks = 2e, 2e + 1 (K chunks 4e + hh and 4e + 2 + hh of the row, Q fragments 2e and 2e + 1), scaled
+// by 1/sqrt(32); P V accumulates into the one tile o[e] from the dt = e half of the V reads.  Nothing head e computes reads a column
+// of the other head.  Same LDS addresses per read as the 64-wide core, so its bank analysis holds; masking, the FULL path and the
+// fold of later segments are its too.  The two heads of a group run as a real two-trip loop over ONE copy of the code, the current
+// head's (m, l, O, Q fragments) swapped with the other's after each trip: unrolled, the scheduler interleaves the two independent
+// heads, keeps both score tiles live and spills (2.4 KB of scratch per lane at 16 key tiles).
+template <int KT, bool FULL, int GKMAX = 4>
+static __device__ __forceinline__ void attention_qblock_core32(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane,
+                                                               AttnState32& S_, bool first) {
+    constexpr int GK = KT < GKMAX ? KT : GKMAX;   // key tiles per group
+    constexpr int NG = (KT + GK - 1) / GK;
+    const int l31 = lane & 31, hh = lane >> 5;
+    const float sl2 = 0.17677669529663688110f * 1.44269504088896340736f;  // 1/sqrt(32) * log2(e)
+    const int tail = len & 31;                                            // != 0: the last real key tile is partially masked
+    float m_run = S_.m_run[0], l_run = S_.l_run[0], m_oth = S_.m_run[1], l_oth = S_.l_run[1];
+    f32x16 o = S_.o[0], o_oth = S_.o[1];
+    bf16x8 q0 = qf[0], q1 = qf[1], q0_oth = qf[2], q1_oth = qf[3];
+    // LDS byte offsets of this lane's reads for head 0 at key tile 0; head 1 is 64 bytes (4 chunks) away in the same row, and both
+    // swizzles only XOR chunk bits, so the head is one XOR with e << 6 and the key tile an immediate
+    const int kb0 = l31 * 128 + ((hh ^ ((l31 >> 1) & 7)) << 4), kb1 = l31 * 128 + (((2 + hh) ^ ((l31 >> 1) & 7)) << 4);
+    const int vrow = 4 * hh + ((lane & 15) >> 2);
+    const int vb = vrow * 128 + (((2 * ((lane >> 4) & 1) + ((lane & 3) >> 1)) ^ (((vrow >> 1) & 1) << 2)) << 4) + 8 * (lane & 1);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        if (!FULL && g * GK >= nkt) continue;  // wave-uniform: nothing real in this group
+#pragma unroll 1
+        for (int e = 0; e < 2; ++e) {
+            const int ka0 = kb0 ^ (e << 6), ka1 = kb1 ^ (e << 6), va = vb ^ (e << 6);
+            // S^T tiles of the group: st[i][r] = score(key = 32 t + (r&3) + 8 (r>>2) + 4 hh, query = l31), t = g*GK + i
+            f32x16 st[GK];
+#pragma unroll
+            for (int i = 0; i < GK; ++i) {
+                const int t = g * GK + i;
+                if (FULL || t < nkt) {
+                    f32x16 acc;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {  // row 32 t + l31, chunk (4 e + 2 ks + hh) ^ ((row >> 1) & 7)
+                        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + 32 * t * 128 + (ks ? ka1 : ka0));
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, ks ? q1 : q0, acc, 0, 0, 0);
+                    }
+                    st[i] = acc;
+                }
+            }
+            float mx = m_run;
+#pragma unroll
+            for (int i = 0; i < GK; ++i) {
+                const int t = g * GK + i;
+                if (FULL || t < nkt) {
+                    if (!FULL && t == nkt - 1 && tail) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh < len) mx = fmaxf(mx, st[i][r]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[i][r]);
+                    }
+                }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mb = mx * sl2;
+            const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, sl2, -mb));  // first group: exp2(-huge) = 0, and O, l are 0 anyway
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < GK; ++i) {
+                const int t = g * GK + i;
+                if (FULL || t < nkt) {
+                    const bool masked = !FULL && (t == nkt - 1) && tail;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float p = __builtin_amdgcn_exp2f(fmaf(st[i][r], sl2, -mb));
+                        if (masked && !(32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh < len)) p = 0.f;
+                        st[i][r] = p;
+                        sum += p;
+                    }
+                }
+            }
+            sum += __shfl_xor(sum, 32, 64);
+            l_run = fmaf(l_run, alpha, sum);
+            m_run = mx;
+            if (g > 0 || !first) {  // rescale O: its rows are queries (r&3) + 8 (r>>2) + 4 hh, alpha lives on lane q -> exchange through LDS
+                xch[l31] = alpha;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const f32x4 al = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) o[4 * g4 + c] *= al[c];
+                }
+            }
+            // O += P V: A operand = P straight from the score registers (k order of step s:
+            // key = 32 t + 16 s + 8 (j>>2) + 4 hh + (j&3)), B operand = columns 32 e .. 32 e + 31 of V by transposed LDS reads
+#pragma unroll
+            for (int i = 0; i < GK; ++i) {
+                const int t = g * GK + i;
+                if (FULL || t < nkt) {
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                        u32x4 pp;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) pp[j] = pack_bf16x2(st[i][8 * s + 2 * j], st[i][8 * s + 2 * j + 1]);
+                        const bf16x8 pf = __builtin_bit_cast(bf16x8, pp);
+                        bf16x8 vf;
+#pragma unroll
+                        for (int piece = 0; piece < 2; ++piece) {
+                            // row 32 t + 16 s + 8 piece + vrow, chunk (4 e + 2 ((lane >> 4) & 1) + ((lane & 3) >> 1)) ^ (((row >> 1) & 1) << 2)
+                            typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
+                            const s16x4 got = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(Vl + (32 * t + 16 * s + 8 * piece) * 128 + va));
+                            vf[4 * piece + 0] = got[0];
+                            vf[4 * piece + 1] = got[1];
+                            vf[4 * piece + 2] = got[2];
+                            vf[4 * piece + 3] = got[3];
+                        }
+                        o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o, 0, 0, 0);
+                    }
+                }
+            }
+            // the other head's turn (after two trips everything is back in place)
+            { const float t = m_run; m_run = m_oth; m_oth = t; }
+            { const float t = l_run; l_run = l_oth; l_oth = t; }
+            { const f32x16 t = o; o = o_oth; o_oth = t; }
+            { const bf16x8 t = q0; q0 = q0_oth; q0_oth = t; }
+            { const bf16x8 t = q1; q1 = q1_oth; q1_oth = t; }
+        }
+    }
+    S_.m_run[0] = m_run;
+    S_.l_run[0] = l_run;
+    S_.m_run[1] = m_oth;
+    S_.l_run[1] = l_oth;
+    S_.o[0] = o;
+    S_.o[1] = o_oth;
+}
+// o[e][r] = O_e[q = (r&3) + 8 (r>>2) + 4 hh][d = l31]: the left half of an output row is head 2j normalised by 1/l_0[q], the right half
+// head 2j + 1 by 1/l_1[q]; staged and stored as attn_state_store does (whole 128-byte rows [q][64]).
+static __device__ __forceinline__ void attn_state32_store(const AttnState32& S_, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
+    const int l31 = lane & 31, hh = lane >> 5;
+    f32x4 il[2][4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {  // LDS runs a wave's instructions in order: the second write follows the first head's reads
+        xch[l31] = 1.0f / S_.l_run[e];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) il[e][g4] = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
+    }
+    bf16_t* og = reinterpret_cast<bf16_t*>(ostg);
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int ql = 4 * hh + c;  // row inside this block of 8
+            og[ql * 64 + l31] = (bf16_t)(pack_bf16x2(S_.o[0][4 * g4 + c] * il[0][g4][c], 0.f) & 0xFFFFu);
+            og[ql * 64 + 32 + l31] = (bf16_t)(pack_bf16x2(S_.o[1][4 * g4 + c] * il[1][g4][c], 0.f) & 0xFFFFu);
         }
         const int ql = lane >> 3, c8 = lane & 7;
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(ostg + ql * 128 + c8 * 16);

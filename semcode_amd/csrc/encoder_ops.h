@@ -39,8 +39,10 @@ void sc_gemm_force_tile128(bool on);
 void sc_launch_embed_ln(const int32_t* ids, int tokens, int S, int H, int vocab, int max_pos, const float* wemb, const float* pemb,
                         const float* temb, const float* g, const float* b, float eps, void* out, hipStream_t s);
 void sc_launch_layernorm(const void* in, int tokens, int H, const float* g, const float* b, float eps, void* out, hipStream_t s);
-bool sc_attention_supported(int S, int H, int heads);
-void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0);
+// head_dim 64, or 32 (plain attention only: slopes must be NULL): a 64-column block of qkv / ctx then holds a pair of heads
+bool sc_attention_supported(int S, int H, int heads, int head_dim = 64);
+void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0,
+                         int head_dim = 64);
 void sc_launch_geglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
 void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
 // rotary positions: in-place rotation of the first `nblocks` 64-column blocks (Q and K heads) of a blocked buffer [blocks][M][64];
@@ -67,10 +69,15 @@ void sc_launch_embed_raw_packed(const int32_t* ids, const int32_t* pos, int toke
                                 const float* pemb, const float* temb, void* out, float* stats, int slots, hipStream_t s);
 void sc_launch_rope_qk_packed(void* qkv, int64_t M, int nblocks, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t, hipStream_t s);
 int sc_packed_attention_class(int len);  // 0: longer than 256 tokens, 1: up to 256, 2: up to 128
-void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked = 0,
+                                int head_dim = 64);
 void sc_launch_mean_pool_packed(const void* x, const int32_t* starts, const int32_t* lens, int B, int H, int normalize, float* out, hipStream_t s);
 void sc_launch_mean_pool_ln_packed(const void* y, const float* stats, int slots, int tokens_pad, const float* gamma, const float* beta, float eps,
                                    const int32_t* starts, const int32_t* lens, int B, int H, float* out, hipStream_t s);
+
+// ---- encoder_attn32.hip: head dimension 32, what the two attention launchers above dispatch to (same arguments, no ALiBi slopes)
+void sc_launch_attention32(const void* qkv, const int32_t* lens, int B, int S, int H, void* ctx, hipStream_t s, int blocked);
+void sc_launch_attention32_packed(const void* qkv, const int32_t* items, const int* nitems, int H, void* ctx, hipStream_t s, int blocked);
 
 // ---- encoder_pairs.hip: the packed embedding with a per-row segment id (types [rows], clamped into type_emb's type_vocab rows), and
 // the classification head of a cross-encoder: cls [B,H] f32 -> logits [B,num_labels] = Wc p + bc, p = tanh(Wp cls + bp), or p = cls when

@@ -371,11 +371,12 @@ static void launch_attn(const void* qkv, const int32_t* lens, int B, int H, cons
     else
         hipLaunchKernelGGL((attention_kernel<KT, ALIBI, 4>), grid, dim3(256), (size_t)KT * 32 * 256 + 4 * 1152, s, (const bf16_t*)qkv, lens, H, slopes, (bf16_t*)ctx, blocked);
 }
-bool sc_attention_supported(int S, int H, int heads) {
-    return heads > 0 && H == heads * 64 && (S == 32 || S == 64 || S == 128 || S == 256 || S == 512 || S == 1024 || S == 2048);
+bool sc_attention_supported(int S, int H, int heads, int head_dim) {
+    return heads > 0 && (head_dim == 64 || head_dim == 32) && H == heads * head_dim && H % 64 == 0 && (S == 32 || S == 64 || S == 128 || S == 256 || S == 512 || S == 1024 || S == 2048);
 }
 // slopes: NULL = plain attention; else [heads] ALiBi slopes (device)
-void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked) {
+void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked, int head_dim) {
+    if (head_dim == 32) return sc_launch_attention32(qkv, lens, B, S, H, ctx, s, blocked);  // encoder_attn32.hip; create refuses 32-wide ALiBi models
 #define SC_ATTN_CASE(SS, KK)                                                      \
     case SS:                                                                      \
         if (slopes) launch_attn<KK, true>(qkv, lens, B, H, slopes, ctx, blocked, s); \

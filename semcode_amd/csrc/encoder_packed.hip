@@ -163,7 +163,9 @@ static void launch_attn_packed(const void* qkv, const int32_t* items, int nitems
                            (bf16_t*)ctx, blocked);
 }
 int sc_packed_attention_class(int len) { return len > 256 ? 0 : (len > 128 ? 1 : 2); }
-void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked) {
+void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked,
+                                int head_dim) {
+    if (head_dim == 32) return sc_launch_attention32_packed(qkv, items, nitems, H, ctx, s, blocked);  // encoder_attn32.hip
     launch_attn_packed<16, 8>(qkv, items, nitems[0], H, slopes, ctx, blocked, s);
     launch_attn_packed<8, 8>(qkv, items + 4 * (size_t)nitems[0], nitems[1], H, slopes, ctx, blocked, s);
     launch_attn_packed<4, 4>(qkv, items + 4 * ((size_t)nitems[0] + nitems[1]), nitems[2], H, slopes, ctx, blocked, s);

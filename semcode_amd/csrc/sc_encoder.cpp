@@ -170,11 +170,15 @@ extern "C" sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* o
 static sc_status check_cfg(const sc_encoder_cfg& c) {
     if (c.vocab < 1 || c.hidden < 1 || c.layers < 1 || c.heads < 1 || c.ffn < 1 || c.max_pos < 1 || c.type_vocab < 1)
         return sc_fail(SC_ERR_INVALID, "sc_encoder_create: non-positive model dimension");
-    if (c.hidden != c.heads * 64) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension must be 64 (hidden=%d heads=%d)", c.hidden, c.heads);
+    if (c.hidden != c.heads * 64 && c.hidden != c.heads * 32)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension must be 64 or 32 (hidden=%d heads=%d)", c.hidden, c.heads);
     if (c.hidden % 128 || c.ffn % 128 || c.hidden > 2048)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: hidden (<=2048) and ffn must be multiples of 128 (got %d, %d)", c.hidden, c.ffn);
     if (!(c.ln_eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: ln_eps must be > 0");
     if (c.pos_type < 0 || c.pos_type > 2 || c.ffn_type < 0 || c.ffn_type > 2) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown pos_type / ffn_type");
+    if (c.hidden == c.heads * 32 && c.pos_type != 0)  // the rotary kernels pair columns (j, j + 32) of a 64-wide head; no 32-wide ALiBi kernel
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension 32 runs with learned positions only (pos_type 0), not pos_type %d (%s)", c.pos_type,
+                       c.pos_type == 1 ? "ALiBi" : "rotary");
     if (c.pos_type == 2 && !(c.rope_theta >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta must be >= 0 (0 = 10000)");
     return SC_OK;
 }
@@ -413,8 +417,9 @@ static void launch_rope(sc_encoder* e, int M, int S, const PackedLayout* pk, hip
     else sc_launch_rope_qk(e->qkv, M, 2 * e->cfg.heads, S, e->rope_cos, e->rope_sin, s);
 }
 static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
-    if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M);
-    else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M);
+    const int hd = e->cfg.hidden / e->cfg.heads;  // 64, or 32: a pair of heads per 64-column block (encoder_attn32.hip)
+    if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
+    else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
 }
 static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
     if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, pk->types ? 0 : e->cfg.normalize, out_dev, s);
@@ -554,7 +559,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
 static sc_status check_embed_args(sc_encoder* e, const void* ids, const void* lens, int32_t B, int32_t S, const void* out) {
     if (!e || !ids || !lens || !out) return sc_fail(SC_ERR_INVALID, "embed: NULL argument");
     if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "embed: batch %d out of range", B);
-    if (!sc_attention_supported(S, e->cfg.hidden, e->cfg.heads))
+    if (!sc_attention_supported(S, e->cfg.hidden, e->cfg.heads, e->cfg.hidden / e->cfg.heads))
         return sc_fail(SC_ERR_UNSUPPORTED, "embed: sequence length %d not in {32,64,128,256,512,1024,2048} (pad on the host)", S);
     if (S > e->cfg.max_pos && e->cfg.pos_type != 1) return sc_fail(SC_ERR_INVALID, "embed: sequence length %d exceeds max_pos %d", S, e->cfg.max_pos);
     return SC_OK;

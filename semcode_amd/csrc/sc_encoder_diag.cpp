@@ -282,12 +282,15 @@ extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const flo
 }
 
 // sc_launch_attention as the pipelines call it.  blocked_rows == 0: qkv [B*S][3H] row-major; > 0: qkv [3 heads][blocked_rows][64], the layout
-// the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.
+// the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.  head_dim 64, or 32 (an even
+// number of heads, no slopes): H = heads * head_dim, the blocks stay 64 columns wide.
 static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                const float* slopes, float* out) {
+                                const float* slopes, float* out, int32_t head_dim = 64) {
     if (!rt || !qkv || !lens || !out || B < 1 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    const int H = heads * 64;
-    if (!sc_attention_supported(S, H, heads)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
+    const int H = heads * head_dim;
+    if (!sc_attention_supported(S, H, heads, head_dim))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048, head_dim 64 or 32 (an even number of heads)", who);
+    if (head_dim != 64 && slopes) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head dimension %d has no ALiBi kernel", who, head_dim);
     const int64_t tokens = (int64_t)B * S;
     if (blocked_rows && blocked_rows < tokens) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
     SC_HIP(hipSetDevice(rt->device));
@@ -297,8 +300,12 @@ static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qk
     SC_TRY(upload(lens, (size_t)B * 4, dl, s));
     if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
     SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
-    sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows);
+    sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
     return download_bf16(dc.p, tokens * H, out, s);
+}
+extern "C" sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                                          int32_t blocked_rows, const float* slopes, float* out) {
+    return diag_attention("sc_diag_attention_hd", rt, qkv, lens, B, S, heads, blocked_rows, slopes, out, head_dim);
 }
 extern "C" sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
                                           const float* slopes, float* out) {
@@ -309,11 +316,13 @@ extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const i
 }
 
 // sc_launch_attention_packed as the packed forward calls it: the work items come from sc_packed_items, as there.
-extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                              int32_t blocked_rows, const float* slopes, float* out) {
-    const char* who = "sc_diag_attention_packed";
-    if (!rt || !qkv || !starts || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1 || heads > 32) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    const int H = heads * 64;
+static sc_status diag_attention_packed(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                       int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out) {
+    if (!rt || !qkv || !starts || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (head_dim != 64 && !(head_dim == 32 && heads % 2 == 0 && !slopes))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads and no ALiBi slopes (got %d, %d heads)", who, head_dim, heads);
+    if (heads * head_dim > 2048) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    const int H = heads * head_dim;
     int64_t end = 0;
     for (int32_t b = 0; b < B; ++b) {
         if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
@@ -333,8 +342,16 @@ extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, 
     SC_TRY(upload(items.data(), items.size() * 4, di, s));
     if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
     SC_TRY(alloc_nan(dc, (size_t)R * H * 2, s));
-    sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows);
+    sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
     return download_bf16(dc.p, R * H, out, s);  // synchronises: items may go
+}
+extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                              int32_t blocked_rows, const float* slopes, float* out) {
+    return diag_attention_packed("sc_diag_attention_packed", rt, qkv, starts, lens, B, heads, 64, blocked_rows, slopes, out);
+}
+extern "C" sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                                 int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out) {
+    return diag_attention_packed("sc_diag_attention_packed_hd", rt, qkv, starts, lens, B, heads, head_dim, blocked_rows, slopes, out);
 }
 
 // rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],

@@ -162,7 +162,11 @@ def flatten_ids(ids: np.ndarray, lens: np.ndarray) -> "tuple[np.ndarray, np.ndar
 
 
 class MI355XEmbeddings:
-    """LangChain-Embeddings-shaped client whose forward runs in libsemcode_hip on the MI355X."""
+    """LangChain-Embeddings-shaped client whose forward runs in libsemcode_hip on the MI355X.
+
+    The model shape: a `.gguf` states it (head count included); a `.safetensors` or `.npy` blob does not, so `cfg` gives what differs
+    from BERT-base.  Heads are 64 wide, or 32 for the 384-hidden family with learned positions -- all-MiniLM-L6-v2 (mean-pooled) is
+    `cfg=dict(hidden=384, heads=12, layers=6, ffn=1536)`, all-MiniLM-L12-v2 the same with `layers=12`."""
 
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,

@@ -7,7 +7,8 @@ pairs on the host, cuts them into packed batches and turns logits into scores.  
 the store's hits to the LLM as they come, src/semcode/rag/pipeline.py:93-129); `services.retrieval.Retriever(reranker=...)` adds it.
 
 Weights: a `.safetensors` file with BertForSequenceClassification names (`bert.embeddings...`, `bert.encoder.layer.N...`,
-`bert.pooler.dense.{weight,bias}`, `classifier.{weight,bias}`); the encoder shape is read from the tensors.  A file without
+`bert.pooler.dense.{weight,bias}`, `classifier.{weight,bias}`); the encoder shape is read from the tensors, the head count from `num_attention_heads` of a `config.json`
+beside the file (MiniLM cross-encoders: 384 hidden = 12 heads of 32), hidden // 64 without one; `cfg` overrides both.  A file without
 `bert.pooler.dense` gives a head without pooler.  Models without a position table are accepted when their type_vocab is at least 2
 and the caller's cfg names the position scheme and the length bound (alibi=True or rotary=True, max_pos: the file cannot), but no
 reference pins what they compute.  Out of scope: SentencePiece vocabularies (XLM-R rerankers),
@@ -15,6 +16,7 @@ Electra-style heads, more than two labels.
 """
 from __future__ import annotations
 
+import json
 import logging
 from pathlib import Path
 from typing import Any, List, Optional, Sequence
@@ -107,8 +109,8 @@ def scores_from_logits(logits: np.ndarray) -> np.ndarray:
 
 
 def load_reranker(path: "str | Path", cfg: Optional[dict] = None) -> "tuple[dict, np.ndarray, dict]":
-    """`.safetensors` with BertForSequenceClassification names -> (encoder cfg read from the tensors and updated by `cfg`, weight blob in
-    ABI order, head = {cls_w, cls_b, pooler_w, pooler_b} with the pooler None when the file has none)."""
+    """`.safetensors` with BertForSequenceClassification names -> (encoder cfg read from the tensors, heads from the config.json beside
+    the file if there is one, all updated by `cfg`; weight blob in ABI order; head = {cls_w, cls_b, pooler_w, pooler_b} with the pooler None when the file has none)."""
     path = Path(path)
     if path.suffix != ".safetensors":
         raise ValueError(f"unsupported reranker file {path} (use .safetensors with BertForSequenceClassification names)")
@@ -131,7 +133,14 @@ def load_reranker(path: "str | Path", cfg: Optional[dict] = None) -> "tuple[dict
     while get(f"encoder.layer.{layers}.attention.self.query.weight") is not None:
         layers += 1
     hidden = int(word.shape[1])
-    out = dict(vocab=int(word.shape[0]), hidden=hidden, layers=layers, heads=hidden // 64,
+    # the tensors do not say how wide a head is (MiniLM cross-encoders: 384 = 12 x 32): the config.json beside the file does
+    heads = hidden // 64
+    cfg_json = path.with_name("config.json")
+    if cfg_json.is_file():
+        n = json.loads(cfg_json.read_text()).get("num_attention_heads")
+        if n is not None:
+            heads = int(n)
+    out = dict(vocab=int(word.shape[0]), hidden=hidden, layers=layers, heads=heads,
                ffn=tensors_rows(tensors, "encoder.layer.0.intermediate.dense.weight"), type_vocab=tensors_rows(tensors, "embeddings.token_type_embeddings.weight"),
                ln_eps=1e-12)
     pos = get("embeddings.position_embeddings.weight")
