@@ -262,7 +262,8 @@ sc_status sc_diag_encoder_read(sc_encoder* enc, int32_t which, void* out, size_t
  * "wide_candidates": 1 = the int8 stage keeps every key within its cut
  * (the form it otherwise switches to on corpora whose certificate fails) wherever it can; "collect_pass": 0 = queries a
  * coarse stage cannot certify go straight to the next stage (no collect pass); "ivf_coarse_nomem": 1 = the IVF coarse stage
- * cannot allocate its centred shadow (the search must then probe exactly instead of failing); "ivf_refine_cap":
+ * cannot allocate its centred shadow (the search must then probe exactly instead of failing), 2 = the stage runs out of memory from
+ * the second 4 096-query chunk of a batch on (the first chunk keeps its results, the exact probes answer the rest); "ivf_refine_cap":
  * rows per query the IVF coarse stage's refine step takes on (-1 = default 4096; a small value sends queries to the exact re-probe). */
 sc_status sc_diag_set_option(const char* name, int32_t value);
 /* "rope_fused" of sc_diag_set_option: how the batch pipeline of a rotary encoder rotates Q and K (-1 = default, 0 = the stand-alone
@@ -682,6 +683,11 @@ sc_status sc_index_last_probe_stats(sc_index* ix, int64_t* unique_rows, int64_t*
  * count elements, padded to 8 bytes}; *need_bytes is their total size, and nothing is written when cap_bytes is smaller. */
 sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, int32_t Q, int32_t nprobe, const int64_t* list_off, int32_t nlist,
                            int32_t k, int32_t ld, int32_t cus, int32_t wide, void* out, int64_t cap_bytes, int64_t* need_bytes);
+/* Which exact probe answers a sub-batch of R queries over rows of stride ld at top-k k and nprobe lists on cus compute units, computed
+ * without a device (tests): the queries the int8 coarse stage of an IVF probe could not certify, or a batch whose coarse stage could
+ * not run.  *path = 4: list-major probing (R >= 2 and the gather merge holds nprobe k-lists: nprobe * k <= 8192); 3: per-query
+ * probing; 0: neither has a plan -- the coarse stage is then not applicable either. */
+sc_status sc_diag_ivf_exact_path(int32_t ld, int32_t R, int32_t k, int32_t nprobe, int32_t cus, int32_t* path);
 
 /* Multi-GPU final step (one process per GPU): merge `lists` per-shard results
  * dist [lists,Q,k] / rows [lists,Q,k] (as produced by sc_index_search* on each shard and

@@ -163,6 +163,7 @@ SIGNATURES = {
     "sc_index_last_probe_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sc_diag_ivf_plan": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_int64, C.POINTER(C.c_int64)]),
+    "sc_diag_ivf_exact_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "sc_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_size_t]),
     "sc_comm_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "sc_comm_destroy": (C.c_int32, [C.c_void_p]),
@@ -1023,6 +1024,14 @@ def diag_ivf_plan(path: str, probes, list_off, k: int, ld: int, cus: int, wide: 
         out[name] = blob[at + 32:at + 32 + n * dt.itemsize].view(dt).copy()
         at += 32 + (n * dt.itemsize + 7) // 8 * 8
     return out
+
+
+def diag_ivf_exact_path(ld: int, R: int, k: int, nprobe: int, cus: int) -> str:
+    """The exact probe that answers a sub-batch of R queries the IVF coarse stage hands on (sc_diag_ivf_exact_path; no device):
+    "ivf_listmajor", "ivf" (per-query probing) or "none"."""
+    path = C.c_int32()
+    _check(lib().sc_diag_ivf_exact_path(int(ld), int(R), int(k), int(nprobe), int(cus), C.byref(path)))
+    return {0: "none", 3: "ivf", 4: "ivf_listmajor"}[path.value]
 
 
 def diag_set_option(name: str, value: int) -> None:

@@ -26,9 +26,15 @@ void sc_shadow_invalidate(sc_shadow& sh) {
     sh.dirty.clear();
 }
 
+void sc_shadow_free_maxima(sc_shadow& sh) {
+    if (sh.maxima) hipFree(sh.maxima);
+    sh.maxima = nullptr;
+    sc_shadow_invalidate(sh);
+}
+
 void sc_shadow_release(sc_shadow& sh) {
     for (sc_buf& a : sh.arr) sc_buf_free(a);
-    sc_shadow_invalidate(sh);
+    sc_shadow_free_maxima(sh);
 }
 
 void sc_invalidate_shadows(sc_index* ix) {

@@ -160,8 +160,10 @@ struct sc_index {
     sc_buf ivf_scratch;
     // int8 coarse stage of list-major probing (L2; ivf_coarse.hip): every list quantised relative to its centroid.
     // arr[0] = Xc8: [ivf_rows padded to 256][ld8] int8 of x - c_list; arr[1] = xcs: [rows][4] f32 per row: {|x - c_list|^2, int8 scale,
-    // 2 |dx|, 2 (|x'| + |dx|)}; rows == ivf_rows when valid; maxima = list_stats: [nlist][2] bits of {max |x' - xq|^2, max |x'|^2} + [4]
-    // bits of max |x|^2 behind them (allocated by ivfc_ensure_shadow, freed by sc_index_destroy only)
+    // 2 |dx|, 2 (|x'| + |dx|)}; rows == ivf_rows when valid; maxima = list_stats: [nlist_trained][2] bits of {max |x' - xq|^2, max |x'|^2}
+    // + [4] bits of max |x|^2 behind them (sc_ivfc_stats_words / sc_ivfc_xmax_slot below).  The TRAINED list count sizes it -- set_ivf and
+    // assign_lists install any number of lists, whatever `nlist` the handle was created with --, so it is allocated by the full build
+    // in ivfc_ensure_shadow and freed whenever lists are installed or dropped (sc_shadow_free_maxima).
     sc_shadow sh_c8;
     sc_shadow* const shadows[3] = {&sh_b16, &sh_i8, &sh_c8};
     static constexpr int64_t SC_SHADOW_DIRTY_MAX = 8192;
@@ -194,6 +196,9 @@ inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
 };
 
 static inline int sc_ld8(const sc_index* ix) { return (ix->ld + 127) / 128 * 128; }  // int8 row stride: whole 128-byte K-tiles
+// list_stats of the centred shadow (sc_index::sh_c8.maxima): two words per TRAINED list, then the bits of max |x|^2 (padded to 4 words)
+static inline size_t sc_ivfc_stats_words(int nlist_trained) { return (size_t)nlist_trained * 2 + 4; }
+static inline unsigned* sc_ivfc_xmax_slot(const sc_index* ix) { return ix->sh_c8.maxima + (size_t)ix->nlist_trained * 2; }
 // Offsets of the pieces of one scratch allocation, each 256-byte aligned: o = carve(bytes) ...; carve.off is the total to sc_grow.
 static inline size_t sc_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct sc_carver {
@@ -218,7 +223,8 @@ static inline bool sc_env_flag(const char* name, bool dflt) { const char* e = ge
 sc_status sc_grow(sc_index* ix, sc_buf& b, size_t need);  // grow a device scratch buffer: synchronises, contents not preserved
 void sc_buf_free(sc_buf& b);
 void sc_shadow_invalidate(sc_shadow& sh);  // stale: the next ensure builds it whole (which covers the pending rows)
-void sc_shadow_release(sc_shadow& sh);     // ... and its arrays are freed (the maxima stay)
+void sc_shadow_release(sc_shadow& sh);     // ... and its arrays and maxima are freed
+void sc_shadow_free_maxima(sc_shadow& sh); // the maxima alone (the centred shadow's are sized by the trained list count); invalidates
 void sc_invalidate_shadows(sc_index* ix);  // all three: the rows or their layout changed wholesale
 // rows[i] (ids, rows below old_n existed before) were written at stored position pos[i]: remember those the shadow covers
 void sc_shadow_note_overwritten(sc_shadow& sh, const int64_t* rows, const int64_t* pos, int64_t n, int64_t old_n);
@@ -261,7 +267,12 @@ sc_status sc_ivf_search_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
 bool sc_ivf_listmajor_applicable(const sc_index* ix, int Q, int k, int nprobe, bool flat_is_batched);
 sc_status sc_ivf_search_listmajor_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
 bool sc_ivf_coarse_applicable(const sc_index* ix, int Q, int k, int nprobe);
-sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
+// chunk: which 4 096-query chunk of its batch this call answers (the forced failure "ivf_coarse_nomem" = 2 reads it)
+sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows, int chunk = 0);
+// Which exact probe answers a sub-batch of R queries -- the queries the coarse stage could not certify, a batch whose coarse stage
+// could not run --: 4 list-major (two queries or more, and the gather merge holds nprobe k-lists), 3 per-query probing, 0 neither
+// has a plan for (ld, k, nprobe).  Plain arithmetic (sc_diag_ivf_exact_path, tests/test_ivf_plan_host.py).
+int sc_ivf_exact_probe_path(int ld, int R, int k, int nprobe, int cus);
 sc_status sc_ivf_untrain_locked(sc_index* ix);  // restore insertion order, drop lists
 void sc_ivf_drop_lists_locked(sc_index* ix);    // drop lists without restoring the order (the rows are about to be discarded)
 sc_status sc_ivf_cover_tail_locked(sc_index* ix);  // extend perm over rows appended since the build (identity): exhaustive search only

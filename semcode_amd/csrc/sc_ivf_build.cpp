@@ -66,6 +66,7 @@ void sc_ivf_drop_lists_locked(sc_index* ix) {
     ix->ivf_rows = 0;
     ix->trained = false;
     sc_invalidate_shadows(ix);  // (the centred shadow of the coarse stage mirrors the lists)
+    sc_shadow_free_maxima(ix->sh_c8);  // ... and its per-list statistics are sized by their number
     ix->ivfc_off = false;
 }
 
@@ -141,6 +142,7 @@ static sc_status ivf_install_lists_locked(sc_index* ix, int nlist, std::vector<i
     ix->dirty_rows.clear();
     ix->nlist_trained = nlist;
     sc_invalidate_shadows(ix);  // new lists (a re-train over the same rows included): the centred shadow too is rebuilt, on the next coarse probe
+    sc_shadow_free_maxima(ix->sh_c8);  // (its per-list statistics are sized by nlist_trained, which may have grown past what they hold)
     ix->ivfc_off = false;
     ix->uncert_frac = -1.0;
     ix->trained = true;

@@ -28,6 +28,8 @@ bool sc_ivf_coarse_applicable(const sc_index* ix, int Q, int k, int nprobe) {
     static const bool env_off = !sc_env_flag("SC_IVF_COARSE", true);
     if (ix->kind != SC_INDEX_IVF_FLAT || !ix->trained || !ix->quant || !ix->perm || (ix->metric != SC_METRIC_L2 && ix->metric != SC_METRIC_IP && ix->metric != SC_METRIC_COSINE)) return false;
     if (nprobe < 2 || nprobe > 512 || nprobe >= ix->nlist_trained || k < 1 || k > sc_batched_kprime8() / 2) return false;
+    // what the stage cannot certify is probed again exactly, one query or many: without a plan for either the whole batch would be refused
+    if (!sc_ivf_exact_probe_path(ix->ld, 1, k, nprobe, ix->rt->cus) || !sc_ivf_exact_probe_path(ix->ld, 2, k, nprobe, ix->rt->cus)) return false;
     if (ix->search_mode == 5) return Q >= 1;
     if (ix->search_mode != 0 || env_off || ix->ivfc_off) return false;
     // auto: any batch over a corpus worth a shadow.  The first rule here (Q >= 64 and Q nprobe >= nlist: "every list wanted by several
@@ -43,7 +45,9 @@ bool sc_ivf_coarse_applicable(const sc_index* ix, int Q, int k, int nprobe) {
     return probed_bytes >= 1.0e9;
 }
 
-static int g_ivfc_nomem = 0;  // sc_diag_set_option("ivf_coarse_nomem", 1): the centred shadow cannot be allocated (tests of the fallback to the exact probe)
+// sc_diag_set_option("ivf_coarse_nomem", 1): the centred shadow cannot be allocated; 2: the stage runs out of memory from the second
+// 4 096-query chunk of a batch on (tests of the fallbacks to the exact probes)
+static int g_ivfc_nomem = 0;
 void sc_ivf_set_coarse_nomem(int v) { g_ivfc_nomem = v; }
 static sc_status ivfc_ensure_shadow(sc_index* ix) {
     sc_shadow& sh = ix->sh_c8;  // arr = {Xc8, xcs}, maxima = list_stats
@@ -64,7 +68,7 @@ static sc_status ivfc_ensure_shadow(sc_index* ix) {
             SC_HIP(hipMemcpyAsync(ix->stage.p, d.data(), d.size() * 8, hipMemcpyHostToDevice, s));
             sc_launch_ivf_center_shadow(ix->X, (int64_t)d.size(), ix->ld, ld8, ix->quant->X, ix->quant->ld, ix->list_off, nlist, sh.arr[0].p, sh.arr[1].as<float>(),
                                         sh.maxima, s, unit ? ix->xnorm : nullptr, unit ? ix->quant->xnorm : nullptr, ix->stage.as<int64_t>());
-            sc_launch_norm_max(ix->xnorm, sh.rows, sh.maxima + (size_t)ix->nlist * 2, s);
+            sc_launch_norm_max(ix->xnorm, sh.rows, sc_ivfc_xmax_slot(ix), s);
             SC_HIP(hipGetLastError());
             SC_HIP(hipStreamSynchronize(s));  // (the position list is a host temporary behind an asynchronous copy)
         }
@@ -72,29 +76,34 @@ static sc_status ivfc_ensure_shadow(sc_index* ix) {
         return SC_OK;
     }
     sh.dirty.clear();  // a full build covers them
-    if (g_ivfc_nomem) return sc_fail(SC_ERR_NOMEM, "ivf coarse stage: out of device memory (forced by sc_diag_set_option)");
+    if (g_ivfc_nomem == 1) return sc_fail(SC_ERR_NOMEM, "ivf coarse stage: out of device memory (forced by sc_diag_set_option)");
     const int64_t rows = ix->ivf_rows, rows_pad = (rows + 255) / 256 * 256 + sh.tail_pad;
     for (int i = 0; i < 2; ++i) {
         const sc_status st = sc_grow(ix, sh.arr[i], (size_t)rows_pad * sh.row_bytes[i]);
         if (st) return st;
     }
-    if (!sh.maxima) SC_HIP(hipMalloc((void**)&sh.maxima, ((size_t)ix->nlist * 2 + 4) * 4));
-    SC_HIP(hipMemsetAsync(sh.maxima, 0, ((size_t)ix->nlist * 2 + 4) * 4, s));
+    // (the statistics were freed with the lists they described -- ivf_install_lists_locked --, so a buffer found here has nlist words)
+    if (!sh.maxima && hipMalloc((void**)&sh.maxima, sc_ivfc_stats_words(nlist) * 4) != hipSuccess) {
+        sh.maxima = nullptr;
+        return sc_fail(SC_ERR_NOMEM, "ivf coarse stage: hipMalloc of the per-list statistics (%d lists) failed", nlist);
+    }
+    SC_HIP(hipMemsetAsync(sh.maxima, 0, sc_ivfc_stats_words(nlist) * 4, s));
     for (int i = 0; i < 2; ++i)
         SC_HIP(hipMemsetAsync(sh.arr[i].as<char>() + (size_t)rows * sh.row_bytes[i], 0, (size_t)(rows_pad - rows) * sh.row_bytes[i], s));
     sc_launch_ivf_center_shadow(ix->X, rows, ix->ld, ld8, ix->quant->X, ix->quant->ld, ix->list_off, nlist, sh.arr[0].p, sh.arr[1].as<float>(), sh.maxima, s,
                                 unit ? ix->xnorm : nullptr, unit ? ix->quant->xnorm : nullptr);
-    sc_launch_norm_max(ix->xnorm, rows, sh.maxima + (size_t)ix->nlist * 2, s);  // bits of max |x|^2: the re-rank's rounding allowance
+    sc_launch_norm_max(ix->xnorm, rows, sc_ivfc_xmax_slot(ix), s);  // bits of max |x|^2: the re-rank's rounding allowance
     SC_HIP(hipGetLastError());
     sh.rows = rows;
     return SC_OK;
 }
 
-sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows) {
+sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows, int chunk) {
     sc_runtime* rt = ix->rt;
     hipStream_t s = rt->stream;
     sc_index* qz = ix->quant;
     const int ld = ix->ld, ld8 = sc_ld8(ix);
+    if (g_ivfc_nomem == 2 && chunk >= 1) return sc_fail(SC_ERR_NOMEM, "ivf coarse stage: out of device memory at chunk %d (forced by sc_diag_set_option)", chunk);
     sc_status st = ivfc_ensure_shadow(ix);
     if (st) return st;
     // 1. coarse probe (the quantizer's own search) -> host; the probes stay in ivf_scratch, which the exact re-probe below reuses
@@ -157,7 +166,7 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
     // phase A is dense: every row of its lists survives, at a known place of survA; the counts are known here
     SC_HIP(hipMemcpyAsync(cnt, cntA.data(), (size_t)Q * 4, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(cntA_d, cntA.data(), (size_t)Q * 4, hipMemcpyHostToDevice, s));
-    const unsigned* xmax_bits = list_stats + (size_t)ix->nlist * 2;  // bits of max |x|^2: the rounding allowance of the exact scores
+    const unsigned* xmax_bits = sc_ivfc_xmax_slot(ix);  // bits of max |x|^2: the rounding allowance of the exact scores
     hipEvent_t e0, e1;
     // 4. phase A: lower bounds of the nearest list(s) -> the kpa best re-scored exactly -> T = their k-th exact distance + allowance
     if (!items[0].empty()) {
@@ -263,7 +272,9 @@ sc_status sc_ivf_search_coarse_locked(sc_index* ix, const float* q_dev, int32_t 
         if (st) return st;
         {
             sc_scoped_set<int> mode(ix->search_mode, 4);
-            if (R >= 2) st = sc_ivf_search_listmajor_locked(ix, sb.q, R, k, nprobe, sb.d, sb.r);
+            // list-major where it has a plan, per-query probing where not (nprobe * k beyond the gather merge; one query): the same
+            // lists either way, so every query of the batch is answered under probe semantics (sc_ivf_coarse_applicable: one of them serves)
+            if (sc_ivf_exact_probe_path(ld, R, k, nprobe, rt->cus) == 4) st = sc_ivf_search_listmajor_locked(ix, sb.q, R, k, nprobe, sb.d, sb.r);
             else st = sc_ivf_search_locked(ix, sb.q, R, k, nprobe, sb.d, sb.r);
         }
         if (st) return st;

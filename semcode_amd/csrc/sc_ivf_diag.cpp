@@ -28,6 +28,12 @@ struct Blob {
 };
 }  // namespace
 
+extern "C" sc_status sc_diag_ivf_exact_path(int32_t ld, int32_t R, int32_t k, int32_t nprobe, int32_t cus, int32_t* path) {
+    if (!path || cus < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_ivf_exact_path: bad argument");
+    *path = sc_ivf_exact_probe_path(ld, R, k, nprobe, cus);
+    return SC_OK;
+}
+
 extern "C" sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, int32_t Q, int32_t nprobe, const int64_t* list_off, int32_t nlist, int32_t k,
                                       int32_t ld, int32_t cus, int32_t wide, void* out, int64_t cap_bytes, int64_t* need_bytes) {
     if (!path || !probes || !list_off || !need_bytes || Q < 1 || nprobe < 1 || nlist < 1 || cus < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_ivf_plan: bad argument");

@@ -108,6 +108,14 @@ bool sc_ivf_plan_params(int ld, int k, int nprobe, int cus, IvfPlanParams* pp, S
     return true;
 }
 
+int sc_ivf_exact_probe_path(int ld, int R, int k, int nprobe, int cus) {
+    if (R < 1 || nprobe < 1 || nprobe > 512) return 0;
+    IvfPlanParams pp;
+    if (R >= 2 && sc_ivf_plan_params(ld, k, nprobe, cus, &pp)) return 4;
+    ScanPlan plan;
+    return sc_scan_exact_plan(ld, R, k, cus, &plan, 1, nprobe) ? 3 : 0;  // (as sc_ivf_search_locked plans it)
+}
+
 bool sc_ivf_listmajor_applicable(const sc_index* ix, int Q, int k, int nprobe, bool flat_is_batched) {
     if (ix->kind != SC_INDEX_IVF_FLAT || !ix->trained || !ix->quant || Q < 2) return false;
     if (nprobe < 1 || nprobe > 512 || nprobe >= ix->nlist_trained || (ix->search_mode >= 1 && ix->search_mode <= 3)) return false;

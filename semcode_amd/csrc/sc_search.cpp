@@ -419,7 +419,7 @@ sc_status sc_search_flat_locked(sc_index* ix, const float* q_dev, int32_t Q, int
 static int64_t g_ivf_tail_rows = 65536;  // sc_diag_set_option("ivf_tail_rows", n): appended rows a trained index leaves behind its lists (0: fold them in at once)
 void sc_set_ivf_tail_rows(int v) { g_ivf_tail_rows = v < 0 ? 65536 : v; }
 
-static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows);
+static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows, bool tail_merged);
 
 sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows) {
     ix->last_probed_lists = 0;
@@ -452,7 +452,7 @@ sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
             char* tb = ix->tailbuf.as<char>();
             float *d1 = (float*)tb, *d2 = (float*)(tb + db);
             int64_t *r1 = (int64_t*)(tb + 2 * db), *r2 = (int64_t*)(tb + 2 * db + rb);
-            st = probe_dispatch_locked(ix, q_dev, Q, k, nprobe, d1, r1);
+            st = probe_dispatch_locked(ix, q_dev, Q, k, nprobe, d1, r1, true);  // (the lists alone: topk_merge2 joins disjoint rows)
             if (st) return st;
             const int path = ix->last_path, unc = ix->last_uncertified;
             st = search_exact_locked(ix, q_dev, Q, k, ix->ivf_rows, tail, nullptr, d2, r2);  // (positions there are row ids)
@@ -476,11 +476,13 @@ sc_status sc_search_dev_locked(sc_index* ix, const float* q_dev, int32_t Q, int3
         }
         if (rst) return rst;
     }
-    return probe_dispatch_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
+    return probe_dispatch_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows, false);
 }
 
-// which path answers (the lists cover every stored row, or the caller takes care of the tail)
-static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows) {
+// which path answers.  tail_merged: rows lie behind the lists and the caller merges an exact scan of them into what this returns, so
+// the answer must come from the lists alone -- never from a scan that covers the tail as well, whose rows would enter the merge twice.
+static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist, int64_t* out_rows, bool tail_merged) {
+    bool lists_only = tail_merged;  // ... or the first chunks of the batch were probed: the rest is probed too, not scanned exhaustively
     if (!sc_ivf_coarse_applicable(ix, Q, k, nprobe) && sc_ivf_applicable(ix, Q, nprobe)) return sc_ivf_search_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
     if (sc_ivf_coarse_applicable(ix, Q, k, nprobe)) {
         // per-query scratch of the coarse stage is ~200 KB (two survivor lists of 8 192 keys, the refine sets): very large batches go
@@ -491,14 +493,17 @@ static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t
         int groups = 0;
         for (int q0 = 0; q0 < Q; q0 += chunk) {
             const int nq = std::min(chunk, Q - q0);
-            const sc_status st = sc_ivf_search_coarse_locked(ix, q_dev + (size_t)q0 * ix->dim, nq, k, nprobe, out_dist + (size_t)q0 * k, out_rows + (size_t)q0 * k);
-            if (st == SC_ERR_NOMEM && q0 == 0) {
-                // no room for the centred shadow (a quarter of the corpus again) or the stage's scratch: the exact probes need neither.
+            const sc_status st = sc_ivf_search_coarse_locked(ix, q_dev + (size_t)q0 * ix->dim, nq, k, nprobe, out_dist + (size_t)q0 * k, out_rows + (size_t)q0 * k, q0 / chunk);
+            if (st == SC_ERR_NOMEM) {
+                // no room for the centred shadow (a quarter of the corpus again) or the stage's scratch: the exact probes need neither, and
+                // they answer this chunk and the ones behind it (the chunks before it are answered already: same results either way).
                 // The stage stays off until the lists are rebuilt (a failed hipMalloc of tens of GB per search is not free either).
                 (void)hipGetLastError();
                 ix->ivfc_off = true;
                 sc_shadow_release(ix->sh_c8);
                 sc_buf_free(ix->ivfc_scratch);
+                q_dev += (size_t)q0 * ix->dim, out_dist += (size_t)q0 * k, out_rows += (size_t)q0 * k, Q -= q0;
+                if (q0 > 0) lists_only = true;
                 goto exact_probe;
             }
             if (st) return st;
@@ -516,7 +521,13 @@ static sc_status probe_dispatch_locked(sc_index* ix, const float* q_dev, int32_t
 exact_probe:
     if (sc_ivf_listmajor_applicable(ix, Q, k, nprobe, batched_applicable(ix, Q, k)))
         return sc_ivf_search_listmajor_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
-    return sc_search_exhaustive_locked(ix, q_dev, Q, k, out_dist, out_rows);  // (a tail behind the lists is scanned as one)
+    if (lists_only) {  // list-major has no plan here or was not the cheaper choice: the lists are probed all the same
+        const int path = sc_ivf_exact_probe_path(ix->ld, Q, k, nprobe, ix->rt->cus);
+        if (path == 4) return sc_ivf_search_listmajor_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
+        if (path == 3) return sc_ivf_search_locked(ix, q_dev, Q, k, nprobe, out_dist, out_rows);
+        return sc_fail(SC_ERR_UNSUPPORTED, "ivf search: k=%d / dim=%d / nprobe=%d not supported by an exact probe", k, ix->dim, nprobe);
+    }
+    return sc_search_exhaustive_locked(ix, q_dev, Q, k, out_dist, out_rows);  // (no tail is merged behind this: every stored row is scanned once)
 }
 
 extern "C" sc_status sc_index_search_dev(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, int32_t nprobe, float* out_dist_dev,

@@ -262,6 +262,32 @@ def test_cases_differ_where_they_should(nv):
     assert scalar(b, "G_big") == 0 and 0 < scalar(c, "G_big") < scalar(c, "G")
 
 
+@pytest.mark.parametrize("ld", [64, 768, 3072])
+@pytest.mark.parametrize("R", [1, 2, 300])
+def test_exact_path_of_a_sub_batch(nv, ld, R):
+    """The queries the coarse stage cannot certify are probed again exactly: list-major from two queries on while the gather merge
+    holds a query's nprobe k-lists (2 * nprobe * k keys of 8 bytes in 128 KiB: nprobe * k <= 8192), per-query probing otherwise --
+    which plans one query at a time and whose segment table (20 bytes per probe) and candidate lists (k + 16 rounded up to 64 keys
+    per wave) stay far below the scan's 160 KiB at k <= 256, nprobe <= 512, so over the coarse stage's whole range some exact probe
+    serves and no batch is refused for its uncertified queries.  The rule and the list-major planner itself agree on where that
+    planner has a plan."""
+    off = np.array([0, 100], np.int64)  # one list of 100 rows, which every query probes
+    for k in (1, 64, 128, 129, 256):
+        for nprobe in (2, 32, 64, 512):
+            want = "ivf_listmajor" if R >= 2 and nprobe * k <= 8192 else "ivf"
+            assert nv.diag_ivf_exact_path(ld, R, k, nprobe, CUS) == want, (ld, R, k, nprobe)
+            pr = np.zeros((max(R, 2), nprobe), np.int64)
+            if nprobe * k <= 8192:
+                nv.diag_ivf_plan("listmajor", pr, off, k, ld, CUS)
+            else:
+                with pytest.raises(nv.ScError) as e:
+                    nv.diag_ivf_plan("listmajor", pr, off, k, ld, CUS)
+                assert e.value.status == -4  # SC_ERR_UNSUPPORTED
+    # outside what any probe accepts: no path, so the coarse stage must not take the request either
+    assert nv.diag_ivf_exact_path(ld, R, 10, 513, CUS) == "none" and nv.diag_ivf_exact_path(ld, R, 1025, 8, CUS) == "none"
+    assert nv.diag_ivf_exact_path(ld, 0, 10, 8, CUS) == "none"
+
+
 if __name__ == "__main__":
     if sys.argv[1:] != ["--record"]:
         sys.exit(__doc__)

@@ -125,3 +125,36 @@ def test_random_collection_operations(rt, tmp_path, metric, index_type):
             assert np.array_equal(r0[0], rows[0])
     assert searches >= 5
     store.close()
+
+
+def test_collection_saved_with_more_lists_than_the_loading_store_is_configured_for(rt, tmp_path):
+    """save() records the trained list count and load() installs the saved lists as they are, whatever nlist the loading store was
+    configured with: 64 lists on a handle created for 16.  Every probe path must index its per-list state by the trained count."""
+    rng = np.random.default_rng(77)
+    centers = rng.standard_normal((30, DIM)).astype(np.float32)
+    X = (centers[rng.integers(0, 30, size=6000)] + 0.35 * rng.standard_normal((6000, DIM))).astype(np.float32)
+    q = (centers[rng.integers(0, 30, size=50)] + 0.3 * rng.standard_normal((50, DIM))).astype(np.float32)
+    meta = {"repo": "r", "path": "p", "language": "py", "start_line": 1, "end_line": 2, "symbol": None}
+    store = MilvusVectorStore(dim=DIM, metric="L2", index_type="IVF_FLAT", nlist=64, nprobe=8, runtime=rt)
+    store.connect()
+    store.upsert_embeddings([EmbeddingPayload(id=f"k{i}", text=f"t{i}", vector=X[i].tolist(), metadata=dict(meta, path=f"k{i}")) for i in range(len(X))])
+    store.build_index(niter=3)
+    assert store._collection.ivf_info()["nlist"] == 64
+    before = {}
+    for mode in ("ivf", "ivf_listmajor", "ivf_coarse"):
+        store._collection.set_search_mode(mode)
+        before[mode] = store.search_batch(q, top_k=10)
+        assert store._collection.last_search_stats()["path"] == mode
+    store.save(tmp_path / "c64")
+    store.close()
+    store = MilvusVectorStore(dim=DIM, metric="L2", index_type="IVF_FLAT", nlist=16, nprobe=8, runtime=rt)
+    store.connect()
+    store.load(tmp_path / "c64")
+    assert store._collection.ivf_info()["nlist"] == 64
+    for mode in ("ivf_coarse", "ivf_listmajor", "ivf"):
+        store._collection.set_search_mode(mode)
+        dist, rows = store.search_batch(q, top_k=10)
+        assert store._collection.last_search_stats()["path"] == mode
+        assert np.array_equal(rows, before[mode][1]) and np.array_equal(bits(dist), bits(before[mode][0])), mode
+        assert np.array_equal(rows, before["ivf"][1]) and np.array_equal(bits(dist), bits(before["ivf"][0])), mode
+    store.close()
