@@ -137,6 +137,18 @@ sc_status sc_encoder_info(sc_encoder* enc, sc_encoder_cfg* cfg_out);
  * consuming one: no LayerNorm kernel); smaller batches -- a query -- run split-K GEMMs with stand-alone LayerNorm kernels.
  * path 0 = that rule, 1 = the batch pipeline for every size, 2 = the small-batch pipeline for every size (tests, A/B runs). */
 sc_status sc_encoder_set_path(sc_encoder* enc, int32_t path);
+/* How a text's vector is taken from the last hidden state: pooling 0 (the default) = the masked mean over its real tokens; 1 = the
+ * row of its first token, [CLS] (llama.cpp's pooling type 2: BAAI/bge-*-en-v1.5, snowflake-arctic-embed-*, mxbai-embed-large, gte-*).
+ * With pooling 1 every embedding entry point -- sc_encoder_embed_ids, _dev, _into, _into_async, sc_encoder_embed_packed, _into,
+ * _into_async, both pipelines -- returns the last hidden state, after its LayerNorm, of row i * S (rectangles) or of the text's first
+ * packed row, L2-normalised when cfg.normalize is set by the rule of the mean kernels (x / max(|x|, 1e-12)).  The last LayerNorm then
+ * runs on B rows (cls_rows_kernel, f32), and -- unless "cls_prune" of sc_diag_set_option is 0 -- so does the last layer behind its QKV
+ * projection: attention of the one query row per text (attention_cls_kernel), output projection and feed-forward on ceil256(B)
+ * compact rows.  Pruned and unpruned vectors agree to bf16 rounding, not bit for bit; a text's vector does not depend on its
+ * batch-mates either way.  The mode takes effect with the next call; any other value is SC_ERR_INVALID and changes nothing.
+ * sc_encoder_score_pairs does not read the mode. */
+sc_status sc_encoder_set_pooling(sc_encoder* enc, int32_t pooling);
+sc_status sc_encoder_get_pooling(sc_encoder* enc, int32_t* out);
 /* Replaces Embeddings.embed_documents / embed_query after tokenisation (indexer.py:150,
  * pipeline.py:171-175): ids [B,S] int32 (S in {32,64,128,256,512}, padded by the caller), lens [B] =
  * number of real tokens per row (keys >= len are masked, pooling = mean over the first len tokens),
@@ -208,7 +220,8 @@ sc_status sc_encoder_embed_packed_into_async(sc_encoder* enc, const int32_t* ids
  * a pair shorter than 2 or longer than 2 048 tokens, or longer than max_pos for models with a position or rotary table,
  * first_lens[i] outside 1 .. len_i, a second segment (first_lens[i] < len_i) on a model with type_vocab < 2, num_labels outside
  * 1 .. 2.  SC_ERR_UNSUPPORTED: more than SC_ENCODER_PACKED_MAX_ROWS token rows (size batches with sc_encoder_packed_rows).
- * Out of scope: CLS-pooled embedding models, heads other than pooler + linear (Electra), more than 2 labels, an asynchronous or
+ * [CLS]-pooled embedding models are sc_encoder_set_pooling's business, not the head's: pairs ignore that mode, embeds ignore the head.
+ * Out of scope: heads other than pooler + linear (Electra), more than 2 labels, an asynchronous or
  * device-pointer form.  ALiBi and rotary models with type_vocab >= 2 run, but no reference pins their result. */
 sc_status sc_encoder_set_pair_head(sc_encoder* enc, const float* pooler_w /*[H,H]*/, const float* pooler_b /*[H]*/,
                                    const float* cls_w /*[num_labels,H]*/, const float* cls_b /*[num_labels]*/, int32_t num_labels);
@@ -329,6 +342,14 @@ sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* 
                                int32_t blocked_rows, const float* slopes, float* out);
 sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
                                       int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out);
+/* "cls_prune" of sc_diag_set_option: the last layer of a [CLS]-pooled forward (-1 = default: pruned, 0 = the full last layer over every
+ * token row, 1 = on the [CLS] rows only).
+ * sc_diag_attention_cls: attention_cls_kernel on its own, rectangle form.  qkv [B*S][3*heads*head_dim] row-major f32 (the harness lays it
+ * out in 64-column blocks, as the QKV projection does), lens [B] clamped to 1 .. S, S <= 2048, head_dim 64 or 32 (an even number of
+ * heads), alibi NULL or [heads] slopes (both head widths) -> out [B, heads*head_dim] = softmax(q_0 K^T / sqrt(head_dim) - slope_h j) V of
+ * each text's first row. */
+sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                                const float* alibi, float* out);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,

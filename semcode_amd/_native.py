@@ -62,6 +62,8 @@ SIGNATURES = {
     "sc_encoder_create": (C.c_int32, [C.c_void_p, C.POINTER(EncoderCfg), C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "sc_encoder_destroy": (C.c_int32, [C.c_void_p]),
     "sc_encoder_set_path": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "sc_encoder_set_pooling": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "sc_encoder_get_pooling": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
     "sc_encoder_info": (C.c_int32, [C.c_void_p, C.POINTER(EncoderCfg)]),
     "sc_encoder_embed_ids": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_encoder_embed_ids_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -98,6 +100,7 @@ SIGNATURES = {
     "sc_diag_attention_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_cls": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -780,13 +783,17 @@ class Comm:
 
 BERT_BASE = dict(vocab=30522, hidden=768, layers=12, heads=12, ffn=3072, max_pos=512, type_vocab=2, ln_eps=1e-12)
 SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: ALiBi or rotary encoders (no position table), or a position table that long
+POOLINGS = {"mean": 0, "cls": 1}  # sc_encoder_set_pooling
 
 
 class Encoder:
-    """Transformer-encoder forward on the device (sc_encoder): token ids in, pooled f32 vectors out."""
+    """Transformer-encoder forward on the device (sc_encoder): token ids in, pooled f32 vectors out.  pooling: "mean" (masked mean over
+    the real tokens) or "cls" (the last hidden state of the first token: bge, arctic-embed, mxbai, gte)."""
 
     def __init__(self, rt: Runtime, cfg: dict | None = None, weights: np.ndarray | None = None, normalize: bool = False,
-                 synth_seed: int = 0):
+                 synth_seed: int = 0, pooling: str = "mean"):
+        if pooling not in POOLINGS:
+            raise ValueError(f"encoder pooling must be one of {sorted(POOLINGS)}, got {pooling!r}")
         c = dict(BERT_BASE)
         c.update(cfg or {})
         if c.get("rotary") and c.get("alibi"):
@@ -810,6 +817,20 @@ class Encoder:
             _check(lib().sc_encoder_create(rt.handle, C.byref(self.cfg), w.ctypes.data_as(C.c_void_p), w.nbytes, C.byref(self._h)))
         else:
             _check(lib().sc_encoder_create(rt.handle, C.byref(self.cfg), None, 0, C.byref(self._h)))
+        if pooling != "mean":
+            self.pooling = pooling
+
+    @property
+    def pooling(self) -> str:
+        v = C.c_int32()
+        _check(lib().sc_encoder_get_pooling(self.handle, C.byref(v)))
+        return next(k for k, n in POOLINGS.items() if n == v.value)
+
+    @pooling.setter
+    def pooling(self, mode: str) -> None:
+        if mode not in POOLINGS:
+            raise ValueError(f"encoder pooling must be one of {sorted(POOLINGS)}, got {mode!r}")
+        _check(lib().sc_encoder_set_pooling(self.handle, POOLINGS[mode]))
 
     def close(self) -> None:
         if self._h:
@@ -1178,6 +1199,19 @@ def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocke
         _check(lib().sc_diag_attention_hd(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(head_dim), int(blocked_rows), _ptr(sl), _ptr(out)))
     else:
         _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    return out
+
+
+def diag_attention_cls(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, slopes=None) -> np.ndarray:
+    """attention_cls_kernel on its own: qkv [B*S, 3H] row-major, one query row per text (its first) -> [B, H], H = heads * head_dim."""
+    qkv = _f32(qkv)
+    lens = np.ascontiguousarray(lens, np.int32)
+    H = heads * head_dim
+    if qkv.shape != (B * S, 3 * H) or lens.shape != (B,):
+        raise ValueError("qkv must be [B*S, 3*heads*head_dim] and lens [B]")
+    sl = None if slopes is None else _f32(slopes)
+    out = np.full((B, H), np.nan, np.float32)
+    _check(lib().sc_diag_attention_cls(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(head_dim), _ptr(sl), _ptr(out)))
     return out
 
 

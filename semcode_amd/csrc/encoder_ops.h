@@ -90,6 +90,18 @@ bool sc_pair_head_supported(int H, int num_labels);
 void sc_launch_pair_head(const float* cls, int B, int H, const float* Wp, const float* bp, const float* Wc, const float* bc, int num_labels, float* logits,
                          hipStream_t s);
 
+// ---- encoder_cls.hip: [CLS] pooling.  starts NULL: text i's first row is i * S (a rectangle), else starts[i] (packed rows).
+// cls_pool: that row of x [rows, H] bf16 -> out [B, H] f32; gamma / beta non-NULL: the rows are raw and are LayerNorm'ed (f32) first; normalize:
+// L2 normalisation by the rule of the mean kernels.  cls_gather: the same rows (optionally LayerNorm'ed) as bf16 [rows_pad, H], rows B .. rows_pad zero.
+// attention_cls: one query row per text (its first) over the text's lens[i] keys (rectangles: clamped to 1 .. S; at most 2048), qkv in 64-column
+// blocks of M rows, head_dim 64 or 32, slopes NULL or [heads] -> ctx [rows_pad, H] bf16 row-major, rows B .. rows_pad zero.
+void sc_launch_cls_pool(const void* x, const int32_t* starts, int B, int S, int H, const float* gamma, const float* beta, float eps, int normalize, float* out,
+                        hipStream_t s);
+void sc_launch_cls_gather(const void* x, const int32_t* starts, int B, int S, int H, const float* gamma, const float* beta, float eps, void* out, int rows_pad,
+                          hipStream_t s);
+void sc_launch_attention_cls(const void* qkv, const int32_t* starts, const int32_t* lens, int B, int S, int M, int H, int head_dim, const float* slopes, void* ctx,
+                             int rows_pad, hipStream_t s);
+
 // ---- sc_encoder.cpp: the attention work items of packed sequences (host): per sequence one item for every 8 query blocks of 32 rows
 // (class 0) or one item (classes 1, 2), written as {start, len, first query block, 0} in class order.  items must hold
 // sc_packed_items_cap(rows, B) items.

@@ -6,7 +6,8 @@
 // the boundary (semcode_amd/embeddings/tokenizer.py).
 //
 // Forward per layer (BERT, post-LN):  QKV = X Wqkv^T + b  ->  attention  ->  Y = ctx Wo^T + bo + X
-//   -> X1 = LN(Y) -> Hm = gelu(X1 W1^T + b1) -> Y2 = Hm W2^T + b2 + X1 -> X = LN(Y2); pooled = masked mean.
+//   -> X1 = LN(Y) -> Hm = gelu(X1 W1^T + b1) -> Y2 = Hm W2^T + b2 + X1 -> X = LN(Y2); pooled = masked mean, or (sc_encoder_set_pooling 1)
+//   the [CLS] row -- the last layer then runs on the [CLS] rows only from its attention on (cls_last_layer, encoder_cls.hip).
 // Activations bf16 in HBM ([tokens, H] row-major, tokens padded to 128), weights bf16 [out, in],
 // biases / LayerNorm parameters / embedding tables f32.
 // Pairs of a cross-encoder (sc_encoder_set_pair_head / sc_encoder_score_pairs) run the packed forward with a segment id per row and
@@ -62,6 +63,7 @@ struct sc_encoder {
     float *fin_a = nullptr, *fin_b = nullptr;    // [ws_tokens][2] their finalised (mu, rs)
     bool foldable = false;                       // shapes allow the folded pipeline (256-tile GEMMs, K % 256 == 0)
     int path = 0;                                // sc_encoder_set_path: 0 auto, 1 batch pipeline always, 2 small-batch pipeline always
+    int pooling = 0;                             // sc_encoder_set_pooling: 0 masked mean, 1 the [CLS] row
     void* splitk = nullptr;  // f32 partial products of the split-K GEMMs (batches of <= 1024 tokens), allocated on first use
     static constexpr size_t SPLITK_BYTES = 64u << 20;
     // pinned host staging for the asynchronous embed -> index path: ids | lens | rows of one batch per slot
@@ -150,6 +152,11 @@ static void launch_gate(const sc_encoder_cfg& c, const void* h, int64_t tokens, 
 static int g_rope_fused = -1;
 static const int ROPE_FUSED_DEFAULT = 1;
 void sc_encoder_set_rope_fused(int v) { g_rope_fused = v < 0 ? -1 : (v ? 1 : 0); }
+// [CLS] pooling: the last layer on the [CLS] rows only ("cls_prune" of sc_diag_set_option): -1 = default, 0 = the full last layer, 1 = pruned
+static int g_cls_prune = -1;
+static const int CLS_PRUNE_DEFAULT = 1;
+void sc_encoder_set_cls_prune(int v) { g_cls_prune = v < 0 ? -1 : (v ? 1 : 0); }
+static bool cls_prune_enabled() { return (g_cls_prune < 0 ? CLS_PRUNE_DEFAULT : g_cls_prune) != 0; }
 // SC_FFN_BLOCKED=0: row-major FFN hidden activations (same-box A/B against the 64-column blocks)
 static bool ffn_blocked_enabled() { static const bool on = sc_env_flag("SC_FFN_BLOCKED", true); return on; }
 
@@ -421,6 +428,43 @@ static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int 
     if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
     else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
 }
+// [CLS] pooling applies to texts only: the pairs of a cross-encoder take their [CLS] row whatever the mode (PackedLayout::types)
+static bool cls_pooling(const sc_encoder* e, const PackedLayout* pk) { return e->pooling == 1 && !(pk && pk->types); }
+// The last layer of a [CLS]-pooled forward from its QKV projection (e->qkv, rotated) on: attention of each text's first row, that row of the
+// layer's input as the residual, then the rest of the layer on Mc = ceil256(B) compact rows with the small-batch pipeline's launches, and the
+// last LayerNorm inside the pooling kernel.  e->x: the layer's input, normalised, or (res_g != NULL) raw with the LayerNorm (res_g, res_b) pending.
+// Buffers: ctx, x1, y, hm, hg are free at this point; every one holds at least M >= Mc rows.
+static sc_status cls_last_layer(sc_encoder* e, const LayerW& w, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, const float* res_g,
+                                const float* res_b, float* out_dev) {
+    const sc_encoder_cfg& c = e->cfg;
+    sc_runtime* rt = e->rt;
+    hipStream_t s = rt->stream;
+    const int H = c.hidden, F = c.ffn, Mc = (B + 255) / 256 * 256;
+    const int32_t* starts = pk ? pk->starts : nullptr;
+    void* sk = nullptr;
+    if (Mc <= 1024 && e->path != 1) {
+        if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
+        sk = e->splitk;
+    }
+    const size_t skb = sk ? sc_encoder::SPLITK_BYTES : 0;
+    sc_with_prof(rt, SC_PROF_ATTN, [&] { sc_launch_attention_cls(e->qkv, starts, lens_dev, B, S, M, H, H / c.heads, e->slopes, e->ctx, Mc, s); });
+    sc_launch_cls_gather(e->x, starts, B, S, H, res_g, res_b, c.ln_eps, e->x1, Mc, s);
+    sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x1, H, e->y, H, Mc, H, H, s, sk, skb); });
+    sc_launch_layernorm(e->y, Mc, H, w.ln1g, w.ln1b, c.ln_eps, e->x1, s);
+    const void* ffn_in = e->hm;
+    sc_with_prof(rt, SC_PROF_GEMM, [&] {
+        if (ffn_gated(c)) sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, Mc, 2 * F, H, s, sk, skb);
+        else sc_launch_gemm_bf16(EPI_BIAS_GELU, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, F, Mc, F, H, s, sk, skb);
+    });
+    if (ffn_gated(c)) {
+        launch_gate(c, e->hm, Mc, F, e->hg, s);
+        ffn_in = e->hg;
+    }
+    sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, F, w.w2, F, w.b2, e->x1, H, e->y, H, Mc, H, F, s, sk, skb); });
+    sc_launch_cls_pool(e->y, nullptr, B, 1, H, w.ln2g, w.ln2b, c.ln_eps, c.normalize, out_dev, s);  // compact rows: text i's row is i
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
 static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
     if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, pk->types ? 0 : e->cfg.normalize, out_dev, s);
     else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, e->cfg.normalize, out_dev, s);
@@ -451,6 +495,7 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !gated && ffn_blocked_enabled();
     const bool rope = c.pos_type == 2, rope_fused = rope && !pk && (g_rope_fused < 0 ? ROPE_FUSED_DEFAULT : g_rope_fused) != 0;
+    const bool cls = cls_pooling(e, pk), prune = cls && cls_prune_enabled();
     if (pk && pk->types)
         sc_launch_embed_raw_pairs(ids_dev, pk->pos, pk->types, tokens, M, H, c.vocab, c.max_pos, c.type_vocab, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
     else if (pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->x, e->stat_b, slots, s);
@@ -466,6 +511,8 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
                                        nullptr, c.ln_eps);
         });
         if (rope && !rope_fused) launch_rope(e, M, S, pk, s);
+        if (prune && l == c.layers - 1)  // the residual rows: LayerNorm of the raw rows by the LayerNorm in front of this layer
+            return cls_last_layer(e, w, lens_dev, B, S, M, pk, w.g_prev, l == 0 ? e->embb : e->layers[l - 1].ln2b, out_dev);
         sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_attention(e, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] {
             sc_launch_gemm_bf16_ln(EPI_RESLN_STATS, e->ctx, H, w.wo, H, w.bb_o, e->x, H, e->y, H, M, H, H, s, nullptr, nullptr, e->fin_b, w.g_prev, e->stat_a, c.ln_eps);
@@ -488,7 +535,9 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
         });
     }
     const LayerW& last = e->layers[c.layers - 1];
-    if (c.normalize && !(pk && pk->types)) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
+    if (cls) {  // the last LayerNorm on B rows, inside the pooling kernel
+        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, last.ln2g, last.ln2b, c.ln_eps, c.normalize, out_dev, s);
+    } else if (c.normalize && !(pk && pk->types)) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
         sc_launch_layernorm(e->x, tokens, H, last.ln2g, last.ln2b, c.ln_eps, e->x1, s);
         launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
     } else if (pk) {
@@ -525,6 +574,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     // in between), and only when F divides into 256-column tiles.
     const bool gated = ffn_gated(c);
     const bool ffn_blocked = !sk && !gated && (F % 256) == 0 && (H % 256) == 0 && ffn_blocked_enabled();
+    const bool cls = cls_pooling(e, pk), prune = cls && cls_prune_enabled();
     if (pk && pk->types)
         sc_launch_embed_ln_pairs(ids_dev, pk->pos, pk->types, tokens, H, c.vocab, c.max_pos, c.type_vocab, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     else if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, e->pemb, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
@@ -536,6 +586,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
             sc_launch_gemm_bf16(EPI_BIAS, e->x, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, sk, skb);
         });
         if (c.pos_type == 2) launch_rope(e, M, S, pk, s);
+        if (prune && l == c.layers - 1) return cls_last_layer(e, w, lens_dev, B, S, M, pk, nullptr, nullptr, out_dev);
         sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_attention(e, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x, H, e->y, H, M, H, H, s, sk, skb); });
         sc_launch_layernorm(e->y, tokens, H, w.ln1g, w.ln1b, c.ln_eps, e->x1, s);
@@ -551,7 +602,8 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, ffn_blocked ? SC_LDC_BLOCKED64 : F, w.w2, F, w.b2, e->x1, H, e->y, H, M, H, F, s, sk, skb); });
         sc_launch_layernorm(e->y, tokens, H, w.ln2g, w.ln2b, c.ln_eps, e->x, s);
     }
-    launch_mean_pool(e, e->x, lens_dev, B, S, pk, out_dev, s);
+    if (cls) sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, nullptr, nullptr, c.ln_eps, c.normalize, out_dev, s);
+    else launch_mean_pool(e, e->x, lens_dev, B, S, pk, out_dev, s);
     SC_HIP(hipGetLastError());
     return SC_OK;
 }
@@ -956,6 +1008,20 @@ extern "C" sc_status sc_encoder_set_path(sc_encoder* e, int32_t path) {
     if (!e || path < 0 || path > 2) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_path: path must be 0 (auto), 1 (batch pipeline) or 2 (small-batch pipeline)");
     std::lock_guard<std::mutex> g(e->mu);
     e->path = path;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_set_pooling(sc_encoder* e, int32_t pooling) {
+    if (!e || pooling < 0 || pooling > 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pooling: pooling must be 0 (masked mean) or 1 ([CLS] row)");
+    std::lock_guard<std::mutex> g(e->mu);
+    e->pooling = pooling;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_get_pooling(sc_encoder* e, int32_t* out) {
+    if (!e || !out) return sc_fail(SC_ERR_INVALID, "sc_encoder_get_pooling: NULL argument");
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->pooling;
     return SC_OK;
 }
 

@@ -315,6 +315,29 @@ extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const i
     return diag_attention("sc_diag_attention", rt, qkv, lens, B, S, heads, 0, nullptr, out);
 }
 
+// sc_launch_attention_cls, rectangle form.  The host lays qkv out in 64-column blocks of M = ceil256(B*S) rows, as the QKV projection writes it.
+extern "C" sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
+                                           const float* alibi, float* out) {
+    const char* who = "sc_diag_attention_cls";
+    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (head_dim != 64 && !(head_dim == 32 && heads % 2 == 0)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads", who);
+    const int H = heads * head_dim;
+    if (S < 1 || S > 2048 || H > 2048) return sc_fail(SC_ERR_INVALID, "%s: S and heads*head_dim must be at most 2048", who);
+    const int64_t tokens = (int64_t)B * S, M = (tokens + 255) / 256 * 256, nblk = 3 * H / 64;
+    std::vector<float> blocked((size_t)nblk * M * 64, 0.f);
+    for (int64_t r = 0; r < tokens; ++r)
+        for (int64_t cb = 0; cb < nblk; ++cb) memcpy(&blocked[(size_t)(cb * M + r) * 64], qkv + r * 3 * H + cb * 64, 64 * sizeof(float));
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fq, dq, dl, dsl, dc;
+    SC_TRY(upload_bf16(blocked.data(), nblk * M * 64, fq, dq, s));
+    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    if (alibi) SC_TRY(upload(alibi, (size_t)heads * 4, dsl, s));
+    SC_TRY(alloc_nan(dc, (size_t)B * H * 2, s));
+    sc_launch_attention_cls(dq.p, nullptr, (const int32_t*)dl.p, B, S, (int)M, H, head_dim, alibi ? (const float*)dsl.p : nullptr, dc.p, B, s);
+    return download_bf16(dc.p, (int64_t)B * H, out, s);  // synchronises: `blocked` may go
+}
+
 // sc_launch_attention_packed as the packed forward calls it: the work items come from sc_packed_items, as there.
 static sc_status diag_attention_packed(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
                                        int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out) {

@@ -45,6 +45,9 @@ _T_STRING, _T_ARRAY = 8, 9
 _MAX_STRING = 1 << 26  # a corrupt length must not turn into a 2^60-byte read
 
 
+_POOLING_TYPES = {1: "mean", 2: "cls"}  # llama.cpp's enum llama_pooling_type, the two this encoder runs
+
+
 class GGUFError(ValueError):
     pass
 
@@ -143,7 +146,9 @@ def tensor_f32(tensors: dict, name: str) -> np.ndarray:
 def gguf_config(meta: dict) -> dict:
     """Encoder configuration stated by the file's metadata (keys of llama.cpp's bert / jina-bert-v2 / nomic-bert architectures).
     nomic-bert: rotary + swiglu, max_pos = nomic-bert.context_length (2048 when absent), rope_theta = nomic-bert.rope.freq_base --
-    1000 when the key is absent, the value of nomic-embed-text and transformers' default for the family (not llama.cpp's 10000)."""
+    1000 when the key is absent, the value of nomic-embed-text and transformers' default for the family (not llama.cpp's 10000).
+    "pooling": {arch}.pooling_type (llama.cpp's enum) 1 -> "mean", 2 -> "cls" (bge, arctic-embed, mxbai, gte), absent -> "mean"; 0 (none),
+    3 (last) and 4 (rank) are refused: this encoder would run something else."""
     arch = str(meta.get("general.architecture", ""))
     if arch not in ("bert", "jina-bert-v2", "nomic-bert"):
         raise GGUFError(f"GGUF architecture {arch!r} is not an encoder this backend runs (bert, jina-bert-v2, nomic-bert)")
@@ -159,7 +164,13 @@ def gguf_config(meta: dict) -> dict:
            "ln_eps": float(meta.get(f"{arch}.attention.layer_norm_epsilon", 1e-12)), "alibi": jina, "geglu": jina}
     if nomic:
         cfg.update(rotary=True, swiglu=True, rope_theta=float(meta.get("nomic-bert.rope.freq_base", 1000.0)))
+    ptype = int(meta.get(f"{arch}.pooling_type", 1))
+    if ptype not in _POOLING_TYPES:
+        name = {0: "none", 3: "last", 4: "rank"}.get(ptype, "unknown")
+        raise GGUFError(f"GGUF metadata says {arch}.pooling_type = {ptype} ({name}); this encoder pools by mean (1) or [CLS] (2) only")
+    cfg["pooling"] = _POOLING_TYPES[ptype]
     return cfg
+
 
 
 

@@ -161,18 +161,51 @@ def flatten_ids(ids: np.ndarray, lens: np.ndarray) -> "tuple[np.ndarray, np.ndar
     return np.ascontiguousarray(ids[keep], dtype=np.int32), offsets
 
 
+def resolve_pooling(pooling: Optional[str] = None, setting: Optional[str] = None, weights: "str | Path | None" = None,
+                    file_pooling: Optional[str] = None) -> str:
+    """"mean" or "cls" for MI355XEmbeddings, the first of: the argument; the setting mi355x_pooling; what a .gguf states (file_pooling =
+    gguf_config(meta)["pooling"], or read from `weights` here); for a .safetensors the sentence-transformers 1_Pooling/config.json in
+    the file's directory (pooling_mode_cls_token true -> cls); mean."""
+    for given, where in ((pooling, "pooling"), (setting, "SEMCODE_MI355X_POOLING")):
+        if given:
+            mode = str(given).strip().lower()
+            if mode not in ("mean", "cls"):
+                raise ValueError(f"{where} must be 'mean' or 'cls', got {given!r}")
+            return mode
+    path = Path(weights) if isinstance(weights, (str, Path)) else None
+    if path is not None and path.suffix.lower() == ".gguf":
+        if file_pooling is None:
+            from .gguf import gguf_config, read_gguf
+
+            file_pooling = gguf_config(read_gguf(path)[0])["pooling"]
+        return file_pooling
+    if path is not None and path.suffix.lower() == ".safetensors":
+        conf = path.parent / "1_Pooling" / "config.json"
+        if conf.is_file():
+            import json
+
+            if bool(json.loads(conf.read_text()).get("pooling_mode_cls_token")):
+                return "cls"
+    return "mean"
+
+
 class MI355XEmbeddings:
     """LangChain-Embeddings-shaped client whose forward runs in libsemcode_hip on the MI355X.
 
     The model shape: a `.gguf` states it (head count included); a `.safetensors` or `.npy` blob does not, so `cfg` gives what differs
     from BERT-base.  Heads are 64 wide, or 32 for the 384-hidden family with learned positions -- all-MiniLM-L6-v2 (mean-pooled) is
-    `cfg=dict(hidden=384, heads=12, layers=6, ffn=1536)`, all-MiniLM-L12-v2 the same with `layers=12`."""
+    `cfg=dict(hidden=384, heads=12, layers=6, ffn=1536)`, all-MiniLM-L12-v2 the same with `layers=12`.
+
+    Pooling: `pooling="mean"` (masked mean over the real tokens) or `"cls"` (the last hidden state of the first token: bge,
+    snowflake-arctic-embed, mxbai-embed-large, gte); None resolves it as resolve_pooling does -- the setting mi355x_pooling, then what
+    the file states (a GGUF's `bert.pooling_type`, a sentence-transformers `1_Pooling/config.json` next to a .safetensors), then mean.
+    bge-small-en-v1.5 is `cfg=dict(hidden=384, heads=12, layers=12, ffn=1536), pooling="cls"`."""
 
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,
                  normalize: bool = False, batch_size: int = 256, runtime: Any = None, synth_seed: int = 0,
                  allow_synthetic: Optional[bool] = None, document_prefix: Optional[str] = None, query_prefix: Optional[str] = None,
-                 packed: Optional[bool] = None, packed_rows_budget: int = 65536) -> None:
+                 packed: Optional[bool] = None, packed_rows_budget: int = 65536, pooling: Optional[str] = None) -> None:
         from .. import _native  # raises loudly when libsemcode_hip.so is missing: there is no CPU fallback
 
         settings = _resolve_settings()
@@ -208,11 +241,13 @@ class MI355XEmbeddings:
         self._native = _native
         self._cfg = dict(_native.BERT_BASE)
         self._vocab_tmp = None
+        file_pooling = None
         if gguf_path is not None:  # the file states its own architecture, and carries the WordPiece vocabulary
             from .gguf import gguf_config, gguf_vocab, read_gguf
 
             meta, tens = read_gguf(gguf_path)
             fcfg = gguf_config(meta)
+            file_pooling = fcfg.pop("pooling")
             fcfg["vocab"] = int(tens["token_embd.weight"][1][0])
             fcfg["type_vocab"] = int(tens["token_types.weight"][1][0])
             if fcfg["alibi"]:
@@ -239,11 +274,12 @@ class MI355XEmbeddings:
         self._fast_tokenizer: Any = None
         self._owns_runtime = False  # an explicit runtime is the caller's; the default one is shared with the vector store
         self._runtime = runtime or _native.shared_runtime(int(device if device is not None else getattr(settings, "mi355x_device", 0)))
+        self.pooling = resolve_pooling(pooling, getattr(settings, "mi355x_pooling", None), weights, file_pooling)
         if isinstance(weights, (str, Path)):
             weights = load_weight_blob(weights, self._cfg["layers"], self._cfg)
         if weights is None:
             log.warning("mi355x embeddings: no weights configured (SEMCODE_MI355X_WEIGHTS_PATH); using random-init weights seed=%d", synth_seed)
-        self._encoder = _native.Encoder(self._runtime, self._cfg, weights=weights, normalize=normalize, synth_seed=synth_seed)
+        self._encoder = _native.Encoder(self._runtime, self._cfg, weights=weights, normalize=normalize, synth_seed=synth_seed, pooling=self.pooling)
         if vocab is None:
             log.warning("mi355x embeddings: no vocab.txt configured (SEMCODE_MI355X_VOCAB_PATH); using the hash tokenizer stand-in")
             self.tokenizer: Any = HashTokenizer(self._cfg["vocab"])

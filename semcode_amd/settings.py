@@ -8,7 +8,7 @@ seams usable (and testable) without pydantic_settings, which is absent in the bu
 Backend-specific keys ride on the reference's extra="allow" (settings.py:36):
     mi355x_device, mi355x_metric, mi355x_index_type, mi355x_nlist, mi355x_nprobe,
     mi355x_weights_path, mi355x_vocab_path, mi355x_allow_synthetic, mi355x_max_tokens, mi355x_store_path, mi355x_ingest_batch,
-    mi355x_document_prefix, mi355x_query_prefix, mi355x_packed, mi355x_lexical,
+    mi355x_document_prefix, mi355x_query_prefix, mi355x_packed, mi355x_pooling, mi355x_lexical,
     mi355x_reranker_path, mi355x_reranker_vocab, mi355x_rerank_fetch_k
 """
 from __future__ import annotations
@@ -51,6 +51,7 @@ _DEFAULTS: dict[str, Any] = {
     "mi355x_store_path": None,
     "mi355x_ingest_batch": 256,       # chunks per embed+upsert batch of services.indexer.ingest_chunks
     "mi355x_packed": False,           # embed variable-length batches packed (no padding to the longest text of a batch)
+    "mi355x_pooling": "",             # "mean" | "cls"; empty: what the weight file states (GGUF pooling_type, 1_Pooling/config.json), else mean
     "mi355x_lexical": False,          # keep a term row per chunk on the device for hybrid (BM25 + dense) search: MilvusVectorStore(lexical=...)
     "mi355x_reranker_path": None,     # .safetensors of a BertForSequenceClassification cross-encoder (embeddings/reranker.py)
     "mi355x_reranker_vocab": None,    # its vocab.txt (default: mi355x_vocab_path)
