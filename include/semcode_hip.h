@@ -429,7 +429,18 @@ sc_status sc_index_release_scratch(sc_index* ix);
 /* Replaces Collection.search(data=[vector], param={metric, nprobe}, limit=top_k)
  * (milvus_store.py:141-147), batched: q [Q,dim] host, out_dist [Q,k] f32, out_rows [Q,k] i64
  * (global ids, best first; ties broken by lower row id; missing hits = -1 / +inf-or--inf).
- * nprobe is ignored by FLAT indexes.  Distances: L2 = squared L2, IP = dot, COSINE = cosine. */
+ * nprobe is ignored by FLAT indexes.  Distances: L2 = squared L2, IP = dot, COSINE = cosine.
+ * Value contract (this and every other search entry point; stored rows and queries alike):
+ *   - covered: vectors of finite f32 components whose squared norm |v|^2 is representable in f32 (neither overflows nor loses
+ *     its terms to underflow; corpora scaled by 2^-40 .. 2^+40 are tested).  upsert accepts whatever the caller sends; what lies
+ *     outside the contract is stored and searched, but nothing is promised about where it ranks.
+ *   - zero-norm rule: under COSINE a row or a query with |v|^2 == 0 scores exactly +0.0 against anything (never 0 / 0): such
+ *     a row ranks between the positive and the negative cosines, and a zero query returns rows 0 .. k-1.  Under IP a zero vector
+ *     scores 0, under L2 the other vector's |.|^2.  (Results are read back from the sort key, where a score of +0.0 under IP /
+ *     COSINE reads -0.0; compare zero scores by value, not by sign bit.)
+ *   - ties: equal scores go to the lower row id, on every path (exact, batched at either coarse stage, masked, every IVF probe)
+ *     -- also when thousands of rows tie with the k-th score.
+ *   - outside the contract: NaN or Inf components, norms that overflow, subnormal intermediates (scales below 2^-40). */
 sc_status sc_index_search(sc_index* ix, const float* q, int32_t Q, int32_t k, int32_t nprobe,
                           float* out_dist, int64_t* out_rows);
 /* Same with DEVICE pointers (q row stride = dim): enqueued on the runtime's stream.  The exact scan (<= 16 queries, no IVF

@@ -51,12 +51,24 @@ __host__ __device__ static inline float sc_synth_value(uint64_t key, uint64_t ro
 __host__ __device__ static inline uint64_t sc_synth_key(uint64_t seed) { return sc_mix64(seed + 0x9E3779B97F4A7C15ull); }
 
 // score from the exact dot product and the two squared norms (metric: sc_metric)
+// COSINE, the zero-norm rule (include/semcode_hip.h, "value contract"): a row or a query with |v|^2 == 0 scores exactly +0.0 against
+// anything.  dot is +0.0 there (an fmaf chain from +0.0 over products of +-0), so only the 0 / 0 changes: the denominator |x| |q|
+// is 0 exactly when one of the norms is, and a floor at the smallest normal float (below every denominator the contract covers)
+// turns it into +0.0 / FLT_MIN = +0.0 -- one v_max_f32, no compare, no select, nothing for hipcc to branch around.  The forms
+// `(xn == 0 || qn == 0) ? 0 : dot / den` and `dot / (den > 0 ? den : 1)` cost the 10M x 768 COSINE batch 9.4 -> 10.0 and 9.7 ms
+// (scan_coarse256_kernel, dense epilogue: 28.5k -> 37.2k / 35.1k instructions).  Bit-exact twin: oracle/sc_oracle.c sc_oracle_score.
+#define SC_NORM_FLOOR 1.17549435e-38f
 template <int METRIC>
 __host__ __device__ static inline float sc_score(float dot, float xn, float qn) {
     if (METRIC == SC_METRIC_L2) return fmaf(-2.0f, dot, xn + qn);
-    if (METRIC == SC_METRIC_COSINE) return dot / (sqrtf(xn) * sqrtf(qn));
+    if (METRIC == SC_METRIC_COSINE) return dot / fmaxf(sqrtf(xn) * sqrtf(qn), SC_NORM_FLOOR);
     return dot;
 }
+// 1 / |x| of a corpus row for the cosine form of the coarse tests (scan_coarse.hip, scan_coarse64.hip; ivf_coarse.hip guards its
+// centred form itself): finite for a zero row, whose coarse dot is exactly 0, so that its coarse score is 0 like its exact one and
+// never 0 * inf.  The floor sits on sqrtf(xn) itself -- the very expression of sc_score, which the precise test evaluates next to this
+// one: floored inside the root, the dense epilogue computed two roots per score (+16 % instructions, the COSINE batch 9.16 -> 9.36 ms)
+__host__ __device__ static inline float sc_inv_norm(float xn) { return 1.0f / fmaxf(sqrtf(xn), 1.0e-19f); }
 
 // 64-bit total order, smaller = better: (order-preserving float map of +-score) << 32 | row
 template <int METRIC>

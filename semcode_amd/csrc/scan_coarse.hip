@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void scan_coarse_kernel(CoarseArgs a) {
     for (int mi = 0; mi < 4; ++mi) {
         rows[mi] = m0 + wm * 64 + mi * 16 + fr;
         xn[mi] = rows[mi] < a.row1 ? a.xnorm[rows[mi]] : 0.f;
-        xs[mi] = (METRIC == SC_METRIC_COSINE) ? 1.0f / sqrtf(xn[mi]) : 0.f;
+        xs[mi] = (METRIC == SC_METRIC_COSINE) ? sc_inv_norm(xn[mi]) : 0.f;
     }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
@@ -189,7 +189,7 @@ static __device__ __forceinline__ void coarse256_epilogue(const CoarseArgs& a, c
         const int rl = wm * 128 + mi * 16 + fr;
         const int Ti = TiA[mi];  // int8 only
         const float xn = x_xn[rl];  // staged at kernel start; rows >= row1 hold +inf (L2) / 0 scale so that they never pass
-        const float xs = (METRIC == SC_METRIC_COSINE) ? 1.0f / sqrtf(xn) : 0.f;  // exact: the precise test below uses it too
+        const float xs = (METRIC == SC_METRIC_COSINE) ? sc_inv_norm(xn) : 0.f;  // exact: the precise test below uses it too
         const float sx = I8 ? q_tf[1280 + rl] : 0.f;  // int8 stage: the integer dot is scaled by s_r s_q
         const float ar = (METRIC == SC_METRIC_L2) ? -2.0f * sx : (METRIC == SC_METRIC_COSINE) ? -sx * xs : -sx;
         // Prefilter: ONE compare per score.  The fast test t <= tf_q is  dot >= (base_r - tf_q) / c_r  with base_r = |x|^2 (L2) or
@@ -306,7 +306,7 @@ static __device__ __forceinline__ void coarse256_epilogue_dense(const CoarseArgs
         const int rl = wm * 128 + mi * 16 + fr;
         const int64_t row = m0 + rl;
         const float xn = x_xn[rl];
-        const float xs = (METRIC == SC_METRIC_COSINE) ? 1.0f / sqrtf(xn) : 0.f;
+        const float xs = (METRIC == SC_METRIC_COSINE) ? sc_inv_norm(xn) : 0.f;
         const float sx = I8 ? q_tf[1280 + rl] : 0.f;
         const float ar = (METRIC == SC_METRIC_L2) ? -2.0f * sx : (METRIC == SC_METRIC_COSINE) ? -sx * xs : -sx;
         const float accv = acc[ni][mi][r], sqv = I8 ? sq[ni][r] : 0.f;

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(512) void scan_coarse64s_kernel(CoarseArgs a, u32x4
                 xn = rs[rl];
                 sx = rs[256 + rl];
             }
-            const float xs = (METRIC == SC_METRIC_COSINE) ? 1.0f / sqrtf(xn) : 0.f;
+            const float xs = (METRIC == SC_METRIC_COSINE) ? sc_inv_norm(xn) : 0.f;
             const float ar = (METRIC == SC_METRIC_L2) ? -2.0f * sx : (METRIC == SC_METRIC_COSINE) ? -sx * xs : -sx;
             if (GROUPED && DENSE) {
 #pragma unroll
