@@ -101,9 +101,21 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
 
 /* ------------------------------------------------------------------- encoder ---- */
 
-/* BERT-family post-LN transformer encoder (the "transformer-encoder forward" of BASELINE.json;
- * BERT-base shape = 30522 / 768 / 12 / 12 / 3072 / 512 / 2, eps 1e-12).  Head dimension hidden / heads must be 64, or 32 with
- * pos_type 0 (MiniLM-L6 shape = 30522 / 384 / 6 / 12 / 1536 / 512 / 2); 32 with ALiBi or rotary positions is SC_ERR_UNSUPPORTED. */
+/* Transformer encoder: the BERT-family post-LN models (arch 0; the "transformer-encoder forward" of BASELINE.json;
+ * BERT-base shape = 30522 / 768 / 12 / 12 / 3072 / 512 / 2, eps 1e-12) and the pre-LN ModernBERT family (arch 1, below).  Head
+ * dimension hidden / heads must be 64, or 32 with
+ * pos_type 0 (MiniLM-L6 shape = 30522 / 384 / 6 / 12 / 1536 / 512 / 2); 32 with ALiBi or rotary positions is SC_ERR_UNSUPPORTED.
+ *
+ * arch 1 (answerdotai/ModernBERT-base, gte-modernbert-base, modernbert-embed-base; base shape = 50368 / 768 / 22 / 12 / 1152, eps 1e-5):
+ *   h = LN_emb(tok_emb[id]);  per layer  h += Attn(attn_norm(h)),  h += MLP(mlp_norm(h))  with attn_norm of layer 0 the identity;
+ *   pooled from final_norm(h).  No position and no type table.  MLP = Wo (gelu(gate) * up) (ffn_type 1).  Rotary positions (pos_type 2)
+ *   with two bases: rope_theta in the global layers, rope_theta_local in the local ones.  Layer l is global iff l % global_every == 0;
+ *   in the other layers a token attends to the real keys with |i - j| <= local_window / 2 only (encoder_window.hip).
+ *   arch 1 requires pos_type 2, ffn_type 1 and head dimension 64; anything else is SC_ERR_UNSUPPORTED.  ffn must be a multiple of 128
+ *   as for every model (base: 1 152), so ModernBERT-large (ffn 2 624) is refused by that rule.  The forward runs the stand-alone
+ *   LayerNorm pipeline for every batch size (sc_encoder_set_path only decides about split-K); a LayerNorm-folded pre-norm pipeline
+ *   is a follow-up.  [CLS] pooling runs the whole last layer (the pruned last layer is the post-LN one).  sc_encoder_score_pairs is
+ *   SC_ERR_UNSUPPORTED (the family's classifier is dense -> GELU -> LayerNorm -> linear, not pooler + linear).  Texts stay capped at 2 048 tokens. */
 typedef struct sc_encoder_cfg {
     int32_t vocab, hidden, layers, heads, ffn, max_pos, type_vocab;
     float ln_eps;
@@ -117,6 +129,11 @@ typedef struct sc_encoder_cfg {
                              rows), hidden = gelu(gate) * up, b1 is [2*ffn] (zeros for bias-free models);
                              2 = SwiGLU (nomic-bert): the same layout, hidden = silu(gate) * up                */
     float rope_theta;     /* pos_type 2: rotary base (1000 for nomic-embed-text); 0 = 10000                   */
+    /* appended; all zero = the behaviour of the struct without them */
+    int32_t arch;           /* 0 = post-LN BERT family; 1 = pre-LN ModernBERT (above)                           */
+    int32_t local_window;   /* arch 1: total window of the local layers, even, 2 .. 128 (128 for the released models) */
+    int32_t global_every;   /* arch 1: layer l is global iff l % global_every == 0; 1 = every layer global; 3 for the released models */
+    float rope_theta_local; /* arch 1: rotary base of the local layers (10000); rope_theta is the global layers' (160000); 0 = 10000 */
 } sc_encoder_cfg;
 
 /* Size in bytes of the f32 weight blob sc_encoder_create expects for cfg.  Blob order (all f32,
@@ -124,7 +141,11 @@ typedef struct sc_encoder_cfg {
  * emb_ln_gamma [H], emb_ln_beta [H], then per layer: Wq [H,H], bq, Wk, bk, Wv, bv, Wo [H,H], bo,
  * ln1_gamma, ln1_beta, W1 [ffn,H], b1 [ffn], W2 [H,ffn], b2 [H], ln2_gamma, ln2_beta.
  * pos_type 1 and 2 drop pos_emb from the blob; ffn_type 1 and 2 make W1 [2*ffn,H] (gate rows, then up rows) and b1 [2*ffn].
- * Bias-free models (nomic-bert) keep their bias slots, filled with zeros. */
+ * Bias-free models (nomic-bert) keep their bias slots, filled with zeros.
+ * arch 1: word_emb [vocab,H], emb_ln_gamma, emb_ln_beta, the same per-layer order with ln1 = attn_norm (layer 0's slot is present and
+ * ignored) and ln2 = mlp_norm, W1 = Wi (its first ffn rows are the activated half, i.e. the gate rows), W2 = mlp.Wo, then
+ * final_norm_gamma [H], final_norm_beta [H].  No pos_emb, no type_emb (type_vocab is not read).  Bias and beta slots stay present:
+ * zeros for the released models, the values of a model with norm_bias / attention_bias / mlp_bias. */
 sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out);
 /* Replaces EmbeddingProviderFactory.create() loading a model (providers.py:69-100): uploads the
  * weights (converted to bf16 on device).  weights_blob == NULL: synthetic weights 0.02*N(0,1) from
@@ -350,6 +371,13 @@ sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const in
  * each text's first row. */
 sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
                                 const float* alibi, float* out);
+/* sc_diag_attention_window: the windowed attention kernels (encoder_window.hip) on their own, head dimension 64, conventions of
+ * sc_diag_attention_ex / sc_diag_attention_packed: out = softmax over the keys j < len with |i - j| <= local_window / 2 of QK^T/8, times V.
+ * starts == NULL: a rectangle, qkv [B*S][3*heads*64] (or blocked), lens clamped to 1 .. S, out [B*S, heads*64]; a row that sees no key
+ * (beyond len + local_window / 2) is zero.  starts != NULL: packed rows, S is not read, R and out as sc_diag_attention_packed (rows
+ * outside every sequence stay NaN).  local_window even, 2 .. 128, else SC_ERR_UNSUPPORTED. */
+sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                   int32_t local_window, int32_t blocked_rows, float* out);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,

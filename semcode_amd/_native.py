@@ -36,7 +36,8 @@ class _Cfg(C.Structure):
 class EncoderCfg(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32),
                 ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float), ("normalize", C.c_int32),
-                ("synth_seed", C.c_uint64), ("pos_type", C.c_int32), ("ffn_type", C.c_int32), ("rope_theta", C.c_float)]
+                ("synth_seed", C.c_uint64), ("pos_type", C.c_int32), ("ffn_type", C.c_int32), ("rope_theta", C.c_float),
+                ("arch", C.c_int32), ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float)]
 
 
 _lib = None
@@ -101,6 +102,7 @@ SIGNATURES = {
     "sc_diag_attention_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_attention_cls": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_attention_window": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -786,6 +788,22 @@ SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: ALiBi or rotary enco
 POOLINGS = {"mean": 0, "cls": 1}  # sc_encoder_set_pooling
 
 
+def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> EncoderCfg:
+    """sc_encoder_cfg of a complete configuration dict (the keys of BERT_BASE plus the architecture switches alibi / rotary / geglu /
+    swiglu / rope_theta and, for the pre-LN ModernBERT family, modernbert / local_window / global_every / rope_theta_local)."""
+    if c.get("rotary") and c.get("alibi"):
+        raise ValueError("encoder configuration: rotary and alibi are two position schemes, pick one")
+    if c.get("swiglu") and c.get("geglu"):
+        raise ValueError("encoder configuration: swiglu and geglu are two feed-forward gates, pick one")
+    return EncoderCfg(vocab=c["vocab"], hidden=c["hidden"], layers=c["layers"], heads=c["heads"], ffn=c["ffn"],
+                      max_pos=c["max_pos"], type_vocab=c["type_vocab"], ln_eps=c["ln_eps"], normalize=1 if normalize else 0,
+                      synth_seed=synth_seed, pos_type=2 if c.get("rotary") else 1 if c.get("alibi") else 0,
+                      ffn_type=2 if c.get("swiglu") else 1 if c.get("geglu") else 0, rope_theta=float(c.get("rope_theta") or 0.0),
+                      # pre-LN ModernBERT (sc_encoder_cfg.arch 1): local attention in the layers with l % global_every != 0
+                      arch=1 if c.get("modernbert") else 0, local_window=int(c.get("local_window") or 0),
+                      global_every=int(c.get("global_every") or 0), rope_theta_local=float(c.get("rope_theta_local") or 0.0))
+
+
 class Encoder:
     """Transformer-encoder forward on the device (sc_encoder): token ids in, pooled f32 vectors out.  pooling: "mean" (masked mean over
     the real tokens) or "cls" (the last hidden state of the first token: bge, arctic-embed, mxbai, gte)."""
@@ -796,14 +814,7 @@ class Encoder:
             raise ValueError(f"encoder pooling must be one of {sorted(POOLINGS)}, got {pooling!r}")
         c = dict(BERT_BASE)
         c.update(cfg or {})
-        if c.get("rotary") and c.get("alibi"):
-            raise ValueError("encoder configuration: rotary and alibi are two position schemes, pick one")
-        if c.get("swiglu") and c.get("geglu"):
-            raise ValueError("encoder configuration: swiglu and geglu are two feed-forward gates, pick one")
-        self.cfg = EncoderCfg(vocab=c["vocab"], hidden=c["hidden"], layers=c["layers"], heads=c["heads"], ffn=c["ffn"],
-                              max_pos=c["max_pos"], type_vocab=c["type_vocab"], ln_eps=c["ln_eps"], normalize=1 if normalize else 0,
-                              synth_seed=synth_seed, pos_type=2 if c.get("rotary") else 1 if c.get("alibi") else 0,
-                              ffn_type=2 if c.get("swiglu") else 1 if c.get("geglu") else 0, rope_theta=float(c.get("rope_theta") or 0.0))
+        self.cfg = encoder_cfg(c, normalize=normalize, synth_seed=synth_seed)
         self.rt = rt
         self.hidden = c["hidden"]
         self.max_pos = c["max_pos"]
@@ -1234,6 +1245,28 @@ def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_ro
                                                  _ptr(out)))
     else:
         _check(lib().sc_diag_attention_packed(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(blocked_rows), _ptr(sl), _ptr(out)))
+    return out
+
+
+def diag_attention_window(rt: Runtime, qkv, lens, heads: int, local_window: int, S: int = 0, starts=None, blocked_rows: int = 0) -> np.ndarray:
+    """The windowed attention kernels on their own (head dimension 64): a query sees the real keys with |i - j| <= local_window / 2.
+    starts None: a rectangle, qkv [B*S, 3H] -> [B*S, H].  Else packed rows as diag_attention_packed: qkv [R, 3H] -> [R, H]."""
+    qkv = _f32(qkv)
+    lens = np.ascontiguousarray(lens, np.int32)
+    H = heads * 64
+    if starts is None:
+        rows = len(lens) * int(S)
+        R = int(blocked_rows) if blocked_rows else rows
+    else:
+        starts = np.ascontiguousarray(starts, np.int32)
+        R = rows = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
+    if qkv.shape != (R, 3 * H) or (starts is not None and starts.shape != lens.shape):
+        raise ValueError(f"diag_attention_window: qkv must be [{R}, {3 * H}], starts (if given) and lens [B]")
+    if blocked_rows:
+        qkv = block64(qkv)
+    out = np.empty((rows, H), np.float32)
+    _check(lib().sc_diag_attention_window(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
+                                          int(local_window), int(blocked_rows), _ptr(out)))
     return out
 
 

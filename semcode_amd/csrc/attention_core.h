@@ -347,3 +347,119 @@ static __device__ __forceinline__ void attn_state32_store(const AttnState32& S_,
         *reinterpret_cast<bf16x8*>(obase + (size_t)(8 * g4 + ql) * H + c8 * 8) = v;
     }
 }
+
+// ------------------------------------------------------------------ windowed (band) attention, head dimension 64 (encoder_window.hip)
+// A query attends to the real keys within `hw` positions of its own: |query - key| <= hw, key < len.  With hw <= 64 the band of a
+// 32-row query block touches at most five 32-key tiles (blocks qb - 2 .. qb + 2), so all of them are ONE group: a single softmax pass
+// with attention_qblock_core's arithmetic per (query, key) -- S^T = K Q^T on the 32x32x16 MFMA, exp2 of the scaled score against
+// the row maximum, P rounded to bf16 straight from the score registers into P V -- and no rescale of O, because there is no
+// second group.  ntiles (1 .. WT, wave-uniform) tiles are live; tile i holds the keys 32 (kt_first + i) .. of the sequence and
+// lies in the LDS images (those of attention_qblock_core) at tile lt_first + i.  A tile the band covers completely and whose
+// keys are all real skips the per-element mask (wave-uniform test).  A query without any visible key -- an alignment row beyond
+// len + hw -- ends with l = 1 and O = 0: its output row is zero, never NaN.
+template <int WT>
+static __device__ __forceinline__ void attention_qblock_window(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, int len, int hw, int lane, int qbase,
+                                                               int kt_first, int lt_first, int ntiles, AttnState& S_) {
+    const int l31 = lane & 31, hh = lane >> 5;
+    const float sl2 = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
+    const int q = qbase + l31;
+    f32x16 o0 = S_.o0, o1 = S_.o1;
+    f32x16 st[WT];
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+        if (i < ntiles) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            const int krow = 32 * (lt_first + i) + l31;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int c = 2 * ks + hh;
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
+            }
+            st[i] = acc;
+        }
+    }
+    // st[i][r] = score(key = 32 (kt_first + i) + (r&3) + 8 (r>>2) + 4 hh, query = q)
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+        if (i < ntiles) {
+            const int k0 = 32 * (kt_first + i);
+            // whole tile visible to every query of the block: |q - key| <= 32 |tile - block| + 31, and every key real
+            const int dt = k0 - qbase;
+            const bool whole = (dt < 0 ? -dt : dt) + 31 <= hw && k0 + 32 <= len;
+            if (whole) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[i][r]);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh, d = key - q;
+                    if (key < len && d <= hw && -d <= hw) mx = fmaxf(mx, st[i][r]);
+                }
+            }
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mb = mx * sl2;
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+        if (i < ntiles) {
+            const int k0 = 32 * (kt_first + i);
+            const int dt = k0 - qbase;
+            const bool whole = (dt < 0 ? -dt : dt) + 31 <= hw && k0 + 32 <= len;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float p = __builtin_amdgcn_exp2f(fmaf(st[i][r], sl2, -mb));
+                if (!whole) {
+                    const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh, d = key - q;
+                    p = (key < len && d <= hw && -d <= hw) ? p : 0.f;  // a select: a masked score may have overflowed exp2
+                }
+                st[i][r] = p;
+                sum += p;
+            }
+        }
+    }
+    sum += __shfl_xor(sum, 32, 64);
+    // O += P V: operands as in attention_qblock_core
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+        if (i < ntiles) {
+            const int t = lt_first + i;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                u32x4 pp;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pp[j] = pack_bf16x2(st[i][8 * s + 2 * j], st[i][8 * s + 2 * j + 1]);
+                const bf16x8 pf = __builtin_bit_cast(bf16x8, pp);
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt) {
+                    bf16x8 vf;
+#pragma unroll
+                    for (int piece = 0; piece < 2; ++piece) {
+                        const int row = 32 * t + 16 * s + 8 * piece + 4 * hh + ((lane & 15) >> 2);
+                        const int d0 = 32 * dt + 16 * ((lane >> 4) & 1);
+                        const int chunk = (d0 >> 3) + ((lane & 3) >> 1);
+                        const int sw = chunk ^ (((row >> 1) & 1) << 2);
+                        typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
+                        const s16x4 got = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(Vl + row * 128 + sw * 16 + 8 * (lane & 1)));
+                        vf[4 * piece + 0] = got[0];
+                        vf[4 * piece + 1] = got[1];
+                        vf[4 * piece + 2] = got[2];
+                        vf[4 * piece + 3] = got[3];
+                    }
+                    if (dt == 0) o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o0, 0, 0, 0);
+                    else o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o1, 0, 0, 0);
+                }
+            }
+        }
+    }
+    S_.m_run = mx;
+    S_.l_run = sum > 0.f ? sum : 1.0f;
+    S_.o0 = o0;
+    S_.o1 = o1;
+}

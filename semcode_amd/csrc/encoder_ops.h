@@ -79,6 +79,13 @@ void sc_launch_mean_pool_ln_packed(const void* y, const float* stats, int slots,
 void sc_launch_attention32(const void* qkv, const int32_t* lens, int B, int S, int H, void* ctx, hipStream_t s, int blocked);
 void sc_launch_attention32_packed(const void* qkv, const int32_t* items, const int* nitems, int H, void* ctx, hipStream_t s, int blocked);
 
+// ---- encoder_window.hip: local (sliding-window) attention, head dimension 64, plain scores: a query sees the real keys with
+// |query - key| <= local_window / 2.  local_window even, 2 .. 128; the other arguments as the two attention launchers above.
+bool sc_attention_window_supported(int local_window);
+void sc_launch_attention_window(const void* qkv, const int32_t* lens, int B, int S, int H, int local_window, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_window_packed(const void* qkv, const int32_t* items, const int* nitems, int H, int local_window, void* ctx, hipStream_t s,
+                                       int blocked = 0);
+
 // ---- encoder_pairs.hip: the packed embedding with a per-row segment id (types [rows], clamped into type_emb's type_vocab rows), and
 // the classification head of a cross-encoder: cls [B,H] f32 -> logits [B,num_labels] = Wc p + bc, p = tanh(Wp cls + bp), or p = cls when
 // Wp is NULL.  Wp [H,H], bp [H], Wc [num_labels,H], bc [num_labels] f32 on the device; H a multiple of 16, <= 2048; num_labels 1 or 2.

@@ -12,6 +12,8 @@
 // biases / LayerNorm parameters / embedding tables f32.
 // Pairs of a cross-encoder (sc_encoder_set_pair_head / sc_encoder_score_pairs) run the packed forward with a segment id per row and
 // take each pair's [CLS] row instead of a mean; the head on those rows is encoder_pairs.hip's.
+// Pre-norm models (cfg.arch 1, ModernBERT): forward_prenorm_locked -- h += Attn(LN(h)), h += MLP(LN(h)) on a raw residual stream, local
+// (sliding-window) attention in the layers with l % global_every != 0 (encoder_window.hip), a rotary table per kind of layer, final_norm.
 // The single-kernel harnesses (sc_diag_*) are in sc_encoder_diag.cpp, the device entry points in encoder_ops.h.
 #include <cmath>
 #include <cstring>
@@ -47,6 +49,8 @@ struct sc_encoder {
     float *wemb = nullptr, *pemb = nullptr, *temb = nullptr, *embg = nullptr, *embb = nullptr;
     float* slopes = nullptr;  // ALiBi head slopes (device) or NULL
     float *rope_cos = nullptr, *rope_sin = nullptr;  // rotary positions: [max_pos][32] f32 each (device) or NULL
+    float *rope_cos_l = nullptr, *rope_sin_l = nullptr;  // arch 1: the table of the local layers (base rope_theta_local); the one above is the global layers'
+    float *fing = nullptr, *finb = nullptr;              // arch 1: final_norm gamma / beta
     std::vector<LayerW> layers;
     // workspace for `ws_tokens` (multiple of 256) tokens
     int64_t ws_tokens = 0;
@@ -163,10 +167,13 @@ static bool ffn_blocked_enabled() { static const bool on = sc_env_flag("SC_FFN_B
 // number of f32 values in the weight blob, in blob order (see include/semcode_hip.h)
 static int64_t blob_floats(const sc_encoder_cfg& c) {
     const int64_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F;
-    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (int64_t)c.type_vocab * H + 2 * H;
+    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch == 1 ? 0 : (int64_t)c.type_vocab * H) + 2 * H;
     n += (int64_t)c.layers * (4 * (H * H + H) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
+    if (c.arch == 1) n += 2 * H;  // final_norm
     return n;
 }
+// arch 1: layer l attends globally iff l % global_every == 0 (global_every 0 counts as 1: every layer global)
+static bool layer_is_local(const sc_encoder_cfg& c, int l) { return c.arch == 1 && c.global_every > 1 && (l % c.global_every) != 0; }
 
 extern "C" sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out) {
     if (!cfg || !out) return sc_fail(SC_ERR_INVALID, "sc_encoder_blob_bytes: NULL argument");
@@ -187,6 +194,22 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension 32 runs with learned positions only (pos_type 0), not pos_type %d (%s)", c.pos_type,
                        c.pos_type == 1 ? "ALiBi" : "rotary");
     if (c.pos_type == 2 && !(c.rope_theta >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta must be >= 0 (0 = 10000)");
+    if (c.arch < 0 || c.arch > 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT)", c.arch);
+    if (c.arch == 0) {
+        if (c.local_window != 0 || c.global_every > 1)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window %d / global_every %d need arch 1 (local attention exists in the pre-LN pipeline only)",
+                           c.local_window, c.global_every);
+        return SC_OK;
+    }
+    // the pre-LN pipeline: rotate-half rotation and the windowed kernel are written for 64-wide heads, its gate is GEGLU
+    if (c.hidden != c.heads * 64)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 1 needs head dimension 64 (hidden=%d heads=%d)", c.hidden, c.heads);
+    if (c.pos_type != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 1 runs with rotary positions only (pos_type 2), not pos_type %d", c.pos_type);
+    if (c.ffn_type != 1) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 1 runs with the GEGLU feed-forward only (ffn_type 1), not ffn_type %d", c.ffn_type);
+    if (c.global_every < 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: global_every must be >= 1 with arch 1 (1 = every layer global), got %d", c.global_every);
+    if (!sc_attention_window_supported(c.local_window))
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window must be even and within 2 .. 128, got %d", c.local_window);
+    if (!(c.rope_theta_local >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta_local must be >= 0 (0 = 10000)");
     return SC_OK;
 }
 
@@ -229,7 +252,11 @@ static void layout_params(sc_encoder* e, Arena& a) {
     e->slopes = c.pos_type == 1 ? a.f32((size_t)c.heads) : nullptr;
     e->rope_cos = c.pos_type == 2 ? a.f32(2 * rope_n) : nullptr;  // sc_rope_table: cos, then sin
     e->rope_sin = e->rope_cos ? e->rope_cos + rope_n : nullptr;
-    e->temb = a.f32((size_t)c.type_vocab * H);
+    e->rope_cos_l = c.arch == 1 ? a.f32(2 * rope_n) : nullptr;
+    e->rope_sin_l = e->rope_cos_l ? e->rope_cos_l + rope_n : nullptr;
+    e->temb = a.f32(c.arch == 1 ? H : (size_t)c.type_vocab * H);  // arch 1 has no type table: one row of zeros for the embedding kernels
+    e->fing = c.arch == 1 ? a.f32(H) : nullptr;
+    e->finb = c.arch == 1 ? a.f32(H) : nullptr;
     e->embg = a.f32(H);
     e->embb = a.f32(H);
     for (LayerW& w : e->layers) {
@@ -279,7 +306,8 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
         return code;
     };
     // the LayerNorm-folded batch pipeline needs every GEMM on the 256 x 256 tile and the statistics in whole 256-column slots
-    e->foldable = (H % 256) == 0 && (F % 256) == 0 && (F1 % 256) == 0 && ((3 * H) % 256) == 0;
+    // (arch 1: the LayerNorm-folded pipeline has no pre-norm form yet)
+    e->foldable = cfg->arch == 0 && (H % 256) == 0 && (F % 256) == 0 && (F1 % 256) == 0 && ((3 * H) % 256) == 0;
     e->layers.resize(L);
     Arena arena;
     layout_params(e, arena);  // measure
@@ -314,7 +342,9 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     if (e->pemb) put_f32(e->pemb, take((int64_t)cfg->max_pos * H), (int64_t)cfg->max_pos * H, COPY);
     if (e->slopes) put_host(e->slopes, alibi_slopes(cfg->heads));
     if (e->rope_cos) put_host(e->rope_cos, sc_rope_table(cfg->max_pos, cfg->rope_theta));
-    put_f32(e->temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, COPY);
+    if (e->rope_cos_l) put_host(e->rope_cos_l, sc_rope_table(cfg->max_pos, cfg->rope_theta_local));
+    if (cfg->arch == 1) hipMemsetAsync(e->temb, 0, (size_t)H * 4, s);
+    else put_f32(e->temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, COPY);
     put_f32(e->embg, take(H), H, ONES);
     put_f32(e->embb, take(H), H, ZEROS);
     for (int64_t l = 0; l < L; ++l) {
@@ -348,6 +378,10 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
             sc_launch_add_vectors(w.bo, bp, w.bb_o, (int)H, s);
             sc_launch_add_vectors(w.b2, w.ln1b, w.bb_2, (int)H, s);
         }
+    }
+    if (e->fing) {
+        put_f32(e->fing, take(H), H, ONES);
+        put_f32(e->finb, take(H), H, ZEROS);
     }
     he = hipStreamSynchronize(s);
     if (he == hipSuccess) he = hipGetLastError();
@@ -419,9 +453,15 @@ static sc_status ensure_ws(sc_encoder* e, int64_t rows, int64_t B) {
 
 // The steps both pipelines launch in a rectangle form and a packed form (pk != NULL).  Packed rotary models always rotate with the
 // stand-alone kernel: the rotation fused into the QKV epilogue (EPI_LNA_BIAS_ROPE) takes its position from row & (S - 1).
-static void launch_rope(sc_encoder* e, int M, int S, const PackedLayout* pk, hipStream_t s) {
-    if (pk) sc_launch_rope_qk_packed(e->qkv, M, 2 * e->cfg.heads, pk->pos, e->cfg.max_pos, e->rope_cos, e->rope_sin, s);
-    else sc_launch_rope_qk(e->qkv, M, 2 * e->cfg.heads, S, e->rope_cos, e->rope_sin, s);
+// local: the table of an arch 1 model's local layers instead of the model's (global) one
+static void launch_rope(sc_encoder* e, int M, int S, const PackedLayout* pk, hipStream_t s, bool local = false) {
+    const float *cos_t = local ? e->rope_cos_l : e->rope_cos, *sin_t = local ? e->rope_sin_l : e->rope_sin;
+    if (pk) sc_launch_rope_qk_packed(e->qkv, M, 2 * e->cfg.heads, pk->pos, e->cfg.max_pos, cos_t, sin_t, s);
+    else sc_launch_rope_qk(e->qkv, M, 2 * e->cfg.heads, S, cos_t, sin_t, s);
+}
+static void launch_attention_window(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
+    if (pk) sc_launch_attention_window_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->cfg.local_window, e->ctx, s, M);
+    else sc_launch_attention_window(e->qkv, lens_dev, B, S, e->cfg.hidden, e->cfg.local_window, e->ctx, s, M);
 }
 static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
     const int hd = e->cfg.hidden / e->cfg.heads;  // 64, or 32: a pair of heads per 64-column block (encoder_attn32.hip)
@@ -549,6 +589,63 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
     return SC_OK;
 }
 
+// The pre-norm forward (cfg.arch 1, ModernBERT), on the stand-alone-LayerNorm launches for every batch size (split-K GEMMs up to 1 024
+// rows, the 256-tile GEMMs beyond).  The residual stream h stays RAW between the sub-layers:
+//   h = LN_emb(word embedding)                                            -> x
+//   per layer:  a = l == 0 ? h : LN_attn(h)                               -> x1 (layer 0 reads x itself: its attn_norm is the identity)
+//               QKV = a Wqkv^T + b (64-column blocks), rotated with the table of the layer's kind (global / local base)
+//               ctx = attention, windowed in the local layers (encoder_window.hip), the model's global kernels otherwise
+//               h = ctx Wo^T + bo + h                                     x -> y   (EPI_BIAS_RES, the raw stream as residual)
+//               m = LN_mlp(h)                                             -> x1
+//               h = (gelu(gate) * up)(m Wi^T + bi) Wo^T + bo + h          y -> x
+//   pooled = masked mean of final_norm(h), or final_norm of the [CLS] row (in f32, inside the pooling kernel; never pruned: cls_last_layer
+//   is the post-LN layer)
+static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
+                                        const PackedLayout* pk) {
+    const sc_encoder_cfg& c = e->cfg;
+    sc_runtime* rt = e->rt;
+    hipStream_t s = rt->stream;
+    const int H = c.hidden, F = c.ffn;
+    const int tokens = pk ? pk->rows : B * S;
+    const int M = (tokens + 255) / 256 * 256;
+    void* sk = nullptr;
+    if (M <= 1024 && e->path != 1) {
+        if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
+        sk = e->splitk;
+    }
+    const size_t skb = sk ? sc_encoder::SPLITK_BYTES : 0;
+    if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    else sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
+    for (int l = 0; l < c.layers; ++l) {
+        const LayerW& w = e->layers[l];
+        const bool local = layer_is_local(c, l);
+        const void* a = e->x;
+        if (l > 0) {
+            sc_launch_layernorm(e->x, tokens, H, w.ln1g, w.ln1b, c.ln_eps, e->x1, s);
+            a = e->x1;
+        }
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, a, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, 3 * H, H, s, sk, skb); });
+        launch_rope(e, M, S, pk, s, local);
+        sc_with_prof(rt, SC_PROF_ATTN, [&] {
+            if (local) launch_attention_window(e, lens_dev, B, S, M, pk, s);
+            else launch_attention(e, lens_dev, B, S, M, pk, s);
+        });
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x, H, e->y, H, M, H, H, s, sk, skb); });
+        sc_launch_layernorm(e->y, tokens, H, w.ln2g, w.ln2b, c.ln_eps, e->x1, s);
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
+        launch_gate(c, e->hm, M, F, e->hg, s);
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
+    }
+    if (cls_pooling(e, pk)) {
+        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, e->fing, e->finb, c.ln_eps, c.normalize, out_dev, s);
+    } else {
+        sc_launch_layernorm(e->x, tokens, H, e->fing, e->finb, c.ln_eps, e->x1, s);
+        launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
 // ids_dev [B,S], lens_dev [B] device pointers; out_dev [B,H] f32 device.  pk != NULL: a packed batch -- ids_dev holds one id per token
 // row of the layout (M of them), S is unused.  Caller holds e->mu.
 static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
@@ -559,6 +656,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     const int H = c.hidden, F = c.ffn;
     const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
+    if (c.arch == 1) return forward_prenorm_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
     // batches beyond 1024 token rows (or sc_encoder_set_path 1) take the LayerNorm-folded pipeline where the model's shapes allow it
     static const bool env_fold = sc_env_flag("SC_ENC_FOLD", true);  // SC_ENC_FOLD=0: same-box A/B against the stand-alone LayerNorm kernels
     if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
@@ -960,6 +1058,8 @@ extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, c
                                             float* out_logits, float* out_cls) {
     const char* who = "sc_encoder_score_pairs";
     if (!e || !ids || !offsets || !first_lens || !out_logits) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (e->cfg.arch == 1)  // ModernBERT's classifier is dense -> GELU -> LayerNorm -> linear; pair_head_kernel is pooler + tanh
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 1 (pre-LN) models have no pair head: their classifier is not pooler + linear", who);
     int64_t used = 0;
     sc_status st = check_packed_offsets(e, offsets, B, who, &used);
     if (st) return st;

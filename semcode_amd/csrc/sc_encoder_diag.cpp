@@ -377,6 +377,47 @@ extern "C" sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qk
     return diag_attention_packed("sc_diag_attention_packed_hd", rt, qkv, starts, lens, B, heads, head_dim, blocked_rows, slopes, out);
 }
 
+// sc_launch_attention_window / _packed as the pre-norm forward calls them (starts == NULL: the rectangle form)
+extern "C" sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                              int32_t local_window, int32_t blocked_rows, float* out) {
+    const char* who = "sc_diag_attention_window";
+    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1 || heads * 64 > 2048) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (!sc_attention_window_supported(local_window)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: local_window must be even and within 2 .. 128, got %d", who, local_window);
+    const int H = heads * 64;
+    int64_t R = 0, rows_out = 0;
+    std::vector<int32_t> items;
+    int nitems[3] = {0, 0, 0};
+    if (starts) {
+        int64_t end = 0;
+        for (int32_t b = 0; b < B; ++b) {
+            if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
+                return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
+            const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
+            if (e > end) end = e;
+        }
+        R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
+        if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
+        rows_out = R;
+        items.resize((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
+        sc_packed_items(starts, lens, B, items.data(), nitems);
+    } else {
+        if (!sc_attention_supported(S, H, heads, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
+        rows_out = (int64_t)B * S;
+        if (blocked_rows && blocked_rows < rows_out) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
+        R = blocked_rows ? (int64_t)blocked_rows : rows_out;
+    }
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fq, dq, dl, dc;
+    SC_TRY(upload_bf16(qkv, R * 3 * H, fq, dq, s));
+    if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
+    else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
+    if (starts) sc_launch_attention_window_packed(dq.p, (const int32_t*)dl.p, nitems, H, local_window, dc.p, s, blocked_rows);
+    else sc_launch_attention_window(dq.p, (const int32_t*)dl.p, B, S, H, local_window, dc.p, s, blocked_rows);
+    return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
+}
+
 // rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],
 // rotated in place, widened and laid out row-major again.
 extern "C" sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta) {

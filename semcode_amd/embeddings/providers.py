@@ -22,7 +22,7 @@ import numpy as np
 
 from ..settings import resolve as _resolve_settings
 from .payload import EmbeddingPayload
-from .tokenizer import HashTokenizer, WordPieceTokenizer, pack
+from .tokenizer import HashTokenizer, HFTokenizer, WordPieceTokenizer, pack
 
 log = logging.getLogger(__name__)
 
@@ -77,6 +77,91 @@ def _nomic_blob(path, tensors: dict, layers: int) -> np.ndarray:
     return np.concatenate(parts)
 
 
+# transformers ModernBertModel names (answerdotai/ModernBERT-base, gte-modernbert-base, modernbert-embed-base), with or without a
+# "model." prefix: pre-norm layers, no position or type table, Wqkv = [Wq; Wk; Wv] row thirds, Wi = [activated half; gate half] -- the
+# activated half is what the GEGLU kernel calls the gate rows, so Wi lands in W1 as it is.  Blob order: arch 1 of include/semcode_hip.h.
+# Norm, attention and MLP biases are optional tensors (norm_bias / attention_bias / mlp_bias models); absent = zeros.
+def _modernbert_blob(path, tensors: dict, layers: int) -> np.ndarray:
+    def find(name: str):
+        for key in (name, "model." + name):
+            if key in tensors:
+                return np.asarray(tensors[key], dtype=np.float32)
+        return None
+
+    def get(name: str) -> np.ndarray:
+        t = find(name)
+        if t is None:
+            raise KeyError(f"{path}: tensor {name!r} not found")
+        return t
+
+    def opt(name: str, n: int) -> np.ndarray:
+        t = find(name)
+        return np.zeros(n, np.float32) if t is None else t.reshape(-1)
+
+    H = get("embeddings.norm.weight").shape[0]
+    parts = [get("embeddings.tok_embeddings.weight").reshape(-1), get("embeddings.norm.weight"), opt("embeddings.norm.bias", H)]
+    for l in range(layers):
+        q = f"layers.{l}."
+        wqkv, bqkv = get(q + "attn.Wqkv.weight"), opt(q + "attn.Wqkv.bias", 3 * H)
+        if wqkv.shape != (3 * H, H):
+            raise ValueError(f"{path}: {q}attn.Wqkv.weight is {wqkv.shape}, expected {(3 * H, H)}")
+        wi = get(q + "mlp.Wi.weight")
+        for third in range(3):
+            parts += [wqkv[third * H:(third + 1) * H].reshape(-1), bqkv[third * H:(third + 1) * H]]
+        attn_norm = find(q + "attn_norm.weight")  # layer 0 has none (identity): the slot is present and never read
+        parts += [get(q + "attn.Wo.weight").reshape(-1), opt(q + "attn.Wo.bias", H),
+                  np.ones(H, np.float32) if attn_norm is None else attn_norm, opt(q + "attn_norm.bias", H),
+                  wi.reshape(-1), opt(q + "mlp.Wi.bias", wi.shape[0]), get(q + "mlp.Wo.weight").reshape(-1), opt(q + "mlp.Wo.bias", H),
+                  get(q + "mlp_norm.weight"), opt(q + "mlp_norm.bias", H)]
+    parts += [get("final_norm.weight"), opt("final_norm.bias", H)]
+    return np.concatenate(parts)
+
+
+def modernbert_config(config: "str | Path | dict") -> dict:
+    """The encoder configuration of a transformers ModernBERT `config.json` (path or parsed dict).  Layer pattern: the integer
+    `global_attn_every_n_layers`, or a `layer_types` list that follows such a pattern ("full_attention" exactly at l % n == 0); any
+    other list is refused.  Rotary bases: `global_rope_theta` / `local_rope_theta`, or `rope_parameters` per layer type."""
+    if not isinstance(config, dict):
+        import json
+
+        config = json.loads(Path(config).read_text())
+    c = config
+    if c.get("model_type") not in (None, "modernbert"):
+        raise ValueError(f"not a ModernBERT configuration (model_type {c.get('model_type')!r})")
+    layers = int(c["num_hidden_layers"])
+    types = c.get("layer_types")
+    if types is not None:
+        if len(types) != layers or any(t not in ("full_attention", "sliding_attention") for t in types):
+            raise ValueError(f"ModernBERT config: layer_types must name full_attention / sliding_attention for each of the {layers} layers")
+        every = next((n for n in range(1, layers + 1) if all((t == "full_attention") == (l % n == 0) for l, t in enumerate(types))), None)
+        if every is None:
+            raise ValueError(f"ModernBERT config: layer_types {types} is not 'global every n-th layer from layer 0'; no other pattern is supported")
+    else:
+        every = int(c.get("global_attn_every_n_layers", 3))
+    rp = c.get("rope_parameters") or {}
+    theta_g = (rp.get("full_attention") or {}).get("rope_theta", c.get("global_rope_theta", 160000.0))
+    theta_l = (rp.get("sliding_attention") or {}).get("rope_theta", c.get("local_rope_theta", theta_g if c.get("local_rope_theta", 0) is None else 10000.0))
+    if c.get("hidden_activation", "gelu") != "gelu":
+        raise ValueError(f"ModernBERT config: hidden_activation {c.get('hidden_activation')!r} is not supported (gelu only)")
+    return dict(vocab=int(c["vocab_size"]), hidden=int(c["hidden_size"]), layers=layers, heads=int(c["num_attention_heads"]),
+                ffn=int(c["intermediate_size"]), max_pos=int(c.get("max_position_embeddings", 8192)), type_vocab=1,
+                ln_eps=float(c.get("norm_eps", 1e-5)), rotary=True, geglu=True, modernbert=True, local_window=int(c.get("local_attention", 128)),
+                global_every=int(every), rope_theta=float(theta_g), rope_theta_local=float(theta_l))
+
+
+def modernbert_config_beside(weights: "str | Path | None") -> Optional[dict]:
+    """modernbert_config of the config.json next to a .safetensors file, None when there is none or it is another model's."""
+    if not isinstance(weights, (str, Path)) or not str(weights).lower().endswith(".safetensors"):
+        return None
+    conf = Path(weights).parent / "config.json"
+    if not conf.is_file():
+        return None
+    import json
+
+    c = json.loads(conf.read_text())
+    return modernbert_config(c) if c.get("model_type") == "modernbert" else None
+
+
 def tensors_rows(tensors: dict, name: str) -> int:
     """Number of rows (output features) of a 2-D checkpoint tensor, with or without the "bert." prefix."""
     for key in (name, "bert." + name):
@@ -88,7 +173,8 @@ def tensors_rows(tensors: dict, name: str) -> int:
 def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None) -> np.ndarray:
     """Flat f32 blob in ABI order from `.npy` (already flat), `.gguf` (llama.cpp's bert / jina-bert-v2 tensor names, F32 / F16 /
     BF16; embeddings/gguf.py) or `.safetensors` (HF BERT names, jina-bert-v2 names when the file holds `mlp.gated_layers`, or
-    transformers' NomicBert names when it holds `layers.0.mlp.gate_proj`; optional "bert." / "nomic_bert." prefix).  cfg: the
+    transformers' NomicBert names when it holds `layers.0.mlp.gate_proj`, or transformers' ModernBert names when it holds
+    `layers.0.attn.Wqkv`; optional "bert." / "nomic_bert." / "model." prefix).  GGUF files of the ModernBERT family are not read.  cfg: the
     encoder configuration the blob is for (checked against the checkpoint's architecture: a jina file needs alibi + geglu, a
     nomic file rotary + swiglu, a BERT file none of them)."""
     path = Path(path)
@@ -107,6 +193,13 @@ def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None
 
         jina = any(k.endswith("encoder.layer.0.mlp.gated_layers.weight") for k in tensors)
         nomic = any(k in ("layers.0.mlp.gate_proj.weight", "nomic_bert.layers.0.mlp.gate_proj.weight") for k in tensors)
+        if any(k in ("layers.0.attn.Wqkv.weight", "model.layers.0.attn.Wqkv.weight") for k in tensors):
+            if cfg is not None and not (cfg.get("modernbert") and cfg.get("rotary") and cfg.get("geglu")):
+                raise ValueError(f"{path} is a ModernBERT checkpoint but the encoder configuration is not modernbert + rotary + geglu "
+                                 "(modernbert_config reads it from the model's config.json)")
+            return _modernbert_blob(path, tensors, layers)
+        if cfg is not None and cfg.get("modernbert"):
+            raise ValueError(f"{path} holds no ModernBERT tensors (layers.0.attn.Wqkv.weight) but the encoder configuration says modernbert")
         if cfg is not None and (bool(cfg.get("alibi")) != jina or bool(cfg.get("geglu")) != jina or bool(cfg.get("rotary")) != nomic
                                 or bool(cfg.get("swiglu")) != nomic):
             kind = "nomic-bert (rotary + SwiGLU)" if nomic else "jina-bert-v2 (ALiBi + GEGLU)" if jina else "BERT"
@@ -199,13 +292,18 @@ class MI355XEmbeddings:
     Pooling: `pooling="mean"` (masked mean over the real tokens) or `"cls"` (the last hidden state of the first token: bge,
     snowflake-arctic-embed, mxbai-embed-large, gte); None resolves it as resolve_pooling does -- the setting mi355x_pooling, then what
     the file states (a GGUF's `bert.pooling_type`, a sentence-transformers `1_Pooling/config.json` next to a .safetensors), then mean.
-    bge-small-en-v1.5 is `cfg=dict(hidden=384, heads=12, layers=12, ffn=1536), pooling="cls"`."""
+    bge-small-en-v1.5 is `cfg=dict(hidden=384, heads=12, layers=12, ffn=1536), pooling="cls"`.
+
+    ModernBERT (answerdotai/ModernBERT-base, gte-modernbert-base, modernbert-embed-base): point `weights` at the model.safetensors of
+    the model directory -- the `config.json` beside it gives the whole configuration (modernbert_config) and the `tokenizer.json`
+    beside it the byte-level BPE tokenizer (HFTokenizer; or `tokenizer_json=` / SEMCODE_MI355X_TOKENIZER_JSON)."""
 
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,
                  normalize: bool = False, batch_size: int = 256, runtime: Any = None, synth_seed: int = 0,
                  allow_synthetic: Optional[bool] = None, document_prefix: Optional[str] = None, query_prefix: Optional[str] = None,
-                 packed: Optional[bool] = None, packed_rows_budget: int = 65536, pooling: Optional[str] = None) -> None:
+                 packed: Optional[bool] = None, packed_rows_budget: int = 65536, pooling: Optional[str] = None,
+                 tokenizer_json: "str | Path | None" = None) -> None:
         from .. import _native  # raises loudly when libsemcode_hip.so is missing: there is no CPU fallback
 
         settings = _resolve_settings()
@@ -266,8 +364,16 @@ class MI355XEmbeddings:
                     self._vocab_tmp.write("\n".join(toks) + "\n")
                     self._vocab_tmp.close()
                     vocab = self._vocab_tmp.name
+        # a ModernBERT directory: config.json beside the .safetensors states the architecture; its tokenizer is a byte-level BPE
+        # tokenizer.json (tokenizer_json=, SEMCODE_MI355X_TOKENIZER_JSON, or the file beside the weights when no vocab.txt is configured)
+        mb_cfg = modernbert_config_beside(weights)
+        if mb_cfg is not None:
+            self._cfg.update(mb_cfg)
+        tokenizer_json = tokenizer_json if tokenizer_json is not None else getattr(settings, "mi355x_tokenizer_json", None)
+        if tokenizer_json is None and vocab is None and isinstance(weights, (str, Path)) and (Path(weights).parent / "tokenizer.json").is_file():
+            tokenizer_json = Path(weights).parent / "tokenizer.json"
         self._cfg.update(cfg or {})
-        if vocab is None and not allow_synthetic:  # (a GGUF file brings its own vocabulary: checked after it was read)
+        if vocab is None and tokenizer_json is None and not allow_synthetic:  # (a GGUF file brings its own vocabulary: checked after it was read)
             raise ValueError("Set SEMCODE_MI355X_VOCAB_PATH (vocab.txt of the model) when using the mi355x embedding provider "
                              "(or SEMCODE_MI355X_ALLOW_SYNTHETIC=1 for the hash-tokenizer stand-in).")
         self.max_tokens = min(self.max_tokens, self._cfg["max_pos"])
@@ -280,7 +386,9 @@ class MI355XEmbeddings:
         if weights is None:
             log.warning("mi355x embeddings: no weights configured (SEMCODE_MI355X_WEIGHTS_PATH); using random-init weights seed=%d", synth_seed)
         self._encoder = _native.Encoder(self._runtime, self._cfg, weights=weights, normalize=normalize, synth_seed=synth_seed, pooling=self.pooling)
-        if vocab is None:
+        if tokenizer_json is not None:  # the `tokenizers` library on the host; the native WordPiece thread pool is not used
+            self.tokenizer = HFTokenizer(tokenizer_json)
+        elif vocab is None:
             log.warning("mi355x embeddings: no vocab.txt configured (SEMCODE_MI355X_VOCAB_PATH); using the hash tokenizer stand-in")
             self.tokenizer: Any = HashTokenizer(self._cfg["vocab"])
         else:

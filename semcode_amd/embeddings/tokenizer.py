@@ -129,6 +129,40 @@ class HashTokenizer:
         return ids[: max_tokens - 1] + [self.sep_id]
 
 
+class HFTokenizer:
+    """A `tokenizer.json` (byte-level BPE of the ModernBERT family, or any other model the `tokenizers` library reads) behind the
+    encode(text, max_tokens) / pad_id interface of the tokenizers above.  The file's own post-processor adds the special tokens
+    ([CLS] ... [SEP]); a text longer than max_tokens keeps its first max_tokens - 1 ids and the last one (the closing special token),
+    as WordPieceTokenizer truncates.  The library is imported here, on first use of the class."""
+
+    def __init__(self, path: "str | Path", pad: "str | None" = None) -> None:
+        try:
+            from tokenizers import Tokenizer
+        except ImportError as exc:  # pragma: no cover - the package is a dependency of transformers
+            raise RuntimeError("the `tokenizers` package is required to read a tokenizer.json (ModernBERT models); install it or "
+                               "configure a WordPiece vocab.txt instead") from exc
+        self._tok = Tokenizer.from_file(str(path))
+        self._tok.no_truncation()
+        self._tok.no_padding()
+        self.pad_id = 0
+        for cand in ([pad] if pad else ["[PAD]", "<pad>", "<|padding|>"]):
+            i = self._tok.token_to_id(cand)
+            if i is not None:
+                self.pad_id = int(i)
+                break
+        self._closes = len(self._tok.encode("").ids) >= 2  # the post-processor closes a text with a special token
+
+    @property
+    def vocab_size(self) -> int:
+        return self._tok.get_vocab_size(with_added_tokens=True)
+
+    def encode(self, text: str, max_tokens: int = 512) -> List[int]:
+        ids = self._tok.encode(text).ids
+        if len(ids) > max_tokens:
+            ids = ids[: max_tokens - 1] + [ids[-1]] if self._closes and max_tokens >= 2 else ids[:max_tokens]
+        return list(ids)
+
+
 def bucket_for(n: int, max_tokens: int = 512) -> int:
     for b in SEQ_BUCKETS:
         if n <= b and b <= max(max_tokens, SEQ_BUCKETS[0]):

@@ -9,7 +9,7 @@ Backend-specific keys ride on the reference's extra="allow" (settings.py:36):
     mi355x_device, mi355x_metric, mi355x_index_type, mi355x_nlist, mi355x_nprobe,
     mi355x_weights_path, mi355x_vocab_path, mi355x_allow_synthetic, mi355x_max_tokens, mi355x_store_path, mi355x_ingest_batch,
     mi355x_document_prefix, mi355x_query_prefix, mi355x_packed, mi355x_pooling, mi355x_lexical,
-    mi355x_reranker_path, mi355x_reranker_vocab, mi355x_rerank_fetch_k
+    mi355x_reranker_path, mi355x_reranker_vocab, mi355x_rerank_fetch_k, mi355x_tokenizer_json
 """
 from __future__ import annotations
 
@@ -44,6 +44,7 @@ _DEFAULTS: dict[str, Any] = {
     "mi355x_nprobe": 16,              # milvus_store.py:144
     "mi355x_weights_path": None,
     "mi355x_vocab_path": None,
+    "mi355x_tokenizer_json": None,    # a `tokenizer.json` (byte-level BPE of ModernBERT models) instead of a WordPiece vocab.txt
     "mi355x_allow_synthetic": False,  # random-init weights / hash tokenizer when the two paths above are unset (benchmarks only)
     "mi355x_max_tokens": 512,
     "mi355x_document_prefix": "",     # put in front of every indexed text ("search_document: " for nomic-embed-text)
