@@ -8,10 +8,12 @@ profiles/encoder_split_ab.log; scripts/ab_encoder.sh drives it).  One process pe
     python scripts/ab_encoder.py speed DIR                  DIR/run_<i>_{new,base}.log + DIR/out_<i>_*/embed_pooled.npy of the bench runs:
                                                             outputs bit for bit, medians; the new build passes if its median is not
                                                             below the parent's by more than the parent's spread (max - min)
+    python scripts/ab_encoder.py attn LIB.so OUT.json       time per launch of the attention kernels on the MiniLM and ModernBERT shapes
+    python scripts/ab_encoder.py attnspeed DIR              DIR/attn_<i>_{new,base}.json of such runs: the same rule per workload
 
 Encoders: BERT, jina (ALiBi + GEGLU), nomic (rotary + SwiGLU, rope_fused 0 and 1) x {hidden 256 / ffn 512 (foldable), hidden 128 /
 ffn 384 (128-tile path)} x normalize {0, 1} x (B, S) {(2, 32), (5, 256)} (256 and 1 280 token rows: either side of the 1 024-row
-pipeline switch) x set_path {auto, batch, small}.
+pipeline switch) x set_path {auto, batch, small}.  Then every instantiation of the attention kernels on its own (attention_section).
 """
 import hashlib
 import sys
@@ -46,6 +48,41 @@ def use_library(lib_path):
 def line(name, a):
     a = np.ascontiguousarray(a)
     return f"{name} {a.dtype}{list(a.shape)} {hashlib.sha256(a.tobytes()).hexdigest()}"
+
+
+def attention_section(nv, rt, rng):
+    """Every instantiation of the attention kernels on its own (written for the head width as a policy of the kernels:
+    profiles/attention_shell_ab.log), hidden 128 = 2 heads of 64 or 4 heads of 32.  Rectangles: every S the launcher knows, lens
+    {S, S - 23, 1} (full, masked tail, one key; 1 024 and 2 048: one, two, up to four segments of 512), plain / ALiBi / head_dim 32,
+    row-major and blocked.  Packed: lens on both sides of the three launch classes, with live and dead waves.  Window: local_window
+    128 and 6 on rectangles and on the packed lens."""
+    out = []
+    H = 128
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    forms = {"plain": dict(heads=2), "alibi": dict(heads=2, slopes=np.array([0.25, 0.0625], np.float32)), "hd32": dict(heads=4, head_dim=32)}
+    ceil256 = lambda n: (n + 255) // 256 * 256
+    rects = [(S, [S, S - 23, 1]) for S in (32, 64, 128, 256, 512)] + [(1024, [1024, 513, 40]), (2048, [2048, 1025])]
+    for S, lens in rects:
+        B = len(lens)
+        qkv, lens = f(B * S, 3 * H), np.array(lens, np.int32)
+        for blocked in (0, ceil256(B * S)):
+            for form, kw in forms.items():
+                out.append(line(f"attn rect S={S} {form} blocked={blocked}", nv.diag_attention_ex(rt, qkv, lens, B, S, blocked_rows=blocked, **kw)))
+            if S in (128, 256, 1024):
+                padded = np.concatenate([qkv, np.zeros((blocked - B * S, 3 * H), np.float32)]) if blocked else qkv  # diag_attention_ex pads by itself
+                for lw in (128, 6):
+                    out.append(line(f"attn window rect S={S} lw={lw} blocked={blocked}", nv.diag_attention_window(rt, padded, lens, 2, lw, S=S, blocked_rows=blocked)))
+    lens = np.array([1, 32, 33, 255, 256, 257, 512, 513, 1500], np.int32)
+    rows = (lens + 31) // 32 * 32
+    starts = (np.cumsum(rows) - rows).astype(np.int32)
+    R = ceil256(int(rows.sum()))
+    qkv = f(R, 3 * H)
+    for blocked in (0, R):
+        for form, kw in forms.items():
+            out.append(line(f"attn packed {form} blocked={blocked}", nv.diag_attention_packed(rt, qkv, starts, lens, blocked_rows=blocked, **kw)))
+        for lw in (128, 6):
+            out.append(line(f"attn window packed lw={lw} blocked={blocked}", nv.diag_attention_window(rt, qkv, lens, 2, lw, starts=starts, blocked_rows=blocked)))
+    return out
 
 
 def dump(lib_path, out_path):
@@ -117,6 +154,7 @@ def dump(lib_path, out_path):
     out.append(line("embed raw rows", rows))
     out.append(line("embed raw stats", st))
     out.append(line("embed ln", nv.diag_embed(rt, ids, wemb, None, temb, 64, ln=(gamma, beta, 1e-12))))
+    out += attention_section(nv, rt, np.random.default_rng(7))
     rt.close()
     Path(out_path).write_text("\n".join(out) + "\n")
     print(f"{len(out)} arrays -> {out_path}")
@@ -164,8 +202,75 @@ def speed(dirname):
     return 0 if ok else 1
 
 
+def attn(lib_path, out_path):
+    """Time per launch of the attention profiling class (3), as scripts/bench_modernbert.py brackets it, on the shapes of
+    scripts/bench_minilm.py (384 hidden, 256 texts of 256 tokens, heads of 32 and of 64) and of scripts/bench_modernbert.py (32k tokens
+    as texts of 256 / 1 024 / 2 048, the windowed and the all-global model), padded and packed, and on rectangles of every other
+    length with heads of 32 (64k tokens): one JSON line per workload."""
+    import json
+
+    nv = use_library(lib_path)
+    rt = nv.Runtime()
+    rng = np.random.default_rng(11)
+    mini = dict(nv.BERT_BASE, hidden=384, layers=6, ffn=1536, max_pos=512)
+    modern = dict(vocab=50368, hidden=768, layers=22, heads=12, ffn=1152, max_pos=8192, type_vocab=1, ln_eps=1e-5, rotary=True, geglu=True, modernbert=True,
+                  local_window=128, global_every=3, rope_theta=160000.0, rope_theta_local=10000.0)
+    models = {"minilm d32": (dict(mini, heads=12), (256,)), "minilm d64": (dict(mini, heads=6), (256,)),
+              "modernbert windowed": (modern, (256, 1024, 2048)), "modernbert global": (dict(modern, global_every=1), (256, 1024, 2048)),
+              # the other rectangle kernels of the 32-wide heads (S = 256 is above): 64 rows of tokens per text length
+              "minilm d32 rect": (dict(mini, heads=12, max_pos=2048), (32, 64, 128, 512, 1024, 2048))}
+    out = []
+    for name, (cfg, lengths) in models.items():
+        enc = nv.Encoder(rt, cfg, weights=None, synth_seed=1)
+        for S in lengths:
+            B = 65536 // S if name.endswith("rect") else (256 if name.startswith("minilm") else 32768 // S)
+            ids, lens = rng.integers(1, 30000, size=(B, S)).astype(np.int32), np.full(B, S, np.int32)
+            flat, offsets = ids.reshape(-1), (np.arange(B + 1) * S).astype(np.int64)
+            for form, call in (("padded", lambda: enc.embed_ids(ids, lens)), ("packed", lambda: enc.embed_packed(flat, offsets)))[: 1 if name.endswith("rect") else 2]:
+                call()  # warm-up: workspace, first touch
+                rt.set_profiling(1)
+                rt.profile_reset()
+                call()
+                call()
+                ms, n = rt.profile_read(3)
+                rt.set_profiling(0)
+                out.append(json.dumps({"name": f"{name} S={S} {form}", "us_per_launch": 1e3 * ms / max(n, 1), "launches": n}))
+        enc.close()
+    rt.close()
+    Path(out_path).write_text("\n".join(out) + "\n")
+    print(f"{len(out)} workloads -> {out_path}")
+
+
+def attnspeed(dirname):
+    """DIR/attn_<i>_{new,base}.json of the alternating `attn` runs: per workload the medians; the new build passes a workload if its
+    median time per launch is not above the parent's by more than the parent's spread (max - min)."""
+    import json
+
+    t = {"new": {}, "base": {}}
+    for f in sorted(Path(dirname).glob("attn_*.json")):
+        which = f.stem.split("_")[2]
+        for l in f.read_text().splitlines():
+            r = json.loads(l)
+            t[which].setdefault(r["name"], []).append(r["us_per_launch"])
+    ok = bool(t["base"]) and t["base"].keys() == t["new"].keys()
+    print("# attention class, us per launch | parent runs | new runs | median parent -> new | parent spread | verdict")
+    for name, base in t["base"].items():
+        new = t["new"].get(name, [])
+        bm, nm, spread = float(np.median(base)), float(np.median(new or [np.inf])), max(base) - min(base)
+        good = len(base) == len(new) >= 3 and nm <= bm + spread
+        ok &= good
+        print(f"{name} | {' '.join(f'{v:.1f}' for v in base)} | {' '.join(f'{v:.1f}' for v in new)} | {bm:.1f} -> {nm:.1f} ({nm / bm:.4f}) | {spread:.1f} | "
+              f"{'pass' if good else 'FAIL'}")
+    print("VERDICT:", "pass" if ok else "FAIL")
+    return 0 if ok else 1
+
+
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "dump":
+    if len(sys.argv) == 4 and sys.argv[1] == "attn":
+        attn(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 3 and sys.argv[1] == "attnspeed":
+        sys.exit(attnspeed(sys.argv[2]))
+    elif len(sys.argv) == 4 and sys.argv[1] == "dump":
         dump(sys.argv[2], sys.argv[3])
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))

@@ -3,7 +3,7 @@
     python scripts/bench_minilm.py [--texts 4096] [--passes 3] >> profiles/headdim32_bench.log
 
 Two encoders of 384 hidden / 6 layers / 1536 ffn / 512 positions: 12 heads of 32 (all-MiniLM-L6-v2's shape) and 6 heads of 64.  Their GEMMs
-are identical; only the attention kernels differ (encoder_attn32.hip against attention_kernel / attention_packed_kernel).  Input: --texts
+are identical; only the attention kernels differ (attention_kernel / attention_packed_kernel on Head32 against Head64, attention_core.h).  Input: --texts
 texts of 256 tokens, as padded rectangles of 256 texts (Encoder.embed_ids) and packed (flatten_ids + Encoder.embed_packed, 65 536 rows a
 call).  Per model and path: texts/s (best of --passes timed passes after a warm-up) and, from a separate pass with every launch
 bracketed by events (sc_runtime_set_profiling(1), sc_runtime_profile_read(which=3)), the time inside the attention class.  The d32 / d64

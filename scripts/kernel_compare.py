@@ -1,11 +1,13 @@
 """Kernels of the scan files in two builds of the library, one line per kernel: registers, scratch, LDS, occupancy, instruction count,
 and whether the instruction text is identical (labels renumbered, comments dropped).  Written for the split of scan_batched.hip
-by stage (profiles/scan_split_kernels.log); `canon` maps the parent's template argument order of scan_coarse256_kernel to the new one.
+by stage (profiles/scan_split_kernels.log); `canon` maps the parent's spelling of an instantiation to the new one: the template argument
+order of scan_coarse256_kernel, the attention kernels on a head-width policy (profiles/attention_shell_kernels.log).
 
     python -m semcode_amd.csrc.build --force --save-temps 2> BUILD.log     (in a checkout of each commit; keep csrc/_obj/*gfx950.s)
     python scripts/kernel_compare.py PARENT_S_DIR PARENT_BUILD.log NEW_S_DIR NEW_BUILD.log [STEM,STEM...]
 
-With a list of stems (e.g. gemm_bf16,encoder_ops: profiles/encoder_split_kernels.log) the same files are compared in both builds.
+With a list of stems (e.g. gemm_bf16,encoder_ops: profiles/encoder_split_kernels.log) the same files are compared in both builds; a stem
+one build lacks (a file removed or added) contributes that build's kernels only.
 """
 import hashlib
 import re
@@ -66,7 +68,8 @@ def demangle(names):
 
 
 def canon(d):
-    """parent -> new spelling of scan_coarse256_kernel<METRIC, DBG, I8, PP, DENSE> ; None = instantiation removed on purpose"""
+    """parent -> new spelling of an instantiation (scan_coarse256_kernel<METRIC, DBG, I8, PP, DENSE>, the attention kernels); None =
+    instantiation removed on purpose"""
     d = re.sub(r"\(.*$", "", d).replace("void ", "")
     m = re.match(r"scan_coarse256_kernel<(\d+), (\d+), (true|false), (\d+), (true|false)>", d)
     if m:
@@ -74,7 +77,17 @@ def canon(d):
         if dbg not in ("0", "2"):
             return None
         return f"scan_coarse256_kernel<{metric}, {i8}, {pp}, {dense}, {'true' if dbg == '2' else 'false'}>"
-    return d
+    # attention kernels on a head-width policy (profiles/attention_shell_kernels.log): <KT, ALIBI, NW> -> <Head64<ALIBI>, KT, NW>,
+    # attention32_* -> <Head32, ...>; the 4-wave instantiations at KT 8 and 16 went with the experiment switch that chose them
+    m = re.match(r"attention_kernel<(\d+), (true|false), (\d+)>", d)
+    if m:
+        kt, alibi, nw = m.groups()
+        return None if (int(kt) >= 8 and nw == "4") else f"attention_kernel<Head64<{alibi}>, {kt}, {nw}>"
+    d = re.sub(r"^attention_long_kernel<(true|false)>", r"attention_long_kernel<Head64<\1>>", d)
+    d = re.sub(r"^attention_packed_kernel<(\d+), (\d+), (true|false)>", r"attention_packed_kernel<Head64<\3>, \1, \2>", d)
+    d = re.sub(r"^attention32_long_kernel$", "attention_long_kernel<Head32>", d)
+    d = re.sub(r"^attention32_(packed_)?kernel<", r"attention_\1kernel<Head32, ", d)
+    return d.replace("> >", ">>")
 
 
 def main(pdir, plog, ndir, nlog, stems=None):
@@ -93,7 +106,7 @@ def main(pdir, plog, ndir, nlog, stems=None):
             removed.append(dm[k].split("(")[0])
         else:
             pk[c] = k
-    nk = {re.sub(r"\(.*$", "", dm[k]).replace("void ", ""): k for k in nr}
+    nk = {re.sub(r"\(.*$", "", dm[k]).replace("void ", "").replace("> >", ">>"): k for k in nr}
     keys = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
     print("# kernel | file | VGPR AGPR scratch LDS occupancy (parent -> new when they differ) | instructions parent -> new | text")
     bad = 0
@@ -107,7 +120,7 @@ def main(pdir, plog, ndir, nlog, stems=None):
         la, lb = pb[pk[c]], nb[nk[c]]
         ia = sum(1 for l in la if not l.endswith(":")); ib = sum(1 for l in lb if not l.endswith(":"))
         same = hashlib.sha1("\n".join(la).encode()).digest() == hashlib.sha1("\n".join(lb).encode()).digest()
-        flag = "identical" if same else ("differs" if ib <= ia else "differs, GREW")
+        flag = "identical" if same else ("differs" if ib <= ia else f"differs, GREW +{ib - ia}")
         if any(a[k] != b[k] for k in keys) or ib > ia:
             bad += 1
         print(f"{c} | {b['src']} | {res} | {ia} -> {ib} | {flag}")

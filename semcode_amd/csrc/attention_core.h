@@ -1,10 +1,21 @@
-// attention_core.h -- the device code the attention kernels share (encoder_ops.hip: rectangles, encoder_packed.hip: packed
-// variable-length rows): the online-softmax state of one 32-row query block, the fold of one segment of keys into it, the store.
+// attention_core.h -- what the attention kernels share (encoder_ops.hip: rectangles, encoder_packed.hip: packed variable-length
+// rows, encoder_window.hip: local attention).
+//   the math   : the online-softmax state of one 32-row query block, the fold of one segment of keys into it, the store
+//                (AttnState / attention_qblock_core / attn_state_store), the band fold of local attention (attention_qblock_window)
+//   head width : Head64<ALIBI> and Head32 name state, init, fold and store of a width; the kernels are templates on one of them.
+//                Head dimension 32: the LDS images hold a PAIR of heads, AttnState32 / attention_qblock_core32 / attn_state32_store
+//                run the softmax once per head of the pair
+//   the shell  : what a kernel does around the math (LDS carve-up, operand addressing, the two staging loops, the Q load, wait +
+//                barrier) stays written out in each kernel: moved into shared functions, each of those steps changed the compiled
+//                text of the kernels that used it, and the 8-tile packed class measured slower (encoder_ops.hip).  What is
+//                shared is the LDS size of a launch, attn_lds_bytes
+//   launching  : attn_launch (dynamic-LDS limit once per instantiation and device), attn_packed_classes (the three launch classes)
 // LDS images: K [keys][64] with chunk ^= (row>>1)&7, V [keys][64] with chunk ^= ((row>>1)&1)<<2 (encoder_ops.hip describes them).
-// Head dimension 32 (encoder_attn32.hip): the same images hold a PAIR of heads, AttnState32 / attention_qblock_core32 / attn_state32_store
-// at the end of this file run the softmax once per head of the pair.
 #pragma once
-#include "gemm_tile.h"  // bf16 helpers, vector types
+#include <type_traits>  // std::integral_constant (attn_packed_classes)
+
+#include "gemm_tile.h"   // bf16 helpers, vector types, LDS-DMA pointer types
+#include "sc_common.h"   // ScDeviceOnce (attn_launch)
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -462,4 +473,58 @@ static __device__ __forceinline__ void attention_qblock_window(const bf16x8 (&qf
     S_.l_run = sum > 0.f ? sum : 1.0f;
     S_.o0 = o0;
     S_.o1 = o1;
+}
+
+// ------------------------------------------------------------------ LDS of a launch
+// Dynamic LDS of a workgroup of `nw` waves that stages `kts` key tiles: the K image, the V image (32 rows x 128 B per tile each), then
+// per wave 32 floats of alpha / 1/l exchange and one [8 q][64 d] bf16 block of output staging.  Every launcher sizes its launch with it.
+static constexpr int attn_lds_bytes(int kts, int nw) { return 2 * kts * 32 * 128 + nw * 128 + nw * 1024; }
+
+// ------------------------------------------------------------------ head width as a policy
+// What a kernel shell needs to know about the head width: the state of a query block, its init, the fold of the staged keys, the store,
+// and Extra, the kernel argument the width brings along (ALiBi slopes; the 32-wide kernels have none: no 32-wide ALiBi model exists).
+template <bool ALIBI>
+struct Head64 {
+    typedef AttnState State;
+    typedef const float* __restrict__ Extra;  // [heads] ALiBi slopes (device), NULL without ALIBI
+    static __device__ __forceinline__ void init(State& st) { attn_state_init(st); }
+    static __device__ __forceinline__ float slope2(Extra slopes, int head) { return ALIBI ? slopes[head] * 1.44269504088896340736f : 0.f; }
+    template <int KT, bool FULL, int GKMAX>
+    static __device__ __forceinline__ void fold(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane, int qbase, float slope2, State& st, bool first,
+                                                int key0) {
+        attention_qblock_core<KT, FULL, ALIBI, GKMAX>(qf, Kl, Vl, xch, len, nkt, lane, qbase, slope2, st, first, key0);
+    }
+    static __device__ __forceinline__ void store(const State& st, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
+        attn_state_store(st, xch, ostg, obase, H, lane);
+    }
+};
+struct Head32 {
+    typedef AttnState32 State;
+    struct Extra {};
+    static __device__ __forceinline__ void init(State& st) { attn_state32_init(st); }
+    static __device__ __forceinline__ float slope2(Extra, int) { return 0.f; }
+    template <int KT, bool FULL, int GKMAX>
+    static __device__ __forceinline__ void fold(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane, int, float, State& st, bool first, int) {
+        attention_qblock_core32<KT, FULL, GKMAX>(qf, Kl, Vl, xch, len, nkt, lane, st, first);
+    }
+    static __device__ __forceinline__ void store(const State& st, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
+        attn_state32_store(st, xch, ostg, obase, H, lane);
+    }
+};
+
+// ------------------------------------------------------------------ launching
+// Raises KERNEL's dynamic-LDS limit to LDS bytes once per instantiation and device, then launches it with that much.
+template <auto KERNEL, int LDS, class... ARGS>
+static void attn_launch(dim3 grid, int threads, hipStream_t s, ARGS... args) {
+    static ScDeviceOnce once;
+    sc_device_once(once, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS); });
+    hipLaunchKernelGGL(KERNEL, grid, dim3((unsigned)threads), (size_t)LDS, s, args...);
+}
+// The three launch classes of a packed work-item table (sc_packed_items: items sorted by class, nitems[3] per class):
+// launch(class as std::integral_constant, first item of the class, their number) for every class that has items.
+template <class F>
+static void attn_packed_classes(const int32_t* items, const int* nitems, F launch) {
+    if (nitems[0] > 0) launch(std::integral_constant<int, 0>(), items, nitems[0]);
+    if (nitems[1] > 0) launch(std::integral_constant<int, 1>(), items + 4 * (size_t)nitems[0], nitems[1]);
+    if (nitems[2] > 0) launch(std::integral_constant<int, 2>(), items + 4 * ((size_t)nitems[0] + nitems[1]), nitems[2]);
 }

@@ -75,10 +75,6 @@ void sc_launch_mean_pool_packed(const void* x, const int32_t* starts, const int3
 void sc_launch_mean_pool_ln_packed(const void* y, const float* stats, int slots, int tokens_pad, const float* gamma, const float* beta, float eps,
                                    const int32_t* starts, const int32_t* lens, int B, int H, float* out, hipStream_t s);
 
-// ---- encoder_attn32.hip: head dimension 32, what the two attention launchers above dispatch to (same arguments, no ALiBi slopes)
-void sc_launch_attention32(const void* qkv, const int32_t* lens, int B, int S, int H, void* ctx, hipStream_t s, int blocked);
-void sc_launch_attention32_packed(const void* qkv, const int32_t* items, const int* nitems, int H, void* ctx, hipStream_t s, int blocked);
-
 // ---- encoder_window.hip: local (sliding-window) attention, head dimension 64, plain scores: a query sees the real keys with
 // |query - key| <= local_window / 2.  local_window even, 2 .. 128; the other arguments as the two attention launchers above.
 bool sc_attention_window_supported(int local_window);

@@ -10,16 +10,16 @@
 //   embed_ln_kernel   HBM-bound  : 1 wave / token, f32 tables -> bf16 activations
 //   layernorm_kernel  HBM-bound  : 1 wave / token, bf16 -> bf16 (the residual add is fused into the
 //                                  producing GEMM's epilogue)
-//   attention_kernel  MFMA + LDS : 1 workgroup / (chunk, head); K and V of the head stay in LDS,
+//   attention_kernel  MFMA + LDS : 1 workgroup / (chunk, head of 64 or pair of heads of 32); K and V stay in LDS,
 //                                  S^T = K Q^T on v_mfma_f32_32x32x16_bf16 so a lane owns one query
 //                                  column, softmax in registers, P feeds P V straight from the
-//                                  accumulator registers, V fragments by ds_read_b64_tr_b16
+//                                  accumulator registers, V fragments by ds_read_b64_tr_b16.  The math and the head
+//                                  widths are attention_core.h's; attention_long_kernel (1 024 / 2 048 tokens) folds
+//                                  the keys in segments of 512
 //   mean_pool_kernel  HBM-bound  : 1 workgroup / chunk, masked mean (+ optional L2 normalise) -> f32
 //   glu_kernel<ACT>   HBM-bound  : gated feed-forward act(gate) * up between the FFN GEMMs (GEGLU: jina-bert-v2, SwiGLU: nomic-bert)
 //   rope_qk_kernel    HBM-bound  : rotary position embedding of Q and K, in place on the blocked QKV buffer (nomic-bert)
-#include <cstdlib>
-
-#include "attention_core.h"  // AttnState, attention_qblock_core, attn_state_store
+#include "attention_core.h"  // Head64 / Head32, attn_lds_bytes, attn_launch
 #include "encoder_ops.h"
 #include "encoder_rows.h"   // the bodies of the embedding, rotary and pooling kernels, wave_sum
 #include "gemm_tile.h"  // bf16 helpers, LDS-DMA pointer types
@@ -178,29 +178,38 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
     }
 }
 
-// ------------------------------------------------------------------ attention (head dim 64)
+// ------------------------------------------------------------------ attention
 // qkv: [tokens, 3H] bf16 rows = [Q | K | V], head h at columns h*64 of each third.  ctx: [tokens, H].
 // KT = S / 32 key tiles.  LDS: K image [S][64] with chunk ^= (row>>1)&7, V image [S][64] with
 // chunk ^= ((row>>1)&1)<<2 (conflict-free for ds_read_b128 rows / ds_read_b64_tr_b16 blocks).
 // One 32-row query block of one wave, keys processed in groups of 4 tiles (128 keys) with an online softmax, so
 // that only 64 score registers are live (S = 256 runs 2 workgroups per CU, S = 512 no longer spills).
 // FULL = every key of the padded sequence is real (len == S): no per-tile guards or masks.
-// ALIBI: scores get the symmetric linear bias -slope_head * |query - key| (jina-bert-v2 style encoders, no position table).
-// AttnState, attention_qblock_core and attn_state_store: attention_core.h.
-template <int KT, bool FULL, bool ALIBI, int GKMAX = 4>
+// HEAD (attention_core.h): Head64<ALIBI> -- one head of 64 per 64-column block; ALIBI: scores get the symmetric linear bias
+// -slope_head * |query - key| (jina-bert-v2 style encoders, no position table) -- or Head32, a pair of heads of 32 per block.
+// State, fold and store stay inside each FULL arm: declared around the branch, the compiler merges the two store tails and the
+// kernels come out with other register counts.
+// The shell around the math (LDS carve-up, operand addressing, staging loops, Q load) is written out in every attention kernel
+// (here, encoder_packed.hip, encoder_window.hip).  As shared functions -- tried: carve-up, operand, staging, Q load, one segmented
+// body under attention_long_kernel and attention_packed_kernel -- each alone changes the compiler's text of these kernels (registers
+// at 1 - 4 key tiles, scratch at S = 512, block order), and the 8-tile packed class measured 1.6 - 1.9 % slower per launch through
+// them.  Written out, every Head64 instantiation is the instruction text it was before the head width became a policy
+// (profiles/attention_shell_kernels.log).
+template <class HEAD, int KT, bool FULL, int GKMAX>
 static __device__ __forceinline__ void attention_qblock(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, char* ostg,
                                                         bf16_t* obase, int H, int len, int nkt, int lane, int qbase, float slope2) {
-    AttnState st;
-    attn_state_init(st);
-    attention_qblock_core<KT, FULL, ALIBI, GKMAX>(qf, Kl, Vl, xch, len, nkt, lane, qbase, slope2, st, true, 0);
-    attn_state_store(st, xch, ostg, obase, H, lane);
+    typename HEAD::State st;
+    HEAD::init(st);
+    HEAD::template fold<KT, FULL, GKMAX>(qf, Kl, Vl, xch, len, nkt, lane, qbase, slope2, st, true, 0);
+    HEAD::store(st, xch, ostg, obase, H, lane);
 }
 
-// NW waves per workgroup (4, or 8 for S = 256: one query block per wave, two key-tile groups of 2 -> half the registers, so that
-// 4 waves instead of 2 share a SIMD and cover each other's MFMA -> softmax -> MFMA dependency stalls)
-template <int KT, bool ALIBI, int NW = 4>
+// One workgroup per (chunk, 64-column block), NW waves (4, or 8 from S = 256 on; at S = 256 one query block per wave and two key-tile
+// groups of 2 -> half the registers, so that 4 waves instead of 2 share a SIMD and cover each other's MFMA -> softmax -> MFMA
+// dependency stalls)
+template <class HEAD, int KT, int NW>
 __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int H,
-                                                            const float* __restrict__ slopes, bf16_t* __restrict__ ctx, int blocked) {
+                                                            typename HEAD::Extra extra, bf16_t* __restrict__ ctx, int blocked) {
     constexpr int S = KT * 32;
     constexpr int NQB = (KT + NW - 1) / NW;  // query blocks per wave
     constexpr int GKMAX = (NW == 8 && KT <= 8) ? 2 : 4;  // S = 512 runs one workgroup per CU anyway (LDS): registers are not its limit
@@ -212,8 +221,8 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_kernel(c
     float* xch = reinterpret_cast<float*>(smem + 2 * S * 128) + w * 32;  // [NW waves][32] alpha / 1/l exchange
     char* ostg = smem + 2 * S * 128 + NW * 128 + w * 1024;               // per-wave [8 q][64 d] bf16 output staging
     const int head = blockIdx.x, b = blockIdx.y;
-    // row-major QKV [tokens][3H] (Q | K | V, head h at column 64 h), or -- blocked -- [3 heads][tokens][64] as the QKV projection
-    // writes it (gemm_bf16.hip c_index; `blocked` = tokens padded to that GEMM's M, 0 = row-major): every operand of this (chunk, head) is then one contiguous [S][64] block
+    // row-major QKV [tokens][3H] (Q | K | V, block j at column 64 j), or -- blocked -- [3H/64][tokens][64] as the QKV projection writes it
+    // (gemm_bf16.hip c_index; `blocked` = tokens padded to that GEMM's M, 0 = row-major): every operand of this (chunk, block) is then one contiguous [S][64] block
     const int ld = blocked ? 64 : 3 * H;
     const size_t T = (size_t)blocked, nh = (size_t)(H >> 6);  // blocked = the row count (M) of the projection that wrote the blocks
     const bf16_t* base = blocked ? qkv + ((size_t)head * T + (size_t)b * S) * 64 : qkv + (size_t)b * S * ld + head * 64;
@@ -223,7 +232,7 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_kernel(c
     len = __builtin_amdgcn_readfirstlane(len);
     const int nkt = (len + 31) >> 5;  // key tiles holding at least one real key; later tiles are skipped entirely
 
-    // ---- stage K then V rows [0, 32 nkt) of this (chunk, head): pieces of 8 rows x 128 B = 1 KiB
+    // ---- stage K then V rows [0, 32 nkt) of this (chunk, block): pieces of 8 rows x 128 B = 1 KiB
     for (int piece = w; piece < nkt * 4; piece += NW) {
         const int p = piece * 64 + lane;
         const int r = p >> 3, ck = (p & 7) ^ ((r >> 1) & 7);
@@ -255,9 +264,9 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_kernel(c
         const int qb = w + NW * i;
         if (qb < KT) {
             bf16_t* obase = ctx + (size_t)(b * S + qb * 32) * H + head * 64;
-            const float slope2 = ALIBI ? slopes[head] * 1.44269504088896340736f : 0.f;
-            if (nkt == KT && (len & 31) == 0) attention_qblock<KT, true, ALIBI, GKMAX>(qf[i], Kl, Vl, xch, ostg, obase, H, len, nkt, lane, qb * 32, slope2);
-            else attention_qblock<KT, false, ALIBI, GKMAX>(qf[i], Kl, Vl, xch, ostg, obase, H, len, nkt, lane, qb * 32, slope2);
+            const float slope2 = HEAD::slope2(extra, head);
+            if (nkt == KT && (len & 31) == 0) attention_qblock<HEAD, KT, true, GKMAX>(qf[i], Kl, Vl, xch, ostg, obase, H, len, nkt, lane, qb * 32, slope2);
+            else attention_qblock<HEAD, KT, false, GKMAX>(qf[i], Kl, Vl, xch, ostg, obase, H, len, nkt, lane, qb * 32, slope2);
         }
     }
 }
@@ -265,13 +274,12 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_kernel(c
 // ---- sequences of 1 024 and 2 048 tokens (the reference's default chunker emits up to 200 lines / 6 000 characters per chunk --
 // src/semcode/chunking/tree_sitter_chunker.py:64-65 -- i.e. 1.5-2k word pieces; jina-embeddings-v2 is an 8k-context ALiBi
 // model).  K and V of 512 keys fill the LDS (128 KiB), so the keys are attended in SEGMENTS of 512: stage a segment, every wave
-// folds it into the online-softmax state of its ONE 32-row query block (AttnState, 34 registers), next segment.  A workgroup
-// takes 8 query blocks (256 queries) of one (chunk, head); the S / 256 workgroups of a (chunk, head) each stage all its keys
-// (from L2 after the first).  Same arithmetic per (query, key) as attention_kernel: a sequence of <= 512 real tokens padded to
-// 1 024 gives the bits the S = 512 kernel gives.
-template <bool ALIBI>
+// folds it into the online-softmax state of its ONE 32-row query block (AttnState, 34 registers), next segment.  A workgroup takes 8 query blocks (256 queries) of one (chunk, block); the S / 256 workgroups of a
+// (chunk, block) each stage all its keys (from L2 after the first).  Same arithmetic per (query, key) as attention_kernel: a
+// sequence of <= 512 real tokens padded to 1 024 gives the bits the S = 512 kernel gives.
+template <class HEAD>
 __global__ __launch_bounds__(512, 1) void attention_long_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int S, int H,
-                                                                const float* __restrict__ slopes, bf16_t* __restrict__ ctx, int blocked) {
+                                                                typename HEAD::Extra extra, bf16_t* __restrict__ ctx, int blocked) {
     constexpr int KT = 16, NW = 8, SEG = 512;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Kl = smem;
@@ -295,9 +303,9 @@ __global__ __launch_bounds__(512, 1) void attention_long_kernel(const bf16_t* __
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks + 8 * hh);
     }
-    AttnState st;
-    attn_state_init(st);
-    const float slope2 = ALIBI ? slopes[head] * 1.44269504088896340736f : 0.f;
+    typename HEAD::State st;
+    HEAD::init(st);
+    const float slope2 = HEAD::slope2(extra, head);
     const int nseg = (len + SEG - 1) / SEG;
 #pragma unroll 1
     for (int seg = 0; seg < nseg; ++seg) {
@@ -317,10 +325,10 @@ __global__ __launch_bounds__(512, 1) void attention_long_kernel(const bf16_t* __
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (nkt == KT && (slen & 31) == 0) attention_qblock_core<KT, true, ALIBI, 4>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
-        else attention_qblock_core<KT, false, ALIBI, 4>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
+        if (nkt == KT && (slen & 31) == 0) HEAD::template fold<KT, true, 4>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
+        else HEAD::template fold<KT, false, 4>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
     }
-    attn_state_store(st, xch, ostg, ctx + (size_t)(b * S + qb * 32) * H + head * 64, H, lane);
+    HEAD::store(st, xch, ostg, ctx + (size_t)(b * S + qb * 32) * H + head * 64, H, lane);
 }
 
 // ------------------------------------------------------------------ masked mean pooling
@@ -355,54 +363,36 @@ void sc_launch_layernorm(const void* in, int tokens, int H, const float* g, cons
     else if (H <= 1024) hipLaunchKernelGGL(layernorm_kernel<4>, grid, block, 0, s, (const bf16_t*)in, tokens, H, g, b, eps, (bf16_t*)out);
     else hipLaunchKernelGGL(layernorm_kernel<8>, grid, block, 0, s, (const bf16_t*)in, tokens, H, g, b, eps, (bf16_t*)out);
 }
-template <int KT, bool ALIBI>
-static void launch_attn(const void* qkv, const int32_t* lens, int B, int H, const float* slopes, void* ctx, int blocked, hipStream_t s) {
-    static const char* env = getenv("SC_ATTN_WAVES");  // A/B aid
-    constexpr int NWD = KT >= 8 ? 8 : 4;
-    const int nw = (env && KT >= 8) ? atoi(env) : NWD;
-    static ScDeviceOnce once;  // per instantiation and device
-    sc_device_once(once, [&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<KT, ALIBI, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, KT * 32 * 256 + 4 * 1152);
-        if (KT >= 8) hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<KT, ALIBI, NWD>), hipFuncAttributeMaxDynamicSharedMemorySize, KT * 32 * 256 + NWD * 1152);
-    });
-    const dim3 grid((unsigned)(H / 64), (unsigned)B);
-    if (KT >= 8 && nw == 8)
-        hipLaunchKernelGGL((attention_kernel<KT, ALIBI, NWD>), grid, dim3(NWD * 64), (size_t)KT * 32 * 256 + NWD * 1152, s, (const bf16_t*)qkv, lens, H, slopes, (bf16_t*)ctx, blocked);
-    else
-        hipLaunchKernelGGL((attention_kernel<KT, ALIBI, 4>), grid, dim3(256), (size_t)KT * 32 * 256 + 4 * 1152, s, (const bf16_t*)qkv, lens, H, slopes, (bf16_t*)ctx, blocked);
-}
 bool sc_attention_supported(int S, int H, int heads, int head_dim) {
     return heads > 0 && (head_dim == 64 || head_dim == 32) && H == heads * head_dim && H % 64 == 0 && (S == 32 || S == 64 || S == 128 || S == 256 || S == 512 || S == 1024 || S == 2048);
 }
-// slopes: NULL = plain attention; else [heads] ALiBi slopes (device)
-void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked, int head_dim) {
-    if (head_dim == 32) return sc_launch_attention32(qkv, lens, B, S, H, ctx, s, blocked);  // encoder_attn32.hip; create refuses 32-wide ALiBi models
-#define SC_ATTN_CASE(SS, KK)                                                      \
-    case SS:                                                                      \
-        if (slopes) launch_attn<KK, true>(qkv, lens, B, H, slopes, ctx, blocked, s); \
-        else launch_attn<KK, false>(qkv, lens, B, H, nullptr, ctx, blocked, s);   \
-        break;
+template <class HEAD, int KT>
+static void launch_attn(const void* qkv, const int32_t* lens, int B, int H, typename HEAD::Extra extra, void* ctx, int blocked, hipStream_t s) {
+    constexpr int NW = KT >= 8 ? 8 : 4;
+    attn_launch<attention_kernel<HEAD, KT, NW>, attn_lds_bytes(KT, NW)>(dim3((unsigned)(H / 64), (unsigned)B), NW * 64, s, (const bf16_t*)qkv, lens, H, extra,
+                                                                         (bf16_t*)ctx, blocked);
+}
+template <class HEAD>
+static void launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, typename HEAD::Extra extra, void* ctx, int blocked, hipStream_t s) {
     if (S > 512) {  // K / V streamed through the LDS in segments of 512 keys
-        static ScDeviceOnce once;
-        const int lds = 2 * 512 * 128 + 8 * 128 + 8 * 1024;
-        sc_device_once(once, [&] {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_long_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        const dim3 grid((unsigned)(H / 64), (unsigned)B, (unsigned)(S / 256));
-        if (slopes) hipLaunchKernelGGL(attention_long_kernel<true>, grid, dim3(512), (size_t)lds, s, (const bf16_t*)qkv, lens, S, H, slopes, (bf16_t*)ctx, blocked);
-        else hipLaunchKernelGGL(attention_long_kernel<false>, grid, dim3(512), (size_t)lds, s, (const bf16_t*)qkv, lens, S, H, (const float*)nullptr, (bf16_t*)ctx, blocked);
+        attn_launch<attention_long_kernel<HEAD>, attn_lds_bytes(16, 8)>(dim3((unsigned)(H / 64), (unsigned)B, (unsigned)(S / 256)), 512, s, (const bf16_t*)qkv, lens, S,
+                                                                         H, extra, (bf16_t*)ctx, blocked);
         return;
     }
     switch (S) {
-        SC_ATTN_CASE(32, 1)
-        SC_ATTN_CASE(64, 2)
-        SC_ATTN_CASE(128, 4)
-        SC_ATTN_CASE(256, 8)
-        SC_ATTN_CASE(512, 16)
+        case 32: launch_attn<HEAD, 1>(qkv, lens, B, H, extra, ctx, blocked, s); break;
+        case 64: launch_attn<HEAD, 2>(qkv, lens, B, H, extra, ctx, blocked, s); break;
+        case 128: launch_attn<HEAD, 4>(qkv, lens, B, H, extra, ctx, blocked, s); break;
+        case 256: launch_attn<HEAD, 8>(qkv, lens, B, H, extra, ctx, blocked, s); break;
+        case 512: launch_attn<HEAD, 16>(qkv, lens, B, H, extra, ctx, blocked, s); break;
         default: break;
     }
-#undef SC_ATTN_CASE
+}
+// slopes: NULL = plain attention; else [heads] ALiBi slopes (device).  head_dim 32: plain only, create refuses 32-wide ALiBi models
+void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int H, const float* slopes, void* ctx, hipStream_t s, int blocked, int head_dim) {
+    if (head_dim == 32) launch_attention<Head32>(qkv, lens, B, S, H, Head32::Extra(), ctx, blocked, s);
+    else if (slopes) launch_attention<Head64<true>>(qkv, lens, B, S, H, slopes, ctx, blocked, s);
+    else launch_attention<Head64<false>>(qkv, lens, B, S, H, nullptr, ctx, blocked, s);
 }
 // Gated feed-forward: out[m][j] = act(h[m][j]) * h[m][F + j], h = [tokens, 2F] bf16 -> out [tokens, F] bf16.
 // GEGLU (jina-bert-v2 GLUMLP): act = erf-GELU.  SwiGLU (nomic-bert): act = silu(g) = g / (1 + exp(-g)) on the hardware exp2 / rcp

@@ -6,7 +6,8 @@
 //
 //   embed_*_packed_kernel       position from a per-row array instead of token % S
 //   rope_qk_packed_kernel       likewise
-//   attention_packed_kernel     one workgroup per (sequence, group of query blocks) x head, read from a table of work items
+//   attention_packed_kernel     one workgroup per (sequence, group of query blocks) x 64-column block (a head of 64, a pair of heads
+//                               of 32), read from a table of work items
 //   mean_pool_*_packed_kernel   rows starts[b] .. starts[b] + lens[b] instead of b * S ..
 //
 // Each shares its device body with the rectangle kernel of encoder_ops.hip (encoder_rows.h, attention_core.h): same arithmetic,
@@ -39,22 +40,28 @@ __global__ __launch_bounds__(256) void rope_qk_packed_kernel(bf16_t* __restrict_
     rope_qk_rows(qkv, M, nblocks, PosArray{pos, max_pos}, cos_t, sin_t);
 }
 
-// ------------------------------------------------------------------ attention (head dim 64)
+// ------------------------------------------------------------------ attention
 // A work item is four int32 {start row of the sequence, its length, first 32-row query block of the item, 0}; a workgroup of NW
-// waves takes one item and one head, wave w the query block `first + w`.  The keys of the sequence are staged into the LDS in
-// segments of 32 KT keys from row `start`, as attention_long_kernel stages them from b * S, and every wave folds each segment into
-// the AttnState of its query block.  A wave whose block lies at or beyond ceil32(len) stages its share of K and V and reaches
-// every barrier, but does no math and stores nothing.  ALiBi distances count from the start of the sequence.
+// waves takes one item and one 64-column block (a head of 64, a pair of heads of 32: HEAD, attention_core.h), wave w the query block
+// `first + w`.  The keys of the sequence are staged into the LDS in segments of 32 KT keys from row `start`, as
+// attention_long_kernel stages them from b * S, and every wave folds each segment into the state of its query block.  A wave whose
+// block lies at or beyond ceil32(len) stages its share of K and V and reaches every barrier, but does no math and stores nothing.
+// ALiBi distances count from the start of the sequence.
+//
+// The shell is written out here as in attention_kernel (encoder_ops.hip says why): through shared shell functions,
+// as a wrapper of one segmented body shared with attention_long_kernel, the 8-tile class ran 1.6 - 1.9 % slower per launch on 256
+// texts of 256 tokens at 384 hidden (heads of 64; 0.7 - 1.0 % with heads of 32) in two measurements, with no register or occupancy
+// change to show for it.  Written out, all nine instantiations are the instruction text of the kernels they replace.
 //
 // Three launch classes keep short sequences from holding a 512-thread workgroup and 128 KiB of LDS (sc_packed_items sorts the
 // items by class; a class depends on the sequence's own length only, so a text's result does not depend on its neighbours):
-//   len <= 128 : KT 4,  4 waves,  37 KiB LDS, 131 registers (ALiBi 195) -> 3 (2) workgroups per CU
-//   len <= 256 : KT 8,  8 waves,  73 KiB LDS, 124 registers (ALiBi 256) -> 2 (1) workgroups per CU, key tiles in groups of 2 (attention_kernel at S = 256)
+//   len <= 128 : KT 4,  4 waves,  37 KiB LDS, 131 registers (ALiBi 195, head_dim 32 165) -> 3 (2, 3) workgroups per CU
+//   len <= 256 : KT 8,  8 waves,  73 KiB LDS, 124 registers (ALiBi 256, head_dim 32 159) -> 2 (1, 1) workgroups per CU, key tiles in groups of 2 (attention_kernel at S = 256)
 //   longer     : KT 16, 8 waves, 137 KiB LDS, 256 registers -> 1 workgroup per CU, one item per 8 query blocks, segments of 512 keys
 // (registers as the compiler reports them; they, not the LDS, bound the two short classes)
-template <int KT, int NW, bool ALIBI>
+template <class HEAD, int KT, int NW>
 __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_packed_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ items, int H,
-                                                                                         const float* __restrict__ slopes, bf16_t* __restrict__ ctx, int blocked) {
+                                                                                         typename HEAD::Extra extra, bf16_t* __restrict__ ctx, int blocked) {
     constexpr int SEG = KT * 32;
     constexpr int GKMAX = (NW == 8 && KT <= 8) ? 2 : 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -83,9 +90,9 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_packed_k
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks + 8 * hh);
     }
-    AttnState st;
-    attn_state_init(st);
-    const float slope2 = ALIBI ? slopes[head] * 1.44269504088896340736f : 0.f;
+    typename HEAD::State st;
+    HEAD::init(st);
+    const float slope2 = HEAD::slope2(extra, head);
     const int nseg = KT == 16 ? (len + SEG - 1) / SEG : 1;  // the shorter classes hold the whole sequence: no loop, no carried state
 #pragma unroll 1
     for (int seg = 0; seg < nseg; ++seg) {
@@ -106,10 +113,10 @@ __global__ __launch_bounds__(NW * 64, (KT <= 8 ? 2 : 1)) void attention_packed_k
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (!live) continue;
-        if (nkt == KT && (slen & 31) == 0) attention_qblock_core<KT, true, ALIBI, GKMAX>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
-        else attention_qblock_core<KT, false, ALIBI, GKMAX>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
+        if (nkt == KT && (slen & 31) == 0) HEAD::template fold<KT, true, GKMAX>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
+        else HEAD::template fold<KT, false, GKMAX>(qf, Kl, Vl, xch, slen, nkt, lane, qb * 32, slope2, st, seg == 0, key0);
     }
-    if (live) attn_state_store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * H + head * 64, H, lane);
+    if (live) HEAD::store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * H + head * 64, H, lane);
 }
 
 // ------------------------------------------------------------------ masked mean pooling
@@ -146,29 +153,20 @@ void sc_launch_rope_qk_packed(void* qkv, int64_t M, int nblocks, const int32_t* 
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(rope_qk_packed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (bf16_t*)qkv, M, nblocks, pos, max_pos, cos_t, sin_t);
 }
-template <int KT, int NW>
-static void launch_attn_packed(const void* qkv, const int32_t* items, int nitems, int H, const float* slopes, void* ctx, int blocked, hipStream_t s) {
-    if (nitems < 1) return;
-    constexpr int lds = 2 * KT * 32 * 128 + NW * 128 + NW * 1024;
-    static ScDeviceOnce once;  // per instantiation and device
-    sc_device_once(once, [&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_packed_kernel<KT, NW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(attention_packed_kernel<KT, NW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
-    const dim3 grid((unsigned)nitems, (unsigned)(H / 64));
-    if (slopes)
-        hipLaunchKernelGGL((attention_packed_kernel<KT, NW, true>), grid, dim3(NW * 64), (size_t)lds, s, (const bf16_t*)qkv, items, H, slopes, (bf16_t*)ctx, blocked);
-    else
-        hipLaunchKernelGGL((attention_packed_kernel<KT, NW, false>), grid, dim3(NW * 64), (size_t)lds, s, (const bf16_t*)qkv, items, H, (const float*)nullptr,
-                           (bf16_t*)ctx, blocked);
-}
 int sc_packed_attention_class(int len) { return len > 256 ? 0 : (len > 128 ? 1 : 2); }
+template <class HEAD>
+static void launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, typename HEAD::Extra extra, void* ctx, int blocked, hipStream_t s) {
+    attn_packed_classes(items, nitems, [&](auto cls, const int32_t* first, int n) {
+        constexpr int KT = 16 >> decltype(cls)::value, NW = KT >= 8 ? 8 : 4;  // 16 / 8 / 4 key tiles
+        attn_launch<attention_packed_kernel<HEAD, KT, NW>, attn_lds_bytes(KT, NW)>(dim3((unsigned)n, (unsigned)(H / 64)), NW * 64, s, (const bf16_t*)qkv, first, H, extra,
+                                                                                    (bf16_t*)ctx, blocked);
+    });
+}
 void sc_launch_attention_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* slopes, void* ctx, hipStream_t s, int blocked,
                                 int head_dim) {
-    if (head_dim == 32) return sc_launch_attention32_packed(qkv, items, nitems, H, ctx, s, blocked);  // encoder_attn32.hip
-    launch_attn_packed<16, 8>(qkv, items, nitems[0], H, slopes, ctx, blocked, s);
-    launch_attn_packed<8, 8>(qkv, items + 4 * (size_t)nitems[0], nitems[1], H, slopes, ctx, blocked, s);
-    launch_attn_packed<4, 4>(qkv, items + 4 * ((size_t)nitems[0] + nitems[1]), nitems[2], H, slopes, ctx, blocked, s);
+    if (head_dim == 32) launch_attention_packed<Head32>(qkv, items, nitems, H, Head32::Extra(), ctx, blocked, s);
+    else if (slopes) launch_attention_packed<Head64<true>>(qkv, items, nitems, H, slopes, ctx, blocked, s);
+    else launch_attention_packed<Head64<false>>(qkv, items, nitems, H, nullptr, ctx, blocked, s);
 }
 void sc_launch_mean_pool_packed(const void* x, const int32_t* starts, const int32_t* lens, int B, int H, int normalize, float* out, hipStream_t s) {
     if (!normalize && (H % 8) == 0)

@@ -113,29 +113,13 @@ __global__ __launch_bounds__(NW * 64, (KTS <= 8 ? 2 : 1)) void attention_window_
 }
 
 // ------------------------------------------------------------------ launchers
-template <int KTS, int NW>
-static constexpr int window_lds() { return 2 * KTS * 32 * 128 + NW * 128 + NW * 1024; }
+bool sc_attention_window_supported(int local_window) { return local_window >= 2 && local_window <= 128 && (local_window & 1) == 0; }
 
 template <int KTS, int NW>
 static void launch_window(const void* qkv, const int32_t* lens, int B, int S, int H, int hw, void* ctx, int blocked, hipStream_t s) {
-    constexpr int lds = window_lds<KTS, NW>();
-    static ScDeviceOnce once;  // per instantiation and device
-    sc_device_once(once, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attention_window_kernel<KTS, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
     const dim3 grid((unsigned)(H / 64), (unsigned)B, (unsigned)((S / 32 + NW - 1) / NW));
-    hipLaunchKernelGGL((attention_window_kernel<KTS, NW>), grid, dim3(NW * 64), (size_t)lds, s, (const bf16_t*)qkv, lens, S, H, hw, (bf16_t*)ctx, blocked);
+    attn_launch<attention_window_kernel<KTS, NW>, attn_lds_bytes(KTS, NW)>(grid, NW * 64, s, (const bf16_t*)qkv, lens, S, H, hw, (bf16_t*)ctx, blocked);
 }
-template <int KTS, int NW>
-static void launch_window_packed(const void* qkv, const int32_t* items, int nitems, int H, int hw, void* ctx, int blocked, hipStream_t s) {
-    if (nitems < 1) return;
-    constexpr int lds = window_lds<KTS, NW>();
-    static ScDeviceOnce once;
-    sc_device_once(once, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(attention_window_packed_kernel<KTS, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    hipLaunchKernelGGL((attention_window_packed_kernel<KTS, NW>), dim3((unsigned)nitems, (unsigned)(H / 64)), dim3(NW * 64), (size_t)lds, s, (const bf16_t*)qkv, items, H,
-                       hw, (bf16_t*)ctx, blocked);
-}
-
-bool sc_attention_window_supported(int local_window) { return local_window >= 2 && local_window <= 128 && (local_window & 1) == 0; }
-
 void sc_launch_attention_window(const void* qkv, const int32_t* lens, int B, int S, int H, int local_window, void* ctx, hipStream_t s, int blocked) {
     const int hw = local_window / 2;
     if (S <= 128) launch_window<4, 4>(qkv, lens, B, S, H, hw, ctx, blocked, s);
@@ -144,7 +128,9 @@ void sc_launch_attention_window(const void* qkv, const int32_t* lens, int B, int
 }
 void sc_launch_attention_window_packed(const void* qkv, const int32_t* items, const int* nitems, int H, int local_window, void* ctx, hipStream_t s, int blocked) {
     const int hw = local_window / 2;
-    launch_window_packed<12, 8>(qkv, items, nitems[0], H, hw, ctx, blocked, s);
-    launch_window_packed<8, 8>(qkv, items + 4 * (size_t)nitems[0], nitems[1], H, hw, ctx, blocked, s);
-    launch_window_packed<4, 4>(qkv, items + 4 * ((size_t)nitems[0] + nitems[1]), nitems[2], H, hw, ctx, blocked, s);
+    attn_packed_classes(items, nitems, [&](auto cls, const int32_t* first, int n) {
+        constexpr int KTS = decltype(cls)::value == 0 ? 12 : (decltype(cls)::value == 1 ? 8 : 4), NW = KTS >= 8 ? 8 : 4;  // 12 / 8 / 4 tiles staged
+        attn_launch<attention_window_packed_kernel<KTS, NW>, attn_lds_bytes(KTS, NW)>(dim3((unsigned)n, (unsigned)(H / 64)), NW * 64, s, (const bf16_t*)qkv, first, H, hw,
+                                                                                       (bf16_t*)ctx, blocked);
+    });
 }

@@ -464,7 +464,7 @@ static void launch_attention_window(sc_encoder* e, const int32_t* lens_dev, int 
     else sc_launch_attention_window(e->qkv, lens_dev, B, S, e->cfg.hidden, e->cfg.local_window, e->ctx, s, M);
 }
 static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
-    const int hd = e->cfg.hidden / e->cfg.heads;  // 64, or 32: a pair of heads per 64-column block (encoder_attn32.hip)
+    const int hd = e->cfg.hidden / e->cfg.heads;  // 64, or 32: a pair of heads per 64-column block (Head32, attention_core.h)
     if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
     else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
 }
