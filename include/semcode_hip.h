@@ -115,7 +115,20 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
  *   as for every model (base: 1 152), so ModernBERT-large (ffn 2 624) is refused by that rule.  The forward runs the stand-alone
  *   LayerNorm pipeline for every batch size (sc_encoder_set_path only decides about split-K); a LayerNorm-folded pre-norm pipeline
  *   is a follow-up.  [CLS] pooling runs the whole last layer (the pruned last layer is the post-LN one).  sc_encoder_score_pairs is
- *   SC_ERR_UNSUPPORTED (the family's classifier is dense -> GELU -> LayerNorm -> linear, not pooler + linear).  Texts stay capped at 2 048 tokens. */
+ *   SC_ERR_UNSUPPORTED (the family's classifier is dense -> GELU -> LayerNorm -> linear, not pooler + linear).  Texts stay capped at 2 048 tokens.
+ *
+ * arch 2 (the Qwen2 / Qwen2.5 decoder backbone behind code-embedding models such as jina-code-embeddings-0.5b, gte-Qwen2, KaLM-mini;
+ *   0.5B shape = 151936 / 896 / 24 layers / 14 heads, 2 K/V heads / 4864, eps 1e-6, rope_theta 1e6): a pre-norm CAUSAL decoder.
+ *   h = tok_emb[id] (no embedding norm, no position and no type table);  per layer  h += Attn(RMS_in(h)),  h += MLP(RMS_post(h));  pooled
+ *   from RMS_final(h).  RMS(x) = x * rsqrt(mean(x^2) + ln_eps) * gamma, statistics in f32, no beta.  MLP = W2 (silu(gate) * up) (ffn_type 2).
+ *   Rotary positions (pos_type 2) with the one base rope_theta.  Scores are q.k / 8 over the keys j <= i, j < len only (encoder_causal.hip).
+ *   Grouped-query attention: K and V have kv_heads heads of 64 (0 = heads); query head h reads K/V head h / (heads / kv_heads) (grouped,
+ *   not interleaved).  arch 2 requires pos_type 2, ffn_type 2, head dimension 64, 1 <= kv_heads <= heads with heads % kv_heads == 0,
+ *   local_window 0 and global_every <= 1, next to the hidden % 128, ffn % 128 and hidden <= 2048 rules of every model; anything else is
+ *   SC_ERR_UNSUPPORTED or SC_ERR_INVALID.  kv_heads != 0 on arch 0 or 1 is SC_ERR_UNSUPPORTED.  The forward runs the stand-alone-norm
+ *   pipeline for every batch size (sc_encoder_set_path only decides about split-K).  Pooling: sc_encoder_set_pooling 2 (the last real
+ *   token's row) or 0 (masked mean); 1 ([CLS]) is SC_ERR_INVALID.  sc_encoder_score_pairs is SC_ERR_UNSUPPORTED.  Texts stay capped at
+ *   2 048 tokens.  Out of scope: head dimension 128 (Qwen3-Embedding, the 1.5B / 7B models), QK-norm, sliding windows. */
 typedef struct sc_encoder_cfg {
     int32_t vocab, hidden, layers, heads, ffn, max_pos, type_vocab;
     float ln_eps;
@@ -130,10 +143,11 @@ typedef struct sc_encoder_cfg {
                              2 = SwiGLU (nomic-bert): the same layout, hidden = silu(gate) * up                */
     float rope_theta;     /* pos_type 2: rotary base (1000 for nomic-embed-text); 0 = 10000                   */
     /* appended; all zero = the behaviour of the struct without them */
-    int32_t arch;           /* 0 = post-LN BERT family; 1 = pre-LN ModernBERT (above)                           */
+    int32_t arch;           /* 0 = post-LN BERT family; 1 = pre-LN ModernBERT; 2 = pre-norm causal decoder, Qwen2 family (above) */
     int32_t local_window;   /* arch 1: total window of the local layers, even, 2 .. 128 (128 for the released models) */
     int32_t global_every;   /* arch 1: layer l is global iff l % global_every == 0; 1 = every layer global; 3 for the released models */
     float rope_theta_local; /* arch 1: rotary base of the local layers (10000); rope_theta is the global layers' (160000); 0 = 10000 */
+    int32_t kv_heads;       /* arch 2: K / V heads of the grouped-query attention, a divisor of heads; 0 = heads.  Must be 0 on arch 0, 1 */
 } sc_encoder_cfg;
 
 /* Size in bytes of the f32 weight blob sc_encoder_create expects for cfg.  Blob order (all f32,
@@ -145,7 +159,13 @@ typedef struct sc_encoder_cfg {
  * arch 1: word_emb [vocab,H], emb_ln_gamma, emb_ln_beta, the same per-layer order with ln1 = attn_norm (layer 0's slot is present and
  * ignored) and ln2 = mlp_norm, W1 = Wi (its first ffn rows are the activated half, i.e. the gate rows), W2 = mlp.Wo, then
  * final_norm_gamma [H], final_norm_beta [H].  No pos_emb, no type_emb (type_vocab is not read).  Bias and beta slots stay present:
- * zeros for the released models, the values of a model with norm_bias / attention_bias / mlp_bias. */
+ * zeros for the released models, the values of a model with norm_bias / attention_bias / mlp_bias.
+ * arch 2, KV = kv_heads * 64: word_emb [vocab,H], then per layer Wq [H,H], bq [H], Wk [KV,H], bk [KV], Wv [KV,H], bv [KV], Wo [H,H], bo [H],
+ * ln1_gamma [H] (= input_layernorm), ln1_beta [H], W1 [2*ffn,H] (gate_proj rows, then up_proj rows), b1 [2*ffn], W2 [H,ffn] (= down_proj),
+ * b2 [H], ln2_gamma [H] (= post_attention_layernorm), ln2_beta [H], then final_norm_gamma [H], final_norm_beta [H].  No embedding norm, no
+ * pos_emb, no type_emb.  The beta slots are present and never read (RMSNorm has none); slots of biases a model lacks (Qwen2: bo, b1, b2)
+ * hold zeros.  On the device the projection is fused as [Wq; Wk; Wv], N = H + 2 KV (always a multiple of 128), written in 64-column
+ * blocks; the rotation covers its first heads + kv_heads blocks. */
 sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out);
 /* Replaces EmbeddingProviderFactory.create() loading a model (providers.py:69-100): uploads the
  * weights (converted to bf16 on device).  weights_blob == NULL: synthetic weights 0.02*N(0,1) from
@@ -167,7 +187,11 @@ sc_status sc_encoder_set_path(sc_encoder* enc, int32_t path);
  * projection: attention of the one query row per text (attention_cls_kernel), output projection and feed-forward on ceil256(B)
  * compact rows.  Pruned and unpruned vectors agree to bf16 rounding, not bit for bit; a text's vector does not depend on its
  * batch-mates either way.  The mode takes effect with the next call; any other value is SC_ERR_INVALID and changes nothing.
- * sc_encoder_score_pairs does not read the mode. */
+ * sc_encoder_score_pairs does not read the mode.
+ * pooling 2 = the row of the text's last real token (row start + len - 1 of a rectangle or of packed rows): the vector of causal
+ * embedding models.  Accepted on arch 2 only (on arch 0 and 1 it is SC_ERR_INVALID like any unknown value): the row gets RMS_final in
+ * f32 and is L2-normalised by the rule above.  On arch 2 pooling 1 is SC_ERR_INVALID (a causal first token sees only itself) and
+ * pooling 0 takes RMS_final over all rows, then the mean kernels. */
 sc_status sc_encoder_set_pooling(sc_encoder* enc, int32_t pooling);
 sc_status sc_encoder_get_pooling(sc_encoder* enc, int32_t* out);
 /* Replaces Embeddings.embed_documents / embed_query after tokenisation (indexer.py:150,
@@ -378,7 +402,17 @@ sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t*
  * outside every sequence stay NaN).  local_window even, 2 .. 128, else SC_ERR_UNSUPPORTED. */
 sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
                                    int32_t local_window, int32_t blocked_rows, float* out);
+/* sc_diag_attention_causal: the causal grouped-query attention kernels (encoder_causal.hip) on their own, head dimension 64, conventions of
+ * sc_diag_attention_window: out = softmax over the keys j <= i, j < len of QK^T/8, times V; query head h reads K/V head h / (heads / kv_heads).
+ * qkv is [rows][(heads + 2 kv_heads) * 64] as [Q | K | V], or (blocked_rows > 0) in 64-column blocks [(heads + 2 kv_heads)][blocked_rows][64].
+ * starts == NULL: a rectangle [B*S rows], lens clamped to 1 .. S, out [B*S, heads*64], every row finite (rows at or beyond len are queries
+ * too).  starts != NULL: packed rows, S is not read, R and out as sc_diag_attention_packed: rows outside every sequence stay NaN, every
+ * row of a sequence is finite.  1 <= kv_heads <= heads <= 32 with heads % kv_heads == 0, else SC_ERR_UNSUPPORTED. */
+sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                   int32_t kv_heads, int32_t blocked_rows, float* out);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
+/* sc_diag_rmsnorm: rmsnorm_kernel, conventions of sc_diag_layernorm: x [tokens,H] -> x * rsqrt(mean(x^2) + eps) * gamma, bf16 rows. */
+sc_status sc_diag_rmsnorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, float eps, float* out);
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,
                                const float* beta, float eps, const int32_t* lens, int32_t B, int32_t S, int32_t H, float* out);

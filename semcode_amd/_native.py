@@ -37,7 +37,8 @@ class EncoderCfg(C.Structure):
     _fields_ = [("vocab", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32),
                 ("max_pos", C.c_int32), ("type_vocab", C.c_int32), ("ln_eps", C.c_float), ("normalize", C.c_int32),
                 ("synth_seed", C.c_uint64), ("pos_type", C.c_int32), ("ffn_type", C.c_int32), ("rope_theta", C.c_float),
-                ("arch", C.c_int32), ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float)]
+                ("arch", C.c_int32), ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float),
+                ("kv_heads", C.c_int32)]
 
 
 _lib = None
@@ -105,6 +106,8 @@ SIGNATURES = {
     "sc_diag_attention_window": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "sc_diag_attention_causal": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -786,11 +789,15 @@ class Comm:
 BERT_BASE = dict(vocab=30522, hidden=768, layers=12, heads=12, ffn=3072, max_pos=512, type_vocab=2, ln_eps=1e-12)
 SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: ALiBi or rotary encoders (no position table), or a position table that long
 POOLINGS = {"mean": 0, "cls": 1}  # sc_encoder_set_pooling
+POOLINGS_QWEN2 = {"mean": 0, "last": 2}  # ... of a qwen2 encoder (arch 2): "last" = the last real token's row; no "cls" there
 
 
 def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> EncoderCfg:
     """sc_encoder_cfg of a complete configuration dict (the keys of BERT_BASE plus the architecture switches alibi / rotary / geglu /
-    swiglu / rope_theta and, for the pre-LN ModernBERT family, modernbert / local_window / global_every / rope_theta_local)."""
+    swiglu / rope_theta and, for the pre-LN ModernBERT family, modernbert / local_window / global_every / rope_theta_local; for the causal
+    Qwen2 family, qwen2 / kv_heads)."""
+    if c.get("modernbert") and c.get("qwen2"):
+        raise ValueError("encoder configuration: modernbert and qwen2 are two architectures, pick one")
     if c.get("rotary") and c.get("alibi"):
         raise ValueError("encoder configuration: rotary and alibi are two position schemes, pick one")
     if c.get("swiglu") and c.get("geglu"):
@@ -800,21 +807,24 @@ def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> Encode
                       synth_seed=synth_seed, pos_type=2 if c.get("rotary") else 1 if c.get("alibi") else 0,
                       ffn_type=2 if c.get("swiglu") else 1 if c.get("geglu") else 0, rope_theta=float(c.get("rope_theta") or 0.0),
                       # pre-LN ModernBERT (sc_encoder_cfg.arch 1): local attention in the layers with l % global_every != 0
-                      arch=1 if c.get("modernbert") else 0, local_window=int(c.get("local_window") or 0),
-                      global_every=int(c.get("global_every") or 0), rope_theta_local=float(c.get("rope_theta_local") or 0.0))
+                      # pre-norm causal decoder (arch 2, Qwen2): kv_heads K / V heads of the grouped-query attention (0 = heads)
+                      arch=2 if c.get("qwen2") else 1 if c.get("modernbert") else 0, local_window=int(c.get("local_window") or 0),
+                      global_every=int(c.get("global_every") or 0), rope_theta_local=float(c.get("rope_theta_local") or 0.0),
+                      kv_heads=int(c.get("kv_heads") or 0))
 
 
 class Encoder:
     """Transformer-encoder forward on the device (sc_encoder): token ids in, pooled f32 vectors out.  pooling: "mean" (masked mean over
-    the real tokens) or "cls" (the last hidden state of the first token: bge, arctic-embed, mxbai, gte)."""
+    the real tokens), "cls" (the last hidden state of the first token: bge, arctic-embed, mxbai, gte) or, on qwen2 encoders only, "last"
+    (the last real token's row: causal embedding models; "cls" is refused there)."""
 
     def __init__(self, rt: Runtime, cfg: dict | None = None, weights: np.ndarray | None = None, normalize: bool = False,
                  synth_seed: int = 0, pooling: str = "mean"):
-        if pooling not in POOLINGS:
-            raise ValueError(f"encoder pooling must be one of {sorted(POOLINGS)}, got {pooling!r}")
         c = dict(BERT_BASE)
         c.update(cfg or {})
         self.cfg = encoder_cfg(c, normalize=normalize, synth_seed=synth_seed)
+        if pooling not in self.poolings:
+            raise ValueError(f"encoder pooling must be one of {sorted(self.poolings)}, got {pooling!r}")
         self.rt = rt
         self.hidden = c["hidden"]
         self.max_pos = c["max_pos"]
@@ -832,16 +842,21 @@ class Encoder:
             self.pooling = pooling
 
     @property
+    def poolings(self) -> dict:
+        """The pooling modes of this encoder's architecture: name -> sc_encoder_set_pooling value."""
+        return POOLINGS_QWEN2 if self.cfg.arch == 2 else POOLINGS
+
+    @property
     def pooling(self) -> str:
         v = C.c_int32()
         _check(lib().sc_encoder_get_pooling(self.handle, C.byref(v)))
-        return next(k for k, n in POOLINGS.items() if n == v.value)
+        return next(k for k, n in self.poolings.items() if n == v.value)
 
     @pooling.setter
     def pooling(self, mode: str) -> None:
-        if mode not in POOLINGS:
-            raise ValueError(f"encoder pooling must be one of {sorted(POOLINGS)}, got {mode!r}")
-        _check(lib().sc_encoder_set_pooling(self.handle, POOLINGS[mode]))
+        if mode not in self.poolings:
+            raise ValueError(f"encoder pooling must be one of {sorted(self.poolings)}, got {mode!r}")
+        _check(lib().sc_encoder_set_pooling(self.handle, self.poolings[mode]))
 
     def close(self) -> None:
         if self._h:
@@ -1267,6 +1282,37 @@ def diag_attention_window(rt: Runtime, qkv, lens, heads: int, local_window: int,
     out = np.empty((rows, H), np.float32)
     _check(lib().sc_diag_attention_window(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
                                           int(local_window), int(blocked_rows), _ptr(out)))
+    return out
+
+
+def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: int = 0, starts=None, blocked_rows: int = 0) -> np.ndarray:
+    """The causal grouped-query attention kernels on their own (head dimension 64): a query sees the real keys at or before its own
+    position; query head h reads K / V head h // (heads // kv_heads).  qkv columns are [Q (heads) | K (kv_heads) | V (kv_heads)] x 64.
+    starts None: a rectangle, qkv [B*S, (heads + 2 kv_heads) * 64] -> [B*S, heads * 64].  Else packed rows as diag_attention_packed."""
+    qkv = _f32(qkv)
+    lens = np.ascontiguousarray(lens, np.int32)
+    H, QN = heads * 64, (heads + 2 * kv_heads) * 64
+    if starts is None:
+        rows = len(lens) * int(S)
+        R = int(blocked_rows) if blocked_rows else rows
+    else:
+        starts = np.ascontiguousarray(starts, np.int32)
+        R = rows = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
+    if qkv.shape != (R, QN) or (starts is not None and starts.shape != lens.shape):
+        raise ValueError(f"diag_attention_causal: qkv must be [{R}, {QN}], starts (if given) and lens [B]")
+    if blocked_rows:
+        qkv = block64(qkv)
+    out = np.empty((rows, H), np.float32)
+    _check(lib().sc_diag_attention_causal(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
+                                          int(kv_heads), int(blocked_rows), _ptr(out)))
+    return out
+
+
+def diag_rmsnorm(rt: Runtime, x, gamma, eps: float) -> np.ndarray:
+    """rmsnorm_kernel: x [tokens, H] -> x * rsqrt(mean(x^2) + eps) * gamma, rows rounded to bf16 on the way in and out."""
+    x, gamma = _f32(x), _f32(gamma)
+    out = np.empty_like(x)
+    _check(lib().sc_diag_rmsnorm(rt.handle, _ptr(x), x.shape[0], x.shape[1], _ptr(gamma), float(eps), _ptr(out)))
     return out
 
 

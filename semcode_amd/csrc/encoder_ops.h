@@ -82,6 +82,19 @@ void sc_launch_attention_window(const void* qkv, const int32_t* lens, int B, int
 void sc_launch_attention_window_packed(const void* qkv, const int32_t* items, const int* nitems, int H, int local_window, void* ctx, hipStream_t s,
                                        int blocked = 0);
 
+// ---- encoder_causal.hip: the causal decoder family (cfg.arch 2).  Causal grouped-query attention, head dimension 64, plain scores: a query
+// sees the real keys at or before its own position; query head h reads K / V head h / (heads / kv_heads).  qkv rows are
+// [Q (heads) | K (kv_heads) | V (kv_heads)] x 64 columns, row-major (blocked 0) or in 64-column blocks of `blocked` rows; ctx [rows, heads * 64];
+// lens / items as the two attention launchers above.  rmsnorm: x * rsqrt(mean(x^2) + eps) * gamma, bf16 rows, H a multiple of 8, <= 2048.
+// last_pool: the row start + len - 1 of every text (starts NULL: a [B, S] rectangle, lens clamped to 1 .. S) of x [rows, H] bf16, RMSNorm in
+// f32, optional L2 normalisation by the rule of the mean kernels -> out [B, H] f32.
+bool sc_attention_causal_supported(int heads, int kv_heads);
+void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_rmsnorm(const void* in, int tokens, int H, const float* g, float eps, void* out, hipStream_t s);
+void sc_launch_last_pool(const void* x, const int32_t* starts, const int32_t* lens, int B, int S, int H, const float* gamma, float eps, int normalize, float* out,
+                         hipStream_t s);
+
 // ---- encoder_pairs.hip: the packed embedding with a per-row segment id (types [rows], clamped into type_emb's type_vocab rows), and
 // the classification head of a cross-encoder: cls [B,H] f32 -> logits [B,num_labels] = Wc p + bc, p = tanh(Wp cls + bp), or p = cls when
 // Wp is NULL.  Wp [H,H], bp [H], Wc [num_labels,H], bc [num_labels] f32 on the device; H a multiple of 16, <= 2048; num_labels 1 or 2.

@@ -14,6 +14,8 @@
 // take each pair's [CLS] row instead of a mean; the head on those rows is encoder_pairs.hip's.
 // Pre-norm models (cfg.arch 1, ModernBERT): forward_prenorm_locked -- h += Attn(LN(h)), h += MLP(LN(h)) on a raw residual stream, local
 // (sliding-window) attention in the layers with l % global_every != 0 (encoder_window.hip), a rotary table per kind of layer, final_norm.
+// Causal decoders (cfg.arch 2, the Qwen2 family): forward_causal_locked -- the same raw residual stream with RMSNorm, grouped-query causal
+// attention (encoder_causal.hip), SwiGLU, no embedding norm; pooled from RMS_final(h): the last real token's row, or the masked mean.
 // The single-kernel harnesses (sc_diag_*) are in sc_encoder_diag.cpp, the device entry points in encoder_ops.h.
 #include <cmath>
 #include <cstring>
@@ -24,8 +26,8 @@
 #include "sc_internal.h"
 
 struct LayerW {
-    void* wqkv;  // bf16 [3H, H]
-    float* bqkv; // [3H]
+    void* wqkv;  // bf16 [3H, H]; arch 2: [H + 2 KV, H], KV = kv_heads * 64
+    float* bqkv; // [3H]; arch 2: [H + 2 KV]
     void* wo;    // bf16 [H, H]
     float* bo;
     float *ln1g, *ln1b;
@@ -67,7 +69,7 @@ struct sc_encoder {
     float *fin_a = nullptr, *fin_b = nullptr;    // [ws_tokens][2] their finalised (mu, rs)
     bool foldable = false;                       // shapes allow the folded pipeline (256-tile GEMMs, K % 256 == 0)
     int path = 0;                                // sc_encoder_set_path: 0 auto, 1 batch pipeline always, 2 small-batch pipeline always
-    int pooling = 0;                             // sc_encoder_set_pooling: 0 masked mean, 1 the [CLS] row
+    int pooling = 0;                             // sc_encoder_set_pooling: 0 masked mean, 1 the [CLS] row, 2 the last real token's row (arch 2)
     void* splitk = nullptr;  // f32 partial products of the split-K GEMMs (batches of <= 1024 tokens), allocated on first use
     static constexpr size_t SPLITK_BYTES = 64u << 20;
     // pinned host staging for the asynchronous embed -> index path: ids | lens | rows of one batch per slot
@@ -146,6 +148,8 @@ struct Arena {
 
 // ffn_type 1 (GEGLU) and 2 (SwiGLU): W1 holds gate and up rows, an element-wise kernel sits between the two FFN GEMMs
 static bool ffn_gated(const sc_encoder_cfg& c) { return c.ffn_type == 1 || c.ffn_type == 2; }
+// arch 2: K and V have kv_heads heads of 64 (0 = heads); every other model projects K and V to hidden columns
+static int64_t kv_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)(c.kv_heads > 0 ? c.kv_heads : c.heads) * 64 : (int64_t)c.hidden; }
 static void launch_gate(const sc_encoder_cfg& c, const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
     if (c.ffn_type == 2) sc_launch_swiglu(h, tokens, F, out, s);
     else sc_launch_geglu(h, tokens, F, out, s);
@@ -167,9 +171,10 @@ static bool ffn_blocked_enabled() { static const bool on = sc_env_flag("SC_FFN_B
 // number of f32 values in the weight blob, in blob order (see include/semcode_hip.h)
 static int64_t blob_floats(const sc_encoder_cfg& c) {
     const int64_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F;
-    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch == 1 ? 0 : (int64_t)c.type_vocab * H) + 2 * H;
-    n += (int64_t)c.layers * (4 * (H * H + H) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
-    if (c.arch == 1) n += 2 * H;  // final_norm
+    const int64_t KV = kv_width(c);
+    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch != 0 ? 0 : (int64_t)c.type_vocab * H) + (c.arch == 2 ? 0 : 2 * H);
+    n += (int64_t)c.layers * (2 * (H * H + H) + 2 * (KV * H + KV) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
+    if (c.arch != 0) n += 2 * H;  // final_norm
     return n;
 }
 // arch 1: layer l attends globally iff l % global_every == 0 (global_every 0 counts as 1: every layer global)
@@ -194,7 +199,24 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension 32 runs with learned positions only (pos_type 0), not pos_type %d (%s)", c.pos_type,
                        c.pos_type == 1 ? "ALiBi" : "rotary");
     if (c.pos_type == 2 && !(c.rope_theta >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta must be >= 0 (0 = 10000)");
-    if (c.arch < 0 || c.arch > 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT)", c.arch);
+    if (c.arch < 0 || c.arch > 2)
+        return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT, 2 = causal Qwen2 decoder)", c.arch);
+    if (c.arch != 2 && c.kv_heads != 0)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: kv_heads %d needs arch 2 (grouped-query attention exists in the causal pipeline only)", c.kv_heads);
+    if (c.arch == 2) {
+        // the causal pipeline: rotate-half rotation and the causal kernel are written for 64-wide heads, its gate is SwiGLU
+        if (c.hidden != c.heads * 64)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 needs head dimension 64 (hidden=%d heads=%d)", c.hidden, c.heads);
+        if (c.pos_type != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 runs with rotary positions only (pos_type 2), not pos_type %d", c.pos_type);
+        if (c.ffn_type != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 runs with the SwiGLU feed-forward only (ffn_type 2), not ffn_type %d", c.ffn_type);
+        if (c.kv_heads < 0 || c.kv_heads > c.heads || (c.kv_heads > 0 && c.heads % c.kv_heads != 0))
+            return sc_fail(SC_ERR_INVALID, "sc_encoder_create: kv_heads must divide heads (1 <= kv_heads <= heads, 0 = heads), got kv_heads %d with heads %d", c.kv_heads,
+                           c.heads);
+        if (c.local_window != 0 || c.global_every > 1)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window %d / global_every %d need arch 1 (arch 2 attends causally in every layer)", c.local_window,
+                           c.global_every);
+        return SC_OK;
+    }
     if (c.arch == 0) {
         if (c.local_window != 0 || c.global_every > 1)
             return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window %d / global_every %d need arch 1 (local attention exists in the pre-LN pipeline only)",
@@ -246,7 +268,7 @@ static std::vector<float> alibi_slopes(int heads) {
 // the parameter arena: f32 tables + per-layer {bf16 matrices, f32 vectors}; e->layers is sized, e->foldable set
 static void layout_params(sc_encoder* e, Arena& a) {
     const sc_encoder_cfg& c = e->cfg;
-    const size_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F, rope_n = (size_t)c.max_pos * 32;
+    const size_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F, rope_n = (size_t)c.max_pos * 32, QN = H + 2 * (size_t)kv_width(c);
     e->wemb = a.f32((size_t)c.vocab * H);
     e->pemb = c.pos_type == 0 ? a.f32((size_t)c.max_pos * H) : nullptr;
     e->slopes = c.pos_type == 1 ? a.f32((size_t)c.heads) : nullptr;
@@ -254,13 +276,13 @@ static void layout_params(sc_encoder* e, Arena& a) {
     e->rope_sin = e->rope_cos ? e->rope_cos + rope_n : nullptr;
     e->rope_cos_l = c.arch == 1 ? a.f32(2 * rope_n) : nullptr;
     e->rope_sin_l = e->rope_cos_l ? e->rope_cos_l + rope_n : nullptr;
-    e->temb = a.f32(c.arch == 1 ? H : (size_t)c.type_vocab * H);  // arch 1 has no type table: one row of zeros for the embedding kernels
-    e->fing = c.arch == 1 ? a.f32(H) : nullptr;
-    e->finb = c.arch == 1 ? a.f32(H) : nullptr;
+    e->temb = a.f32(c.arch != 0 ? H : (size_t)c.type_vocab * H);  // arch 1, 2 have no type table: one row of zeros for the embedding kernels
+    e->fing = c.arch != 0 ? a.f32(H) : nullptr;
+    e->finb = c.arch != 0 ? a.f32(H) : nullptr;
     e->embg = a.f32(H);
     e->embb = a.f32(H);
     for (LayerW& w : e->layers) {
-        w.wqkv = a.bf16(3 * H * H); w.bqkv = a.f32(3 * H);
+        w.wqkv = a.bf16(QN * H);    w.bqkv = a.f32(QN);
         w.wo = a.bf16(H * H);       w.bo = a.f32(H);
         w.ln1g = a.f32(H);          w.ln1b = a.f32(H);
         w.w1 = a.bf16(F1 * H);      w.b1 = a.f32(F1);
@@ -288,7 +310,8 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     e->rt = rt;
     sc_runtime_retain(rt);
     e->cfg = *cfg;
-    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = ffn_gated(*cfg) ? 2 * F : F;
+    if (e->cfg.arch == 2 && e->cfg.kv_heads == 0) e->cfg.kv_heads = e->cfg.heads;  // (sc_encoder_info reports the count in use)
+    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = ffn_gated(*cfg) ? 2 * F : F, KV = kv_width(*cfg);
 
     // staging copy of the f32 blob on device (freed after conversion)
     float* blob = nullptr;
@@ -343,18 +366,21 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     if (e->slopes) put_host(e->slopes, alibi_slopes(cfg->heads));
     if (e->rope_cos) put_host(e->rope_cos, sc_rope_table(cfg->max_pos, cfg->rope_theta));
     if (e->rope_cos_l) put_host(e->rope_cos_l, sc_rope_table(cfg->max_pos, cfg->rope_theta_local));
-    if (cfg->arch == 1) hipMemsetAsync(e->temb, 0, (size_t)H * 4, s);
+    if (cfg->arch != 0) hipMemsetAsync(e->temb, 0, (size_t)H * 4, s);
     else put_f32(e->temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, COPY);
-    put_f32(e->embg, take(H), H, ONES);
-    put_f32(e->embb, take(H), H, ZEROS);
+    if (cfg->arch != 2) {  // arch 2 has no embedding norm
+        put_f32(e->embg, take(H), H, ONES);
+        put_f32(e->embb, take(H), H, ZEROS);
+    }
     for (int64_t l = 0; l < L; ++l) {
         LayerW& w = e->layers[l];
-        // blob order: Wq bq Wk bk Wv bv Wo bo ln1g ln1b W1 b1 W2 b2 ln2g ln2b ; device: Wqkv = [Wq; Wk; Wv]
+        // blob order: Wq bq Wk bk Wv bv Wo bo ln1g ln1b W1 b1 W2 b2 ln2g ln2b ; device: Wqkv = [Wq; Wk; Wv] (Wk, Wv: KV rows each)
         const float* wqkv_f32[3];
         for (int p = 0; p < 3; ++p) {
-            wqkv_f32[p] = take(H * H);
-            put_bf16((char*)w.wqkv + (size_t)p * H * H * 2, wqkv_f32[p], H * H);
-            put_f32(w.bqkv + p * H, take(H), H, ZEROS);
+            const int64_t rows = p == 0 ? H : KV, row0 = p == 0 ? 0 : H + (p - 1) * KV;
+            wqkv_f32[p] = take(rows * H);
+            put_bf16((char*)w.wqkv + (size_t)row0 * H * 2, wqkv_f32[p], rows * H);
+            put_f32(w.bqkv + row0, take(rows), rows, ZEROS);
         }
         put_bf16(w.wo, take(H * H), H * H);
         put_f32(w.bo, take(H), H, ZEROS);
@@ -456,8 +482,9 @@ static sc_status ensure_ws(sc_encoder* e, int64_t rows, int64_t B) {
 // local: the table of an arch 1 model's local layers instead of the model's (global) one
 static void launch_rope(sc_encoder* e, int M, int S, const PackedLayout* pk, hipStream_t s, bool local = false) {
     const float *cos_t = local ? e->rope_cos_l : e->rope_cos, *sin_t = local ? e->rope_sin_l : e->rope_sin;
-    if (pk) sc_launch_rope_qk_packed(e->qkv, M, 2 * e->cfg.heads, pk->pos, e->cfg.max_pos, cos_t, sin_t, s);
-    else sc_launch_rope_qk(e->qkv, M, 2 * e->cfg.heads, S, cos_t, sin_t, s);
+    const int nblocks = e->cfg.arch == 2 ? e->cfg.heads + e->cfg.kv_heads : 2 * e->cfg.heads;  // the Q and K heads
+    if (pk) sc_launch_rope_qk_packed(e->qkv, M, nblocks, pk->pos, e->cfg.max_pos, cos_t, sin_t, s);
+    else sc_launch_rope_qk(e->qkv, M, nblocks, S, cos_t, sin_t, s);
 }
 static void launch_attention_window(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
     if (pk) sc_launch_attention_window_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->cfg.local_window, e->ctx, s, M);
@@ -646,6 +673,56 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
     return SC_OK;
 }
 
+// The causal decoder forward (cfg.arch 2, the Qwen2 family), on the stand-alone-norm launches for every batch size as the pre-norm forward:
+//   h = bf16(tok_emb[id])                                                 -> x   (the raw embedding kernels, no position table, zero type row)
+//   per layer:  a = RMS_in(h)                                             -> x1
+//               QKV = a [Wq; Wk; Wv]^T + b, N = H + 2 KV in 64-column blocks; the first heads + kv_heads blocks (Q and K) rotated
+//               ctx = causal grouped-query attention (encoder_causal.hip)
+//               h = ctx Wo^T + bo + h                                     x -> y
+//               m = RMS_post(h)                                           -> x1
+//               h = (silu(gate) * up)(m W1^T + b1) W2^T + b2 + h          y -> x
+//   pooled = RMS_final of the last real token's row (in f32, inside the pooling kernel), or the masked mean of RMS_final(h)
+static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
+                                       const PackedLayout* pk) {
+    const sc_encoder_cfg& c = e->cfg;
+    sc_runtime* rt = e->rt;
+    hipStream_t s = rt->stream;
+    const int H = c.hidden, F = c.ffn, QN = H + 2 * (int)kv_width(c);
+    const int tokens = pk ? pk->rows : B * S;
+    const int M = (tokens + 255) / 256 * 256;
+    void* sk = nullptr;
+    if (M <= 1024 && e->path != 1) {
+        if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
+        sk = e->splitk;
+    }
+    const size_t skb = sk ? sc_encoder::SPLITK_BYTES : 0;
+    if (pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
+    else sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
+    for (int l = 0; l < c.layers; ++l) {
+        const LayerW& w = e->layers[l];
+        sc_launch_rmsnorm(e->x, tokens, H, w.ln1g, c.ln_eps, e->x1, s);
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, QN, H, s, sk, skb); });
+        launch_rope(e, M, S, pk, s);
+        sc_with_prof(rt, SC_PROF_ATTN, [&] {
+            if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
+            else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, e->ctx, s, M);
+        });
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x, H, e->y, H, M, H, H, s, sk, skb); });
+        sc_launch_rmsnorm(e->y, tokens, H, w.ln2g, c.ln_eps, e->x1, s);
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
+        launch_gate(c, e->hm, M, F, e->hg, s);
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
+    }
+    if (e->pooling == 2) {
+        sc_launch_last_pool(e->x, pk ? pk->starts : nullptr, lens_dev, B, S, H, e->fing, c.ln_eps, c.normalize, out_dev, s);
+    } else {
+        sc_launch_rmsnorm(e->x, tokens, H, e->fing, c.ln_eps, e->x1, s);
+        launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
 // ids_dev [B,S], lens_dev [B] device pointers; out_dev [B,H] f32 device.  pk != NULL: a packed batch -- ids_dev holds one id per token
 // row of the layout (M of them), S is unused.  Caller holds e->mu.
 static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
@@ -657,6 +734,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     if (c.arch == 1) return forward_prenorm_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
+    if (c.arch == 2) return forward_causal_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
     // batches beyond 1024 token rows (or sc_encoder_set_path 1) take the LayerNorm-folded pipeline where the model's shapes allow it
     static const bool env_fold = sc_env_flag("SC_ENC_FOLD", true);  // SC_ENC_FOLD=0: same-box A/B against the stand-alone LayerNorm kernels
     if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
@@ -1060,6 +1138,8 @@ extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, c
     if (!e || !ids || !offsets || !first_lens || !out_logits) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
     if (e->cfg.arch == 1)  // ModernBERT's classifier is dense -> GELU -> LayerNorm -> linear; pair_head_kernel is pooler + tanh
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 1 (pre-LN) models have no pair head: their classifier is not pooler + linear", who);
+    if (e->cfg.arch == 2)  // no segment ids, no [CLS] row, no pooler: rerankers of this family are out of scope
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models do not score pairs: the family has no [CLS] row and no pair head", who);
     int64_t used = 0;
     sc_status st = check_packed_offsets(e, offsets, B, who, &used);
     if (st) return st;
@@ -1112,7 +1192,10 @@ extern "C" sc_status sc_encoder_set_path(sc_encoder* e, int32_t path) {
 }
 
 extern "C" sc_status sc_encoder_set_pooling(sc_encoder* e, int32_t pooling) {
-    if (!e || pooling < 0 || pooling > 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pooling: pooling must be 0 (masked mean) or 1 ([CLS] row)");
+    if (!e || pooling < 0 || pooling > (e->cfg.arch == 2 ? 2 : 1))
+        return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pooling: pooling must be 0 (masked mean) or 1 ([CLS] row); 2 (the last token's row) needs an arch 2 encoder");
+    if (e->cfg.arch == 2 && pooling == 1)
+        return sc_fail(SC_ERR_INVALID, "sc_encoder_set_pooling: pooling 1 ([CLS] row) is refused on arch 2: a causal first token sees only itself; use 0 (mean) or 2 (last token)");
     std::lock_guard<std::mutex> g(e->mu);
     e->pooling = pooling;
     return SC_OK;

@@ -418,6 +418,63 @@ extern "C" sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, 
     return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
 }
 
+// sc_launch_attention_causal / _packed as the causal forward calls them (starts == NULL: the rectangle form).  qkv rows are
+// [Q (heads) | K (kv_heads) | V (kv_heads)] x 64 columns; out [rows, heads * 64]
+extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                              int32_t kv_heads, int32_t blocked_rows, float* out) {
+    const char* who = "sc_diag_attention_causal";
+    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (!sc_attention_causal_supported(heads, kv_heads))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: need 1 <= kv_heads <= heads <= 32 with heads %% kv_heads == 0, got heads %d, kv_heads %d", who, heads, kv_heads);
+    const int H = heads * 64, QN = (heads + 2 * kv_heads) * 64;
+    int64_t R = 0, rows_out = 0;
+    std::vector<int32_t> items;
+    int nitems[3] = {0, 0, 0};
+    if (starts) {
+        int64_t end = 0;
+        for (int32_t b = 0; b < B; ++b) {
+            if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
+                return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
+            const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
+            if (e > end) end = e;
+        }
+        R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
+        if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
+        rows_out = R;
+        items.resize((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
+        sc_packed_items(starts, lens, B, items.data(), nitems);
+    } else {
+        if (!sc_attention_supported(S, H, heads, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
+        rows_out = (int64_t)B * S;
+        if (blocked_rows && blocked_rows < rows_out) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
+        R = blocked_rows ? (int64_t)blocked_rows : rows_out;
+    }
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fq, dq, dl, dc;
+    SC_TRY(upload_bf16(qkv, R * QN, fq, dq, s));
+    if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
+    else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
+    SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
+    if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
+    else sc_launch_attention_causal(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, dc.p, s, blocked_rows);
+    return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
+}
+
+// rmsnorm_kernel<3|4|8>: x [tokens,H] -> out [tokens,H] = x * rsqrt(mean(x^2) + eps) * gamma
+extern "C" sc_status sc_diag_rmsnorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, float eps, float* out) {
+    if (!rt || !x || !gamma || !out || tokens < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_rmsnorm: bad argument");
+    if (H < 8 || (H % 8) || H > 2048 || !(eps > 0.f)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_rmsnorm: H must be a multiple of 8, <= 2048");
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fx, dx, dg, dc;
+    SC_TRY(upload_bf16(x, (int64_t)tokens * H, fx, dx, s));
+    SC_TRY(upload(gamma, (size_t)H * 4, dg, s));
+    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
+    sc_launch_rmsnorm(dx.p, tokens, H, (const float*)dg.p, eps, dc.p, s);
+    return download_bf16(dc.p, (int64_t)tokens * H, out, s);
+}
+
 // rope_qk_kernel on its own: qk [rows, heads * 64] f32 (row r = position r % S) -> bf16 in the blocked layout [heads][rows][64],
 // rotated in place, widened and laid out row-major again.
 extern "C" sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta) {

@@ -162,6 +162,86 @@ def modernbert_config_beside(weights: "str | Path | None") -> Optional[dict]:
     return modernbert_config(c) if c.get("model_type") == "modernbert" else None
 
 
+# transformers Qwen2Model names (Qwen2 / Qwen2.5 backbones of jina-code-embeddings-0.5b, gte-Qwen2, KaLM-mini), with or without a "model."
+# prefix: a pre-norm causal decoder, no position or type table, no embedding norm, biases on q / k / v only, gate_proj (SiLU-activated) and
+# up_proj stacked into W1 = [2F, H], gate rows first.  Blob order: arch 2 of include/semcode_hip.h (beta slots and the bo / b1 / b2 slots are
+# zeros).  Written from the published module layout and checked against transformers' Qwen2Model on seeded weights
+# (scripts/gen_qwen2_fixtures.py); no released checkpoint exists offline, so parity for real files is unpinned.
+def _qwen2_blob(path, tensors: dict, layers: int, cfg: Optional[dict] = None) -> np.ndarray:
+    def find(name: str):
+        for key in (name, "model." + name):
+            if key in tensors:
+                return np.asarray(tensors[key], dtype=np.float32)
+        return None
+
+    def get(name: str) -> np.ndarray:
+        t = find(name)
+        if t is None:
+            raise KeyError(f"{path}: tensor {name!r} not found")
+        return t
+
+    def opt(name: str, n: int) -> np.ndarray:
+        t = find(name)
+        return np.zeros(n, np.float32) if t is None else t.reshape(-1)
+
+    emb = get("embed_tokens.weight")
+    H = emb.shape[1]
+    zeros = np.zeros(H, np.float32)
+    parts = [emb.reshape(-1)]
+    for l in range(layers):
+        q = f"layers.{l}."
+        wq, wk, wv = get(q + "self_attn.q_proj.weight"), get(q + "self_attn.k_proj.weight"), get(q + "self_attn.v_proj.weight")
+        KV = wk.shape[0]
+        if wq.shape != (H, H) or wk.shape != (KV, H) or wv.shape != (KV, H) or KV % 64:
+            raise ValueError(f"{path}: {q}self_attn q / k / v projections are {wq.shape} / {wk.shape} / {wv.shape}, expected [{H}, {H}] and two [64 * kv_heads, {H}]")
+        if cfg is not None and KV != 64 * int(cfg.get("kv_heads") or cfg["heads"]):
+            raise ValueError(f"{path}: {q}self_attn.k_proj has {KV // 64} heads of 64, the encoder configuration {int(cfg.get('kv_heads') or cfg['heads'])}")
+        gate, up = get(q + "mlp.gate_proj.weight"), get(q + "mlp.up_proj.weight")
+        parts += [wq.reshape(-1), opt(q + "self_attn.q_proj.bias", H), wk.reshape(-1), opt(q + "self_attn.k_proj.bias", KV), wv.reshape(-1),
+                  opt(q + "self_attn.v_proj.bias", KV), get(q + "self_attn.o_proj.weight").reshape(-1), opt(q + "self_attn.o_proj.bias", H),
+                  get(q + "input_layernorm.weight"), zeros, gate.reshape(-1), up.reshape(-1), np.zeros(2 * gate.shape[0], np.float32),
+                  get(q + "mlp.down_proj.weight").reshape(-1), zeros, get(q + "post_attention_layernorm.weight"), zeros]
+    parts += [get("norm.weight"), zeros]
+    return np.concatenate(parts)
+
+
+def qwen2_config(config: "str | Path | dict") -> dict:
+    """The encoder configuration of a transformers Qwen2 `config.json` (path or parsed dict): grouped-query heads from
+    `num_key_value_heads`, the rotary base `rope_theta`, `rms_norm_eps`, and `max_position_embeddings` capped at the 2 048 tokens a text
+    may have here (the cap sizes the rotary table; the released models state 32 768).  A sliding window shorter than that is refused:
+    the causal kernel attends to every earlier token."""
+    if not isinstance(config, dict):
+        import json
+
+        config = json.loads(Path(config).read_text())
+    c = config
+    if c.get("model_type") not in (None, "qwen2"):
+        raise ValueError(f"not a Qwen2 configuration (model_type {c.get('model_type')!r})")
+    if c.get("use_sliding_window") and int(c.get("sliding_window") or 0) < 2048:
+        raise ValueError(f"Qwen2 config: use_sliding_window with sliding_window {c.get('sliding_window')} < 2048 is not supported (the causal kernel sees every earlier token)")
+    if c.get("hidden_act", "silu") != "silu":
+        raise ValueError(f"Qwen2 config: hidden_act {c.get('hidden_act')!r} is not supported (silu only)")
+    heads = int(c["num_attention_heads"])
+    rp = c.get("rope_parameters") or {}
+    return dict(vocab=int(c["vocab_size"]), hidden=int(c["hidden_size"]), layers=int(c["num_hidden_layers"]), heads=heads,
+                kv_heads=int(c.get("num_key_value_heads") or heads), ffn=int(c["intermediate_size"]),
+                max_pos=min(int(c.get("max_position_embeddings", 32768)), 2048), type_vocab=1, ln_eps=float(c.get("rms_norm_eps", 1e-6)), rotary=True,
+                swiglu=True, qwen2=True, rope_theta=float(rp.get("rope_theta", c.get("rope_theta", 10000.0))))
+
+
+def qwen2_config_beside(weights: "str | Path | None") -> Optional[dict]:
+    """qwen2_config of the config.json next to a .safetensors file, None when there is none or it is another model's."""
+    if not isinstance(weights, (str, Path)) or not str(weights).lower().endswith(".safetensors"):
+        return None
+    conf = Path(weights).parent / "config.json"
+    if not conf.is_file():
+        return None
+    import json
+
+    c = json.loads(conf.read_text())
+    return qwen2_config(c) if c.get("model_type") == "qwen2" else None
+
+
 def tensors_rows(tensors: dict, name: str) -> int:
     """Number of rows (output features) of a 2-D checkpoint tensor, with or without the "bert." prefix."""
     for key in (name, "bert." + name):
@@ -174,7 +254,8 @@ def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None
     """Flat f32 blob in ABI order from `.npy` (already flat), `.gguf` (llama.cpp's bert / jina-bert-v2 tensor names, F32 / F16 /
     BF16; embeddings/gguf.py) or `.safetensors` (HF BERT names, jina-bert-v2 names when the file holds `mlp.gated_layers`, or
     transformers' NomicBert names when it holds `layers.0.mlp.gate_proj`, or transformers' ModernBert names when it holds
-    `layers.0.attn.Wqkv`; optional "bert." / "nomic_bert." / "model." prefix).  GGUF files of the ModernBERT family are not read.  cfg: the
+    `layers.0.attn.Wqkv`, or transformers' Qwen2 names when it holds `embed_tokens`; optional "bert." / "nomic_bert." / "model." prefix).
+    GGUF files of the ModernBERT and Qwen2 families are not read.  cfg: the
     encoder configuration the blob is for (checked against the checkpoint's architecture: a jina file needs alibi + geglu, a
     nomic file rotary + swiglu, a BERT file none of them)."""
     path = Path(path)
@@ -191,6 +272,13 @@ def load_weight_blob(path: "str | Path", layers: int, cfg: Optional[dict] = None
                     return np.asarray(tensors[key], dtype=np.float32).reshape(-1)
             raise KeyError(f"{path}: tensor {name!r} not found")
 
+        if any(k in ("embed_tokens.weight", "model.embed_tokens.weight") for k in tensors):
+            if cfg is not None and not (cfg.get("qwen2") and cfg.get("rotary") and cfg.get("swiglu")):
+                raise ValueError(f"{path} is a Qwen2 checkpoint but the encoder configuration is not qwen2 + rotary + swiglu "
+                                 "(qwen2_config reads it from the model's config.json)")
+            return _qwen2_blob(path, tensors, layers, cfg)
+        if cfg is not None and cfg.get("qwen2"):
+            raise ValueError(f"{path} holds no Qwen2 tensors (embed_tokens.weight) but the encoder configuration says qwen2")
         jina = any(k.endswith("encoder.layer.0.mlp.gated_layers.weight") for k in tensors)
         nomic = any(k in ("layers.0.mlp.gate_proj.weight", "nomic_bert.layers.0.mlp.gate_proj.weight") for k in tensors)
         if any(k in ("layers.0.attn.Wqkv.weight", "model.layers.0.attn.Wqkv.weight") for k in tensors):
@@ -256,14 +344,17 @@ def flatten_ids(ids: np.ndarray, lens: np.ndarray) -> "tuple[np.ndarray, np.ndar
 
 def resolve_pooling(pooling: Optional[str] = None, setting: Optional[str] = None, weights: "str | Path | None" = None,
                     file_pooling: Optional[str] = None) -> str:
-    """"mean" or "cls" for MI355XEmbeddings, the first of: the argument; the setting mi355x_pooling; what a .gguf states (file_pooling =
-    gguf_config(meta)["pooling"], or read from `weights` here); for a .safetensors the sentence-transformers 1_Pooling/config.json in
-    the file's directory (pooling_mode_cls_token true -> cls); mean."""
+    """"mean", "cls" or "last" for MI355XEmbeddings, the first of: the argument; the setting mi355x_pooling; what a .gguf states
+    (file_pooling = gguf_config(meta)["pooling"], or read from `weights` here); for a .safetensors the sentence-transformers
+    1_Pooling/config.json in the file's directory (pooling_mode_cls_token true -> cls, pooling_mode_lasttoken true -> last); mean.
+    "last" (the last real token's row) exists on Qwen2 encoders only: as an argument or a setting it is taken when `weights` is the
+    .safetensors of a Qwen2 directory (config.json with model_type qwen2) and refused like any unknown value otherwise; "cls" on such
+    a model is refused by the encoder."""
     for given, where in ((pooling, "pooling"), (setting, "SEMCODE_MI355X_POOLING")):
         if given:
             mode = str(given).strip().lower()
-            if mode not in ("mean", "cls"):
-                raise ValueError(f"{where} must be 'mean' or 'cls', got {given!r}")
+            if mode not in ("mean", "cls") and not (mode == "last" and qwen2_config_beside(weights) is not None):
+                raise ValueError(f"{where} must be 'mean' or 'cls' (or 'last' with the weights of a Qwen2 model directory), got {given!r}")
             return mode
     path = Path(weights) if isinstance(weights, (str, Path)) else None
     if path is not None and path.suffix.lower() == ".gguf":
@@ -277,8 +368,11 @@ def resolve_pooling(pooling: Optional[str] = None, setting: Optional[str] = None
         if conf.is_file():
             import json
 
-            if bool(json.loads(conf.read_text()).get("pooling_mode_cls_token")):
+            pc = json.loads(conf.read_text())
+            if bool(pc.get("pooling_mode_cls_token")):
                 return "cls"
+            if bool(pc.get("pooling_mode_lasttoken")):
+                return "last"
     return "mean"
 
 
@@ -296,7 +390,12 @@ class MI355XEmbeddings:
 
     ModernBERT (answerdotai/ModernBERT-base, gte-modernbert-base, modernbert-embed-base): point `weights` at the model.safetensors of
     the model directory -- the `config.json` beside it gives the whole configuration (modernbert_config) and the `tokenizer.json`
-    beside it the byte-level BPE tokenizer (HFTokenizer; or `tokenizer_json=` / SEMCODE_MI355X_TOKENIZER_JSON)."""
+    beside it the byte-level BPE tokenizer (HFTokenizer; or `tokenizer_json=` / SEMCODE_MI355X_TOKENIZER_JSON).
+
+    Qwen2 embedding models (the Qwen2 / Qwen2.5 0.5B backbone: jina-code-embeddings-0.5b, gte-Qwen2, KaLM-mini; heads of 64 only): the
+    same three files of the model directory (qwen2_config); `pooling="last"` -- the last real token's row -- is what their
+    1_Pooling/config.json states (pooling_mode_lasttoken) and what resolve_pooling then returns; their task prefixes go into
+    document_prefix / query_prefix.  Texts stay capped at 2 048 tokens."""
 
     def __init__(self, model: Optional[str] = None, *, cfg: Optional[dict] = None, weights: "np.ndarray | str | Path | None" = None,
                  vocab: "dict | str | Path | None" = None, device: Optional[int] = None, max_tokens: Optional[int] = None,
@@ -369,6 +468,10 @@ class MI355XEmbeddings:
         mb_cfg = modernbert_config_beside(weights)
         if mb_cfg is not None:
             self._cfg.update(mb_cfg)
+        # a Qwen2 directory (jina-code-embeddings-0.5b, gte-Qwen2, KaLM-mini): the same three files; 1_Pooling/config.json states "last"
+        q2_cfg = qwen2_config_beside(weights)
+        if q2_cfg is not None:
+            self._cfg.update(q2_cfg)
         tokenizer_json = tokenizer_json if tokenizer_json is not None else getattr(settings, "mi355x_tokenizer_json", None)
         if tokenizer_json is None and vocab is None and isinstance(weights, (str, Path)) and (Path(weights).parent / "tokenizer.json").is_file():
             tokenizer_json = Path(weights).parent / "tokenizer.json"

@@ -52,7 +52,7 @@ _DEFAULTS: dict[str, Any] = {
     "mi355x_store_path": None,
     "mi355x_ingest_batch": 256,       # chunks per embed+upsert batch of services.indexer.ingest_chunks
     "mi355x_packed": False,           # embed variable-length batches packed (no padding to the longest text of a batch)
-    "mi355x_pooling": "",             # "mean" | "cls"; empty: what the weight file states (GGUF pooling_type, 1_Pooling/config.json), else mean
+    "mi355x_pooling": "",             # "mean" | "cls" | "last" (Qwen2 models only); empty: what the weight file states (GGUF pooling_type, 1_Pooling/config.json), else mean
     "mi355x_lexical": False,          # keep a term row per chunk on the device for hybrid (BM25 + dense) search: MilvusVectorStore(lexical=...)
     "mi355x_reranker_path": None,     # .safetensors of a BertForSequenceClassification cross-encoder (embeddings/reranker.py)
     "mi355x_reranker_vocab": None,    # its vocab.txt (default: mi355x_vocab_path)
