@@ -123,12 +123,21 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
  *   from RMS_final(h).  RMS(x) = x * rsqrt(mean(x^2) + ln_eps) * gamma, statistics in f32, no beta.  MLP = W2 (silu(gate) * up) (ffn_type 2).
  *   Rotary positions (pos_type 2) with the one base rope_theta.  Scores are q.k / 8 over the keys j <= i, j < len only (encoder_causal.hip).
  *   Grouped-query attention: K and V have kv_heads heads of 64 (0 = heads); query head h reads K/V head h / (heads / kv_heads) (grouped,
- *   not interleaved).  arch 2 requires pos_type 2, ffn_type 2, head dimension 64, 1 <= kv_heads <= heads with heads % kv_heads == 0,
+ *   not interleaved).  arch 2 requires pos_type 2, ffn_type 2, head dimension 64 (or 128, stated: below), 1 <= kv_heads <= heads with heads % kv_heads == 0,
  *   local_window 0 and global_every <= 1, next to the hidden % 128, ffn % 128 and hidden <= 2048 rules of every model; anything else is
  *   SC_ERR_UNSUPPORTED or SC_ERR_INVALID.  kv_heads != 0 on arch 0 or 1 is SC_ERR_UNSUPPORTED.  The forward runs the stand-alone-norm
  *   pipeline for every batch size (sc_encoder_set_path only decides about split-K).  Pooling: sc_encoder_set_pooling 2 (the last real
  *   token's row) or 0 (masked mean); 1 ([CLS]) is SC_ERR_INVALID.  sc_encoder_score_pairs is SC_ERR_UNSUPPORTED.  Texts stay capped at
- *   2 048 tokens.  Out of scope: head dimension 128 (Qwen3-Embedding, the 1.5B / 7B models), QK-norm, sliding windows. */
+ *   2 048 tokens.
+ *   Heads of 128 (head_dim 128: Qwen3-Embedding-0.6B = 151669 / 1024 / 28 layers / 16 heads, 8 K/V heads of 128 / 3072, qk_norm 1, no q/k/v
+ *   bias; Qwen2.5-1.5B behind jina-code-embeddings-1.5b and gte-Qwen2-1.5B-instruct = 1536 / 28 / 12 heads, 2 K/V heads of 128 / 8960, biases,
+ *   no QK-norm).  head_dim 0 keeps the rule above (hidden / heads, which must be 64); 64 states it; 128 must be stated -- it is never derived
+ *   from hidden / heads -- and then hidden need not equal heads * 128: the attention width AW = heads * head_dim (a multiple of 128, at most
+ *   2 048) is the width of Q and of the attention output, the output projection is [H, AW].  Scores are q.k / sqrt(head_dim); the rotation pairs
+ *   the columns (j, j + head_dim / 2) of a head with the angle p * rope_theta^(-2j / head_dim).  qk_norm 1: Q and K get an RMSNorm over each
+ *   head's head_dim columns BEFORE the rotation (f32 statistics, eps = ln_eps, one gamma [head_dim] for Q and one for K per layer), at either
+ *   head width.  Any other head_dim is SC_ERR_UNSUPPORTED, any other qk_norm SC_ERR_INVALID; a non-zero head_dim or qk_norm on arch 0 or 1 is
+ *   SC_ERR_UNSUPPORTED.  Out of scope: heads of 128 on arch 0 / 1, hidden above 2 048 (Qwen3-Embedding-4B / 8B, the 7B models), sliding windows. */
 typedef struct sc_encoder_cfg {
     int32_t vocab, hidden, layers, heads, ffn, max_pos, type_vocab;
     float ln_eps;
@@ -148,6 +157,8 @@ typedef struct sc_encoder_cfg {
     int32_t global_every;   /* arch 1: layer l is global iff l % global_every == 0; 1 = every layer global; 3 for the released models */
     float rope_theta_local; /* arch 1: rotary base of the local layers (10000); rope_theta is the global layers' (160000); 0 = 10000 */
     int32_t kv_heads;       /* arch 2: K / V heads of the grouped-query attention, a divisor of heads; 0 = heads.  Must be 0 on arch 0, 1 */
+    int32_t head_dim;       /* arch 2: 0 = hidden / heads (must be 64), 64, or 128 (stated; hidden need not be heads * 128).  Must be 0 on arch 0, 1 */
+    int32_t qk_norm;        /* arch 2: 1 = per-head RMSNorm of Q and K before the rotation (Qwen3); 0 = none.  Must be 0 on arch 0, 1 */
 } sc_encoder_cfg;
 
 /* Size in bytes of the f32 weight blob sc_encoder_create expects for cfg.  Blob order (all f32,
@@ -165,7 +176,11 @@ typedef struct sc_encoder_cfg {
  * b2 [H], ln2_gamma [H] (= post_attention_layernorm), ln2_beta [H], then final_norm_gamma [H], final_norm_beta [H].  No embedding norm, no
  * pos_emb, no type_emb.  The beta slots are present and never read (RMSNorm has none); slots of biases a model lacks (Qwen2: bo, b1, b2)
  * hold zeros.  On the device the projection is fused as [Wq; Wk; Wv], N = H + 2 KV (always a multiple of 128), written in 64-column
- * blocks; the rotation covers its first heads + kv_heads blocks. */
+ * blocks; the rotation covers its first heads + kv_heads blocks.
+ * arch 2 with head_dim 128 (or 64 stated), AW = heads * head_dim, KV = kv_heads * head_dim: Wq [AW,H], bq [AW], Wk [KV,H], bk [KV], Wv [KV,H],
+ * bv [KV], Wo [H,AW], bo [H], the rest as above; with qk_norm, q_norm_gamma [head_dim] and k_norm_gamma [head_dim] follow each layer's ln2_beta.
+ * The fused projection stays in 64-column blocks, N = AW + 2 KV: a 128-wide head is two consecutive blocks.  sc_encoder_info reports the
+ * head_dim in use on arch 2 (64 or 128, never 0). */
 sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out);
 /* Replaces EmbeddingProviderFactory.create() loading a model (providers.py:69-100): uploads the
  * weights (converted to bf16 on device).  weights_blob == NULL: synthetic weights 0.02*N(0,1) from
@@ -410,6 +425,18 @@ sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32
  * row of a sequence is finite.  1 <= kv_heads <= heads <= 32 with heads % kv_heads == 0, else SC_ERR_UNSUPPORTED. */
 sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
                                    int32_t kv_heads, int32_t blocked_rows, float* out);
+/* sc_diag_attention_causal_hd: the same with the head dimension stated: 64 (the kernels above) or 128 (attention_causal128_kernel and its
+ * packed form: scores QK^T/sqrt(128), a head two consecutive 64-column blocks).  Columns are x head_dim instead of x 64 throughout; heads *
+ * head_dim <= 2048, else SC_ERR_UNSUPPORTED. */
+sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                      int32_t kv_heads, int32_t head_dim, int32_t blocked_rows, float* out);
+/* sc_diag_qknorm_rope: qknorm_rope_kernel (pos NULL: position = row % S, S a power of two <= 65536) or its packed form (pos [rows], clamped to
+ * max_pos - 1; S then is the table's length, max_pos) on their own.  x [rows, (heads + 2 kv_heads) * head_dim] f32 as [Q | K | V] is rounded to
+ * bf16, laid out in 64-column blocks, processed in place and returned widened in the same row-major form: the first heads + kv_heads heads
+ * normalised (gamma_q / gamma_k [head_dim] non-NULL, both or neither; eps) and rotated (theta, 0 = 10000), the V columns as they went in.
+ * head_dim 64 or 128. */
+sc_status sc_diag_qknorm_rope(sc_runtime* rt, float* x, int32_t rows, int32_t S, const int32_t* pos, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                              float theta, const float* gamma_q, const float* gamma_k, float eps);
 sc_status sc_diag_layernorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, const float* beta, float eps, float* out);
 /* sc_diag_rmsnorm: rmsnorm_kernel, conventions of sc_diag_layernorm: x [tokens,H] -> x * rsqrt(mean(x^2) + eps) * gamma, bf16 rows. */
 sc_status sc_diag_rmsnorm(sc_runtime* rt, const float* x, int32_t tokens, int32_t H, const float* gamma, float eps, float* out);

@@ -40,6 +40,17 @@ class EncoderCfg(C.Structure):
                 ("arch", C.c_int32), ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float),
                 ("kv_heads", C.c_int32)]
 
+    # The fields above are sc_encoder_cfg as it stood when kv_heads was appended; what later models append lives in EncoderCfgFull, the
+    # whole struct.  The library reads and writes sizeof(sc_encoder_cfg) bytes through every sc_encoder_cfg pointer (sc_encoder_info
+    # fills all of it), so an object of the shorter layout must never reach it: constructing EncoderCfg gives the whole struct.
+    def __new__(cls, *args, **kw):
+        return super().__new__(EncoderCfgFull if cls is EncoderCfg else cls, *args, **kw)
+
+
+class EncoderCfgFull(EncoderCfg):
+    """sc_encoder_cfg in full: EncoderCfg's fields, then head_dim and qk_norm (arch 2: Qwen3-Embedding, Qwen2.5-1.5B)."""
+    _fields_ = [("head_dim", C.c_int32), ("qk_norm", C.c_int32)]
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -107,6 +118,10 @@ SIGNATURES = {
     "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_attention_causal": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_attention_causal_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p]),
+    "sc_diag_qknorm_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                         C.c_float]),
     "sc_diag_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
@@ -795,7 +810,7 @@ POOLINGS_QWEN2 = {"mean": 0, "last": 2}  # ... of a qwen2 encoder (arch 2): "las
 def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> EncoderCfg:
     """sc_encoder_cfg of a complete configuration dict (the keys of BERT_BASE plus the architecture switches alibi / rotary / geglu /
     swiglu / rope_theta and, for the pre-LN ModernBERT family, modernbert / local_window / global_every / rope_theta_local; for the causal
-    Qwen2 family, qwen2 / kv_heads)."""
+    Qwen2 / Qwen3 family, qwen2 / kv_heads / head_dim (0, 64 or 128: heads of 128 are stated, never derived) / qk_norm)."""
     if c.get("modernbert") and c.get("qwen2"):
         raise ValueError("encoder configuration: modernbert and qwen2 are two architectures, pick one")
     if c.get("rotary") and c.get("alibi"):
@@ -810,7 +825,7 @@ def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> Encode
                       # pre-norm causal decoder (arch 2, Qwen2): kv_heads K / V heads of the grouped-query attention (0 = heads)
                       arch=2 if c.get("qwen2") else 1 if c.get("modernbert") else 0, local_window=int(c.get("local_window") or 0),
                       global_every=int(c.get("global_every") or 0), rope_theta_local=float(c.get("rope_theta_local") or 0.0),
-                      kv_heads=int(c.get("kv_heads") or 0))
+                      kv_heads=int(c.get("kv_heads") or 0), head_dim=int(c.get("head_dim") or 0), qk_norm=1 if c.get("qk_norm") else 0)
 
 
 class Encoder:
@@ -1285,13 +1300,15 @@ def diag_attention_window(rt: Runtime, qkv, lens, heads: int, local_window: int,
     return out
 
 
-def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: int = 0, starts=None, blocked_rows: int = 0) -> np.ndarray:
-    """The causal grouped-query attention kernels on their own (head dimension 64): a query sees the real keys at or before its own
-    position; query head h reads K / V head h // (heads // kv_heads).  qkv columns are [Q (heads) | K (kv_heads) | V (kv_heads)] x 64.
-    starts None: a rectangle, qkv [B*S, (heads + 2 kv_heads) * 64] -> [B*S, heads * 64].  Else packed rows as diag_attention_packed."""
+def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: int = 0, starts=None, blocked_rows: int = 0, head_dim: int = 64) -> np.ndarray:
+    """The causal grouped-query attention kernels on their own (head dimension 64, or 128 through sc_diag_attention_causal_hd): a query sees
+    the real keys at or before its own position; query head h reads K / V head h // (heads // kv_heads).  qkv columns are
+    [Q (heads) | K (kv_heads) | V (kv_heads)] x head_dim.
+    starts None: a rectangle, qkv [B*S, (heads + 2 kv_heads) * head_dim] -> [B*S, heads * head_dim].  Else packed rows as diag_attention_packed."""
     qkv = _f32(qkv)
     lens = np.ascontiguousarray(lens, np.int32)
-    H, QN = heads * 64, (heads + 2 * kv_heads) * 64
+    head_dim = int(head_dim)
+    H, QN = heads * head_dim, (heads + 2 * kv_heads) * head_dim
     if starts is None:
         rows = len(lens) * int(S)
         R = int(blocked_rows) if blocked_rows else rows
@@ -1303,8 +1320,32 @@ def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: 
     if blocked_rows:
         qkv = block64(qkv)
     out = np.empty((rows, H), np.float32)
+    if head_dim != 64:
+        _check(lib().sc_diag_attention_causal_hd(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
+                                                 int(kv_heads), head_dim, int(blocked_rows), _ptr(out)))
+        return out
     _check(lib().sc_diag_attention_causal(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
                                           int(kv_heads), int(blocked_rows), _ptr(out)))
+    return out
+
+
+def diag_qknorm_rope(rt: Runtime, x, heads: int, kv_heads: int, head_dim: int, S: int, theta: float, pos=None, gamma_q=None, gamma_k=None,
+                     eps: float = 1e-6) -> np.ndarray:
+    """qknorm_rope_kernel (pos None: row r = position r % S) or its packed form (pos [rows]; S = the table's length) on
+    x [rows, (heads + 2 kv_heads) * head_dim] as [Q | K | V]: the Q and K heads RMS-normalised per head (gamma_q, gamma_k [head_dim]; both
+    None: no norm) and rotated, the V columns untouched; everything bf16-rounded."""
+    out = np.array(x, dtype=np.float32, order="C")
+    rows = out.shape[0]
+    if out.shape != (rows, (heads + 2 * kv_heads) * head_dim):
+        raise ValueError("x must be [rows, (heads + 2 kv_heads) * head_dim]")
+    if pos is not None:
+        pos = np.ascontiguousarray(pos, np.int32)
+        if pos.shape != (rows,):
+            raise ValueError("pos must be [rows]")
+    gq = None if gamma_q is None else _f32(gamma_q)
+    gk = None if gamma_k is None else _f32(gamma_k)
+    _check(lib().sc_diag_qknorm_rope(rt.handle, _ptr(out), rows, int(S), None if pos is None else _ptr(pos), int(heads), int(kv_heads), int(head_dim),
+                                     float(theta), None if gq is None else _ptr(gq), None if gk is None else _ptr(gk), float(eps)))
     return out
 
 

@@ -26,6 +26,21 @@
 //   up to 128 keys : segments of 4 tiles,  4 waves,  37 KiB LDS
 //   up to 256 keys : segments of 8 tiles,  8 waves,  73 KiB LDS
 //   longer         : segments of 16 tiles, 8 waves, 137 KiB LDS, one workgroup per 8 query blocks
+//
+// Head dimension 128 (cfg.head_dim 128: Qwen3-Embedding, Qwen2.5-1.5B) has kernels of its own, attention_causal128_kernel /
+// attention_causal128_packed_kernel -- same shell, same rules for tiles, groups of four, masks, grids and bits; a width parameter on the
+// kernels above would have renamed them and risked their text, which stays instruction-identical (profiles/qwen3_kernels.log).  A head is
+// two consecutive 64-column blocks; a key tile is 8 KiB of K and 8 KiB of V, each staged as two of the 64-wide images (low half, high
+// half of the head); a wave holds 8 Q fragments, the score tile of a (query block, key tile) is 8 MFMA steps, the output four 32 x 32 tiles.
+// With 160 KiB of LDS a segment is at most 8 tiles.  Two instantiations:
+//   S or text up to 128 keys : segments of 4 tiles, 4 waves,  72.5 KiB LDS (64 KiB of K / V + 4 x 128 B exchange + 4 x 2 KiB output block),
+//                              204 VGPRs, two workgroups a CU
+//   longer                   : segments of 8 tiles, 8 waves, 145 KiB LDS (128 KiB + 1 KiB + 16 KiB), 249 VGPRs, one workgroup a CU; a text
+//                              beyond 256 keys walks its segments with the state carried along (packed: one item per 8 query blocks, LONG)
+// No scratch in either (the compiler's summary is in profiles/qwen3_kernels.log).
+//   qknorm_rope_kernel              HBM-bound  : the per-head RMSNorm of Q and K (cfg.qk_norm) and the rotate-half rotation in one pass over the
+//   qknorm_rope_packed_kernel                    blocked QKV buffer, head dimension 64 or 128, 16-byte accesses, one rounding to bf16.  The forward
+//                                                calls it when head_dim == 128 or qk_norm; the 64-wide model without QK-norm keeps rope_qk_kernel
 #include "attention_core.h"
 #include "encoder_ops.h"
 #include "encoder_rows.h"  // wave_sum, RectRows / PackedRows, LN_MAXJ
@@ -120,6 +135,174 @@ __global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal_
     len = __builtin_amdgcn_readfirstlane(len);
     const int qb0 = __builtin_amdgcn_readfirstlane(it[2]);
     attention_causal_body<KTS, NW>(qkv, start, len, qb0, (len + 31) >> 5, head, heads, kvh, ctx, blocked, smem);
+}
+
+// ------------------------------------------------------------------ causal attention, head dimension 128
+// attention_causal_body for 128-wide heads (Qwen3-Embedding, Qwen2.5-1.5B).  A head is two consecutive 64-column blocks of the fused
+// projection, row-major or blocked: block j of a row lies at j * bs, bs = 64 elements (row-major) or blocked * 64 (64-column blocks).
+// K and V of a segment are staged as two 64-wide images each (attention_core.h), every image by attention_causal_body's loop.
+template <int KTS, int NW>
+static __device__ __forceinline__ void attention_causal_body128(const bf16_t* __restrict__ qkv, int start, int len, int qb0, int nqb, int head, int heads, int kvh,
+                                                                bf16_t* __restrict__ ctx, int blocked, char* smem) {
+    constexpr int IMG = KTS * 32 * 128;
+    char* Kl = smem;
+    char* Vl = smem + 2 * IMG;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* xch = reinterpret_cast<float*>(smem + 4 * IMG) + w * 32;
+    char* ostg = smem + 4 * IMG + NW * 128 + w * 2048;
+    const int qb = qb0 + w;      // this wave's query block
+    const bool live = qb < nqb;  // wave-uniform
+    const int kvhead = head / (heads / kvh);  // grouped mapping: consecutive query heads share a K / V head
+    const int AW = heads * 128;
+    const int ld = blocked ? 64 : (heads + 2 * kvh) * 128;
+    const size_t bs = blocked ? (size_t)blocked * 64 : 64;  // blocked = the row count (M) of the projection that wrote the blocks
+    const bf16_t* row0 = qkv + (size_t)start * ld;
+    const bf16_t* qbase = row0 + (size_t)(2 * head) * bs;
+    const bf16_t* kbase = row0 + (size_t)(2 * (heads + kvhead)) * bs;
+    const bf16_t* vbase = row0 + (size_t)(2 * (heads + kvh + kvhead)) * bs;
+    const int l31 = lane & 31, hh = lane >> 5;
+    bf16x8 qf[8];
+    if (live) {
+        const bf16_t* qrow = qbase + (size_t)(qb * 32 + l31) * ld;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + (size_t)(ks >> 2) * bs + 16 * (ks & 3) + 8 * hh);
+    }
+    const int nrt = (len + 31) >> 5;                          // key tiles holding at least one real key
+    const int ntw = qb0 + NW < nrt ? qb0 + NW : nrt;          // tiles this workgroup stages: up to its last block's diagonal
+    const int ntq = live ? (qb + 1 < nrt ? qb + 1 : nrt) : 0; // tiles this wave folds: up to its own diagonal
+    const int nseg = (ntw + KTS - 1) / KTS;
+    AttnState128 st;
+    attn_state128_init(st);
+#pragma unroll 1
+    for (int seg = 0; seg < nseg; ++seg) {
+        const int t0 = seg * KTS;
+        const int nst = ntw - t0 < KTS ? ntw - t0 : KTS;  // tiles staged in this segment
+        if (seg) __syncthreads();  // every wave is done with the previous segment's K / V
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {  // the low and the high half of the head
+            for (int piece = w; piece < nst * 4; piece += NW) {  // pieces of 8 rows x 128 B = 1 KiB
+                const int p = piece * 64 + lane;
+                const int r = p >> 3, ck = (p & 7) ^ ((r >> 1) & 7);
+                __builtin_amdgcn_global_load_lds((gbl_vptr)(kbase + e * bs + (size_t)(t0 * 32 + r) * ld + ck * 8), (lds_vptr)(Kl + e * IMG + piece * 1024), 16, 0, 0);
+            }
+            for (int piece = w; piece < nst * 4; piece += NW) {
+                const int p = piece * 64 + lane;
+                const int r = p >> 3, cv = (p & 7) ^ (((r >> 1) & 1) << 2);
+                __builtin_amdgcn_global_load_lds((gbl_vptr)(vbase + e * bs + (size_t)(t0 * 32 + r) * ld + cv * 8), (lds_vptr)(Vl + e * IMG + piece * 1024), 16, 0, 0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        int nt = ntq - t0;
+        nt = nt < 0 ? 0 : (nt > nst ? nst : nt);  // never beyond what was staged
+        nt = __builtin_amdgcn_readfirstlane(nt);
+        if (nt > 0) attention_qblock_causal128<KTS>(qf, Kl, Vl, xch, len, nt, lane, qb * 32, t0 * 32, st);
+    }
+    if (live) attn_state128_store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * AW + head * 128, AW, lane);
+}
+
+template <int KTS, int NW>
+__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal128_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int S, int heads, int kvh,
+                                                                         bf16_t* __restrict__ ctx, int blocked) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int head = blockIdx.x, b = blockIdx.y;
+    int len = lens[b];
+    len = len < 1 ? 1 : (len > S ? S : len);
+    len = __builtin_amdgcn_readfirstlane(len);
+    // the groups of query blocks of a sequence from the last -- the most key tiles -- to the first, as attention_causal_kernel
+    attention_causal_body128<KTS, NW>(qkv, b * S, len, (int)(gridDim.z - 1 - blockIdx.z) * NW, S >> 5, head, heads, kvh, ctx, blocked, smem);
+}
+
+// LONG: the items are groups of 8 query blocks of texts of any length (the class of sc_packed_items whose 64-wide kernel stages 16 tiles):
+// heads fastest, items from the last to the first, for attention_causal_packed_kernel's reasons.  Else one item per text of at most
+// KTS * 32 tokens, the item the fastest index.
+template <int KTS, int NW, bool LONG>
+__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal128_packed_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ items, int nitems,
+                                                                                int heads, int kvh, bf16_t* __restrict__ ctx, int blocked) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int head = LONG ? (int)(blockIdx.x % (unsigned)heads) : (int)(blockIdx.x / (unsigned)nitems);
+    const int32_t* it = items + 4 * (size_t)(LONG ? nitems - 1 - (int)(blockIdx.x / (unsigned)heads) : (int)(blockIdx.x % (unsigned)nitems));
+    const int start = __builtin_amdgcn_readfirstlane(it[0]);
+    int len = it[1];
+    len = len < 1 ? 1 : (len > KTS * 32 && !LONG ? KTS * 32 : len);  // (an item of a short class never holds a longer text)
+    len = __builtin_amdgcn_readfirstlane(len);
+    const int qb0 = __builtin_amdgcn_readfirstlane(it[2]);
+    attention_causal_body128<KTS, NW>(qkv, start, len, qb0, (len + 31) >> 5, head, heads, kvh, ctx, blocked, smem);
+}
+
+// ------------------------------------------------------------------ QK-norm + rotation
+// Per (row, Q or K head) of the blocked QKV buffer [64-column blocks][M][64], in place: optionally RMSNorm over the head's HD values
+// (f32 sum of squares, x * rsqrt(mean + eps) * gamma in f32; Q heads gamma_q, K heads gamma_k), then the rotate-half rotation with the
+// pairs (j, j + HD / 2) and the angle p * theta^(-2j / HD) from the table [max_pos][HD / 2], then ONE rounding to bf16.  HBM-bound: a
+// lane owns 8 columns of the head's low half and the same 8 of its high half (two 16-byte loads, two 16-byte stores), so both members
+// of every pair sit in its registers; HD / 16 lanes per (row, head), their sum of squares combined by 2 or 3 shuffles inside the group.
+// At HD 64 the halves are the two halves of one 128-byte block (rope_qk_rows' ownership), at 128 the same columns of the head's two
+// blocks, M * 64 elements apart.  nq of the nheads heads are Q heads.  Positions as rope_qk_rows gets them.
+template <int HD, bool NORM, class POS>
+static __device__ __forceinline__ void qknorm_rope_rows(bf16_t* __restrict__ qkv, int64_t M, int nheads, int nq, POS pos_of, const float* __restrict__ cos_t,
+                                                        const float* __restrict__ sin_t, const float* __restrict__ gq, const float* __restrict__ gk, float eps) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr int L = HD / 16, HALF = HD / 2;  // lanes per (row, head); columns per half
+    const int64_t total = (int64_t)nheads * M * L;  // a multiple of L: the lanes of a group run, or stop, together
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t vec = i / L;  // head * M + row
+        const int c = (int)(i % L) * 8;
+        const int64_t row = vec % M, head = vec / M;
+        const int p = pos_of(row);
+        bf16_t* vlo = HD == 64 ? qkv + vec * 64 + c : qkv + (2 * head * M + row) * 64 + c;
+        bf16_t* vhi = HD == 64 ? vlo + 32 : vlo + M * 64;
+        const u32x4 lo = *reinterpret_cast<const u32x4*>(vlo), hi = *reinterpret_cast<const u32x4*>(vhi);
+        float a[8], b[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a[2 * k] = __builtin_bit_cast(float, lo[k] << 16);
+            a[2 * k + 1] = __builtin_bit_cast(float, lo[k] & 0xFFFF0000u);
+            b[2 * k] = __builtin_bit_cast(float, hi[k] << 16);
+            b[2 * k + 1] = __builtin_bit_cast(float, hi[k] & 0xFFFF0000u);
+        }
+        if (NORM) {
+            float sq = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sq = fmaf(a[k], a[k], sq);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sq = fmaf(b[k], b[k], sq);
+#pragma unroll
+            for (int off = L / 2; off >= 1; off >>= 1) sq += __shfl_xor(sq, off, 64);
+            const float rstd = 1.0f / sqrtf(sq * (1.0f / (float)HD) + eps);
+            const float* g = head < nq ? gq : gk;
+            const f32x4 g0 = *reinterpret_cast<const f32x4*>(g + c), g1 = *reinterpret_cast<const f32x4*>(g + c + 4);
+            const f32x4 h0 = *reinterpret_cast<const f32x4*>(g + HALF + c), h1 = *reinterpret_cast<const f32x4*>(g + HALF + c + 4);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                a[k] = a[k] * rstd * (k < 4 ? g0[k & 3] : g1[k & 3]);
+                b[k] = b[k] * rstd * (k < 4 ? h0[k & 3] : h1[k & 3]);
+            }
+        }
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(cos_t + (size_t)p * HALF + c), c1 = *reinterpret_cast<const f32x4*>(cos_t + (size_t)p * HALF + c + 4);
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(sin_t + (size_t)p * HALF + c), s1 = *reinterpret_cast<const f32x4*>(sin_t + (size_t)p * HALF + c + 4);
+        u32x4 olo, ohi;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float cc0 = k < 2 ? c0[2 * k] : c1[2 * k - 4], cc1 = k < 2 ? c0[2 * k + 1] : c1[2 * k - 3];
+            const float ss0 = k < 2 ? s0[2 * k] : s1[2 * k - 4], ss1 = k < 2 ? s0[2 * k + 1] : s1[2 * k - 3];
+            olo[k] = pack_bf16x2(fmaf(a[2 * k], cc0, -b[2 * k] * ss0), fmaf(a[2 * k + 1], cc1, -b[2 * k + 1] * ss1));
+            ohi[k] = pack_bf16x2(fmaf(b[2 * k], cc0, a[2 * k] * ss0), fmaf(b[2 * k + 1], cc1, a[2 * k + 1] * ss1));
+        }
+        *reinterpret_cast<u32x4*>(vlo) = olo;
+        *reinterpret_cast<u32x4*>(vhi) = ohi;
+    }
+}
+template <int HD, bool NORM>
+__global__ __launch_bounds__(256) void qknorm_rope_kernel(bf16_t* __restrict__ qkv, int64_t M, int nheads, int nq, int smask, const float* __restrict__ cos_t,
+                                                           const float* __restrict__ sin_t, const float* __restrict__ gq, const float* __restrict__ gk, float eps) {
+    qknorm_rope_rows<HD, NORM>(qkv, M, nheads, nq, PosMasked{smask}, cos_t, sin_t, gq, gk, eps);
+}
+template <int HD, bool NORM>
+__global__ __launch_bounds__(256) void qknorm_rope_packed_kernel(bf16_t* __restrict__ qkv, int64_t M, int nheads, int nq, const int32_t* __restrict__ pos, int max_pos,
+                                                                  const float* __restrict__ cos_t, const float* __restrict__ sin_t, const float* __restrict__ gq,
+                                                                  const float* __restrict__ gk, float eps) {
+    qknorm_rope_rows<HD, NORM>(qkv, M, nheads, nq, PosArray{pos, max_pos}, cos_t, sin_t, gq, gk, eps);
 }
 
 // ------------------------------------------------------------------ RMSNorm
@@ -252,7 +435,47 @@ __global__ __launch_bounds__(256) void last_rows_packed_kernel(const bf16_t* __r
 }
 
 // ------------------------------------------------------------------ launchers
-bool sc_attention_causal_supported(int heads, int kv_heads) { return heads >= 1 && heads * 64 <= 2048 && kv_heads >= 1 && kv_heads <= heads && heads % kv_heads == 0; }
+bool sc_attention_causal_supported(int heads, int kv_heads, int head_dim) {
+    return (head_dim == 64 || head_dim == 128) && heads >= 1 && heads * head_dim <= 2048 && kv_heads >= 1 && kv_heads <= heads && heads % kv_heads == 0;
+}
+
+template <int KTS, int NW>
+static void launch_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kvh, void* ctx, int blocked, hipStream_t s) {
+    const dim3 grid((unsigned)heads, (unsigned)B, (unsigned)((S / 32 + NW - 1) / NW));
+    attn_launch<attention_causal128_kernel<KTS, NW>, attn_lds_bytes128(KTS, NW)>(grid, NW * 64, s, (const bf16_t*)qkv, lens, S, heads, kvh, (bf16_t*)ctx, blocked);
+}
+void sc_launch_attention_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
+    if (S <= 128) launch_causal128<4, 4>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+    else launch_causal128<8, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+}
+void sc_launch_attention_causal128_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
+    attn_packed_classes(items, nitems, [&](auto cls, const int32_t* first, int n) {
+        constexpr int C = decltype(cls)::value, KTS = C == 2 ? 4 : 8, NW = KTS;  // texts beyond 256 tokens and up to 256: 8 tiles; up to 128: 4
+        attn_launch<attention_causal128_packed_kernel<KTS, NW, C == 0>, attn_lds_bytes128(KTS, NW)>(dim3((unsigned)n * (unsigned)heads), NW * 64, s, (const bf16_t*)qkv, first,
+                                                                                                    n, heads, kv_heads, (bf16_t*)ctx, blocked);
+    });
+}
+template <int HD, bool NORM>
+static void launch_qknorm_rope(void* qkv, int64_t M, int nheads, int nq, int S, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t, const float* gq,
+                               const float* gk, float eps, hipStream_t s) {
+    int64_t blocks = ((int64_t)nheads * M * (HD / 16) + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (pos) hipLaunchKernelGGL((qknorm_rope_packed_kernel<HD, NORM>), grid, block, 0, s, (bf16_t*)qkv, M, nheads, nq, pos, max_pos, cos_t, sin_t, gq, gk, eps);
+    else hipLaunchKernelGGL((qknorm_rope_kernel<HD, NORM>), grid, block, 0, s, (bf16_t*)qkv, M, nheads, nq, S - 1, cos_t, sin_t, gq, gk, eps);
+}
+void sc_launch_qknorm_rope(void* qkv, int64_t M, int heads, int kv_heads, int head_dim, int S, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t,
+                           const float* gq, const float* gk, float eps, hipStream_t s) {
+    const int nh = heads + kv_heads;
+    const bool norm = gq != nullptr;
+    if (head_dim == 128) {
+        if (norm) launch_qknorm_rope<128, true>(qkv, M, nh, heads, S, pos, max_pos, cos_t, sin_t, gq, gk, eps, s);
+        else launch_qknorm_rope<128, false>(qkv, M, nh, heads, S, pos, max_pos, cos_t, sin_t, gq, gk, eps, s);
+    } else {
+        if (norm) launch_qknorm_rope<64, true>(qkv, M, nh, heads, S, pos, max_pos, cos_t, sin_t, gq, gk, eps, s);
+        else launch_qknorm_rope<64, false>(qkv, M, nh, heads, S, pos, max_pos, cos_t, sin_t, gq, gk, eps, s);
+    }
+}
 
 template <int KTS, int NW>
 static void launch_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kvh, void* ctx, int blocked, hipStream_t s) {

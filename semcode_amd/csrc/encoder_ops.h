@@ -82,15 +82,23 @@ void sc_launch_attention_window(const void* qkv, const int32_t* lens, int B, int
 void sc_launch_attention_window_packed(const void* qkv, const int32_t* items, const int* nitems, int H, int local_window, void* ctx, hipStream_t s,
                                        int blocked = 0);
 
-// ---- encoder_causal.hip: the causal decoder family (cfg.arch 2).  Causal grouped-query attention, head dimension 64, plain scores: a query
+// ---- encoder_causal.hip: the causal decoder family (cfg.arch 2).  Causal grouped-query attention, head dimension 64 (128 below), plain scores: a query
 // sees the real keys at or before its own position; query head h reads K / V head h / (heads / kv_heads).  qkv rows are
 // [Q (heads) | K (kv_heads) | V (kv_heads)] x 64 columns, row-major (blocked 0) or in 64-column blocks of `blocked` rows; ctx [rows, heads * 64];
 // lens / items as the two attention launchers above.  rmsnorm: x * rsqrt(mean(x^2) + eps) * gamma, bf16 rows, H a multiple of 8, <= 2048.
 // last_pool: the row start + len - 1 of every text (starts NULL: a [B, S] rectangle, lens clamped to 1 .. S) of x [rows, H] bf16, RMSNorm in
 // f32, optional L2 normalisation by the rule of the mean kernels -> out [B, H] f32.
-bool sc_attention_causal_supported(int heads, int kv_heads);
+// Head dimension 128 (the ...128 launchers): a head is two consecutive 64-column blocks, qkv rows are [Q | K | V] x 128 columns, ctx [rows, heads * 128].
+// qknorm_rope: in place on the 64-column blocks [(heads + kv_heads) * head_dim / 64 ...][M][64] of the Q and K heads: RMSNorm over each head's
+// head_dim values when gq / gk [head_dim] are non-NULL (both or neither), then the rotate-half rotation from the tables [max_pos][head_dim / 2].
+// pos NULL: position = row & (S - 1), S a power of two; else pos [M], clamped to max_pos - 1.
+bool sc_attention_causal_supported(int heads, int kv_heads, int head_dim = 64);
 void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
 void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_causal128_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_qknorm_rope(void* qkv, int64_t M, int heads, int kv_heads, int head_dim, int S, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t,
+                           const float* gq, const float* gk, float eps, hipStream_t s);
 void sc_launch_rmsnorm(const void* in, int tokens, int H, const float* g, float eps, void* out, hipStream_t s);
 void sc_launch_last_pool(const void* x, const int32_t* starts, const int32_t* lens, int B, int S, int H, const float* gamma, float eps, int normalize, float* out,
                          hipStream_t s);
@@ -125,5 +133,5 @@ inline int64_t sc_packed_items_cap(int64_t rows, int64_t B) { return B + rows / 
 void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int32_t* items, int nitems[3]);
 
 // ---- sc_encoder.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
-// angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000
-std::vector<float> sc_rope_table(int64_t positions, float theta);
+// angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000.  head_dim 128: [positions][64] each, p * theta^(-2 i / 128)
+std::vector<float> sc_rope_table(int64_t positions, float theta, int head_dim = 64);

@@ -26,10 +26,11 @@
 #include "sc_internal.h"
 
 struct LayerW {
-    void* wqkv;  // bf16 [3H, H]; arch 2: [H + 2 KV, H], KV = kv_heads * 64
-    float* bqkv; // [3H]; arch 2: [H + 2 KV]
-    void* wo;    // bf16 [H, H]
+    void* wqkv;  // bf16 [3H, H]; arch 2: [AW + 2 KV, H], AW = heads * head_dim, KV = kv_heads * head_dim
+    float* bqkv; // [3H]; arch 2: [AW + 2 KV]
+    void* wo;    // bf16 [H, H]; arch 2: [H, AW]
     float* bo;
+    float *qng = nullptr, *kng = nullptr;  // arch 2 with qk_norm: the per-head RMSNorm gammas of Q and K, [head_dim] each
     float *ln1g, *ln1b;
     void* w1;    // bf16 [F, H]
     float* b1;
@@ -50,7 +51,7 @@ struct sc_encoder {
     char* params = nullptr;  // one device allocation holding every parameter
     float *wemb = nullptr, *pemb = nullptr, *temb = nullptr, *embg = nullptr, *embb = nullptr;
     float* slopes = nullptr;  // ALiBi head slopes (device) or NULL
-    float *rope_cos = nullptr, *rope_sin = nullptr;  // rotary positions: [max_pos][32] f32 each (device) or NULL
+    float *rope_cos = nullptr, *rope_sin = nullptr;  // rotary positions: [max_pos][32] f32 each (device) or NULL; arch 2 at head_dim 128: [max_pos][64]
     float *rope_cos_l = nullptr, *rope_sin_l = nullptr;  // arch 1: the table of the local layers (base rope_theta_local); the one above is the global layers'
     float *fing = nullptr, *finb = nullptr;              // arch 1: final_norm gamma / beta
     std::vector<LayerW> layers;
@@ -148,8 +149,11 @@ struct Arena {
 
 // ffn_type 1 (GEGLU) and 2 (SwiGLU): W1 holds gate and up rows, an element-wise kernel sits between the two FFN GEMMs
 static bool ffn_gated(const sc_encoder_cfg& c) { return c.ffn_type == 1 || c.ffn_type == 2; }
-// arch 2: K and V have kv_heads heads of 64 (0 = heads); every other model projects K and V to hidden columns
-static int64_t kv_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)(c.kv_heads > 0 ? c.kv_heads : c.heads) * 64 : (int64_t)c.hidden; }
+// arch 2: heads of 64, or of 128 when cfg.head_dim says so; K and V have kv_heads of them (0 = heads), Q has heads of them -- the attention
+// width AW, which need not be hidden at 128.  Every other model projects Q, K and V to hidden columns
+static int head_width(const sc_encoder_cfg& c) { return c.arch == 2 && c.head_dim == 128 ? 128 : 64; }
+static int64_t kv_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)(c.kv_heads > 0 ? c.kv_heads : c.heads) * head_width(c) : (int64_t)c.hidden; }
+static int64_t attn_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)c.heads * head_width(c) : (int64_t)c.hidden; }
 static void launch_gate(const sc_encoder_cfg& c, const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
     if (c.ffn_type == 2) sc_launch_swiglu(h, tokens, F, out, s);
     else sc_launch_geglu(h, tokens, F, out, s);
@@ -171,9 +175,10 @@ static bool ffn_blocked_enabled() { static const bool on = sc_env_flag("SC_FFN_B
 // number of f32 values in the weight blob, in blob order (see include/semcode_hip.h)
 static int64_t blob_floats(const sc_encoder_cfg& c) {
     const int64_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F;
-    const int64_t KV = kv_width(c);
+    const int64_t KV = kv_width(c), AW = attn_width(c);
     int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch != 0 ? 0 : (int64_t)c.type_vocab * H) + (c.arch == 2 ? 0 : 2 * H);
-    n += (int64_t)c.layers * (2 * (H * H + H) + 2 * (KV * H + KV) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
+    n += (int64_t)c.layers * ((AW * H + AW) + (H * AW + H) + 2 * (KV * H + KV) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
+    if (c.arch == 2 && c.qk_norm) n += (int64_t)c.layers * 2 * head_width(c);  // q_norm, k_norm gammas behind each layer's ln2_beta
     if (c.arch != 0) n += 2 * H;  // final_norm
     return n;
 }
@@ -189,7 +194,8 @@ extern "C" sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* o
 static sc_status check_cfg(const sc_encoder_cfg& c) {
     if (c.vocab < 1 || c.hidden < 1 || c.layers < 1 || c.heads < 1 || c.ffn < 1 || c.max_pos < 1 || c.type_vocab < 1)
         return sc_fail(SC_ERR_INVALID, "sc_encoder_create: non-positive model dimension");
-    if (c.hidden != c.heads * 64 && c.hidden != c.heads * 32)
+    const bool wide = c.arch == 2 && c.head_dim == 128;  // heads of 128 are stated, never derived: hidden need not be heads * 128
+    if (!wide && c.hidden != c.heads * 64 && c.hidden != c.heads * 32)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension must be 64 or 32 (hidden=%d heads=%d)", c.hidden, c.heads);
     if (c.hidden % 128 || c.ffn % 128 || c.hidden > 2048)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: hidden (<=2048) and ffn must be multiples of 128 (got %d, %d)", c.hidden, c.ffn);
@@ -203,9 +209,18 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
         return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT, 2 = causal Qwen2 decoder)", c.arch);
     if (c.arch != 2 && c.kv_heads != 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: kv_heads %d needs arch 2 (grouped-query attention exists in the causal pipeline only)", c.kv_heads);
+    if (c.arch != 2 && c.head_dim != 0)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim %d needs arch 2 (a stated head dimension exists in the causal pipeline only; 0 elsewhere)", c.head_dim);
+    if (c.arch != 2 && c.qk_norm != 0)
+        return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: qk_norm %d needs arch 2 (the per-head RMSNorm of Q and K exists in the causal pipeline only)", c.qk_norm);
     if (c.arch == 2) {
-        // the causal pipeline: rotate-half rotation and the causal kernel are written for 64-wide heads, its gate is SwiGLU
-        if (c.hidden != c.heads * 64)
+        // the causal pipeline: heads of 64 (rope_qk_kernel, attention_causal_kernel) or, stated, of 128 (qknorm_rope_kernel, attention_causal128_kernel); SwiGLU
+        if (c.head_dim != 0 && c.head_dim != 64 && c.head_dim != 128)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim must be 0 (hidden / heads, which must be 64), 64 or 128 on arch 2, got %d", c.head_dim);
+        if (c.qk_norm != 0 && c.qk_norm != 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: qk_norm must be 0 or 1, got %d", c.qk_norm);
+        if (wide && c.heads * 128 > 2048)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim 128 needs heads * 128 <= 2048 (the attention width), got heads %d", c.heads);
+        if (!wide && c.hidden != c.heads * 64)
             return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 needs head dimension 64 (hidden=%d heads=%d)", c.hidden, c.heads);
         if (c.pos_type != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 runs with rotary positions only (pos_type 2), not pos_type %d", c.pos_type);
         if (c.ffn_type != 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 2 runs with the SwiGLU feed-forward only (ffn_type 2), not ffn_type %d", c.ffn_type);
@@ -235,15 +250,16 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
     return SC_OK;
 }
 
-std::vector<float> sc_rope_table(int64_t positions, float theta_arg) {
+std::vector<float> sc_rope_table(int64_t positions, float theta_arg, int head_dim) {
     const double theta = theta_arg > 0.f ? (double)theta_arg : 10000.0;
-    const size_t n = (size_t)positions * 32;
+    const int half = head_dim / 2;
+    const size_t n = (size_t)positions * half;
     std::vector<float> tab(2 * n);
-    for (int i = 0; i < 32; ++i) {
-        const double f = std::pow(theta, -2.0 * i / 64.0);
+    for (int i = 0; i < half; ++i) {
+        const double f = std::pow(theta, -2.0 * i / (double)head_dim);
         for (int64_t p = 0; p < positions; ++p) {
-            tab[(size_t)p * 32 + i] = (float)std::cos((double)p * f);
-            tab[n + (size_t)p * 32 + i] = (float)std::sin((double)p * f);
+            tab[(size_t)p * half + i] = (float)std::cos((double)p * f);
+            tab[n + (size_t)p * half + i] = (float)std::sin((double)p * f);
         }
     }
     return tab;
@@ -268,7 +284,8 @@ static std::vector<float> alibi_slopes(int heads) {
 // the parameter arena: f32 tables + per-layer {bf16 matrices, f32 vectors}; e->layers is sized, e->foldable set
 static void layout_params(sc_encoder* e, Arena& a) {
     const sc_encoder_cfg& c = e->cfg;
-    const size_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F, rope_n = (size_t)c.max_pos * 32, QN = H + 2 * (size_t)kv_width(c);
+    const size_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F, rope_n = (size_t)c.max_pos * (head_width(c) / 2), AW = (size_t)attn_width(c),
+                 QN = AW + 2 * (size_t)kv_width(c);
     e->wemb = a.f32((size_t)c.vocab * H);
     e->pemb = c.pos_type == 0 ? a.f32((size_t)c.max_pos * H) : nullptr;
     e->slopes = c.pos_type == 1 ? a.f32((size_t)c.heads) : nullptr;
@@ -283,7 +300,9 @@ static void layout_params(sc_encoder* e, Arena& a) {
     e->embb = a.f32(H);
     for (LayerW& w : e->layers) {
         w.wqkv = a.bf16(QN * H);    w.bqkv = a.f32(QN);
-        w.wo = a.bf16(H * H);       w.bo = a.f32(H);
+        w.wo = a.bf16(H * AW);      w.bo = a.f32(H);
+        w.qng = c.arch == 2 && c.qk_norm ? a.f32((size_t)head_width(c)) : nullptr;
+        w.kng = c.arch == 2 && c.qk_norm ? a.f32((size_t)head_width(c)) : nullptr;  // (by the configuration: a measuring arena hands out NULL)
         w.ln1g = a.f32(H);          w.ln1b = a.f32(H);
         w.w1 = a.bf16(F1 * H);      w.b1 = a.f32(F1);
         w.w2 = a.bf16(H * F);       w.b2 = a.f32(H);
@@ -311,7 +330,8 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     sc_runtime_retain(rt);
     e->cfg = *cfg;
     if (e->cfg.arch == 2 && e->cfg.kv_heads == 0) e->cfg.kv_heads = e->cfg.heads;  // (sc_encoder_info reports the count in use)
-    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = ffn_gated(*cfg) ? 2 * F : F, KV = kv_width(*cfg);
+    if (e->cfg.arch == 2) e->cfg.head_dim = head_width(*cfg);                       // (... and the head dimension in use: 64 or 128)
+    const int64_t H = cfg->hidden, F = cfg->ffn, L = cfg->layers, F1 = ffn_gated(*cfg) ? 2 * F : F, KV = kv_width(*cfg), AW = attn_width(*cfg), HD = head_width(*cfg);
 
     // staging copy of the f32 blob on device (freed after conversion)
     float* blob = nullptr;
@@ -364,7 +384,7 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     put_f32(e->wemb, take((int64_t)cfg->vocab * H), (int64_t)cfg->vocab * H, COPY);
     if (e->pemb) put_f32(e->pemb, take((int64_t)cfg->max_pos * H), (int64_t)cfg->max_pos * H, COPY);
     if (e->slopes) put_host(e->slopes, alibi_slopes(cfg->heads));
-    if (e->rope_cos) put_host(e->rope_cos, sc_rope_table(cfg->max_pos, cfg->rope_theta));
+    if (e->rope_cos) put_host(e->rope_cos, sc_rope_table(cfg->max_pos, cfg->rope_theta, (int)HD));
     if (e->rope_cos_l) put_host(e->rope_cos_l, sc_rope_table(cfg->max_pos, cfg->rope_theta_local));
     if (cfg->arch != 0) hipMemsetAsync(e->temb, 0, (size_t)H * 4, s);
     else put_f32(e->temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, COPY);
@@ -377,12 +397,12 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
         // blob order: Wq bq Wk bk Wv bv Wo bo ln1g ln1b W1 b1 W2 b2 ln2g ln2b ; device: Wqkv = [Wq; Wk; Wv] (Wk, Wv: KV rows each)
         const float* wqkv_f32[3];
         for (int p = 0; p < 3; ++p) {
-            const int64_t rows = p == 0 ? H : KV, row0 = p == 0 ? 0 : H + (p - 1) * KV;
+            const int64_t rows = p == 0 ? AW : KV, row0 = p == 0 ? 0 : AW + (p - 1) * KV;
             wqkv_f32[p] = take(rows * H);
             put_bf16((char*)w.wqkv + (size_t)row0 * H * 2, wqkv_f32[p], rows * H);
             put_f32(w.bqkv + row0, take(rows), rows, ZEROS);
         }
-        put_bf16(w.wo, take(H * H), H * H);
+        put_bf16(w.wo, take(H * AW), H * AW);
         put_f32(w.bo, take(H), H, ZEROS);
         put_f32(w.ln1g, take(H), H, ONES);
         put_f32(w.ln1b, take(H), H, ZEROS);
@@ -393,6 +413,10 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
         put_f32(w.b2, take(H), H, ZEROS);
         put_f32(w.ln2g, take(H), H, ONES);
         put_f32(w.ln2b, take(H), H, ZEROS);
+        if (w.qng) {
+            put_f32(w.qng, take(HD), HD, ONES);
+            put_f32(w.kng, take(HD), HD, ONES);
+        }
         if (e->foldable) {
             // the LayerNorm in front of this layer: the embeddings' for layer 0, else the previous layer's second one
             const float* gp = l == 0 ? e->embg : e->layers[l - 1].ln2g;
@@ -438,11 +462,12 @@ extern "C" sc_status sc_encoder_destroy(sc_encoder* e) {
 // the workspace for `tokens` token rows and `nb` chunks
 static void layout_ws(sc_encoder* e, Arena& a, size_t tokens, size_t nb) {
     const size_t H = e->cfg.hidden, F = e->cfg.ffn, F1 = ffn_gated(e->cfg) ? 2 * F : F, slots = H / 256;
+    const size_t AW = (size_t)attn_width(e->cfg), QN = AW + 2 * (size_t)kv_width(e->cfg);  // arch 2 at head dimension 128: AW may exceed H, QN 3 H
     e->x = a.bf16(tokens * H);
     e->x1 = a.bf16(tokens * H);
     e->y = a.bf16(tokens * H);
-    e->qkv = a.bf16(tokens * 3 * H);
-    e->ctx = a.bf16(tokens * H);
+    e->qkv = a.bf16(tokens * (QN > 3 * H ? QN : 3 * H));
+    e->ctx = a.bf16(tokens * (AW > H ? AW : H));
     e->hm = a.bf16(tokens * F1);
     e->hg = ffn_gated(e->cfg) ? a.bf16(tokens * F) : nullptr;
     e->ids = (int32_t*)a.take(tokens * 4);
@@ -676,9 +701,10 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
 // The causal decoder forward (cfg.arch 2, the Qwen2 family), on the stand-alone-norm launches for every batch size as the pre-norm forward:
 //   h = bf16(tok_emb[id])                                                 -> x   (the raw embedding kernels, no position table, zero type row)
 //   per layer:  a = RMS_in(h)                                             -> x1
-//               QKV = a [Wq; Wk; Wv]^T + b, N = H + 2 KV in 64-column blocks; the first heads + kv_heads blocks (Q and K) rotated
+//               QKV = a [Wq; Wk; Wv]^T + b, N = AW + 2 KV in 64-column blocks (AW = heads * head_dim: H at heads of 64); the Q and K heads
+//               rotated -- at head_dim 128 or with qk_norm by qknorm_rope_kernel, which first RMS-normalises every Q and K head (qk_norm)
 //               ctx = causal grouped-query attention (encoder_causal.hip)
-//               h = ctx Wo^T + bo + h                                     x -> y
+//               h = ctx Wo^T + bo + h   (Wo [H, AW])                      x -> y
 //               m = RMS_post(h)                                           -> x1
 //               h = (silu(gate) * up)(m W1^T + b1) W2^T + b2 + h          y -> x
 //   pooled = RMS_final of the last real token's row (in f32, inside the pooling kernel), or the masked mean of RMS_final(h)
@@ -687,7 +713,7 @@ static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, co
     const sc_encoder_cfg& c = e->cfg;
     sc_runtime* rt = e->rt;
     hipStream_t s = rt->stream;
-    const int H = c.hidden, F = c.ffn, QN = H + 2 * (int)kv_width(c);
+    const int H = c.hidden, F = c.ffn, AW = (int)attn_width(c), QN = AW + 2 * (int)kv_width(c), HD = head_width(c);
     const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     void* sk = nullptr;
@@ -702,12 +728,16 @@ static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, co
         const LayerW& w = e->layers[l];
         sc_launch_rmsnorm(e->x, tokens, H, w.ln1g, c.ln_eps, e->x1, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.wqkv, H, w.bqkv, nullptr, 0, e->qkv, SC_LDC_BLOCKED64, M, QN, H, s, sk, skb); });
-        launch_rope(e, M, S, pk, s);
+        if (HD == 128 || c.qk_norm)  // per-head RMSNorm of Q and K (qk_norm) and the rotation in one pass; the 64-wide model without it keeps rope_qk_kernel
+            sc_launch_qknorm_rope(e->qkv, M, c.heads, c.kv_heads, HD, S, pk ? pk->pos : nullptr, c.max_pos, e->rope_cos, e->rope_sin, w.qng, w.kng, c.ln_eps, s);
+        else launch_rope(e, M, S, pk, s);
         sc_with_prof(rt, SC_PROF_ATTN, [&] {
-            if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
+            if (HD == 128 && pk) sc_launch_attention_causal128_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
+            else if (HD == 128) sc_launch_attention_causal128(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, e->ctx, s, M);
+            else if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
             else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, e->ctx, s, M);
         });
-        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, H, w.wo, H, w.bo, e->x, H, e->y, H, M, H, H, s, sk, skb); });
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, AW, w.wo, AW, w.bo, e->x, H, e->y, H, M, H, AW, s, sk, skb); });
         sc_launch_rmsnorm(e->y, tokens, H, w.ln2g, c.ln_eps, e->x1, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
         launch_gate(c, e->hm, M, F, e->hg, s);
@@ -787,7 +817,8 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
 static sc_status check_embed_args(sc_encoder* e, const void* ids, const void* lens, int32_t B, int32_t S, const void* out) {
     if (!e || !ids || !lens || !out) return sc_fail(SC_ERR_INVALID, "embed: NULL argument");
     if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "embed: batch %d out of range", B);
-    if (!sc_attention_supported(S, e->cfg.hidden, e->cfg.heads, e->cfg.hidden / e->cfg.heads))
+    // (arch 2: the head width is the configuration's, hidden need not be heads * head_dim -- only the rule for S is asked for)
+    if (e->cfg.arch == 2 ? !sc_attention_supported(S, 64, 1, 64) : !sc_attention_supported(S, e->cfg.hidden, e->cfg.heads, e->cfg.hidden / e->cfg.heads))
         return sc_fail(SC_ERR_UNSUPPORTED, "embed: sequence length %d not in {32,64,128,256,512,1024,2048} (pad on the host)", S);
     if (S > e->cfg.max_pos && e->cfg.pos_type != 1) return sc_fail(SC_ERR_INVALID, "embed: sequence length %d exceeds max_pos %d", S, e->cfg.max_pos);
     return SC_OK;

@@ -420,13 +420,24 @@ extern "C" sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, 
 
 // sc_launch_attention_causal / _packed as the causal forward calls them (starts == NULL: the rectangle form).  qkv rows are
 // [Q (heads) | K (kv_heads) | V (kv_heads)] x 64 columns; out [rows, heads * 64]
+static sc_status diag_attention_causal(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                       int32_t kv_heads, int32_t hd, int32_t blocked_rows, float* out);
 extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
                                               int32_t kv_heads, int32_t blocked_rows, float* out) {
-    const char* who = "sc_diag_attention_causal";
+    return diag_attention_causal("sc_diag_attention_causal", rt, qkv, starts, lens, B, S, heads, kv_heads, 64, blocked_rows, out);
+}
+// ... with the head dimension stated: 64, or 128 (sc_launch_attention_causal128 / _packed); columns x head_dim
+extern "C" sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                                 int32_t kv_heads, int32_t head_dim, int32_t blocked_rows, float* out) {
+    return diag_attention_causal("sc_diag_attention_causal_hd", rt, qkv, starts, lens, B, S, heads, kv_heads, head_dim, blocked_rows, out);
+}
+static sc_status diag_attention_causal(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
+                                       int32_t kv_heads, int32_t hd, int32_t blocked_rows, float* out) {
     if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    if (!sc_attention_causal_supported(heads, kv_heads))
-        return sc_fail(SC_ERR_UNSUPPORTED, "%s: need 1 <= kv_heads <= heads <= 32 with heads %% kv_heads == 0, got heads %d, kv_heads %d", who, heads, kv_heads);
-    const int H = heads * 64, QN = (heads + 2 * kv_heads) * 64;
+    if (!sc_attention_causal_supported(heads, kv_heads, hd))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: need head_dim 64 or 128 and 1 <= kv_heads <= heads <= 2048 / head_dim with heads %% kv_heads == 0, got heads %d, kv_heads %d, head_dim %d",
+                       who, heads, kv_heads, hd);
+    const int H = heads * hd, QN = (heads + 2 * kv_heads) * hd;
     int64_t R = 0, rows_out = 0;
     std::vector<int32_t> items;
     int nitems[3] = {0, 0, 0};
@@ -444,7 +455,7 @@ extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, 
         items.resize((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
         sc_packed_items(starts, lens, B, items.data(), nitems);
     } else {
-        if (!sc_attention_supported(S, H, heads, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
+        if (!sc_attention_supported(S, 64, 1, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
         rows_out = (int64_t)B * S;
         if (blocked_rows && blocked_rows < rows_out) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
         R = blocked_rows ? (int64_t)blocked_rows : rows_out;
@@ -456,9 +467,46 @@ extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, 
     if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
     else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
     SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
-    if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
+    if (hd == 128 && starts) sc_launch_attention_causal128_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
+    else if (hd == 128) sc_launch_attention_causal128(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, dc.p, s, blocked_rows);
+    else if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
     else sc_launch_attention_causal(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, dc.p, s, blocked_rows);
     return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
+}
+
+// qknorm_rope_kernel / qknorm_rope_packed_kernel on their own: x [rows, (heads + 2 kv_heads) * head_dim] f32 as [Q | K | V] -> bf16 in 64-column
+// blocks [N / 64][rows][64], the Q and K heads normalised (gamma_q non-NULL) and rotated in place, everything widened and laid out row-major again
+extern "C" sc_status sc_diag_qknorm_rope(sc_runtime* rt, float* x, int32_t rows, int32_t S, const int32_t* pos, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                         float theta, const float* gamma_q, const float* gamma_k, float eps) {
+    const char* who = "sc_diag_qknorm_rope";
+    if (!rt || !x || rows < 1 || rows > (1 << 24) || (gamma_q == nullptr) != (gamma_k == nullptr)) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (!sc_attention_causal_supported(heads, kv_heads, head_dim))
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: need head_dim 64 or 128 and 1 <= kv_heads <= heads <= 2048 / head_dim with heads %% kv_heads == 0, got heads %d, kv_heads %d, head_dim %d",
+                       who, heads, kv_heads, head_dim);
+    if (S < 1 || S > 65536 || (!pos && (S & (S - 1)))) return sc_fail(SC_ERR_INVALID, "%s: S must be a power of two (the table's length, 1 .. 65536, with pos)", who);
+    if (gamma_q && !(eps > 0.f)) return sc_fail(SC_ERR_INVALID, "%s: eps must be > 0", who);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    const int nb = (heads + 2 * kv_heads) * head_dim / 64;
+    const int64_t n = (int64_t)rows * nb * 64;
+    std::vector<float> blk((size_t)n);
+    const std::vector<float> tab = sc_rope_table(S, theta, head_dim);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int b = 0; b < nb; ++b) memcpy(&blk[((size_t)b * rows + r) * 64], x + ((size_t)r * nb + b) * 64, 256);
+    sc_devbuf fb, db, dt, dp, dgq, dgk;
+    SC_TRY(upload_bf16(blk.data(), n, fb, db, s));
+    SC_TRY(upload(tab.data(), tab.size() * 4, dt, s));
+    if (pos) SC_TRY(upload(pos, (size_t)rows * 4, dp, s));
+    if (gamma_q) {
+        SC_TRY(upload(gamma_q, (size_t)head_dim * 4, dgq, s));
+        SC_TRY(upload(gamma_k, (size_t)head_dim * 4, dgk, s));
+    }
+    sc_launch_qknorm_rope(db.p, rows, heads, kv_heads, head_dim, S, pos ? (const int32_t*)dp.p : nullptr, S, (const float*)dt.p, (const float*)dt.p + tab.size() / 2,
+                          gamma_q ? (const float*)dgq.p : nullptr, gamma_q ? (const float*)dgk.p : nullptr, eps, s);
+    SC_TRY(download_bf16(db.p, n, blk.data(), s));
+    for (int64_t r = 0; r < rows; ++r)
+        for (int b = 0; b < nb; ++b) memcpy(x + ((size_t)r * nb + b) * 64, &blk[((size_t)b * rows + r) * 64], 256);
+    return SC_OK;
 }
 
 // rmsnorm_kernel<3|4|8>: x [tokens,H] -> out [tokens,H] = x * rsqrt(mean(x^2) + eps) * gamma

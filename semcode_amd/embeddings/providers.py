@@ -167,6 +167,9 @@ def modernbert_config_beside(weights: "str | Path | None") -> Optional[dict]:
 # up_proj stacked into W1 = [2F, H], gate rows first.  Blob order: arch 2 of include/semcode_hip.h (beta slots and the bo / b1 / b2 slots are
 # zeros).  Written from the published module layout and checked against transformers' Qwen2Model on seeded weights
 # (scripts/gen_qwen2_fixtures.py); no released checkpoint exists offline, so parity for real files is unpinned.
+# The widths come from the configuration: heads of cfg["head_dim"] (64 without it), q_proj [heads * head_dim, H], o_proj [H, heads * head_dim].
+# Qwen3 (cfg["qk_norm"]): self_attn.q_norm.weight / k_norm.weight [head_dim] go behind each layer's ln2 beta slot; a file that has them under a
+# configuration without qk_norm, or lacks them under one with it, is an error (scripts/gen_qwen3_fixtures.py checks the layout against Qwen3Model).
 def _qwen2_blob(path, tensors: dict, layers: int, cfg: Optional[dict] = None) -> np.ndarray:
     def find(name: str):
         for key in (name, "model." + name):
@@ -186,21 +189,35 @@ def _qwen2_blob(path, tensors: dict, layers: int, cfg: Optional[dict] = None) ->
 
     emb = get("embed_tokens.weight")
     H = emb.shape[1]
+    hd = int((cfg or {}).get("head_dim") or 64)
+    qk_norm = bool((cfg or {}).get("qk_norm"))
+    AW = hd * int(cfg["heads"]) if cfg is not None else H  # the attention width: heads * head_dim, which need not be H at 128
     zeros = np.zeros(H, np.float32)
     parts = [emb.reshape(-1)]
     for l in range(layers):
         q = f"layers.{l}."
         wq, wk, wv = get(q + "self_attn.q_proj.weight"), get(q + "self_attn.k_proj.weight"), get(q + "self_attn.v_proj.weight")
+        wo = get(q + "self_attn.o_proj.weight")
         KV = wk.shape[0]
-        if wq.shape != (H, H) or wk.shape != (KV, H) or wv.shape != (KV, H) or KV % 64:
-            raise ValueError(f"{path}: {q}self_attn q / k / v projections are {wq.shape} / {wk.shape} / {wv.shape}, expected [{H}, {H}] and two [64 * kv_heads, {H}]")
-        if cfg is not None and KV != 64 * int(cfg.get("kv_heads") or cfg["heads"]):
-            raise ValueError(f"{path}: {q}self_attn.k_proj has {KV // 64} heads of 64, the encoder configuration {int(cfg.get('kv_heads') or cfg['heads'])}")
+        if wq.shape != (AW, H) or wk.shape != (KV, H) or wv.shape != (KV, H) or KV % hd or wo.shape != (H, AW):
+            raise ValueError(f"{path}: {q}self_attn q / k / v / o projections are {wq.shape} / {wk.shape} / {wv.shape} / {wo.shape}, expected [{AW}, {H}], "
+                             f"two [{hd} * kv_heads, {H}] and [{H}, {AW}]")
+        if cfg is not None and KV != hd * int(cfg.get("kv_heads") or cfg["heads"]):
+            raise ValueError(f"{path}: {q}self_attn.k_proj has {KV // hd} heads of {hd}, the encoder configuration {int(cfg.get('kv_heads') or cfg['heads'])}")
+        norms = []
+        for name in ("self_attn.q_norm.weight", "self_attn.k_norm.weight"):
+            t = find(q + name)
+            if qk_norm and (t is None or t.shape != (hd,)):
+                raise ValueError(f"{path}: tensor {q + name!r} [{hd}] not found, the encoder configuration says qk_norm")
+            if not qk_norm and t is not None:
+                raise ValueError(f"{path}: unexpected tensor {q + name!r}: the encoder configuration has no qk_norm (a Qwen3 file needs its own config.json)")
+            if qk_norm:
+                norms.append(t.reshape(-1))
         gate, up = get(q + "mlp.gate_proj.weight"), get(q + "mlp.up_proj.weight")
-        parts += [wq.reshape(-1), opt(q + "self_attn.q_proj.bias", H), wk.reshape(-1), opt(q + "self_attn.k_proj.bias", KV), wv.reshape(-1),
-                  opt(q + "self_attn.v_proj.bias", KV), get(q + "self_attn.o_proj.weight").reshape(-1), opt(q + "self_attn.o_proj.bias", H),
+        parts += [wq.reshape(-1), opt(q + "self_attn.q_proj.bias", AW), wk.reshape(-1), opt(q + "self_attn.k_proj.bias", KV), wv.reshape(-1),
+                  opt(q + "self_attn.v_proj.bias", KV), wo.reshape(-1), opt(q + "self_attn.o_proj.bias", H),
                   get(q + "input_layernorm.weight"), zeros, gate.reshape(-1), up.reshape(-1), np.zeros(2 * gate.shape[0], np.float32),
-                  get(q + "mlp.down_proj.weight").reshape(-1), zeros, get(q + "post_attention_layernorm.weight"), zeros]
+                  get(q + "mlp.down_proj.weight").reshape(-1), zeros, get(q + "post_attention_layernorm.weight"), zeros] + norms
     parts += [get("norm.weight"), zeros]
     return np.concatenate(parts)
 
@@ -221,12 +238,46 @@ def qwen2_config(config: "str | Path | dict") -> dict:
         raise ValueError(f"Qwen2 config: use_sliding_window with sliding_window {c.get('sliding_window')} < 2048 is not supported (the causal kernel sees every earlier token)")
     if c.get("hidden_act", "silu") != "silu":
         raise ValueError(f"Qwen2 config: hidden_act {c.get('hidden_act')!r} is not supported (silu only)")
+    out = _qwen_common(c)
+    if int(c.get("head_dim") or out["hidden"] // out["heads"]) == 128:  # Qwen2.5-1.5B: heads of 128 are stated to the library, never derived
+        out["head_dim"] = 128
+    return out
+
+
+def _qwen_common(c: dict) -> dict:
     heads = int(c["num_attention_heads"])
     rp = c.get("rope_parameters") or {}
     return dict(vocab=int(c["vocab_size"]), hidden=int(c["hidden_size"]), layers=int(c["num_hidden_layers"]), heads=heads,
                 kv_heads=int(c.get("num_key_value_heads") or heads), ffn=int(c["intermediate_size"]),
                 max_pos=min(int(c.get("max_position_embeddings", 32768)), 2048), type_vocab=1, ln_eps=float(c.get("rms_norm_eps", 1e-6)), rotary=True,
                 swiglu=True, qwen2=True, rope_theta=float(rp.get("rope_theta", c.get("rope_theta", 10000.0))))
+
+
+def qwen3_config(config: "str | Path | dict") -> dict:
+    """The encoder configuration of a transformers Qwen3 `config.json` (Qwen3-Embedding-0.6B): qwen2_config's fields, `head_dim` from the
+    file (hidden_size / num_attention_heads without it; the 0.6B model states 128 at hidden 1 024), qk_norm=True -- the per-head RMSNorm of Q
+    and K before the rotation -- and attention_bias honoured (the released models have none; a file with biases loads them).  The same
+    max_pos cap and sliding_window refusal; a `layer_types` entry other than "full_attention" is refused by name."""
+    if not isinstance(config, dict):
+        import json
+
+        config = json.loads(Path(config).read_text())
+    c = config
+    if c.get("model_type") != "qwen3":
+        raise ValueError(f"not a Qwen3 configuration (model_type {c.get('model_type')!r})")
+    if c.get("use_sliding_window") and int(c.get("sliding_window") or 0) < 2048:
+        raise ValueError(f"Qwen3 config: use_sliding_window with sliding_window {c.get('sliding_window')} < 2048 is not supported (the causal kernel sees every earlier token)")
+    for kind in c.get("layer_types") or ():
+        if kind != "full_attention":
+            raise ValueError(f"Qwen3 config: layer_types entry {kind!r} is not supported (full_attention only)")
+    if c.get("hidden_act", "silu") != "silu":
+        raise ValueError(f"Qwen3 config: hidden_act {c.get('hidden_act')!r} is not supported (silu only)")
+    out = _qwen_common(c)
+    hd = int(c.get("head_dim") or out["hidden"] // out["heads"])
+    if hd not in (64, 128):
+        raise ValueError(f"Qwen3 config: head_dim {hd} is not supported (64 or 128)")
+    out.update(head_dim=hd, qk_norm=True)
+    return out
 
 
 def qwen2_config_beside(weights: "str | Path | None") -> Optional[dict]:
@@ -239,6 +290,8 @@ def qwen2_config_beside(weights: "str | Path | None") -> Optional[dict]:
     import json
 
     c = json.loads(conf.read_text())
+    if c.get("model_type") == "qwen3":  # a causal directory too: the same pipeline with QK-norm
+        return qwen3_config(c)
     return qwen2_config(c) if c.get("model_type") == "qwen2" else None
 
 
