@@ -115,7 +115,8 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
  *   as for every model (base: 1 152), so ModernBERT-large (ffn 2 624) is refused by that rule.  The forward runs the stand-alone
  *   LayerNorm pipeline for every batch size (sc_encoder_set_path only decides about split-K); a LayerNorm-folded pre-norm pipeline
  *   is a follow-up.  [CLS] pooling runs the whole last layer (the pruned last layer is the post-LN one).  sc_encoder_score_pairs is
- *   SC_ERR_UNSUPPORTED (the family's classifier is dense -> GELU -> LayerNorm -> linear, not pooler + linear).  Texts stay capped at 2 048 tokens.
+ *   SC_ERR_UNSUPPORTED (the family's classifier is dense -> GELU -> LayerNorm -> linear, not pooler + linear: sc_encoder_set_score_head /
+ *   sc_encoder_score_seqs run it).  Texts stay capped at 2 048 tokens.
  *
  * arch 2 (the Qwen2 / Qwen2.5 decoder backbone behind code-embedding models such as jina-code-embeddings-0.5b, gte-Qwen2, KaLM-mini;
  *   0.5B shape = 151936 / 896 / 24 layers / 14 heads, 2 K/V heads / 4864, eps 1e-6, rope_theta 1e6): a pre-norm CAUSAL decoder.
@@ -127,7 +128,8 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
  *   local_window 0 and global_every <= 1, next to the hidden % 128, ffn % 128 and hidden <= 2048 rules of every model; anything else is
  *   SC_ERR_UNSUPPORTED or SC_ERR_INVALID.  kv_heads != 0 on arch 0 or 1 is SC_ERR_UNSUPPORTED.  The forward runs the stand-alone-norm
  *   pipeline for every batch size (sc_encoder_set_path only decides about split-K).  Pooling: sc_encoder_set_pooling 2 (the last real
- *   token's row) or 0 (masked mean); 1 ([CLS]) is SC_ERR_INVALID.  sc_encoder_score_pairs is SC_ERR_UNSUPPORTED.  Texts stay capped at
+ *   token's row) or 0 (masked mean); 1 ([CLS]) is SC_ERR_INVALID.  sc_encoder_score_pairs is SC_ERR_UNSUPPORTED (rerankers of this family:
+ *   sc_encoder_set_score_head / sc_encoder_score_seqs).  Texts stay capped at
  *   2 048 tokens.
  *   Heads of 128 (head_dim 128: Qwen3-Embedding-0.6B = 151669 / 1024 / 28 layers / 16 heads, 8 K/V heads of 128 / 3072, qk_norm 1, no q/k/v
  *   bias; Qwen2.5-1.5B behind jina-code-embeddings-1.5b and gte-Qwen2-1.5B-instruct = 1536 / 28 / 12 heads, 2 K/V heads of 128 / 8960, biases,
@@ -287,6 +289,56 @@ sc_status sc_encoder_set_pair_head(sc_encoder* enc, const float* pooler_w /*[H,H
                                    const float* cls_w /*[num_labels,H]*/, const float* cls_b /*[num_labels]*/, int32_t num_labels);
 sc_status sc_encoder_score_pairs(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, const int32_t* first_lens, int32_t B,
                                  float* out_logits, float* out_cls);
+
+/* Score heads of the other two families (rerankers on ModernBERT and on the Qwen2 / Qwen3 decoders).  New surface next to the pair head:
+ * sc_encoder_set_pair_head / sc_encoder_score_pairs stay as they are on every arch, their refusals on arch 1 and 2 included.
+ * A sequence is ONE packed text the caller built ([CLS] question [SEP] passage [SEP], or a decoder's prompt around query and document);
+ * there are no segment ids -- neither family has a type table.  The forward is the packed forward's, with one choice taken away: a scored
+ * call never takes the split-K GEMMs, which the embedding calls pick, with their factor, by the call's row count (up to 1 024 rows).  Every
+ * GEMM is the 256-tile kernel, whose sums for a row do not depend on the rows around it, so sc_encoder_set_path is accepted and leaves the
+ * logits unchanged; a call of few rows pays for it with GEMMs that fill less of the chip (DESIGN.md has the measured cost).  What else
+ * differs is the row that is pooled and what happens to it:
+ *   the row r [H], f32, NEVER L2-normalised whatever cfg.normalize and sc_encoder_set_pooling say --
+ *     kind 1, pooling 1: final_norm of the text's first row;  pooling 0: the mean of the final_norm rows over the text's real tokens
+ *       (alignment rows and tail rows are never included);
+ *     kind 2 (pooling 2): RMS_final of row start + len - 1, the last real token.
+ *   the head, in f32 from f32 weights kept on the device --
+ *     kind 1 (score_head_kernel):  a_n = sum_k dense_w[n][k] r[k] + dense_b[n];  g_n = gelu_erf(a_n) (the FFN epilogue's erf GELU, |error| <=
+ *       2.5e-7);  mean = (sum_n g_n) / H;  var = (sum_n (g_n - mean)^2) / H -- two passes, the mean first, then centred squares;
+ *       rstd = 1 / sqrt(var + norm_eps);  p_n = (g_n - mean) * rstd * norm_g[n] + norm_b[n];  logit_c = sum_n cls_w[c][n] p_n + cls_b[c].
+ *       Reduction orders: a_n accumulates k in 16-wide stages, k = 16 st + 4 j + c taken by the f32 MFMA of (j, c), even and odd stages in
+ *       two chains added at the end, then the bias.  The three sums over n each run per lane over n = 16 w + 64 t + 4 j + c in (t, c)
+ *       order (squares and classifier terms by fmaf) for the 16 (w, j) lanes of a row, whose partials are added in (w, j) order, w < 4,
+ *       j < 4; cls_b last.  16 rows per workgroup; the activated values never leave the registers between the three passes.
+ *     kind 2 (score_linear_kernel):  logit_c = sum_k cls_w[c][k] r[k] + cls_b[c]; lane j < 64 takes the 4-element pieces j, j + 64, ... in
+ *       ascending order into one fmaf chain, the 64 chains are added by the xor butterfly 32, 16, .. 1; cls_b last.
+ *   No atomics, every order fixed and independent of the batch, in the forward as in the head: a text's logits are the same bits
+ *   whichever batch-mates it has and wherever it stands among them, on every sc_encoder_set_path setting.  What the logits mean is the model's business: logit[0] for one
+ *   label, logit[1] - logit[0] for two -- for a causal LM scored through two vocabulary rows the caller passes (false row, true row).
+ * sc_encoder_set_score_head installs, replaces or (head == NULL) removes the head; the arrays are copied before it returns, and it waits for
+ * the stream before a head goes.  Validation comes first: SC_ERR_UNSUPPORTED on an arch 0 encoder (its head is sc_encoder_set_pair_head's);
+ * SC_ERR_INVALID for a kind other than 1 on arch 1 / 2 on arch 2, a pooling the kind does not have, num_labels outside 1 .. 2, norm_eps
+ * not > 0 (kind 1), a NULL dense_w / norm_g (kind 1) or cls_w, a non-NULL dense / norm array on kind 2 -- the installed head stays.
+ * The head is independent of the pair head's slot and of the embedding calls: those are unaffected by it, and it by them.
+ * sc_encoder_score_seqs: ids / offsets as sc_encoder_embed_packed; out_logits [B,num_labels]; out_rows [B,hidden] (the rows r the head
+ * read) or NULL.  Host pointers; synchronises; shares the two pinned slots and the in-flight rules of the packed calls.  With nothing
+ * launched and nothing changed -- SC_ERR_INVALID: no head installed, a NULL pointer, B outside 1 .. 65536, offsets[0] != 0, a text shorter
+ * than 1 token, longer than 2 048 tokens or than max_pos; SC_ERR_UNSUPPORTED: an arch 0 encoder (sc_encoder_score_pairs), more than
+ * SC_ENCODER_PACKED_MAX_ROWS token rows.
+ * Out of scope: a _dev or asynchronous form, other activations, more than 2 labels, hidden above 2 048, heads on arch 0; sharing the K / V
+ * of a prompt prefix across the pairs of one question (the real lever for decoder rerankers: it needs a new attention launch form) and
+ * pruning the last layer to the scored rows. */
+typedef struct sc_score_head {
+    int32_t kind;        /* 1 = prediction head of the pre-norm family (arch 1 only); 2 = linear head on the last token (arch 2 only) */
+    int32_t pooling;     /* kind 1: 0 = masked mean over the text's real rows, 1 = its first row; kind 2: must be 2 (last real token) */
+    int32_t num_labels;  /* 1 or 2 */
+    float   norm_eps;    /* kind 1 */
+    const float *dense_w /*[H,H]*/, *dense_b /*[H] or NULL*/, *norm_g /*[H]*/, *norm_b /*[H] or NULL*/;   /* kind 1; all NULL on kind 2 */
+    const float *cls_w /*[num_labels,H]*/, *cls_b /*[num_labels] or NULL*/;
+} sc_score_head;
+sc_status sc_encoder_set_score_head(sc_encoder* enc, const sc_score_head* head /* NULL removes */);
+sc_status sc_encoder_score_seqs(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, float* out_logits /*[B,num_labels]*/,
+                                float* out_rows /*[B,H] or NULL*/);
 
 /* ----------------------------------------------------------------- tokenizer ---- */
 typedef struct sc_tokenizer sc_tokenizer;
@@ -456,6 +508,10 @@ sc_status sc_diag_embed_pairs(sc_runtime* rt, int32_t ln, const int32_t* ids, co
                               const float* gamma, const float* beta, float eps, int32_t tokens_pad, int32_t slots, float* rows, float* stats);
 sc_status sc_diag_pair_head(sc_runtime* rt, const float* cls, int32_t B, int32_t H, const float* pooler_w, const float* pooler_b,
                             const float* cls_w, const float* cls_b, int32_t num_labels, float* out_logits);
+/* sc_diag_score_head: the kernels of sc_encoder_set_score_head on f32 data as they are (tests/test_score_head_gpu.py): rows [B,H], the
+ * head's host arrays -> out_logits [B,num_labels].  head->pooling is not read (the rows are given); the other rules of the head hold,
+ * B 1 .. 65536, H a multiple of 16 up to 2 048. */
+sc_status sc_diag_score_head(sc_runtime* rt, const float* rows, int32_t B, int32_t H, const sc_score_head* head, float* out_logits);
 
 /* -------------------------------------------------------------- vector index ---- */
 

@@ -52,6 +52,12 @@ class EncoderCfgFull(EncoderCfg):
     _fields_ = [("head_dim", C.c_int32), ("qk_norm", C.c_int32)]
 
 
+class ScoreHead(C.Structure):
+    """sc_score_head: the score head of an arch 1 (kind 1) or arch 2 (kind 2) reranker; the pointers are host f32 arrays the library copies."""
+    _fields_ = [("kind", C.c_int32), ("pooling", C.c_int32), ("num_labels", C.c_int32), ("norm_eps", C.c_float),
+                ("dense_w", C.c_void_p), ("dense_b", C.c_void_p), ("norm_g", C.c_void_p), ("norm_b", C.c_void_p), ("cls_w", C.c_void_p), ("cls_b", C.c_void_p)]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -87,6 +93,9 @@ SIGNATURES = {
     "sc_encoder_embed_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "sc_encoder_set_pair_head": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32]),
     "sc_encoder_score_pairs": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_encoder_set_score_head": (C.c_int32, [C.c_void_p, C.POINTER(ScoreHead)]),
+    "sc_encoder_score_seqs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_diag_score_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ScoreHead), C.c_void_p]),
     "sc_diag_embed_pairs": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32,
                                                                                                                        C.c_void_p, C.c_void_p]),
     "sc_diag_pair_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
@@ -844,6 +853,7 @@ class Encoder:
         self.hidden = c["hidden"]
         self.max_pos = c["max_pos"]
         self.num_labels = 0  # of the installed pair head (set_pair_head)
+        self.score_labels = 0  # of the installed score head (set_score_head)
         self._h = C.c_void_p()
         need = C.c_int64()
         _check(lib().sc_encoder_blob_bytes(C.byref(self.cfg), C.byref(need)))
@@ -1002,6 +1012,25 @@ class Encoder:
         cls = np.empty((B, self.hidden), dtype=np.float32) if want_cls else None
         _check(lib().sc_encoder_score_pairs(self.handle, _ptr(ids_flat), _ptr(offsets), _ptr(first_lens), B, _ptr(logits), _ptr(cls)))
         return (logits, cls) if want_cls else logits
+
+    # ---- score heads of the ModernBERT (kind 1) and Qwen2 / Qwen3 (kind 2) rerankers: one packed sequence per pair, no segment ids
+    def set_score_head(self, head: "dict | None") -> None:
+        """Install (or replace) the score head; None removes it.  head: see score_head_struct."""
+        if head is None:
+            _check(lib().sc_encoder_set_score_head(self.handle, None))
+            self.score_labels = 0
+            return
+        st, _keep = score_head_struct(head, self.hidden)
+        _check(lib().sc_encoder_set_score_head(self.handle, C.byref(st)))
+        self.score_labels = int(st.num_labels)
+
+    def score_seqs(self, ids_flat, offsets, want_rows: bool = False):
+        """Packed sequences -> logits [B, num_labels] (and, with want_rows, the f32 rows [B, hidden] the head read)."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        logits = np.empty((B, max(1, self.score_labels)), dtype=np.float32)
+        rows = np.empty((B, self.hidden), dtype=np.float32) if want_rows else None
+        _check(lib().sc_encoder_score_seqs(self.handle, _ptr(ids_flat), _ptr(offsets), B, _ptr(logits), _ptr(rows)))
+        return (logits, rows) if want_rows else logits
 
     def embed_ids_dev(self, ids_ptr: int, lens_ptr: int, B: int, S: int, out_ptr: int) -> None:
         _check(lib().sc_encoder_embed_ids_dev(self.handle, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), int(B), int(S), C.c_void_p(out_ptr)))
@@ -1459,4 +1488,37 @@ def diag_pair_head(rt: Runtime, cls, cls_w, cls_b, pooler_w=None, pooler_b=None)
     pooler_b = None if pooler_w is None else _f32(pooler_b)
     out = np.empty((B, nl), np.float32)
     _check(lib().sc_diag_pair_head(rt.handle, _ptr(cls), B, H, _ptr(pooler_w), _ptr(pooler_b), _ptr(cls_w), _ptr(cls_b), nl, _ptr(out)))
+    return out
+
+
+SCORE_POOLING = {"mean": 0, "cls": 1, "last": 2}
+
+
+def score_head_struct(head: dict, hidden: int) -> "tuple[ScoreHead, list]":
+    """head = {kind: 1 | 2, pooling: "mean" | "cls" | "last" (or 0 / 1 / 2), cls_w [num_labels, H], cls_b or None, and for kind 1 dense_w [H, H],
+    dense_b or None, norm_g [H], norm_b or None, norm_eps} -> (sc_score_head, the arrays it points into: keep them alive for the call)."""
+    pooling = head.get("pooling", "last" if head.get("kind") == 2 else "cls")
+    st = ScoreHead(kind=int(head.get("kind", 0)), pooling=int(SCORE_POOLING.get(pooling, pooling)), norm_eps=float(head.get("norm_eps", 0.0)))
+    keep = []
+    for name, shape in (("dense_w", (hidden, hidden)), ("dense_b", (hidden,)), ("norm_g", (hidden,)), ("norm_b", (hidden,)), ("cls_w", (-1, hidden)), ("cls_b", (-1,))):
+        a = head.get(name)
+        if a is None:
+            continue
+        a = _f32(a).reshape(shape)
+        keep.append(a)
+        setattr(st, name, a.ctypes.data)
+    cls_w, cls_b = head.get("cls_w"), head.get("cls_b")
+    st.num_labels = int(head["num_labels"]) if "num_labels" in head else (0 if cls_w is None else int(_f32(cls_w).reshape(-1, hidden).shape[0]))
+    if cls_w is not None and cls_b is not None and _f32(cls_b).size != _f32(cls_w).size // hidden:
+        raise ValueError("cls_w must be [num_labels, hidden] and cls_b [num_labels]")
+    return st, keep
+
+
+def diag_score_head(rt: Runtime, rows, head: dict) -> np.ndarray:
+    """score_head_kernel (kind 1) / score_linear_kernel (kind 2) on rows [B, H] f32 as they are -> logits [B, num_labels]."""
+    rows = _f32(rows)
+    B, H = rows.shape
+    st, _keep = score_head_struct(head, H)
+    out = np.empty((B, max(1, int(st.num_labels))), np.float32)
+    _check(lib().sc_diag_score_head(rt.handle, _ptr(rows), B, H, C.byref(st), _ptr(out)))
     return out

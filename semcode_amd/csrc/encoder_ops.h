@@ -114,6 +114,14 @@ bool sc_pair_head_supported(int H, int num_labels);
 void sc_launch_pair_head(const float* cls, int B, int H, const float* Wp, const float* bp, const float* Wc, const float* bc, int num_labels, float* logits,
                          hipStream_t s);
 
+// ---- encoder_heads.hip: the score heads of the arch 1 / arch 2 rerankers on r [B,H] f32 (device) -> logits [B,num_labels].  Wd non-NULL (kind 1):
+// g = gelu_erf(Wd r + bd), p = LayerNorm(g; gam, bet, eps) with two-pass statistics, logits = Wc p + bc.  Wd NULL (kind 2): logits = Wc r + bc.
+// Wd [H,H], bd / gam / bet [H], Wc [num_labels,H], bc [num_labels] f32 on the device, 16-byte aligned; bd, bet, bc may be NULL (zeros);
+// H a multiple of 16, <= 2048; num_labels 1 or 2; eps > 0.
+bool sc_score_head_supported(int H, int num_labels);
+void sc_launch_score_head(const float* r, int B, int H, const float* Wd, const float* bd, const float* gam, const float* bet, float eps, const float* Wc,
+                          const float* bc, int num_labels, float* logits, hipStream_t s);
+
 // ---- encoder_cls.hip: [CLS] pooling.  starts NULL: text i's first row is i * S (a rectangle), else starts[i] (packed rows).
 // cls_pool: that row of x [rows, H] bf16 -> out [B, H] f32; gamma / beta non-NULL: the rows are raw and are LayerNorm'ed (f32) first; normalize:
 // L2 normalisation by the rule of the mean kernels.  cls_gather: the same rows (optionally LayerNorm'ed) as bf16 [rows_pad, H], rows B .. rows_pad zero.
@@ -131,6 +139,10 @@ void sc_launch_attention_cls(const void* qkv, const int32_t* starts, const int32
 // sc_packed_items_cap(rows, B) items.
 inline int64_t sc_packed_items_cap(int64_t rows, int64_t B) { return B + rows / 256; }
 void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int32_t* items, int nitems[3]);
+
+// ---- sc_encoder.cpp: the rules of a score head, with sc_fail's message under `who`.  arch: the encoder's (0 is refused), or -1 for the kernels
+// alone (sc_diag_score_head: any kind, pooling not read)
+sc_status sc_score_head_check(const sc_score_head* h, int arch, int H, const char* who);
 
 // ---- sc_encoder.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
 // angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000.  head_dim 128: [positions][64] each, p * theta^(-2 i / 128)

@@ -12,6 +12,9 @@
 // biases / LayerNorm parameters / embedding tables f32.
 // Pairs of a cross-encoder (sc_encoder_set_pair_head / sc_encoder_score_pairs) run the packed forward with a segment id per row and
 // take each pair's [CLS] row instead of a mean; the head on those rows is encoder_pairs.hip's.
+// Rerankers of the other two families (sc_encoder_set_score_head / sc_encoder_score_seqs) run the packed forward as it is and pool the row
+// their head reads -- [CLS] or masked mean of final_norm (arch 1), RMS_final of the last token (arch 2), never L2-normalised
+// (PackedLayout::head_pool); the heads on those rows are encoder_heads.hip's.
 // Pre-norm models (cfg.arch 1, ModernBERT): forward_prenorm_locked -- h += Attn(LN(h)), h += MLP(LN(h)) on a raw residual stream, local
 // (sliding-window) attention in the layers with l % global_every != 0 (encoder_window.hip), a rotary table per kind of layer, final_norm.
 // Causal decoders (cfg.arch 2, the Qwen2 family): forward_causal_locked -- the same raw residual stream with RMSNorm, grouped-query causal
@@ -87,6 +90,12 @@ struct sc_encoder {
     float *head_wp = nullptr, *head_bp = nullptr, *head_wc = nullptr, *head_bc = nullptr;
     int head_labels = 0;
     float* logits = nullptr;  // [ws_batch][2] (workspace)
+    // the score head of an arch 1 / arch 2 reranker (sc_encoder_set_score_head), a slot of its own next to the pair head's: one device allocation
+    // dense_w [H,H] | dense_b [H] | norm_g [H] | norm_b [H] | cls_w [labels,H] | cls_b [labels], all f32, an absent array NULL; sh_wc NULL = none
+    char* shead = nullptr;
+    float *sh_wd = nullptr, *sh_bd = nullptr, *sh_g = nullptr, *sh_b = nullptr, *sh_wc = nullptr, *sh_bc = nullptr;
+    int sh_kind = 0, sh_pooling = 0, sh_labels = 0;
+    float sh_eps = 0.f;
     std::mutex mu;
 };
 
@@ -103,6 +112,9 @@ struct PackedLayout {
     // lens the forward gets are ones (pooling then returns the [CLS] row; attention reads the real lengths from its items) and
     // the output is never L2-normalised.  NULL: texts to embed.
     const int32_t* types = nullptr;
+    // sequences of sc_encoder_score_seqs: the pooling of the installed score head (0 mean, 1 first row, 2 last token) instead of the encoder's
+    // mode, and no L2 normalisation.  -1: texts to embed.
+    int head_pool = -1;
 };
 // The plan of one packed call, laid out alike in pinned host staging and in e->plan (M token rows, B sequences): monotone in both, so
 // a call's plan fits the buffer of any larger workspace
@@ -449,6 +461,7 @@ extern "C" sc_status sc_encoder_destroy(sc_encoder* e) {
     hipFree(e->ws);
     hipFree(e->splitk);
     hipFree(e->head);
+    hipFree(e->shead);
     for (auto& slot : e->pin) {
         if (slot.host) hipHostFree(slot.host);
         if (slot.done) hipEventDestroy(slot.done);
@@ -558,7 +571,7 @@ static sc_status cls_last_layer(sc_encoder* e, const LayerW& w, const int32_t* l
     return SC_OK;
 }
 static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
-    if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, pk->types ? 0 : e->cfg.normalize, out_dev, s);
+    if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, pk->types || pk->head_pool >= 0 ? 0 : e->cfg.normalize, out_dev, s);
     else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, e->cfg.normalize, out_dev, s);
 }
 
@@ -661,7 +674,10 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
     const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     void* sk = nullptr;
-    if (M <= 1024 && e->path != 1) {
+    const bool scored = pk && pk->head_pool >= 0;  // the row a score head reads: its own pooling, never L2-normalised
+    // A scored call (sc_encoder_score_seqs) never splits K: the split and its factor follow the call's row count, and a pair's logits must be
+    // the same bits whichever batch-mates it has.  Every GEMM is then the 256-tile kernel, whose sums for a row do not depend on M.
+    if (M <= 1024 && e->path != 1 && !scored) {
         if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
         sk = e->splitk;
     }
@@ -688,8 +704,8 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
         launch_gate(c, e->hm, M, F, e->hg, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
     }
-    if (cls_pooling(e, pk)) {
-        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, e->fing, e->finb, c.ln_eps, c.normalize, out_dev, s);
+    if (scored ? pk->head_pool == 1 : cls_pooling(e, pk)) {
+        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, e->fing, e->finb, c.ln_eps, scored ? 0 : c.normalize, out_dev, s);
     } else {
         sc_launch_layernorm(e->x, tokens, H, e->fing, e->finb, c.ln_eps, e->x1, s);
         launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
@@ -717,7 +733,9 @@ static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, co
     const int tokens = pk ? pk->rows : B * S;
     const int M = (tokens + 255) / 256 * 256;
     void* sk = nullptr;
-    if (M <= 1024 && e->path != 1) {
+    const bool scored = pk && pk->head_pool >= 0;  // the row a score head reads: the last token's, never L2-normalised
+    // no split-K for a scored call, as in the pre-norm forward
+    if (M <= 1024 && e->path != 1 && !scored) {
         if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
         sk = e->splitk;
     }
@@ -743,8 +761,8 @@ static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, co
         launch_gate(c, e->hm, M, F, e->hg, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
     }
-    if (e->pooling == 2) {
-        sc_launch_last_pool(e->x, pk ? pk->starts : nullptr, lens_dev, B, S, H, e->fing, c.ln_eps, c.normalize, out_dev, s);
+    if (scored || e->pooling == 2) {
+        sc_launch_last_pool(e->x, pk ? pk->starts : nullptr, lens_dev, B, S, H, e->fing, c.ln_eps, scored ? 0 : c.normalize, out_dev, s);
     } else {
         sc_launch_rmsnorm(e->x, tokens, H, e->fing, c.ln_eps, e->x1, s);
         launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
@@ -979,8 +997,9 @@ extern "C" sc_status sc_encoder_packed_rows(sc_encoder* e, const int64_t* offset
 // offsets (`used` = check_packed_offsets' row count); nothing is synchronised.
 // first_lens (NULL or [B], validated): the batch holds the pairs of a cross-encoder -- the first first_lens[i] rows of pair i take segment
 // id 0, the rest of the pair 1, and e->pooled receives the last hidden state of every pair's first row.
+// head_pool >= 0 (sc_encoder_score_seqs): e->pooled receives the rows the score head reads (PackedLayout::head_pool).
 static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, int64_t used, sc_encoder::PinSlot& slot,
-                                     const int64_t* index_rows, const int64_t** rows_out, const int32_t* first_lens = nullptr) {
+                                     const int64_t* index_rows, const int64_t** rows_out, const int32_t* first_lens = nullptr, int head_pool = -1) {
     const int64_t M = (used + 255) / 256 * 256;
     const PlanOffsets po((size_t)M, (size_t)B, first_lens != nullptr);
     sc_status st = pin_slot_reserve(slot, po.total + (size_t)B * 8);
@@ -1025,6 +1044,7 @@ static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const in
     pk.items = (const int32_t*)(e->plan + po.items);
     pk.rows = (int)used;
     if (first_lens) pk.types = (const int32_t*)(e->plan + po.types);
+    pk.head_pool = head_pool;
     return forward_locked(e, (const int32_t*)(e->plan + po.ids), (const int32_t*)(e->plan + (first_lens ? po.ones : po.lens)), B, 0, e->pooled, &pk);
 }
 
@@ -1199,6 +1219,121 @@ extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, c
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(out_logits, e->logits, (size_t)B * nl * 4, hipMemcpyDeviceToHost, s));
     if (out_cls) SC_HIP(hipMemcpyAsync(out_cls, e->pooled, (size_t)B * H * 4, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------ score heads of the arch 1 / arch 2 rerankers
+// arch: the encoder's, or -1 (sc_diag_score_head: the kernels alone, any kind, pooling not read)
+sc_status sc_score_head_check(const sc_score_head* h, int arch, int H, const char* who) {
+    if (arch == 0)
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 0 (post-LN BERT family) models take the pooler + linear head of sc_encoder_set_pair_head / sc_encoder_score_pairs", who);
+    if (h->kind != 1 && h->kind != 2)
+        return sc_fail(SC_ERR_INVALID, "%s: unknown kind %d (1 = prediction head of the pre-norm family, 2 = linear head on the last token)", who, h->kind);
+    if (arch > 0 && h->kind != arch)
+        return sc_fail(SC_ERR_INVALID, "%s: kind %d needs an arch %d encoder, this one is arch %d (kind 1: arch 1, kind 2: arch 2)", who, h->kind, h->kind, arch);
+    if (arch > 0 && h->kind == 1 && h->pooling != 0 && h->pooling != 1)
+        return sc_fail(SC_ERR_INVALID, "%s: pooling %d is not valid for kind 1 (0 = masked mean, 1 = the first row)", who, h->pooling);
+    if (arch > 0 && h->kind == 2 && h->pooling != 2) return sc_fail(SC_ERR_INVALID, "%s: pooling %d is not valid for kind 2 (must be 2, the last real token)", who, h->pooling);
+    if (h->num_labels < 1 || h->num_labels > 2) return sc_fail(SC_ERR_INVALID, "%s: num_labels %d outside 1 .. 2", who, h->num_labels);
+    if (!h->cls_w) return sc_fail(SC_ERR_INVALID, "%s: cls_w is NULL", who);
+    if (h->kind == 1) {
+        if (!h->dense_w) return sc_fail(SC_ERR_INVALID, "%s: dense_w is NULL (kind 1)", who);
+        if (!h->norm_g) return sc_fail(SC_ERR_INVALID, "%s: norm_g is NULL (kind 1)", who);
+        if (!(h->norm_eps > 0.f)) return sc_fail(SC_ERR_INVALID, "%s: norm_eps must be > 0 (kind 1), got %g", who, (double)h->norm_eps);
+    } else if (h->dense_w || h->dense_b || h->norm_g || h->norm_b) {
+        return sc_fail(SC_ERR_INVALID, "%s: dense_w / dense_b / norm_g / norm_b must be NULL on kind 2 (a linear head)", who);
+    }
+    if (!sc_score_head_supported(H, h->num_labels)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: hidden %d must be a multiple of 16, at most 2048", who, H);
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_set_score_head(sc_encoder* e, const sc_score_head* h) {
+    const char* who = "sc_encoder_set_score_head";
+    if (!e) return sc_fail(SC_ERR_INVALID, "%s: NULL encoder", who);
+    const size_t H = (size_t)e->cfg.hidden;
+    if (h) {
+        sc_status st = sc_score_head_check(h, e->cfg.arch, (int)H, who);
+        if (st) return st;
+    }
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    hipStream_t s = e->rt->stream;
+    char* fresh = nullptr;
+    Arena a;
+    float *wd = nullptr, *bd = nullptr, *ng = nullptr, *nb = nullptr, *wc = nullptr, *bc = nullptr;
+    auto lay = [&] {
+        wd = h->dense_w ? a.f32(H * H) : nullptr;
+        bd = h->dense_b ? a.f32(H) : nullptr;
+        ng = h->norm_g ? a.f32(H) : nullptr;
+        nb = h->norm_b ? a.f32(H) : nullptr;
+        wc = a.f32((size_t)h->num_labels * H);
+        bc = h->cls_b ? a.f32((size_t)h->num_labels) : nullptr;
+    };
+    if (h) {
+        lay();  // measure
+        hipError_t he = hipMalloc((void**)&fresh, a.used);
+        if (he != hipSuccess) return sc_fail(SC_ERR_NOMEM, "hipMalloc score head (%zu B) failed: %s", a.used, hipGetErrorString(he));
+        a = Arena{fresh};
+        lay();  // place
+        hipError_t up = hipSuccess;
+        auto put = [&](float* d, const float* src, size_t n) {
+            if (d && up == hipSuccess) up = hipMemcpyAsync(d, src, n * 4, hipMemcpyHostToDevice, s);
+        };
+        put(wd, h->dense_w, H * H);
+        put(bd, h->dense_b, H);
+        put(ng, h->norm_g, H);
+        put(nb, h->norm_b, H);
+        put(wc, h->cls_w, (size_t)h->num_labels * H);
+        put(bc, h->cls_b, (size_t)h->num_labels);
+        if (up == hipSuccess) up = hipStreamSynchronize(s);  // the caller's arrays are free on return, and nothing still reads the head that goes
+        if (up != hipSuccess) {
+            hipFree(fresh);
+            return sc_fail(SC_ERR_HIP, "score head upload failed: %s", hipGetErrorString(up));
+        }
+    } else {
+        SC_HIP(hipStreamSynchronize(s));  // nothing may still read the head that goes
+    }
+    hipFree(e->shead);
+    e->shead = fresh;
+    e->sh_wd = wd;
+    e->sh_bd = bd;
+    e->sh_g = ng;
+    e->sh_b = nb;
+    e->sh_wc = h ? wc : nullptr;
+    e->sh_bc = bc;
+    e->sh_kind = h ? h->kind : 0;
+    e->sh_pooling = h ? h->pooling : 0;
+    e->sh_labels = h ? h->num_labels : 0;
+    e->sh_eps = h ? h->norm_eps : 0.f;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_score_seqs(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, float* out_logits, float* out_rows) {
+    const char* who = "sc_encoder_score_seqs";
+    if (!e || !ids || !offsets || !out_logits) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (e->cfg.arch == 0)
+        return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 0 (post-LN BERT family) models score pairs through sc_encoder_set_pair_head / sc_encoder_score_pairs", who);
+    int64_t used = 0;
+    sc_status st = check_packed_offsets(e, offsets, B, who, &used);
+    if (st) return st;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->sh_wc) return sc_fail(SC_ERR_INVALID, "%s: no score head installed (sc_encoder_set_score_head)", who);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);
+    if (st) return st;
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, nullptr, nullptr, nullptr, e->sh_pooling);
+    hipStream_t s = e->rt->stream;
+    if (st) {
+        hipStreamSynchronize(s);  // the slot's upload may be in flight
+        return st;
+    }
+    const int H = e->cfg.hidden, nl = e->sh_labels;
+    sc_launch_score_head(e->pooled, B, H, e->sh_wd, e->sh_bd, e->sh_g, e->sh_b, e->sh_eps, e->sh_wc, e->sh_bc, nl, e->logits, s);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(out_logits, e->logits, (size_t)B * nl * 4, hipMemcpyDeviceToHost, s));
+    if (out_rows) SC_HIP(hipMemcpyAsync(out_rows, e->pooled, (size_t)B * H * 4, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }

@@ -702,3 +702,25 @@ extern "C" sc_status sc_diag_pair_head(sc_runtime* rt, const float* cls, int32_t
                         (const float*)dbc.p, num_labels, (float*)dout.p, s);
     return download(dout.p, (size_t)B * num_labels * 4, out_logits, s);
 }
+
+// score_head_kernel / score_linear_kernel on host f32 data, as they are: rows [B,H] and the head's arrays -> out_logits [B,num_labels].
+extern "C" sc_status sc_diag_score_head(sc_runtime* rt, const float* rows, int32_t B, int32_t H, const sc_score_head* h, float* out_logits) {
+    if (!rt || !rows || !h || !out_logits) return sc_fail(SC_ERR_INVALID, "sc_diag_score_head: NULL argument");
+    if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "sc_diag_score_head: batch %d out of range", B);
+    SC_TRY(sc_score_head_check(h, -1, H, "sc_diag_score_head"));
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    const int nl = h->num_labels;
+    sc_devbuf dx, dwd, dbd, dg, db, dwc, dbc, dout;
+    SC_TRY(upload(rows, (size_t)B * H * 4, dx, s));
+    if (h->dense_w) SC_TRY(upload(h->dense_w, (size_t)H * H * 4, dwd, s));
+    if (h->dense_b) SC_TRY(upload(h->dense_b, (size_t)H * 4, dbd, s));
+    if (h->norm_g) SC_TRY(upload(h->norm_g, (size_t)H * 4, dg, s));
+    if (h->norm_b) SC_TRY(upload(h->norm_b, (size_t)H * 4, db, s));
+    SC_TRY(upload(h->cls_w, (size_t)nl * H * 4, dwc, s));
+    if (h->cls_b) SC_TRY(upload(h->cls_b, (size_t)nl * 4, dbc, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * nl * 4, s));
+    sc_launch_score_head((const float*)dx.p, B, H, (const float*)dwd.p, (const float*)dbd.p, (const float*)dg.p, (const float*)db.p, h->norm_eps, (const float*)dwc.p,
+                         (const float*)dbc.p, nl, (float*)dout.p, s);
+    return download(dout.p, (size_t)B * nl * 4, out_logits, s);
+}

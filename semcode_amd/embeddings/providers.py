@@ -709,12 +709,21 @@ class EmbeddingProviderFactory:
 
 
 def create_reranker(model: "str | None" = None, **kwargs: Any) -> Any:
-    """The cross-encoder for `Retriever(reranker=...)`: an MI355XReranker on settings.mi355x_reranker_path (or `model`), None when
+    """The cross-encoder for `Retriever(reranker=...)`: an MI355XReranker on settings.mi355x_reranker_path (or `model`) -- a `.safetensors`
+    file of a BERT cross-encoder, or a directory of a ModernBERT / Qwen2 / Qwen3 reranker --, None when
     neither is set -- reranking is opt-in, the reference's pipeline has no such stage."""
-    path = model or getattr(_resolve_settings(), "mi355x_reranker_path", None)
+    settings = _resolve_settings()
+    path = model or getattr(settings, "mi355x_reranker_path", None)
     if not path:
         return None
-    from .reranker import MI355XReranker
+    from . import reranker
 
-    log.info("initializing_mi355x_reranker model=%s", path)
-    return MI355XReranker(path, **kwargs)
+    if Path(path).is_dir():  # a transformers directory: a ModernBERT or Qwen2 / Qwen3 reranker, its prompt and score tokens from the settings
+        for key, name in (("instruction", "mi355x_reranker_instruction"), ("true_token", "mi355x_reranker_true_token"), ("false_token", "mi355x_reranker_false_token")):
+            value = getattr(settings, name, None)
+            if value and key not in kwargs:
+                kwargs[key] = value
+        log.info("initializing_mi355x_reranker directory=%s", path)
+    else:
+        log.info("initializing_mi355x_reranker model=%s", path)
+    return reranker.MI355XReranker(path, **kwargs)

@@ -162,6 +162,10 @@ class HFTokenizer:
             ids = ids[: max_tokens - 1] + [ids[-1]] if self._closes and max_tokens >= 2 else ids[:max_tokens]
         return list(ids)
 
+    def encode_plain(self, text: str) -> List[int]:
+        """ids of the text alone, without the post-processor's special tokens and uncut: a decoder reranker's prompt spells its own"""
+        return list(self._tok.encode(text, add_special_tokens=False).ids)
+
 
 def bucket_for(n: int, max_tokens: int = 512) -> int:
     for b in SEQ_BUCKETS:
