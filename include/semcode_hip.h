@@ -477,7 +477,7 @@ sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32
  * row of a sequence is finite.  1 <= kv_heads <= heads <= 32 with heads % kv_heads == 0, else SC_ERR_UNSUPPORTED. */
 sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
                                    int32_t kv_heads, int32_t blocked_rows, float* out);
-/* sc_diag_attention_causal_hd: the same with the head dimension stated: 64 (the kernels above) or 128 (attention_causal128_kernel and its
+/* sc_diag_attention_causal_hd: the same with the head dimension stated: 64 (the kernels above) or 128 (attention_causal_kernel<2, ..> and its
  * packed form: scores QK^T/sqrt(128), a head two consecutive 64-column blocks).  Columns are x head_dim instead of x 64 throughout; heads *
  * head_dim <= 2048, else SC_ERR_UNSUPPORTED. */
 sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,

@@ -8,12 +8,14 @@ profiles/encoder_split_ab.log; scripts/ab_encoder.sh drives it).  One process pe
     python scripts/ab_encoder.py speed DIR                  DIR/run_<i>_{new,base}.log + DIR/out_<i>_*/embed_pooled.npy of the bench runs:
                                                             outputs bit for bit, medians; the new build passes if its median is not
                                                             below the parent's by more than the parent's spread (max - min)
-    python scripts/ab_encoder.py attn LIB.so OUT.json       time per launch of the attention kernels on the MiniLM and ModernBERT shapes
+    python scripts/ab_encoder.py attn LIB.so OUT.json [ONLY]  time per launch of the attention kernels on the MiniLM, ModernBERT and causal
+                                                            shapes (ONLY: the workloads whose name starts with it, e.g. causal)
     python scripts/ab_encoder.py attnspeed DIR              DIR/attn_<i>_{new,base}.json of such runs: the same rule per workload
 
 Encoders: BERT, jina (ALiBi + GEGLU), nomic (rotary + SwiGLU, rope_fused 0 and 1) x {hidden 256 / ffn 512 (foldable), hidden 128 /
 ffn 384 (128-tile path)} x normalize {0, 1} x (B, S) {(2, 32), (5, 256)} (256 and 1 280 token rows: either side of the 1 024-row
-pipeline switch) x set_path {auto, batch, small}.  Then every instantiation of the attention kernels on its own (attention_section).
+pipeline switch) x set_path {auto, batch, small}.  Then every instantiation of the attention kernels on its own (attention_section,
+causal_section).
 """
 import hashlib
 import sys
@@ -82,6 +84,33 @@ def attention_section(nv, rt, rng):
             out.append(line(f"attn packed {form} blocked={blocked}", nv.diag_attention_packed(rt, qkv, starts, lens, blocked_rows=blocked, **kw)))
         for lw in (128, 6):
             out.append(line(f"attn window packed lw={lw} blocked={blocked}", nv.diag_attention_window(rt, qkv, lens, 2, lw, starts=starts, blocked_rows=blocked)))
+    return out
+
+
+def causal_section(nv, rt, rng):
+    """Every instantiation of the causal attention kernels on its own (written for the head width as a template parameter of those
+    kernels: profiles/causal_width_ab.log), head_dim 64 and 128, heads / kv_heads (2, 1) and (4, 2).  Rectangles: lens {S, S - 23, 1}
+    (2 048: 1 100 and 33 tokens, segments carried along); packed: lens on both sides of the launch classes; row-major and blocked."""
+    out = []
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    ceil256 = lambda n: (n + 255) // 256 * 256
+    rects = [(S, [S, S - 23, 1]) for S in (32, 64, 128, 256, 512)] + [(2048, [1100, 33])]
+    plens = np.array([1, 32, 33, 127, 128, 129, 255, 256, 257, 513, 1100], np.int32)
+    prows = (plens + 31) // 32 * 32
+    pstarts = (np.cumsum(prows) - prows).astype(np.int32)
+    R = ceil256(int(prows.sum()))
+    for hd in (64, 128):
+        for heads, kvh in ((2, 1), (4, 2)):
+            QN, tag = (heads + 2 * kvh) * hd, f"hd={hd} heads={heads}/{kvh}"
+            for S, lens in rects:
+                B, lens = len(lens), np.array(lens, np.int32)
+                qkv = f(B * S, QN)
+                for blocked in (0, ceil256(B * S)):
+                    padded = np.concatenate([qkv, np.zeros((blocked - B * S, QN), np.float32)]) if blocked else qkv
+                    out.append(line(f"causal rect S={S} {tag} blocked={blocked}", nv.diag_attention_causal(rt, padded, lens, heads, kvh, S=S, blocked_rows=blocked, head_dim=hd)))
+            qkv = f(R, QN)
+            for blocked in (0, R):
+                out.append(line(f"causal packed {tag} blocked={blocked}", nv.diag_attention_causal(rt, qkv, plens, heads, kvh, starts=pstarts, blocked_rows=blocked, head_dim=hd)))
     return out
 
 
@@ -155,6 +184,7 @@ def dump(lib_path, out_path):
     out.append(line("embed raw stats", st))
     out.append(line("embed ln", nv.diag_embed(rt, ids, wemb, None, temb, 64, ln=(gamma, beta, 1e-12))))
     out += attention_section(nv, rt, np.random.default_rng(7))
+    out += causal_section(nv, rt, np.random.default_rng(8))
     rt.close()
     Path(out_path).write_text("\n".join(out) + "\n")
     print(f"{len(out)} arrays -> {out_path}")
@@ -202,11 +232,13 @@ def speed(dirname):
     return 0 if ok else 1
 
 
-def attn(lib_path, out_path):
+def attn(lib_path, out_path, only=""):
     """Time per launch of the attention profiling class (3), as scripts/bench_modernbert.py brackets it, on the shapes of
     scripts/bench_minilm.py (384 hidden, 256 texts of 256 tokens, heads of 32 and of 64) and of scripts/bench_modernbert.py (32k tokens
-    as texts of 256 / 1 024 / 2 048, the windowed and the all-global model), padded and packed, and on rectangles of every other
-    length with heads of 32 (64k tokens): one JSON line per workload."""
+    as texts of 256 / 1 024 / 2 048, the windowed and the all-global model), padded and packed, on rectangles of every other
+    length with heads of 32 (64k tokens), and on the causal shapes of scripts/bench_qwen3.py (W64: 32 / 16 heads of 64, W128: 16 / 8
+    heads of 128; 2 layers, only the attention class is timed; 32k tokens as texts of 128 / 256 / 1 024 / 2 048 -- every causal
+    instantiation of both widths): one JSON line per workload.  only: the workloads whose model name starts with it."""
     import json
 
     nv = use_library(lib_path)
@@ -219,12 +251,17 @@ def attn(lib_path, out_path):
               "modernbert windowed": (modern, (256, 1024, 2048)), "modernbert global": (dict(modern, global_every=1), (256, 1024, 2048)),
               # the other rectangle kernels of the 32-wide heads (S = 256 is above): 64 rows of tokens per text length
               "minilm d32 rect": (dict(mini, heads=12, max_pos=2048), (32, 64, 128, 512, 1024, 2048))}
+    causal = dict(vocab=1024, layers=2, ffn=3072, max_pos=2048, type_vocab=1, ln_eps=1e-6, rotary=True, swiglu=True, qwen2=True, rope_theta=1000000.0)
+    models["causal d64"] = (dict(causal, hidden=2048, heads=32, kv_heads=16), (128, 256, 1024, 2048))
+    models["causal d128"] = (dict(causal, hidden=1024, heads=16, kv_heads=8, head_dim=128, qk_norm=True), (128, 256, 1024, 2048))
     out = []
     for name, (cfg, lengths) in models.items():
-        enc = nv.Encoder(rt, cfg, weights=None, synth_seed=1)
+        if not name.startswith(only):
+            continue
+        enc = nv.Encoder(rt, cfg, weights=None, synth_seed=1, **(dict(pooling="last") if name.startswith("causal") else {}))
         for S in lengths:
             B = 65536 // S if name.endswith("rect") else (256 if name.startswith("minilm") else 32768 // S)
-            ids, lens = rng.integers(1, 30000, size=(B, S)).astype(np.int32), np.full(B, S, np.int32)
+            ids, lens = rng.integers(1, min(30000, cfg["vocab"]), size=(B, S)).astype(np.int32), np.full(B, S, np.int32)
             flat, offsets = ids.reshape(-1), (np.arange(B + 1) * S).astype(np.int64)
             for form, call in (("padded", lambda: enc.embed_ids(ids, lens)), ("packed", lambda: enc.embed_packed(flat, offsets)))[: 1 if name.endswith("rect") else 2]:
                 call()  # warm-up: workspace, first touch
@@ -266,8 +303,8 @@ def attnspeed(dirname):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "attn":
-        attn(sys.argv[2], sys.argv[3])
+    if len(sys.argv) in (4, 5) and sys.argv[1] == "attn":
+        attn(*sys.argv[2:])
     elif len(sys.argv) == 3 and sys.argv[1] == "attnspeed":
         sys.exit(attnspeed(sys.argv[2]))
     elif len(sys.argv) == 4 and sys.argv[1] == "dump":

@@ -87,6 +87,13 @@ def canon(d):
     d = re.sub(r"^attention_packed_kernel<(\d+), (\d+), (true|false)>", r"attention_packed_kernel<Head64<\3>, \1, \2>", d)
     d = re.sub(r"^attention32_long_kernel$", "attention_long_kernel<Head32>", d)
     d = re.sub(r"^attention32_(packed_)?kernel<", r"attention_\1kernel<Head32, ", d)
+    # causal attention on the head width (profiles/causal_width_kernels.log): <NB, KTS, NW[, LONG]>, NB 64-column blocks a head
+    d = re.sub(r"^attention_causal_kernel<(\d+), (\d+)>", r"attention_causal_kernel<1, \1, \2>", d)
+    d = re.sub(r"^attention_causal128_kernel<(\d+), (\d+)>", r"attention_causal_kernel<2, \1, \2>", d)
+    m = re.match(r"attention_causal_packed_kernel<(\d+), (\d+)>", d)
+    if m:
+        d = f"attention_causal_packed_kernel<1, {m.group(1)}, {m.group(2)}, {'true' if m.group(1) == '16' else 'false'}>"
+    d = re.sub(r"^attention_causal128_packed_kernel<(\d+), (\d+), (true|false)>", r"attention_causal_packed_kernel<2, \1, \2, \3>", d)
     return d.replace("> >", ">>")
 
 

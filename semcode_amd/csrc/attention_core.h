@@ -2,8 +2,8 @@
 // rows, encoder_window.hip: local attention, encoder_causal.hip: causal grouped-query attention).
 //   the math   : the online-softmax state of one 32-row query block, the fold of one segment of keys into it, the store
 //                (AttnState / attention_qblock_core / attn_state_store), the band fold of local attention (attention_qblock_window),
-//                the causal fold (attention_qblock_causal) and its 128-wide form (AttnState128 / attention_qblock_causal128 /
-//                attn_state128_store: K and V as two 64-wide images each, attn_lds_bytes128)
+//                the causal fold for heads of 64 and of 128 (AttnStateCausal<NB> / attention_qblock_causal<NB, KT>, NB blocks of 64
+//                columns a head; at 128 K and V are two 64-wide images each)
 //   head width : Head64<ALIBI> and Head32 name state, init, fold and store of a width; the kernels are templates on one of them.
 //                Head dimension 32: the LDS images hold a PAIR of heads, AttnState32 / attention_qblock_core32 / attn_state32_store
 //                run the softmax once per head of the pair
@@ -477,7 +477,7 @@ static __device__ __forceinline__ void attention_qblock_window(const bf16x8 (&qf
     S_.o1 = o1;
 }
 
-// ------------------------------------------------------------------ causal attention, head dimension 64 (encoder_causal.hip)
+// ------------------------------------------------------------------ causal attention, head dimension 64 NB (encoder_causal.hip)
 // A query attends to the real keys at or before its own position: key <= query, key < len.  One segment of keys (the KT tiles in Kl / Vl
 // = keys key0 .. key0 + 32 KT of the sequence, key0 a multiple of 128) folded into the state with attention_qblock_core's arithmetic per
 // (query, key); `ntiles` (0 .. KT, wave-uniform) of them are live for this query block: the tiles up to its diagonal or up to the last
@@ -485,17 +485,37 @@ static __device__ __forceinline__ void attention_qblock_window(const bf16x8 (&qf
 // the sequence of maxima, rescales and sums of a query block -- its bits -- does not depend on the segment size of the launch.  A tile
 // strictly below the block's diagonal whose keys are all real skips the per-element mask (wave-uniform test); the diagonal tile masks
 // key > query, the tile that holds len masks key >= len.  A group of four such whole tiles -- most groups of a long text -- runs
-// as straight-line code without bounds (attention_causal_group<true>).  Every query sees key 0, so group 0 always leaves a finite maximum and l > 0:
-// nothing is ever NaN, alignment and padding rows included.
+// as straight-line code without bounds (attention_causal_group<.., true, ..>).  Every query sees key 0, so group 0 always leaves a finite
+// maximum and l > 0: nothing is ever NaN, alignment and padding rows included.
+// NB: the head is NB blocks of 64 columns wide (1 or 2).  At NB 2 K and V of a segment lie in LDS as TWO of the 64-wide images each: the
+// low half of the head (columns 0 .. 63) in the first IMG = KT * 4096 bytes, the high half (64 .. 127) in the next IMG -- every read
+// keeps the 64-wide core's address inside its image (swizzles, ds_read_tr16_b64 addressing and bank analysis are unchanged), the half is
+// one added constant.  The score tile of a (query block, key tile) is then 8 MFMA steps (Q fragments 0 .. 3 against the low image, 4 .. 7
+// against the high one), the scale 1/sqrt(128), the output four 32 x 32 f32 tiles o[dt], d = 32 dt + l31 (dt 0, 1 from the low V image,
+// 2, 3 from the high one), and there is no straight-line arm: it pays for itself in the 16-tile segments, which do not exist at NB 2.
+template <int NB>
+struct AttnStateCausal {
+    float m_run, l_run;
+    f32x16 o[2 * NB];
+};
+template <int NB>
+static __device__ __forceinline__ void attn_state_init(AttnStateCausal<NB>& a) {
+    a.m_run = -3.0e38f;
+    a.l_run = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 2 * NB; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a.o[dt][r] = 0.f;
+}
 // One group of four key tiles (tiles TB .. TB + 3 of the segment).  WHOLE: all four are live, lie strictly below the block's diagonal and
 // hold real keys only -- no bounds, no masks, straight-line code as the FULL arm of attention_qblock_core; else the guarded form.  Both
 // run the same operations on the same values in the same order for every visible key: which arm ran does not show in the bits.
-template <bool WHOLE, int TB>
-static __device__ __forceinline__ void attention_causal_group(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane, int qbase,
-                                                              int key0, float& m_run, float& l_run, f32x16& o0, f32x16& o1) {
-    constexpr int GK = 4;
+template <int NB, int KT, bool WHOLE, int TB>
+static __device__ __forceinline__ void attention_causal_group(const bf16x8 (&qf)[4 * NB], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
+                                                              int qbase, int key0, float& m_run, float& l_run, f32x16 (&o)[2 * NB]) {
+    constexpr int GK = 4, IMG = KT * 32 * 128;
     const int l31 = lane & 31, hh = lane >> 5;
-    const float sl2 = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
+    const float sl2 = (NB == 1 ? 0.125f : 0.08838834764831844055f) * 1.44269504088896340736f;  // 1/sqrt(64 NB) * log2(e)
     const int q = qbase + l31;
     // S^T tiles of the group: st[i][r] = score(key = key0 + 32 t + (r&3) + 8 (r>>2) + 4 hh, query = q), t = TB + i
     f32x16 st[GK];
@@ -508,9 +528,9 @@ static __device__ __forceinline__ void attention_causal_group(const bf16x8 (&qf)
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             const int krow = 32 * t + l31;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int c = 2 * ks + hh;
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
+            for (int ks = 0; ks < 4 * NB; ++ks) {
+                const int c = 2 * (ks & 3) + hh;
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + (ks >> 2) * IMG + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
             }
             st[i] = acc;
@@ -566,10 +586,12 @@ static __device__ __forceinline__ void attention_causal_group(const bf16x8 (&qf)
         for (int g4 = 0; g4 < 4; ++g4) {
             const f32x4 al = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { o0[4 * g4 + c] *= al[c]; o1[4 * g4 + c] *= al[c]; }
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int dt = 0; dt < 2 * NB; ++dt) o[dt][4 * g4 + c] *= al[c];
         }
     }
-    // O += P V: operands as in attention_qblock_core
+    // O += P V: operands as in attention_qblock_core, the V image of the output tile's half
 #pragma unroll
     for (int i = 0; i < GK; ++i) {
         const int t = TB + i;
@@ -582,172 +604,7 @@ static __device__ __forceinline__ void attention_causal_group(const bf16x8 (&qf)
                 for (int j = 0; j < 4; ++j) pp[j] = pack_bf16x2(st[i][8 * s + 2 * j], st[i][8 * s + 2 * j + 1]);
                 const bf16x8 pf = __builtin_bit_cast(bf16x8, pp);
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    bf16x8 vf;
-#pragma unroll
-                    for (int piece = 0; piece < 2; ++piece) {
-                        const int row = 32 * t + 16 * s + 8 * piece + 4 * hh + ((lane & 15) >> 2);
-                        const int d0 = 32 * dt + 16 * ((lane >> 4) & 1);
-                        const int chunk = (d0 >> 3) + ((lane & 3) >> 1);
-                        const int sw = chunk ^ (((row >> 1) & 1) << 2);
-                        typedef __attribute__((address_space(3))) s16x4* lds_s16x4p;
-                        const s16x4 got = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4p)(Vl + row * 128 + sw * 16 + 8 * (lane & 1)));
-                        vf[4 * piece + 0] = got[0];
-                        vf[4 * piece + 1] = got[1];
-                        vf[4 * piece + 2] = got[2];
-                        vf[4 * piece + 3] = got[3];
-                    }
-                    if (dt == 0) o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o0, 0, 0, 0);
-                    else o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, vf, o1, 0, 0, 0);
-                }
-            }
-        }
-    }
-}
-template <int KT, int G = 0>
-static __device__ __forceinline__ void attention_causal_groups(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane, int qbase,
-                                                               int key0, float& m_run, float& l_run, f32x16& o0, f32x16& o1) {
-    if constexpr (4 * G < KT) {
-        if (4 * G >= ntiles) return;  // wave-uniform: nothing for this query block in this group or a later one
-        const int klast = key0 + 32 * (4 * G + 3);  // first key of the group's last tile
-        // (segments of 4 tiles: no group lies below a diagonal; of 8: one group of half the blocks does, and the second arm cost the
-        // 256-token class more in registers than it saved -- 82 against 70 us a launch)
-        if (KT > 8 && 4 * G + 4 <= ntiles && klast + 31 <= qbase && klast + 32 <= len)
-            attention_causal_group<true, 4 * G>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o0, o1);
-        else
-            attention_causal_group<false, 4 * G>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o0, o1);
-        attention_causal_groups<KT, G + 1>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o0, o1);
-    }
-}
-template <int KT>
-static __device__ __forceinline__ void attention_qblock_causal(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
-                                                               int qbase, int key0, AttnState& S_) {
-    static_assert(KT % 4 == 0, "segments are whole groups of four key tiles");
-    float m_run = S_.m_run, l_run = S_.l_run;
-    f32x16 o0 = S_.o0, o1 = S_.o1;
-    attention_causal_groups<KT>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o0, o1);
-    S_.m_run = m_run;
-    S_.l_run = l_run;
-    S_.o0 = o0;
-    S_.o1 = o1;
-}
-
-// ------------------------------------------------------------------ causal attention, head dimension 128 (encoder_causal.hip)
-// attention_qblock_causal for a 128-wide head.  K and V of a segment lie in LDS as TWO of the 64-wide images each: the low half of the head
-// (columns 0 .. 63) in the first IMG = KT * 4096 bytes, the high half (64 .. 127) in the next IMG -- every read keeps the 64-wide core's
-// address inside its image (swizzles, ds_read_tr16_b64 addressing and bank analysis are unchanged), the half is one added constant.
-// The score tile of a (query block, key tile) is 8 MFMA steps (Q fragments 0 .. 3 against the low image, 4 .. 7 against the high one), the
-// scale 1/sqrt(128), the output four 32 x 32 f32 tiles o[dt], d = 32 dt + l31 (dt 0, 1 from the low V image, 2, 3 from the high one).
-// Online softmax, the three wave-uniform mask cases, the select and the groups of FOUR key tiles counted from key 0 are those of the
-// 64-wide fold: a query block's bits do not depend on the segment size.  One arm only (the guarded one): the straight-line arm of the
-// 64-wide fold pays for itself in the 16-tile segments, which do not exist at this width.
-struct AttnState128 {
-    float m_run, l_run;
-    f32x16 o[4];
-};
-static __device__ __forceinline__ void attn_state128_init(AttnState128& a) {
-    a.m_run = -3.0e38f;
-    a.l_run = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a.o[dt][r] = 0.f;
-}
-template <int KT, int TB>
-static __device__ __forceinline__ void attention_causal_group128(const bf16x8 (&qf)[8], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane, int qbase,
-                                                                 int key0, float& m_run, float& l_run, f32x16 (&o)[4]) {
-    constexpr int GK = 4, IMG = KT * 32 * 128;
-    const int l31 = lane & 31, hh = lane >> 5;
-    const float sl2 = 0.08838834764831844055f * 1.44269504088896340736f;  // 1/sqrt(128) * log2(e)
-    const int q = qbase + l31;
-    // S^T tiles of the group: st[i][r] = score(key = key0 + 32 t + (r&3) + 8 (r>>2) + 4 hh, query = q), t = TB + i
-    f32x16 st[GK];
-#pragma unroll
-    for (int i = 0; i < GK; ++i) {
-        const int t = TB + i;
-        if (t < ntiles) {
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            const int krow = 32 * t + l31;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const int c = 2 * (ks & 3) + hh;
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + (ks >> 2) * IMG + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
-            }
-            st[i] = acc;
-        }
-    }
-    float mx = m_run;
-#pragma unroll
-    for (int i = 0; i < GK; ++i) {
-        const int t = TB + i;
-        if (t < ntiles) {
-            const int k0 = key0 + 32 * t;
-            const bool whole = k0 + 31 <= qbase && k0 + 32 <= len;  // below the diagonal of every query of the block, every key real
-            if (whole) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[i][r]);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    if (key <= q && key < len) mx = fmaxf(mx, st[i][r]);
-                }
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mb = mx * sl2;
-    const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, sl2, -mb));  // group 0 of the sequence: exp2(-huge) = 0, and O, l are 0 anyway
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < GK; ++i) {
-        const int t = TB + i;
-        if (t < ntiles) {
-            const int k0 = key0 + 32 * t;
-            const bool whole = k0 + 31 <= qbase && k0 + 32 <= len;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float p = __builtin_amdgcn_exp2f(fmaf(st[i][r], sl2, -mb));
-                if (!whole) {
-                    const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                    p = (key <= q && key < len) ? p : 0.f;  // a select: a masked score may have overflowed exp2
-                }
-                st[i][r] = p;
-                sum += p;
-            }
-        }
-    }
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = fmaf(l_run, alpha, sum);
-    m_run = mx;
-    if (TB > 0 || key0 > 0) {  // rescale O (attention_qblock_core): alpha lives on lane q -> exchange through LDS
-        xch[l31] = alpha;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const f32x4 al = *reinterpret_cast<const f32x4*>(xch + 8 * g4 + 4 * hh);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) o[dt][4 * g4 + c] *= al[c];
-        }
-    }
-    // O += P V: operands as in attention_qblock_core, the V image of the output tile's half
-#pragma unroll
-    for (int i = 0; i < GK; ++i) {
-        const int t = TB + i;
-        if (t < ntiles) {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                u32x4 pp;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pp[j] = pack_bf16x2(st[i][8 * s + 2 * j], st[i][8 * s + 2 * j + 1]);
-                const bf16x8 pf = __builtin_bit_cast(bf16x8, pp);
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
+                for (int dt = 0; dt < 2 * NB; ++dt) {
                     bf16x8 vf;
 #pragma unroll
                     for (int piece = 0; piece < 2; ++piece) {
@@ -768,24 +625,35 @@ static __device__ __forceinline__ void attention_causal_group128(const bf16x8 (&
         }
     }
 }
-template <int KT, int G = 0>
-static __device__ __forceinline__ void attention_causal_groups128(const bf16x8 (&qf)[8], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
-                                                                  int qbase, int key0, float& m_run, float& l_run, f32x16 (&o)[4]) {
+template <int NB, int KT, int G = 0>
+static __device__ __forceinline__ void attention_causal_groups(const bf16x8 (&qf)[4 * NB], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
+                                                               int qbase, int key0, float& m_run, float& l_run, f32x16 (&o)[2 * NB]) {
     if constexpr (4 * G < KT) {
         if (4 * G >= ntiles) return;  // wave-uniform: nothing for this query block in this group or a later one
-        attention_causal_group128<KT, 4 * G>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o);
-        attention_causal_groups128<KT, G + 1>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o);
+        const int klast = key0 + 32 * (4 * G + 3);  // first key of the group's last tile
+        // (segments of 4 tiles: no group lies below a diagonal; of 8: one group of half the blocks does, and the second arm cost the
+        // 256-token class more in registers than it saved -- 82 against 70 us a launch)
+        if (KT > 8 && 4 * G + 4 <= ntiles && klast + 31 <= qbase && klast + 32 <= len)
+            attention_causal_group<NB, KT, true, 4 * G>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o);
+        else
+            attention_causal_group<NB, KT, false, 4 * G>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o);
+        attention_causal_groups<NB, KT, G + 1>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, m_run, l_run, o);
     }
 }
-template <int KT>
-static __device__ __forceinline__ void attention_qblock_causal128(const bf16x8 (&qf)[8], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
-                                                                  int qbase, int key0, AttnState128& S_) {
+template <int NB, int KT>
+static __device__ __forceinline__ void attention_qblock_causal(const bf16x8 (&qf)[4 * NB], const char* Kl, const char* Vl, float* xch, int len, int ntiles, int lane,
+                                                               int qbase, int key0, AttnStateCausal<NB>& S_) {
     static_assert(KT % 4 == 0, "segments are whole groups of four key tiles");
-    attention_causal_groups128<KT>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, S_.m_run, S_.l_run, S_.o);
+    static_assert(NB == 1 || KT <= 8, "two images a key tile for K and for V: a 128-wide segment is at most 8 tiles of the 160 KiB");
+    attention_causal_groups<NB, KT>(qf, Kl, Vl, xch, len, ntiles, lane, qbase, key0, S_.m_run, S_.l_run, S_.o);
 }
-// o[dt][r] = O[q = (r&3) + 8 (r>>2) + 4 hh][d = 32 dt + l31]: normalise by 1/l[q], stage as bf16 [q][128 d] in LDS 8 query rows at a
+// The store of a causal state, by its width.  64: attn_state_store above, the one of the non-causal kernels.
+static __device__ __forceinline__ void attn_state_store(const AttnStateCausal<1>& S_, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
+    attn_state_store(AttnState{S_.m_run, S_.l_run, S_.o[0], S_.o[1]}, xch, ostg, obase, H, lane);
+}
+// 128: o[dt][r] = O[q = (r&3) + 8 (r>>2) + 4 hh][d = 32 dt + l31]: normalise by 1/l[q], stage as bf16 [q][128 d] in LDS 8 query rows at a
 // time (2 KiB, wave-private), then leave as whole 256-byte rows, two 16-byte stores per lane.
-static __device__ __forceinline__ void attn_state128_store(const AttnState128& S_, float* xch, char* ostg, bf16_t* obase, int AW, int lane) {
+static __device__ __forceinline__ void attn_state_store(const AttnStateCausal<2>& S_, float* xch, char* ostg, bf16_t* obase, int AW, int lane) {
     const int l31 = lane & 31, hh = lane >> 5;
     xch[l31] = 1.0f / S_.l_run;
     bf16_t* og = reinterpret_cast<bf16_t*>(ostg);
@@ -808,11 +676,10 @@ static __device__ __forceinline__ void attn_state128_store(const AttnState128& S
 }
 
 // ------------------------------------------------------------------ LDS of a launch
-// Dynamic LDS of a workgroup of `nw` waves that stages `kts` key tiles: the K image, the V image (32 rows x 128 B per tile each), then
-// per wave 32 floats of alpha / 1/l exchange and one [8 q][64 d] bf16 block of output staging.  Every launcher sizes its launch with it.
-static constexpr int attn_lds_bytes(int kts, int nw) { return 2 * kts * 32 * 128 + nw * 128 + nw * 1024; }
-// ... at head dimension 128: two images each for K and V (16 KiB a key tile), the exchange, one [8 q][128 d] block per wave
-static constexpr int attn_lds_bytes128(int kts, int nw) { return 4 * kts * 32 * 128 + nw * 128 + nw * 2048; }
+// Dynamic LDS of a workgroup of `nw` waves that stages `kts` key tiles of heads nb blocks of 64 columns wide: nb K images, nb V images
+// (32 rows x 128 B per tile each), then per wave 32 floats of alpha / 1/l exchange and one [8 q][64 nb d] bf16 block of output staging.
+// Every launcher sizes its launch with it.
+static constexpr int attn_lds_bytes(int kts, int nw, int nb = 1) { return 2 * nb * kts * 32 * 128 + nw * 128 + nw * nb * 1024; }
 
 // ------------------------------------------------------------------ head width as a policy
 // What a kernel shell needs to know about the head width: the state of a query block, its init, the fold of the staged keys, the store,

@@ -22,22 +22,23 @@
 // position and the text's length only: the bits of a text's rows do not depend on the rectangle's S, on the packed launch class or on
 // its batch-mates.  Rows of a rectangle at or beyond len, and alignment rows of packed texts, are queries too: they see key 0 at least.
 //
-// Three instantiations, by the rectangle's S or the packed item's class (sc_packed_items):
-//   up to 128 keys : segments of 4 tiles,  4 waves,  37 KiB LDS
-//   up to 256 keys : segments of 8 tiles,  8 waves,  73 KiB LDS
-//   longer         : segments of 16 tiles, 8 waves, 137 KiB LDS, one workgroup per 8 query blocks
-//
-// Head dimension 128 (cfg.head_dim 128: Qwen3-Embedding, Qwen2.5-1.5B) has kernels of its own, attention_causal128_kernel /
-// attention_causal128_packed_kernel -- same shell, same rules for tiles, groups of four, masks, grids and bits; a width parameter on the
-// kernels above would have renamed them and risked their text, which stays instruction-identical (profiles/qwen3_kernels.log).  A head is
-// two consecutive 64-column blocks; a key tile is 8 KiB of K and 8 KiB of V, each staged as two of the 64-wide images (low half, high
-// half of the head); a wave holds 8 Q fragments, the score tile of a (query block, key tile) is 8 MFMA steps, the output four 32 x 32 tiles.
-// With 160 KiB of LDS a segment is at most 8 tiles.  Two instantiations:
-//   S or text up to 128 keys : segments of 4 tiles, 4 waves,  72.5 KiB LDS (64 KiB of K / V + 4 x 128 B exchange + 4 x 2 KiB output block),
-//                              204 VGPRs, two workgroups a CU
-//   longer                   : segments of 8 tiles, 8 waves, 145 KiB LDS (128 KiB + 1 KiB + 16 KiB), 249 VGPRs, one workgroup a CU; a text
-//                              beyond 256 keys walks its segments with the state carried along (packed: one item per 8 query blocks, LONG)
-// No scratch in either (the compiler's summary is in profiles/qwen3_kernels.log).
+// Both kernels are templates on NB, the 64-column blocks of a head: 1 (head dimension 64) or 2 (cfg.head_dim 128: Qwen3-Embedding,
+// Qwen2.5-1.5B) -- one shell, one set of rules for tiles, groups of four, masks, grids and bits.  At NB 2 a head is two consecutive
+// 64-column blocks; a key tile is 8 KiB of K and 8 KiB of V, each staged as two of the 64-wide images (low half, high half of the head);
+// a wave holds 8 Q fragments, the score tile of a (query block, key tile) is 8 MFMA steps, the output four 32 x 32 tiles.  With 160 KiB
+// of LDS a 128-wide segment is at most 8 tiles.  The instantiations <NB, KTS, NW>, by the rectangle's S or the packed item's class
+// (sc_packed_items):
+//   head dimension 64
+//     up to 128 keys : <1, 4, 4>   segments of 4 tiles,  4 waves,  37 KiB LDS
+//     up to 256 keys : <1, 8, 8>   segments of 8 tiles,  8 waves,  73 KiB LDS
+//     longer         : <1, 16, 8>  segments of 16 tiles, 8 waves, 137 KiB LDS, one workgroup per 8 query blocks
+//   head dimension 128
+//     up to 128 keys : <2, 4, 4>   segments of 4 tiles, 4 waves,  72.5 KiB LDS (64 KiB of K / V + 4 x 128 B exchange + 4 x 2 KiB output
+//                                  block), 204 VGPRs, two workgroups a CU
+//     longer         : <2, 8, 8>   segments of 8 tiles, 8 waves, 145 KiB LDS (128 KiB + 1 KiB + 16 KiB), 249 VGPRs, one workgroup a CU; a
+//                                  text beyond 256 keys walks its segments with the state carried along (packed: one item per 8 query
+//                                  blocks, LONG)
+// No scratch in any (the compiler's summaries are in profiles/qwen3_kernels.log and profiles/causal_width_kernels.log).
 //   qknorm_rope_kernel              HBM-bound  : the per-head RMSNorm of Q and K (cfg.qk_norm) and the rotate-half rotation in one pass over the
 //   qknorm_rope_packed_kernel                    blocked QKV buffer, head dimension 64 or 128, 16-byte accesses, one rounding to bf16.  The forward
 //                                                calls it when head_dim == 128 or qk_norm; the 64-wide model without QK-norm keeps rope_qk_kernel
@@ -48,139 +49,58 @@
 
 // start: first token row of the sequence, len its real length (>= 1), qb0 the workgroup's first 32-row query block, nqb the query
 // blocks of the sequence that exist as rows (S / 32, or ceil32(len) / 32 of packed rows).  heads / kvh: query heads, K / V heads.
-template <int KTS, int NW>
+// NB: a head is NB consecutive 64-column blocks of the fused projection, row-major or blocked: block j of a row lies at j * bs, bs = 64
+// elements (row-major) or blocked * 64 (64-column blocks).  K and V of a segment are staged as NB 64-wide images each (attention_core.h).
+template <int NB, int KTS, int NW>
 static __device__ __forceinline__ void attention_causal_body(const bf16_t* __restrict__ qkv, int start, int len, int qb0, int nqb, int head, int heads, int kvh,
                                                              bf16_t* __restrict__ ctx, int blocked, char* smem) {
+    constexpr int IMG = KTS * 32 * 128;
     char* Kl = smem;
-    char* Vl = smem + KTS * 32 * 128;
+    char* Vl = smem + NB * IMG;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* xch = reinterpret_cast<float*>(smem + 2 * KTS * 32 * 128) + w * 32;
-    char* ostg = smem + 2 * KTS * 32 * 128 + NW * 128 + w * 1024;
+    float* xch = reinterpret_cast<float*>(smem + 2 * NB * IMG) + w * 32;
+    char* ostg = smem + 2 * NB * IMG + NW * 128 + w * (NB * 1024);
     const int qb = qb0 + w;      // this wave's query block
     const bool live = qb < nqb;  // wave-uniform
     const int kvhead = head / (heads / kvh);  // grouped mapping: consecutive query heads share a K / V head
-    const int H = heads * 64;
-    const int ld = blocked ? 64 : (heads + 2 * kvh) * 64;
-    const size_t T = (size_t)blocked;  // blocked = the row count (M) of the projection that wrote the blocks
-    const bf16_t* qbase = blocked ? qkv + ((size_t)head * T + (size_t)start) * 64 : qkv + (size_t)start * ld + head * 64;
-    const bf16_t* kbase = blocked ? qkv + ((size_t)(heads + kvhead) * T + (size_t)start) * 64 : qkv + (size_t)start * ld + (heads + kvhead) * 64;
-    const bf16_t* vbase = blocked ? qkv + ((size_t)(heads + kvh + kvhead) * T + (size_t)start) * 64 : qkv + (size_t)start * ld + (heads + kvh + kvhead) * 64;
+    const int H = heads * (NB * 64);
+    const int ld = blocked ? 64 : (heads + 2 * kvh) * (NB * 64);
+    const size_t bs = blocked ? (size_t)blocked * 64 : 64;  // blocked = the row count (M) of the projection that wrote the blocks
+    // The same three addresses in two spellings.  At 64 the one the kernels had before they took NB: with row0 + NB * head * bs the packed
+    // 8-tile kernel takes one register more (157 against 156, profiles/causal_width_kernels.log); at 128 this one is its text to the letter.
+    const bf16_t *qbase, *kbase, *vbase;
+    if constexpr (NB == 1) {
+        const size_t T = (size_t)blocked;  // the row count (M) of the blocks
+        qbase = blocked ? qkv + ((size_t)head * T + (size_t)start) * 64 : qkv + (size_t)start * ld + head * 64;
+        kbase = blocked ? qkv + ((size_t)(heads + kvhead) * T + (size_t)start) * 64 : qkv + (size_t)start * ld + (heads + kvhead) * 64;
+        vbase = blocked ? qkv + ((size_t)(heads + kvh + kvhead) * T + (size_t)start) * 64 : qkv + (size_t)start * ld + (heads + kvh + kvhead) * 64;
+    } else {
+        const bf16_t* row0 = qkv + (size_t)start * ld;
+        qbase = row0 + (size_t)(NB * head) * bs;
+        kbase = row0 + (size_t)(NB * (heads + kvhead)) * bs;
+        vbase = row0 + (size_t)(NB * (heads + kvh + kvhead)) * bs;
+    }
     const int l31 = lane & 31, hh = lane >> 5;
-    bf16x8 qf[4];
+    bf16x8 qf[4 * NB];
     if (live) {
         const bf16_t* qrow = qbase + (size_t)(qb * 32 + l31) * ld;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + 16 * ks + 8 * hh);
+        for (int ks = 0; ks < 4 * NB; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + (size_t)(ks >> 2) * bs + 16 * (ks & 3) + 8 * hh);
     }
     const int nrt = (len + 31) >> 5;                          // key tiles holding at least one real key
     const int ntw = qb0 + NW < nrt ? qb0 + NW : nrt;          // tiles this workgroup stages: up to its last block's diagonal
     const int ntq = live ? (qb + 1 < nrt ? qb + 1 : nrt) : 0; // tiles this wave folds: up to its own diagonal
     const int nseg = (ntw + KTS - 1) / KTS;
-    AttnState st;
+    AttnStateCausal<NB> st;
     attn_state_init(st);
 #pragma unroll 1
     for (int seg = 0; seg < nseg; ++seg) {
         const int t0 = seg * KTS;
         const int nst = ntw - t0 < KTS ? ntw - t0 : KTS;  // tiles staged in this segment
         if (seg) __syncthreads();  // every wave is done with the previous segment's K / V
-        for (int piece = w; piece < nst * 4; piece += NW) {  // pieces of 8 rows x 128 B = 1 KiB
-            const int p = piece * 64 + lane;
-            const int r = p >> 3, ck = (p & 7) ^ ((r >> 1) & 7);
-            __builtin_amdgcn_global_load_lds((gbl_vptr)(kbase + (size_t)(t0 * 32 + r) * ld + ck * 8), (lds_vptr)(Kl + piece * 1024), 16, 0, 0);
-        }
-        for (int piece = w; piece < nst * 4; piece += NW) {
-            const int p = piece * 64 + lane;
-            const int r = p >> 3, cv = (p & 7) ^ (((r >> 1) & 1) << 2);
-            __builtin_amdgcn_global_load_lds((gbl_vptr)(vbase + (size_t)(t0 * 32 + r) * ld + cv * 8), (lds_vptr)(Vl + piece * 1024), 16, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int nt = ntq - t0;
-        nt = nt < 0 ? 0 : (nt > nst ? nst : nt);  // never beyond what was staged
-        nt = __builtin_amdgcn_readfirstlane(nt);
-        if (nt > 0) attention_qblock_causal<KTS>(qf, Kl, Vl, xch, len, nt, lane, qb * 32, t0 * 32, st);
-    }
-    if (live) attn_state_store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * H + head * 64, H, lane);
-}
-
-template <int KTS, int NW>
-__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int S, int heads, int kvh,
-                                                                      bf16_t* __restrict__ ctx, int blocked) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int head = blockIdx.x, b = blockIdx.y;
-    int len = lens[b];
-    len = len < 1 ? 1 : (len > S ? S : len);
-    len = __builtin_amdgcn_readfirstlane(len);
-    // the groups of query blocks of a sequence from the last -- the most key tiles -- to the first: the long workgroups start first
-    attention_causal_body<KTS, NW>(qkv, b * S, len, (int)(gridDim.z - 1 - blockIdx.z) * NW, S >> 5, head, heads, kvh, ctx, blocked, smem);
-}
-
-template <int KTS, int NW>
-__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal_packed_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ items, int nitems, int heads,
-                                                                             int kvh, bf16_t* __restrict__ ctx, int blocked) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // One grid dimension, the head fastest, the items from the last to the first.  The items of a long text are its groups of 8 query
-    // blocks in ascending order, 8 per 2 048 tokens: with the item as the fastest index, workgroup id mod 8 -- the XCD a workgroup lands
-    // on -- would be the group's position in its text, i.e. one XCD would get all the groups with the most key tiles.  Heads fastest
-    // spreads every item over the XCDs and puts the query heads that share a K / V head next to each other in time.
-    // The two short classes have one item per text, nothing to balance: the item is the fastest index there, so that the heads of a
-    // text -- 7 of them read the same K / V head -- land on one XCD and find it in that L2 (60 us a launch at 128 x 256 tokens, against 69
-    // for the same work as a rectangle, whose grid runs the heads fastest).
-    const int head = KTS == 16 ? (int)(blockIdx.x % (unsigned)heads) : (int)(blockIdx.x / (unsigned)nitems);
-    const int32_t* it = items + 4 * (size_t)(KTS == 16 ? nitems - 1 - (int)(blockIdx.x / (unsigned)heads) : (int)(blockIdx.x % (unsigned)nitems));
-    const int start = __builtin_amdgcn_readfirstlane(it[0]);
-    int len = it[1];
-    len = len < 1 ? 1 : (len > KTS * 32 && KTS < 16 ? KTS * 32 : len);  // (an item of a short class never holds a longer text)
-    len = __builtin_amdgcn_readfirstlane(len);
-    const int qb0 = __builtin_amdgcn_readfirstlane(it[2]);
-    attention_causal_body<KTS, NW>(qkv, start, len, qb0, (len + 31) >> 5, head, heads, kvh, ctx, blocked, smem);
-}
-
-// ------------------------------------------------------------------ causal attention, head dimension 128
-// attention_causal_body for 128-wide heads (Qwen3-Embedding, Qwen2.5-1.5B).  A head is two consecutive 64-column blocks of the fused
-// projection, row-major or blocked: block j of a row lies at j * bs, bs = 64 elements (row-major) or blocked * 64 (64-column blocks).
-// K and V of a segment are staged as two 64-wide images each (attention_core.h), every image by attention_causal_body's loop.
-template <int KTS, int NW>
-static __device__ __forceinline__ void attention_causal_body128(const bf16_t* __restrict__ qkv, int start, int len, int qb0, int nqb, int head, int heads, int kvh,
-                                                                bf16_t* __restrict__ ctx, int blocked, char* smem) {
-    constexpr int IMG = KTS * 32 * 128;
-    char* Kl = smem;
-    char* Vl = smem + 2 * IMG;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* xch = reinterpret_cast<float*>(smem + 4 * IMG) + w * 32;
-    char* ostg = smem + 4 * IMG + NW * 128 + w * 2048;
-    const int qb = qb0 + w;      // this wave's query block
-    const bool live = qb < nqb;  // wave-uniform
-    const int kvhead = head / (heads / kvh);  // grouped mapping: consecutive query heads share a K / V head
-    const int AW = heads * 128;
-    const int ld = blocked ? 64 : (heads + 2 * kvh) * 128;
-    const size_t bs = blocked ? (size_t)blocked * 64 : 64;  // blocked = the row count (M) of the projection that wrote the blocks
-    const bf16_t* row0 = qkv + (size_t)start * ld;
-    const bf16_t* qbase = row0 + (size_t)(2 * head) * bs;
-    const bf16_t* kbase = row0 + (size_t)(2 * (heads + kvhead)) * bs;
-    const bf16_t* vbase = row0 + (size_t)(2 * (heads + kvh + kvhead)) * bs;
-    const int l31 = lane & 31, hh = lane >> 5;
-    bf16x8 qf[8];
-    if (live) {
-        const bf16_t* qrow = qbase + (size_t)(qb * 32 + l31) * ld;
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + (size_t)(ks >> 2) * bs + 16 * (ks & 3) + 8 * hh);
-    }
-    const int nrt = (len + 31) >> 5;                          // key tiles holding at least one real key
-    const int ntw = qb0 + NW < nrt ? qb0 + NW : nrt;          // tiles this workgroup stages: up to its last block's diagonal
-    const int ntq = live ? (qb + 1 < nrt ? qb + 1 : nrt) : 0; // tiles this wave folds: up to its own diagonal
-    const int nseg = (ntw + KTS - 1) / KTS;
-    AttnState128 st;
-    attn_state128_init(st);
-#pragma unroll 1
-    for (int seg = 0; seg < nseg; ++seg) {
-        const int t0 = seg * KTS;
-        const int nst = ntw - t0 < KTS ? ntw - t0 : KTS;  // tiles staged in this segment
-        if (seg) __syncthreads();  // every wave is done with the previous segment's K / V
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {  // the low and the high half of the head
+        for (int e = 0; e < NB; ++e) {  // the 64-column blocks of the head: one image each
             for (int piece = w; piece < nst * 4; piece += NW) {  // pieces of 8 rows x 128 B = 1 KiB
                 const int p = piece * 64 + lane;
                 const int r = p >> 3, ck = (p & 7) ^ ((r >> 1) & 7);
@@ -197,30 +117,36 @@ static __device__ __forceinline__ void attention_causal_body128(const bf16_t* __
         int nt = ntq - t0;
         nt = nt < 0 ? 0 : (nt > nst ? nst : nt);  // never beyond what was staged
         nt = __builtin_amdgcn_readfirstlane(nt);
-        if (nt > 0) attention_qblock_causal128<KTS>(qf, Kl, Vl, xch, len, nt, lane, qb * 32, t0 * 32, st);
+        if (nt > 0) attention_qblock_causal<NB, KTS>(qf, Kl, Vl, xch, len, nt, lane, qb * 32, t0 * 32, st);
     }
-    if (live) attn_state128_store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * AW + head * 128, AW, lane);
+    if (live) attn_state_store(st, xch, ostg, ctx + ((size_t)start + (size_t)qb * 32) * H + head * (NB * 64), H, lane);
 }
 
-template <int KTS, int NW>
-__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal128_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int S, int heads, int kvh,
-                                                                         bf16_t* __restrict__ ctx, int blocked) {
+template <int NB, int KTS, int NW>
+__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ lens, int S, int heads, int kvh,
+                                                                      bf16_t* __restrict__ ctx, int blocked) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int head = blockIdx.x, b = blockIdx.y;
     int len = lens[b];
     len = len < 1 ? 1 : (len > S ? S : len);
     len = __builtin_amdgcn_readfirstlane(len);
-    // the groups of query blocks of a sequence from the last -- the most key tiles -- to the first, as attention_causal_kernel
-    attention_causal_body128<KTS, NW>(qkv, b * S, len, (int)(gridDim.z - 1 - blockIdx.z) * NW, S >> 5, head, heads, kvh, ctx, blocked, smem);
+    // the groups of query blocks of a sequence from the last -- the most key tiles -- to the first: the long workgroups start first
+    attention_causal_body<NB, KTS, NW>(qkv, b * S, len, (int)(gridDim.z - 1 - blockIdx.z) * NW, S >> 5, head, heads, kvh, ctx, blocked, smem);
 }
 
-// LONG: the items are groups of 8 query blocks of texts of any length (the class of sc_packed_items whose 64-wide kernel stages 16 tiles):
-// heads fastest, items from the last to the first, for attention_causal_packed_kernel's reasons.  Else one item per text of at most
-// KTS * 32 tokens, the item the fastest index.
-template <int KTS, int NW, bool LONG>
-__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal128_packed_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ items, int nitems,
-                                                                                int heads, int kvh, bf16_t* __restrict__ ctx, int blocked) {
+// LONG: the items are groups of 8 query blocks of texts of any length (the first class of sc_packed_items: 16-tile segments at head
+// dimension 64, 8-tile ones at 128).  Else one item per text of at most KTS * 32 tokens.
+template <int NB, int KTS, int NW, bool LONG>
+__global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal_packed_kernel(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ items, int nitems, int heads,
+                                                                             int kvh, bf16_t* __restrict__ ctx, int blocked) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // One grid dimension, the head fastest, the items from the last to the first.  The items of a long text are its groups of 8 query
+    // blocks in ascending order, 8 per 2 048 tokens: with the item as the fastest index, workgroup id mod 8 -- the XCD a workgroup lands
+    // on -- would be the group's position in its text, i.e. one XCD would get all the groups with the most key tiles.  Heads fastest
+    // spreads every item over the XCDs and puts the query heads that share a K / V head next to each other in time.
+    // The two short classes have one item per text, nothing to balance: the item is the fastest index there, so that the heads of a
+    // text -- 7 of them read the same K / V head -- land on one XCD and find it in that L2 (60 us a launch at 128 x 256 tokens, against 69
+    // for the same work as a rectangle, whose grid runs the heads fastest).
     const int head = LONG ? (int)(blockIdx.x % (unsigned)heads) : (int)(blockIdx.x / (unsigned)nitems);
     const int32_t* it = items + 4 * (size_t)(LONG ? nitems - 1 - (int)(blockIdx.x / (unsigned)heads) : (int)(blockIdx.x % (unsigned)nitems));
     const int start = __builtin_amdgcn_readfirstlane(it[0]);
@@ -228,7 +154,7 @@ __global__ __launch_bounds__(NW * 64, (KTS <= 4 ? 2 : 1)) void attention_causal1
     len = len < 1 ? 1 : (len > KTS * 32 && !LONG ? KTS * 32 : len);  // (an item of a short class never holds a longer text)
     len = __builtin_amdgcn_readfirstlane(len);
     const int qb0 = __builtin_amdgcn_readfirstlane(it[2]);
-    attention_causal_body128<KTS, NW>(qkv, start, len, qb0, (len + 31) >> 5, head, heads, kvh, ctx, blocked, smem);
+    attention_causal_body<NB, KTS, NW>(qkv, start, len, qb0, (len + 31) >> 5, head, heads, kvh, ctx, blocked, smem);
 }
 
 // ------------------------------------------------------------------ QK-norm + rotation
@@ -439,22 +365,6 @@ bool sc_attention_causal_supported(int heads, int kv_heads, int head_dim) {
     return (head_dim == 64 || head_dim == 128) && heads >= 1 && heads * head_dim <= 2048 && kv_heads >= 1 && kv_heads <= heads && heads % kv_heads == 0;
 }
 
-template <int KTS, int NW>
-static void launch_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kvh, void* ctx, int blocked, hipStream_t s) {
-    const dim3 grid((unsigned)heads, (unsigned)B, (unsigned)((S / 32 + NW - 1) / NW));
-    attn_launch<attention_causal128_kernel<KTS, NW>, attn_lds_bytes128(KTS, NW)>(grid, NW * 64, s, (const bf16_t*)qkv, lens, S, heads, kvh, (bf16_t*)ctx, blocked);
-}
-void sc_launch_attention_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
-    if (S <= 128) launch_causal128<4, 4>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
-    else launch_causal128<8, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
-}
-void sc_launch_attention_causal128_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
-    attn_packed_classes(items, nitems, [&](auto cls, const int32_t* first, int n) {
-        constexpr int C = decltype(cls)::value, KTS = C == 2 ? 4 : 8, NW = KTS;  // texts beyond 256 tokens and up to 256: 8 tiles; up to 128: 4
-        attn_launch<attention_causal128_packed_kernel<KTS, NW, C == 0>, attn_lds_bytes128(KTS, NW)>(dim3((unsigned)n * (unsigned)heads), NW * 64, s, (const bf16_t*)qkv, first,
-                                                                                                    n, heads, kv_heads, (bf16_t*)ctx, blocked);
-    });
-}
 template <int HD, bool NORM>
 static void launch_qknorm_rope(void* qkv, int64_t M, int nheads, int nq, int S, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t, const float* gq,
                                const float* gk, float eps, hipStream_t s) {
@@ -477,22 +387,33 @@ void sc_launch_qknorm_rope(void* qkv, int64_t M, int heads, int kv_heads, int he
     }
 }
 
-template <int KTS, int NW>
+template <int NB, int KTS, int NW>
 static void launch_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kvh, void* ctx, int blocked, hipStream_t s) {
     const dim3 grid((unsigned)heads, (unsigned)B, (unsigned)((S / 32 + NW - 1) / NW));
-    attn_launch<attention_causal_kernel<KTS, NW>, attn_lds_bytes(KTS, NW)>(grid, NW * 64, s, (const bf16_t*)qkv, lens, S, heads, kvh, (bf16_t*)ctx, blocked);
+    attn_launch<attention_causal_kernel<NB, KTS, NW>, attn_lds_bytes(KTS, NW, NB)>(grid, NW * 64, s, (const bf16_t*)qkv, lens, S, heads, kvh, (bf16_t*)ctx, blocked);
 }
-void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
-    if (S <= 128) launch_causal<4, 4>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
-    else if (S <= 256) launch_causal<8, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
-    else launch_causal<16, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, int head_dim, void* ctx, hipStream_t s, int blocked) {
+    if (head_dim == 128) {
+        if (S <= 128) launch_causal<2, 4, 4>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+        else launch_causal<2, 8, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+    } else {
+        if (S <= 128) launch_causal<1, 4, 4>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+        else if (S <= 256) launch_causal<1, 8, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+        else launch_causal<1, 16, 8>(qkv, lens, B, S, heads, kv_heads, ctx, blocked, s);
+    }
 }
-void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked) {
+template <int NB>
+static void launch_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kvh, void* ctx, int blocked, hipStream_t s) {
     attn_packed_classes(items, nitems, [&](auto cls, const int32_t* first, int n) {
-        constexpr int KTS = 16 >> decltype(cls)::value, NW = KTS >= 8 ? 8 : 4;  // 16 / 8 / 4 tiles per segment
-        attn_launch<attention_causal_packed_kernel<KTS, NW>, attn_lds_bytes(KTS, NW)>(dim3((unsigned)n * (unsigned)heads), NW * 64, s, (const bf16_t*)qkv, first, n, heads,
-                                                                                      kv_heads, (bf16_t*)ctx, blocked);
+        // texts beyond 256 tokens (items of 8 query blocks), up to 256, up to 128: segments of 16 / 8 / 4 tiles at 64, 8 / 8 / 4 at 128
+        constexpr int C = decltype(cls)::value, KTS = C == 2 ? 4 : (C == 0 && NB == 1 ? 16 : 8), NW = KTS >= 8 ? 8 : 4;
+        attn_launch<attention_causal_packed_kernel<NB, KTS, NW, C == 0>, attn_lds_bytes(KTS, NW, NB)>(dim3((unsigned)n * (unsigned)heads), NW * 64, s, (const bf16_t*)qkv, first, n,
+                                                                                                     heads, kvh, (bf16_t*)ctx, blocked);
     });
+}
+void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, int head_dim, void* ctx, hipStream_t s, int blocked) {
+    if (head_dim == 128) launch_causal_packed<2>(qkv, items, nitems, heads, kv_heads, ctx, blocked, s);
+    else launch_causal_packed<1>(qkv, items, nitems, heads, kv_heads, ctx, blocked, s);
 }
 void sc_launch_rmsnorm(const void* in, int tokens, int H, const float* g, float eps, void* out, hipStream_t s) {
     int blocks = (tokens + 7) / 8;  // 8 rows per workgroup per sweep

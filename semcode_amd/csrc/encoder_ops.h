@@ -88,15 +88,14 @@ void sc_launch_attention_window_packed(const void* qkv, const int32_t* items, co
 // lens / items as the two attention launchers above.  rmsnorm: x * rsqrt(mean(x^2) + eps) * gamma, bf16 rows, H a multiple of 8, <= 2048.
 // last_pool: the row start + len - 1 of every text (starts NULL: a [B, S] rectangle, lens clamped to 1 .. S) of x [rows, H] bf16, RMSNorm in
 // f32, optional L2 normalisation by the rule of the mean kernels -> out [B, H] f32.
-// Head dimension 128 (the ...128 launchers): a head is two consecutive 64-column blocks, qkv rows are [Q | K | V] x 128 columns, ctx [rows, heads * 128].
+// head_dim 128: a head is two consecutive 64-column blocks, qkv rows are [Q | K | V] x 128 columns, ctx [rows, heads * 128].
 // qknorm_rope: in place on the 64-column blocks [(heads + kv_heads) * head_dim / 64 ...][M][64] of the Q and K heads: RMSNorm over each head's
 // head_dim values when gq / gk [head_dim] are non-NULL (both or neither), then the rotate-half rotation from the tables [max_pos][head_dim / 2].
 // pos NULL: position = row & (S - 1), S a power of two; else pos [M], clamped to max_pos - 1.
 bool sc_attention_causal_supported(int heads, int kv_heads, int head_dim = 64);
-void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
-void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
-void sc_launch_attention_causal128(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
-void sc_launch_attention_causal128_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_causal(const void* qkv, const int32_t* lens, int B, int S, int heads, int kv_heads, int head_dim, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_causal_packed(const void* qkv, const int32_t* items, const int* nitems, int heads, int kv_heads, int head_dim, void* ctx, hipStream_t s,
+                                       int blocked = 0);
 void sc_launch_qknorm_rope(void* qkv, int64_t M, int heads, int kv_heads, int head_dim, int S, const int32_t* pos, int max_pos, const float* cos_t, const float* sin_t,
                            const float* gq, const float* gk, float eps, hipStream_t s);
 void sc_launch_rmsnorm(const void* in, int tokens, int H, const float* g, float eps, void* out, hipStream_t s);

@@ -226,7 +226,7 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
     if (c.arch != 2 && c.qk_norm != 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: qk_norm %d needs arch 2 (the per-head RMSNorm of Q and K exists in the causal pipeline only)", c.qk_norm);
     if (c.arch == 2) {
-        // the causal pipeline: heads of 64 (rope_qk_kernel, attention_causal_kernel) or, stated, of 128 (qknorm_rope_kernel, attention_causal128_kernel); SwiGLU
+        // the causal pipeline: heads of 64 (rope_qk_kernel, attention_causal_kernel) or, stated, of 128 (qknorm_rope_kernel, attention_causal_kernel<2, ..>); SwiGLU
         if (c.head_dim != 0 && c.head_dim != 64 && c.head_dim != 128)
             return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim must be 0 (hidden / heads, which must be 64), 64 or 128 on arch 2, got %d", c.head_dim);
         if (c.qk_norm != 0 && c.qk_norm != 1) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: qk_norm must be 0 or 1, got %d", c.qk_norm);
@@ -533,6 +533,11 @@ static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int 
     if (pk) sc_launch_attention_packed(e->qkv, pk->items, pk->nitems, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
     else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
 }
+static void launch_attention_causal(sc_encoder* e, const int32_t* lens_dev, int B, int S, int M, const PackedLayout* pk, hipStream_t s) {
+    const sc_encoder_cfg& c = e->cfg;
+    if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, head_width(c), e->ctx, s, M);
+    else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, head_width(c), e->ctx, s, M);
+}
 // [CLS] pooling applies to texts only: the pairs of a cross-encoder take their [CLS] row whatever the mode (PackedLayout::types)
 static bool cls_pooling(const sc_encoder* e, const PackedLayout* pk) { return e->pooling == 1 && !(pk && pk->types); }
 // The last layer of a [CLS]-pooled forward from its QKV projection (e->qkv, rotated) on: attention of each text's first row, that row of the
@@ -749,12 +754,7 @@ static sc_status forward_causal_locked(sc_encoder* e, const int32_t* ids_dev, co
         if (HD == 128 || c.qk_norm)  // per-head RMSNorm of Q and K (qk_norm) and the rotation in one pass; the 64-wide model without it keeps rope_qk_kernel
             sc_launch_qknorm_rope(e->qkv, M, c.heads, c.kv_heads, HD, S, pk ? pk->pos : nullptr, c.max_pos, e->rope_cos, e->rope_sin, w.qng, w.kng, c.ln_eps, s);
         else launch_rope(e, M, S, pk, s);
-        sc_with_prof(rt, SC_PROF_ATTN, [&] {
-            if (HD == 128 && pk) sc_launch_attention_causal128_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
-            else if (HD == 128) sc_launch_attention_causal128(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, e->ctx, s, M);
-            else if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, e->ctx, s, M);
-            else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, e->ctx, s, M);
-        });
+        sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_attention_causal(e, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, AW, w.wo, AW, w.bo, e->x, H, e->y, H, M, H, AW, s, sk, skb); });
         sc_launch_rmsnorm(e->y, tokens, H, w.ln2g, c.ln_eps, e->x1, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });

@@ -426,7 +426,7 @@ extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, 
                                               int32_t kv_heads, int32_t blocked_rows, float* out) {
     return diag_attention_causal("sc_diag_attention_causal", rt, qkv, starts, lens, B, S, heads, kv_heads, 64, blocked_rows, out);
 }
-// ... with the head dimension stated: 64, or 128 (sc_launch_attention_causal128 / _packed); columns x head_dim
+// ... with the head dimension stated: 64 or 128; columns x head_dim
 extern "C" sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
                                                  int32_t kv_heads, int32_t head_dim, int32_t blocked_rows, float* out) {
     return diag_attention_causal("sc_diag_attention_causal_hd", rt, qkv, starts, lens, B, S, heads, kv_heads, head_dim, blocked_rows, out);
@@ -467,10 +467,8 @@ static sc_status diag_attention_causal(const char* who, sc_runtime* rt, const fl
     if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
     else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
     SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
-    if (hd == 128 && starts) sc_launch_attention_causal128_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
-    else if (hd == 128) sc_launch_attention_causal128(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, dc.p, s, blocked_rows);
-    else if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, dc.p, s, blocked_rows);
-    else sc_launch_attention_causal(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, dc.p, s, blocked_rows);
+    if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, hd, dc.p, s, blocked_rows);
+    else sc_launch_attention_causal(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, hd, dc.p, s, blocked_rows);
     return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
 }
 

@@ -1,5 +1,5 @@
 """GPU: heads of 128 and QK-norm on the causal decoder pipeline (sc_encoder_cfg.arch 2 with head_dim / qk_norm: Qwen3-Embedding, Qwen2.5-1.5B)
-through the C ABI -- attention_causal128_kernel and qknorm_rope_kernel of encoder_causal.hip on their own, the whole forward against
+through the C ABI -- attention_causal_kernel<2, ..> and qknorm_rope_kernel of encoder_causal.hip on their own, the whole forward against
 transformers, its properties and its refusals.
 
 Bounds.
@@ -162,6 +162,42 @@ def test_causal128_kernel_packed_and_rectangle_agree_bit_for_bit(rt, heads, kvh)
     alone[:160] = qkv[2 * S:2 * S + 160]
     one = _native.diag_attention_causal(rt, alone, lens[2:3], heads, kvh, starts=np.zeros(1, np.int32), head_dim=HD)
     assert np.array_equal(bits(one[:129]), bits(rect[2 * S:2 * S + 129]))
+
+
+def test_causal_widths_agree_on_a_zero_padded_head(rt):
+    """One fold, one body and one launch path serve both widths, told apart by the number of 64-column blocks of a head: this pins the
+    width-dependent strides, image offsets, fragment and tile counts against each other.  A 129-token text (second segment of the 8-tile
+    class, first of the 16-tile class), 4 / 2 heads, in a rectangle of S = 256 and as a packed item.  The 128-wide input is the 64-wide
+    one with 64 zero columns appended to every head; its Q is rounded to bf16 from sqrt(2) times the unrounded values the 64-wide Q is
+    rounded from, so that q . k / sqrt(128) is the 64-wide q . k / sqrt(64) up to the two roundings of q and of the scale constant.  The
+    float64 reference is the 64-wide one, from the 64-wide Q, K, V as they are; each width is held against it by the kernel bound of this
+    file (max 3e-2, median 3e-3).  The extra rounding of the 128-wide Q moves a score by at most 2^-8 relative per term with random signs:
+    about 2^-8 / sqrt(3) * sqrt(64) * 2 * 0.8 / 8 = 3.6e-3 on a score of standard deviation 2, the size of term (a) above.  The appended
+    columns see V = 0 only: exactly zero."""
+    heads, kvh, n, S = 4, 2, 129, 256
+    rng = np.random.default_rng(8700)
+    raw = rng.standard_normal((S, heads + 2 * kvh, 64)).astype(np.float32)
+    raw[:, :heads] *= 2.0  # scores of standard deviation 2, as make_qkv
+    x64 = bf16_round(raw)
+    x128 = np.zeros((S, heads + 2 * kvh, HD), np.float32)
+    x128[:, :, :64] = x64
+    x128[:, :heads, :64] = bf16_round(raw[:, :heads] * np.float32(np.sqrt(2.0)))
+    x64, x128 = x64.reshape(S, -1), x128.reshape(S, -1)
+    lens, zero = np.array([n], np.int32), np.zeros(1, np.int32)
+    q, k, v = (x64[:n].astype(np.float64).reshape(n, -1, 64)[:, a:b].transpose(1, 0, 2) for a, b in ((0, heads), (heads, heads + kvh), (heads + kvh, heads + 2 * kvh)))
+    of = [h // (heads // kvh) for h in range(heads)]
+    s = np.where((np.arange(n)[None, :] <= np.arange(n)[:, None])[None], q @ k[of].transpose(0, 2, 1) / 8.0, -np.inf)
+    e = np.exp(s - s.max(-1, keepdims=True))
+    ref = ((e / e.sum(-1, keepdims=True)) @ v[of]).transpose(1, 0, 2)  # [n, heads, 64]
+    for form, kw in (("rect", dict(S=S)), ("packed", dict(starts=zero))):
+        o64 = _native.diag_attention_causal(rt, x64, lens, heads, kvh, **kw)[:n].reshape(n, heads, 64)
+        o128 = _native.diag_attention_causal(rt, x128, lens, heads, kvh, head_dim=HD, **kw)[:n].reshape(n, heads, HD)
+        e64, e128 = np.abs(o64 - ref), np.abs(o128[:, :, :64] - ref)
+        print(f"{form}: 64-wide max err {e64.max():.3e} median {np.median(e64):.3e}; 128-wide max err {e128.max():.3e} median {np.median(e128):.3e}; "
+              f"128 against 64 max {np.abs(o128[:, :, :64] - o64).max():.3e}")
+        assert e64.max() <= 3e-2 and np.median(e64) <= 3e-3, (form, e64.max(), np.median(e64))
+        assert e128.max() <= 3e-2 and np.median(e128) <= 3e-3, (form, e128.max(), np.median(e128))
+        assert (o128[:, :, 64:] == 0).all(), form
 
 
 # ------------------------------------------------------------------ 2. QK-norm + rotation
