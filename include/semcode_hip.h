@@ -340,6 +340,55 @@ sc_status sc_encoder_set_score_head(sc_encoder* enc, const sc_score_head* head /
 sc_status sc_encoder_score_seqs(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, float* out_logits /*[B,num_labels]*/,
                                 float* out_rows /*[B,H] or NULL*/);
 
+/* Late interaction (ColBERT): one vector per token and MaxSim, the second kind of reranker next to the cross-encoders above.  A document is
+ * encoded once, independently of the question; a (question, document) pair then costs one small matrix product.  New surface: the pair
+ * head, the score head, the pooling mode and every embedding call stay as they are and are unaffected by the token head, and it by them.
+ * The forward is the packed forward's up to and including the model's last norm, with no pooling kernel and no pruned [CLS] last layer;
+ * the token head then runs on the rows that are asked for.  As a scored call, a token call never takes the split-K GEMMs, and on arch 0 its
+ * pipeline does not follow its row count: the LayerNorm-folded pipeline where the model's shapes allow it, the stand-alone one otherwise
+ * (sc_encoder_set_path 2 still forces the stand-alone one, and the two differ in their rounding points).  So a text's vectors are the same
+ * bits whichever batch-mates it has and wherever it stands among them.
+ *   token head (token_head_kernel):  v = Wt x, Wt [W,H] rounded to bf16 once at install, x the bf16 row after the last norm (arch 0: the last
+ *     layer's second LayerNorm; arch 1: final_norm), f32 accumulation by v_mfma_f32_16x16x32_bf16 over k ascending in steps of 32; then
+ *     v * (1 / max(sqrt(|v|^2), 1e-12)), |v|^2 reduced in a fixed order (per lane over its 4-column pieces in ascending column tile, then the
+ *     four lanes of a row by the xor butterfly 16, 32).  No bias.  W a multiple of 16 within 16 .. 128.  No atomics.
+ *   rows asked for:  expand_id < 0 (documents): the len_i real rows of text i.  expand_id >= 0 (queries): all ceil32(len_i) rows of the text's
+ *     32-row span; the alignment rows len_i .. ceil32(len_i) carry token expand_id (the model's [MASK]) at the positions that continue the
+ *     text's, are attended as queries and stay masked as keys -- ColBERT's query augmentation with unattended [MASK] tokens at query_maxlen
+ *     32.  A query has at most 128 tokens.  Vectors are written compactly, text after text: out[tok_start[i] + t][W].
+ *   MaxSim (maxsim_kernel; the rule lives once, in semcode_amd/csrc/maxsim_rule.h):  dot(Q_t, D_j) = one fmaf chain from +0 in the canonical
+ *     k order of the f32 MFMA (inside each block of 16: k = 16 t + 4 g + c, c outer, g inner);  m_t = the maximum over the kept j < nd under
+ *     the total order of the order-preserving score key (-0 < +0);  score = ((+0 + m_0) + m_1) + ..., t ascending, one correctly rounded
+ *     addition at a time, never fused.  One workgroup per pair, document tokens in tiles of 16 spread over four waves, the waves' maxima
+ *     combined through the LDS under the same order, the sum taken by one lane.  Bit-identical to sc_diag_maxsim_host for every finite input.
+ * sc_encoder_set_token_head installs, replaces or (w == NULL) removes the head; the array is copied before it returns and it waits for the
+ * stream before a head goes.  SC_ERR_UNSUPPORTED on an arch 2 encoder; SC_ERR_INVALID for a W outside the rule -- the installed head stays.
+ * sc_encoder_embed_tokens: ids / offsets as sc_encoder_embed_packed; out [sum n_i, W] f32 and out_counts [B] = n_i (host).  Synchronises.
+ * sc_encoder_score_late: the queries' forward into one device buffer, the documents' into a second, maxsim_kernel over the P pairs
+ * (pair_q[p], pair_d[p]); out_scores [P].  d_keep: one byte per document token in d_ids order, 0 = the token takes no part in a maximum
+ * (punctuation), NULL = every token does.  The token vectors never leave the device; the call synchronises once, at its end.  It uses the two
+ * pinned plan slots, one per side; the token buffers belong to the encoder and grow on demand.
+ * With nothing launched and nothing changed -- SC_ERR_INVALID: no head installed, a NULL pointer, B outside 1 .. 65536, offsets[0] != 0, a
+ * text shorter than 1 token, longer than 2 048 tokens or than max_pos, a query longer than 128 tokens, on an arch 1 model with local layers a query whose last expansion row lies more than local_window / 2
+ * behind its last token (it would see no key there; never the case at the released window of 128), expand_id outside the vocabulary, P < 1,
+ * a pair index out of range, a document without a kept token; SC_ERR_UNSUPPORTED: an arch 2 encoder, either side over
+ * SC_ENCODER_PACKED_MAX_ROWS token rows.
+ * sc_diag_maxsim runs the kernel alone on uploaded arrays, sc_diag_maxsim_host the rule on the CPU (no GPU involved): Q / D [.., W] f32 token
+ * vectors, text i's at rows [off[i], off[i + 1]) (int32 offsets from 0), keep NULL or one byte per document token.  A document without a
+ * kept token scores nq * -inf = -inf there.
+ * Out of scope: arch 2; _dev / asynchronous forms; storing token vectors in the index (a multi-vector collection); query lengths above
+ * 128; XLM-R backbones (jina-colbert-v2); a projection with a bias. */
+sc_status sc_encoder_set_token_head(sc_encoder* enc, const float* w /*[W,H] or NULL*/, int32_t W);
+sc_status sc_encoder_embed_tokens(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, int32_t expand_id, float* out /*[sum n_i,W]*/,
+                                  int32_t* out_counts /*[B]*/);
+sc_status sc_encoder_score_late(sc_encoder* enc, const int32_t* q_ids, const int64_t* q_offsets, int32_t Bq, int32_t expand_id, const int32_t* d_ids,
+                                const int64_t* d_offsets, int32_t Bd, const uint8_t* d_keep /*or NULL*/, const int32_t* pair_q, const int32_t* pair_d, int32_t P,
+                                float* out_scores /*[P]*/);
+sc_status sc_diag_maxsim(sc_runtime* rt, const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const uint8_t* keep,
+                         const int32_t* pair_q, const int32_t* pair_d, int32_t P, int32_t W, float* out);
+sc_status sc_diag_maxsim_host(const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const uint8_t* keep,
+                              const int32_t* pair_q, const int32_t* pair_d, int32_t P, int32_t W, float* out);
+
 /* ----------------------------------------------------------------- tokenizer ---- */
 typedef struct sc_tokenizer sc_tokenizer;
 /* Host-side WordPiece tokenizer (BERT scheme), the step the reference leaves to its provider's library (raw strings

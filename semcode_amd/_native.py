@@ -95,6 +95,13 @@ SIGNATURES = {
     "sc_encoder_score_pairs": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_encoder_set_score_head": (C.c_int32, [C.c_void_p, C.POINTER(ScoreHead)]),
     "sc_encoder_score_seqs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_encoder_set_token_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "sc_encoder_embed_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_encoder_score_late": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+                              + [C.c_int32, C.c_void_p]),
+    "sc_diag_maxsim": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+                       + [C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_maxsim_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_score_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ScoreHead), C.c_void_p]),
     "sc_diag_embed_pairs": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32,
                                                                                                                        C.c_void_p, C.c_void_p]),
@@ -854,6 +861,7 @@ class Encoder:
         self.max_pos = c["max_pos"]
         self.num_labels = 0  # of the installed pair head (set_pair_head)
         self.score_labels = 0  # of the installed score head (set_score_head)
+        self.token_width = 0  # W of the installed token head (set_token_head)
         self._h = C.c_void_p()
         need = C.c_int64()
         _check(lib().sc_encoder_blob_bytes(C.byref(self.cfg), C.byref(need)))
@@ -1031,6 +1039,49 @@ class Encoder:
         rows = np.empty((B, self.hidden), dtype=np.float32) if want_rows else None
         _check(lib().sc_encoder_score_seqs(self.handle, _ptr(ids_flat), _ptr(offsets), B, _ptr(logits), _ptr(rows)))
         return (logits, rows) if want_rows else logits
+
+    # ---- late interaction (ColBERT): one vector per token, MaxSim over (query, document) pairs
+    def set_token_head(self, w) -> None:
+        """Install (or replace) the per-token projection w [W, hidden] (no bias; rounded to bf16 once); None removes it."""
+        if w is None:
+            _check(lib().sc_encoder_set_token_head(self.handle, None, 0))
+            self.token_width = 0
+            return
+        w = _f32(w)
+        if w.ndim != 2 or w.shape[1] != self.hidden:
+            raise ValueError("w must be [W, hidden]")
+        _check(lib().sc_encoder_set_token_head(self.handle, _ptr(w), int(w.shape[0])))
+        self.token_width = int(w.shape[0])
+
+    def embed_tokens(self, ids_flat, offsets, expand_id: int = -1) -> "tuple[np.ndarray, np.ndarray]":
+        """Packed texts -> (vectors [sum n_i, W] f32, L2-normalised, text after text; counts [B] = n_i).  expand_id < 0 (documents):
+        n_i = len_i.  expand_id >= 0 (queries): n_i = len_i rounded up to 32, the added rows carry that token ([MASK]) and are
+        never attended as keys."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        lens = np.diff(offsets)
+        n = (lens + 31) // 32 * 32 if expand_id >= 0 else lens
+        out = np.empty((int(n.sum()), max(1, getattr(self, "token_width", 0))), dtype=np.float32)
+        counts = np.empty(B, dtype=np.int32)
+        _check(lib().sc_encoder_embed_tokens(self.handle, _ptr(ids_flat), _ptr(offsets), B, int(expand_id), _ptr(out), _ptr(counts)))
+        return out, counts
+
+    def score_late(self, q_ids, q_offsets, d_ids, d_offsets, pair_q, pair_d, expand_id: int = -1, d_keep=None) -> np.ndarray:
+        """MaxSim scores [P] of the pairs (pair_q[p], pair_d[p]) over the token vectors of the packed queries and documents; the vectors
+        stay on the device.  d_keep: one uint8 per document token, 0 = left out of every maximum (punctuation); None = all kept."""
+        q_ids, q_offsets, Bq = self._packed_args(q_ids, q_offsets)
+        d_ids, d_offsets, Bd = self._packed_args(d_ids, d_offsets)
+        pair_q = np.ascontiguousarray(pair_q, dtype=np.int32)
+        pair_d = np.ascontiguousarray(pair_d, dtype=np.int32)
+        if pair_q.ndim != 1 or pair_q.shape != pair_d.shape:
+            raise ValueError("pair_q and pair_d must be [P]")
+        if d_keep is not None:
+            d_keep = np.ascontiguousarray(d_keep, dtype=np.uint8)
+            if d_keep.shape != d_ids.shape:
+                raise ValueError("d_keep must hold one flag per document token")
+        out = np.empty(max(1, len(pair_q)), dtype=np.float32)
+        _check(lib().sc_encoder_score_late(self.handle, _ptr(q_ids), _ptr(q_offsets), Bq, int(expand_id), _ptr(d_ids), _ptr(d_offsets), Bd, _ptr(d_keep),
+                                           _ptr(pair_q), _ptr(pair_d), len(pair_q), _ptr(out)))
+        return out[: len(pair_q)]
 
     def embed_ids_dev(self, ids_ptr: int, lens_ptr: int, B: int, S: int, out_ptr: int) -> None:
         _check(lib().sc_encoder_embed_ids_dev(self.handle, C.c_void_p(ids_ptr), C.c_void_p(lens_ptr), int(B), int(S), C.c_void_p(out_ptr)))

@@ -121,6 +121,15 @@ bool sc_score_head_supported(int H, int num_labels);
 void sc_launch_score_head(const float* r, int B, int H, const float* Wd, const float* bd, const float* gam, const float* bet, float eps, const float* Wc,
                           const float* bc, int num_labels, float* logits, hipStream_t s);
 
+// ---- encoder_tokens.hip: late interaction.  token_head: x [rows, H] bf16 (rows a multiple of 32), w [W, H] bf16, dst [rows] = the compact output
+// row of every packed row or -1 -> out[dst][W] f32 = the L2-normalised projection (the pooling kernels' 1e-12 rule).  W % 16 == 0, 16 .. 128;
+// H % 32 == 0.  maxsim: the rule of maxsim_rule.h over P pairs: Q [.., W] / D [.., W] f32 token vectors, text i's at rows [off[i], off[i + 1]),
+// keep NULL or one byte per document token, pair_q / pair_d [P] -> out [P].  A query has at most 128 tokens.  All device pointers.
+bool sc_token_head_supported(int H, int W);
+void sc_launch_token_head(const void* x, int rows, int H, const void* w, int W, const int32_t* dst, float* out, hipStream_t s);
+void sc_launch_maxsim(const float* Q, const int32_t* q_off, const float* D, const int32_t* d_off, const uint8_t* keep, const int32_t* pair_q, const int32_t* pair_d,
+                      int P, int W, float* out, hipStream_t s);
+
 // ---- encoder_cls.hip: [CLS] pooling.  starts NULL: text i's first row is i * S (a rectangle), else starts[i] (packed rows).
 // cls_pool: that row of x [rows, H] bf16 -> out [B, H] f32; gamma / beta non-NULL: the rows are raw and are LayerNorm'ed (f32) first; normalize:
 // L2 normalisation by the rule of the mean kernels.  cls_gather: the same rows (optionally LayerNorm'ed) as bf16 [rows_pad, H], rows B .. rows_pad zero.

@@ -15,6 +15,8 @@
 // Rerankers of the other two families (sc_encoder_set_score_head / sc_encoder_score_seqs) run the packed forward as it is and pool the row
 // their head reads -- [CLS] or masked mean of final_norm (arch 1), RMS_final of the last token (arch 2), never L2-normalised
 // (PackedLayout::head_pool); the heads on those rows are encoder_heads.hip's.
+// Late-interaction models (sc_encoder_set_token_head / sc_encoder_embed_tokens / sc_encoder_score_late) run the packed forward without any pooling:
+// the token head projects every row that is asked for (PackedLayout::tok_dst) and MaxSim scores pairs over those vectors (encoder_tokens.hip).
 // Pre-norm models (cfg.arch 1, ModernBERT): forward_prenorm_locked -- h += Attn(LN(h)), h += MLP(LN(h)) on a raw residual stream, local
 // (sliding-window) attention in the layers with l % global_every != 0 (encoder_window.hip), a rotary table per kind of layer, final_norm.
 // Causal decoders (cfg.arch 2, the Qwen2 family): forward_causal_locked -- the same raw residual stream with RMSNorm, grouped-query causal
@@ -26,6 +28,7 @@
 #include <vector>
 
 #include "encoder_ops.h"
+#include "maxsim_rule.h"
 #include "sc_internal.h"
 
 struct LayerW {
@@ -96,6 +99,15 @@ struct sc_encoder {
     float *sh_wd = nullptr, *sh_bd = nullptr, *sh_g = nullptr, *sh_b = nullptr, *sh_wc = nullptr, *sh_bc = nullptr;
     int sh_kind = 0, sh_pooling = 0, sh_labels = 0;
     float sh_eps = 0.f;
+    // the token head of a late-interaction model (sc_encoder_set_token_head), a third slot: the projection [W, H] as bf16; NULL = none
+    void* thead = nullptr;
+    int th_w = 0;
+    // token vectors of sc_encoder_embed_tokens / sc_encoder_score_late: the queries' (0) and the documents' (1) [rows][W] f32, and the
+    // pair call's offsets | keep flags | pair list | scores; each grows on demand and is kept
+    struct Grown {
+        char* p = nullptr;
+        size_t cap = 0;
+    } tok[2], late_aux;
     std::mutex mu;
 };
 
@@ -115,13 +127,18 @@ struct PackedLayout {
     // sequences of sc_encoder_score_seqs: the pooling of the installed score head (0 mean, 1 first row, 2 last token) instead of the encoder's
     // mode, and no L2 normalisation.  -1: texts to embed.
     int head_pool = -1;
+    // token calls (sc_encoder_embed_tokens, sc_encoder_score_late): the compact output row of every packed row, -1 for a row that is not
+    // asked for.  Nothing is pooled and the last layer is never pruned: the token head runs on the rows after the model's last norm and writes
+    // tok_out [.., W] f32 (device); the forward's out_dev is not written.  NULL: one row per text.
+    const int32_t* tok_dst = nullptr;
+    float* tok_out = nullptr;
 };
 // The plan of one packed call, laid out alike in pinned host staging and in e->plan (M token rows, B sequences): monotone in both, so
 // a call's plan fits the buffer of any larger workspace
 // (pairs: the segment id of every row and a length of one per pair come behind the rest, so that a plan without them lies as before).
 struct PlanOffsets {
-    size_t ids, pos, starts, lens, items, types = 0, ones = 0, total;
-    PlanOffsets(size_t M, size_t B, bool pairs = false) {
+    size_t ids, pos, starts, lens, items, types = 0, ones = 0, dst = 0, total;
+    PlanOffsets(size_t M, size_t B, bool pairs = false, bool tokens = false) {
         size_t u = 0;
         auto take = [&](size_t bytes) { const size_t at = u; u += sc_align256(bytes); return at; };
         ids = take(M * 4);
@@ -133,6 +150,7 @@ struct PlanOffsets {
             types = take(M * 4);
             ones = take(B * 4);
         }
+        if (tokens) dst = take(M * 4);  // (never together with pairs, and no larger than what pairs add: the workspace's plan holds either)
         total = u;
     }
 };
@@ -462,6 +480,10 @@ extern "C" sc_status sc_encoder_destroy(sc_encoder* e) {
     hipFree(e->splitk);
     hipFree(e->head);
     hipFree(e->shead);
+    hipFree(e->thead);
+    hipFree(e->tok[0].p);
+    hipFree(e->tok[1].p);
+    hipFree(e->late_aux.p);
     for (auto& slot : e->pin) {
         if (slot.host) hipHostFree(slot.host);
         if (slot.done) hipEventDestroy(slot.done);
@@ -539,7 +561,15 @@ static void launch_attention_causal(sc_encoder* e, const int32_t* lens_dev, int 
     else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, head_width(c), e->ctx, s, M);
 }
 // [CLS] pooling applies to texts only: the pairs of a cross-encoder take their [CLS] row whatever the mode (PackedLayout::types)
-static bool cls_pooling(const sc_encoder* e, const PackedLayout* pk) { return e->pooling == 1 && !(pk && pk->types); }
+// (a token call pools nothing)
+static bool token_call(const PackedLayout* pk) { return pk && pk->tok_dst; }
+static bool cls_pooling(const sc_encoder* e, const PackedLayout* pk) { return e->pooling == 1 && !(pk && pk->types) && !token_call(pk); }
+// the token head on the rows `x` after the model's last norm, in place of a pooling kernel
+static sc_status launch_token_head(sc_encoder* e, const void* x, const PackedLayout* pk, hipStream_t s) {
+    sc_launch_token_head(x, pk->rows, e->cfg.hidden, e->thead, e->th_w, pk->tok_dst, pk->tok_out, s);
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
 // The last layer of a [CLS]-pooled forward from its QKV projection (e->qkv, rotated) on: attention of each text's first row, that row of the
 // layer's input as the residual, then the rest of the layer on Mc = ceil256(B) compact rows with the small-batch pipeline's launches, and the
 // last LayerNorm inside the pooling kernel.  e->x: the layer's input, normalised, or (res_g != NULL) raw with the LayerNorm (res_g, res_b) pending.
@@ -645,6 +675,10 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
         });
     }
     const LayerW& last = e->layers[c.layers - 1];
+    if (token_call(pk)) {  // the token head reads normalised rows, as the plain pooling kernel below
+        sc_launch_layernorm(e->x, tokens, H, last.ln2g, last.ln2b, c.ln_eps, e->x1, s);
+        return launch_token_head(e, e->x1, pk, s);
+    }
     if (cls) {  // the last LayerNorm on B rows, inside the pooling kernel
         sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, last.ln2g, last.ln2b, c.ln_eps, c.normalize, out_dev, s);
     } else if (c.normalize && !(pk && pk->types)) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
@@ -682,7 +716,8 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
     const bool scored = pk && pk->head_pool >= 0;  // the row a score head reads: its own pooling, never L2-normalised
     // A scored call (sc_encoder_score_seqs) never splits K: the split and its factor follow the call's row count, and a pair's logits must be
     // the same bits whichever batch-mates it has.  Every GEMM is then the 256-tile kernel, whose sums for a row do not depend on M.
-    if (M <= 1024 && e->path != 1 && !scored) {
+    // (a token call neither: a text's vectors are the same bits whichever batch-mates it has)
+    if (M <= 1024 && e->path != 1 && !scored && !token_call(pk)) {
         if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
         sk = e->splitk;
     }
@@ -708,6 +743,10 @@ static sc_status forward_prenorm_locked(sc_encoder* e, const int32_t* ids_dev, c
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
         launch_gate(c, e->hm, M, F, e->hg, s);
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
+    }
+    if (token_call(pk)) {
+        sc_launch_layernorm(e->x, tokens, H, e->fing, e->finb, c.ln_eps, e->x1, s);
+        return launch_token_head(e, e->x1, pk, s);
     }
     if (scored ? pk->head_pool == 1 : cls_pooling(e, pk)) {
         sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, e->fing, e->finb, c.ln_eps, scored ? 0 : c.normalize, out_dev, s);
@@ -785,9 +824,12 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
     if (c.arch == 2) return forward_causal_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
     // batches beyond 1024 token rows (or sc_encoder_set_path 1) take the LayerNorm-folded pipeline where the model's shapes allow it
     static const bool env_fold = sc_env_flag("SC_ENC_FOLD", true);  // SC_ENC_FOLD=0: same-box A/B against the stand-alone LayerNorm kernels
-    if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
+    // A token call's pipeline does not follow its row count (a text's vectors are the same bits whichever batch-mates it has): the folded one
+    // where the model allows it, the stand-alone one without split-K otherwise or under sc_encoder_set_path 2
+    const bool tok = token_call(pk);
+    if (e->foldable && e->path != 2 && (M > 1024 || e->path == 1 || tok) && env_fold) return forward_folded_locked(e, ids_dev, lens_dev, B, S, out_dev, pk);
     void* sk = nullptr;
-    if (M <= 1024 && e->path != 1) {  // a query or a few chunks: too few tiles for the chip, split K (gemm_bf16.hip)
+    if (M <= 1024 && e->path != 1 && !tok) {  // a query or a few chunks: too few tiles for the chip, split K (gemm_bf16.hip)
         if (!e->splitk) SC_HIP(hipMalloc(&e->splitk, sc_encoder::SPLITK_BYTES));
         sk = e->splitk;
     }
@@ -826,6 +868,7 @@ static sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, ffn_blocked ? SC_LDC_BLOCKED64 : F, w.w2, F, w.b2, e->x1, H, e->y, H, M, H, F, s, sk, skb); });
         sc_launch_layernorm(e->y, tokens, H, w.ln2g, w.ln2b, c.ln_eps, e->x, s);
     }
+    if (tok) return launch_token_head(e, e->x, pk, s);
     if (cls) sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, nullptr, nullptr, c.ln_eps, c.normalize, out_dev, s);
     else launch_mean_pool(e, e->x, lens_dev, B, S, pk, out_dev, s);
     SC_HIP(hipGetLastError());
@@ -998,10 +1041,18 @@ extern "C" sc_status sc_encoder_packed_rows(sc_encoder* e, const int64_t* offset
 // first_lens (NULL or [B], validated): the batch holds the pairs of a cross-encoder -- the first first_lens[i] rows of pair i take segment
 // id 0, the rest of the pair 1, and e->pooled receives the last hidden state of every pair's first row.
 // head_pool >= 0 (sc_encoder_score_seqs): e->pooled receives the rows the score head reads (PackedLayout::head_pool).
+// tk != NULL (sc_encoder_embed_tokens, sc_encoder_score_late): a token call -- tk->out (device) receives the token vectors of the rows asked for,
+// compactly and in text order; e->pooled is not written.  tk->expand_id >= 0: queries -- every row of a text's 32-row span is asked for and its
+// alignment rows carry that token instead of token 0; < 0: documents -- the len_i real rows.
+struct TokenCall {
+    int32_t expand_id;
+    float* out;
+};
 static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, int64_t used, sc_encoder::PinSlot& slot,
-                                     const int64_t* index_rows, const int64_t** rows_out, const int32_t* first_lens = nullptr, int head_pool = -1) {
+                                     const int64_t* index_rows, const int64_t** rows_out, const int32_t* first_lens = nullptr, int head_pool = -1,
+                                     const TokenCall* tk = nullptr) {
     const int64_t M = (used + 255) / 256 * 256;
-    const PlanOffsets po((size_t)M, (size_t)B, first_lens != nullptr);
+    const PlanOffsets po((size_t)M, (size_t)B, first_lens != nullptr, tk != nullptr);
     sc_status st = pin_slot_reserve(slot, po.total + (size_t)B * 8);
     if (st) return st;
     int32_t* h_ids = (int32_t*)(slot.host + po.ids);
@@ -1029,6 +1080,16 @@ static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const in
             h_ones[i] = 1;
         }
     }
+    if (tk) {
+        int32_t* h_dst = (int32_t*)(slot.host + po.dst);
+        memset(h_dst, 0xFF, (size_t)M * 4);  // -1: alignment rows of documents and the tail are not asked for
+        int32_t at = 0;
+        for (int32_t i = 0; i < B; ++i) {
+            const int32_t n = tk->expand_id >= 0 ? (int32_t)ceil32(h_lens[i]) : h_lens[i];
+            for (int32_t j = h_lens[i]; j < n; ++j) h_ids[h_starts[i] + j] = tk->expand_id;
+            for (int32_t j = 0; j < n; ++j) h_dst[h_starts[i] + j] = at++;
+        }
+    }
     PackedLayout pk{};
     sc_packed_items(h_starts, h_lens, B, h_items, pk.nitems);
     if (index_rows) {
@@ -1045,6 +1106,10 @@ static sc_status embed_packed_locked(sc_encoder* e, const int32_t* ids, const in
     pk.rows = (int)used;
     if (first_lens) pk.types = (const int32_t*)(e->plan + po.types);
     pk.head_pool = head_pool;
+    if (tk) {
+        pk.tok_dst = (const int32_t*)(e->plan + po.dst);
+        pk.tok_out = tk->out;
+    }
     return forward_locked(e, (const int32_t*)(e->plan + po.ids), (const int32_t*)(e->plan + (first_lens ? po.ones : po.lens)), B, 0, e->pooled, &pk);
 }
 
@@ -1335,6 +1400,201 @@ extern "C" sc_status sc_encoder_score_seqs(sc_encoder* e, const int32_t* ids, co
     SC_HIP(hipMemcpyAsync(out_logits, e->logits, (size_t)B * nl * 4, hipMemcpyDeviceToHost, s));
     if (out_rows) SC_HIP(hipMemcpyAsync(out_rows, e->pooled, (size_t)B * H * 4, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------ late interaction (ColBERT): token vectors and MaxSim
+extern "C" sc_status sc_encoder_set_token_head(sc_encoder* e, const float* w, int32_t W) {
+    const char* who = "sc_encoder_set_token_head";
+    if (!e) return sc_fail(SC_ERR_INVALID, "%s: NULL encoder", who);
+    if (e->cfg.arch == 2) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models have no token head: late interaction needs bidirectional token rows", who);
+    const size_t H = (size_t)e->cfg.hidden;
+    if (w && !sc_token_head_supported((int)H, W)) return sc_fail(SC_ERR_INVALID, "%s: W = %d must be a multiple of 16 within 16 .. 128", who, W);
+    std::lock_guard<std::mutex> g(e->mu);
+    SC_HIP(hipSetDevice(e->rt->device));
+    hipStream_t s = e->rt->stream;
+    void* fresh = nullptr;
+    if (w) {
+        const size_t n = (size_t)W * H;
+        sc_devbuf stage;
+        if (stage.alloc(n * 4) != hipSuccess) return sc_fail(SC_ERR_NOMEM, "hipMalloc token head staging (%zu B) failed", n * 4);
+        hipError_t he = hipMalloc(&fresh, n * 2);
+        if (he != hipSuccess) return sc_fail(SC_ERR_NOMEM, "hipMalloc token head (%zu B) failed: %s", n * 2, hipGetErrorString(he));
+        hipError_t up = hipMemcpyAsync(stage.p, w, n * 4, hipMemcpyHostToDevice, s);
+        if (up == hipSuccess) {
+            sc_launch_f32_to_bf16((const float*)stage.p, fresh, (int64_t)n, s);  // rounded once, as every encoder weight
+            up = hipGetLastError();
+        }
+        const hipError_t sy = hipStreamSynchronize(s);  // the caller's array and the staging copy are free on return; nothing still reads the head that goes
+        if (up == hipSuccess) up = sy;
+        if (up != hipSuccess) {
+            hipFree(fresh);
+            return sc_fail(SC_ERR_HIP, "token head upload failed: %s", hipGetErrorString(up));
+        }
+    } else {
+        SC_HIP(hipStreamSynchronize(s));  // nothing may still read the head that goes
+    }
+    hipFree(e->thead);
+    e->thead = fresh;
+    e->th_w = w ? W : 0;
+    return SC_OK;
+}
+
+// offsets of a token call: the packed rules, a query (expand_id >= 0) of at most 128 tokens, expand_id inside the vocabulary.
+// *used = packed rows, *nrows = token vectors asked for
+static sc_status check_token_offsets(sc_encoder* e, const int64_t* offsets, int32_t B, int32_t expand_id, const char* who, int64_t* used, int64_t* nrows) {
+    sc_status st = check_packed_offsets(e, offsets, B, who, used);
+    if (st) return st;
+    if (expand_id >= e->cfg.vocab) return sc_fail(SC_ERR_INVALID, "%s: expand_id %d outside the vocabulary (%d tokens)", who, expand_id, e->cfg.vocab);
+    if (expand_id < 0) {
+        *nrows = offsets[B];
+        return SC_OK;
+    }
+    const bool local_layers = e->cfg.arch == 1 && e->cfg.global_every > 1;
+    for (int32_t i = 0; i < B; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        if (len > MAXSIM_MAX_NQ) return sc_fail(SC_ERR_INVALID, "%s: query %d has %lld tokens, more than %d", who, i, (long long)len, MAXSIM_MAX_NQ);
+        // an expansion row attends the real keys only: in a local layer its last one must still reach the text's last token
+        if (local_layers && ceil32(len) - len > e->cfg.local_window / 2)
+            return sc_fail(SC_ERR_INVALID, "%s: query %d has %lld tokens: its last expansion row would see no key within local_window %d", who, i, (long long)len,
+                           e->cfg.local_window);
+    }
+    *nrows = *used;
+    return SC_OK;
+}
+
+static sc_status grow_locked(sc_encoder* e, sc_encoder::Grown& g, size_t bytes) {
+    if (bytes <= g.cap) return SC_OK;
+    SC_HIP(hipStreamSynchronize(e->rt->stream));
+    hipFree(g.p);
+    g.p = nullptr;
+    g.cap = 0;
+    const size_t cap = (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);
+    hipError_t he = hipMalloc((void**)&g.p, cap);
+    if (he != hipSuccess) return sc_fail(SC_ERR_NOMEM, "hipMalloc token buffer (%zu B) failed: %s", cap, hipGetErrorString(he));
+    g.cap = cap;
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_embed_tokens(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, int32_t expand_id, float* out,
+                                             int32_t* out_counts) {
+    const char* who = "sc_encoder_embed_tokens";
+    if (!e || !ids || !offsets || !out || !out_counts) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (e->cfg.arch == 2) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models have no token head", who);
+    int64_t used = 0, nrows = 0;
+    sc_status st = check_token_offsets(e, offsets, B, expand_id, who, &used, &nrows);
+    if (st) return st;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->thead) return sc_fail(SC_ERR_INVALID, "%s: no token head installed (sc_encoder_set_token_head)", who);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot& slot = e->pin[e->pin_next];
+    st = pin_slot_wait(slot);
+    if (st) return st;
+    const size_t bytes = (size_t)nrows * e->th_w * 4;
+    st = grow_locked(e, e->tok[1], bytes);
+    if (st) return st;
+    const TokenCall tk{expand_id, (float*)e->tok[1].p};
+    st = embed_packed_locked(e, ids, offsets, B, used, slot, nullptr, nullptr, nullptr, -1, &tk);
+    hipStream_t s = e->rt->stream;
+    if (st) {
+        hipStreamSynchronize(s);  // the slot's upload may be in flight
+        return st;
+    }
+    SC_HIP(hipMemcpyAsync(out, e->tok[1].p, bytes, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    for (int32_t i = 0; i < B; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i];
+        out_counts[i] = (int32_t)(expand_id >= 0 ? ceil32(len) : len);
+    }
+    return SC_OK;
+}
+
+extern "C" sc_status sc_encoder_score_late(sc_encoder* e, const int32_t* q_ids, const int64_t* q_offsets, int32_t Bq, int32_t expand_id, const int32_t* d_ids,
+                                           const int64_t* d_offsets, int32_t Bd, const uint8_t* d_keep, const int32_t* pair_q, const int32_t* pair_d, int32_t P,
+                                           float* out_scores) {
+    const char* who = "sc_encoder_score_late";
+    if (!e || !q_ids || !q_offsets || !d_ids || !d_offsets || !pair_q || !pair_d || !out_scores) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (e->cfg.arch == 2) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models have no token head", who);
+    if (P < 1) return sc_fail(SC_ERR_INVALID, "%s: P = %d pairs (needs at least 1)", who, P);
+    int64_t q_used = 0, q_rows = 0, d_used = 0, d_rows = 0;
+    sc_status st = check_token_offsets(e, q_offsets, Bq, expand_id, who, &q_used, &q_rows);
+    if (st) return st;
+    st = check_token_offsets(e, d_offsets, Bd, -1, who, &d_used, &d_rows);
+    if (st) return st;
+    if (expand_id < 0)  // (queries without expansion rows still have to fit the kernel)
+        for (int32_t i = 0; i < Bq; ++i)
+            if (q_offsets[i + 1] - q_offsets[i] > MAXSIM_MAX_NQ)
+                return sc_fail(SC_ERR_INVALID, "%s: query %d has %lld tokens, more than %d", who, i, (long long)(q_offsets[i + 1] - q_offsets[i]), MAXSIM_MAX_NQ);
+    for (int32_t p = 0; p < P; ++p)
+        if (pair_q[p] < 0 || pair_q[p] >= Bq || pair_d[p] < 0 || pair_d[p] >= Bd)
+            return sc_fail(SC_ERR_INVALID, "%s: pair %d = (%d, %d) outside the %d queries / %d documents", who, p, pair_q[p], pair_d[p], Bq, Bd);
+    if (d_keep)
+        for (int32_t i = 0; i < Bd; ++i) {
+            bool any = false;
+            for (int64_t j = d_offsets[i]; j < d_offsets[i + 1] && !any; ++j) any = d_keep[j] != 0;
+            if (!any) return sc_fail(SC_ERR_INVALID, "%s: document %d has no kept token", who, i);
+        }
+    // token offsets of both sides, as the kernel reads them
+    std::vector<int32_t> q_off((size_t)Bq + 1, 0), d_off((size_t)Bd + 1, 0);
+    for (int32_t i = 0; i < Bq; ++i) {
+        const int64_t len = q_offsets[i + 1] - q_offsets[i];
+        q_off[(size_t)i + 1] = q_off[(size_t)i] + (int32_t)(expand_id >= 0 ? ceil32(len) : len);
+    }
+    for (int32_t i = 0; i <= Bd; ++i) d_off[(size_t)i] = (int32_t)d_offsets[i];
+
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->thead) return sc_fail(SC_ERR_INVALID, "%s: no token head installed (sc_encoder_set_token_head)", who);
+    SC_HIP(hipSetDevice(e->rt->device));
+    sc_encoder::PinSlot &slot_q = e->pin[e->pin_next], &slot_d = e->pin[e->pin_next ^ 1];  // one plan slot per side
+    st = pin_slot_wait(slot_q);
+    if (st) return st;
+    st = pin_slot_wait(slot_d);
+    if (st) return st;
+    const int W = e->th_w;
+    Arena aux;
+    int32_t *a_qoff = nullptr, *a_doff = nullptr, *a_pq = nullptr, *a_pd = nullptr;
+    float* a_out = nullptr;
+    uint8_t* a_keep = nullptr;
+    auto lay = [&] {
+        a_qoff = (int32_t*)aux.take(((size_t)Bq + 1) * 4);
+        a_doff = (int32_t*)aux.take(((size_t)Bd + 1) * 4);
+        a_pq = (int32_t*)aux.take((size_t)P * 4);
+        a_pd = (int32_t*)aux.take((size_t)P * 4);
+        a_out = aux.f32((size_t)P);
+        a_keep = d_keep ? (uint8_t*)aux.take((size_t)d_rows) : nullptr;
+    };
+    lay();  // measure
+    st = grow_locked(e, e->late_aux, aux.used);
+    if (!st) st = grow_locked(e, e->tok[0], (size_t)q_rows * W * 4);
+    if (!st) st = grow_locked(e, e->tok[1], (size_t)d_rows * W * 4);
+    const int64_t Mq = (q_used + 255) / 256 * 256, Md = (d_used + 255) / 256 * 256;
+    if (!st) st = ensure_ws(e, Mq > Md ? Mq : Md, Bq > Bd ? Bq : Bd);  // (both forwards in one workspace: no growth between them)
+    if (st) return st;
+    aux = Arena{e->late_aux.p};
+    lay();  // place
+    hipStream_t s = e->rt->stream;
+    auto run = [&]() -> sc_status {
+        SC_HIP(hipMemcpyAsync(a_qoff, q_off.data(), q_off.size() * 4, hipMemcpyHostToDevice, s));
+        SC_HIP(hipMemcpyAsync(a_doff, d_off.data(), d_off.size() * 4, hipMemcpyHostToDevice, s));
+        SC_HIP(hipMemcpyAsync(a_pq, pair_q, (size_t)P * 4, hipMemcpyHostToDevice, s));
+        SC_HIP(hipMemcpyAsync(a_pd, pair_d, (size_t)P * 4, hipMemcpyHostToDevice, s));
+        if (a_keep) SC_HIP(hipMemcpyAsync(a_keep, d_keep, (size_t)d_rows, hipMemcpyHostToDevice, s));
+        const TokenCall tq{expand_id, (float*)e->tok[0].p}, td{-1, (float*)e->tok[1].p};
+        sc_status r = embed_packed_locked(e, q_ids, q_offsets, Bq, q_used, slot_q, nullptr, nullptr, nullptr, -1, &tq);
+        if (r) return r;
+        r = embed_packed_locked(e, d_ids, d_offsets, Bd, d_used, slot_d, nullptr, nullptr, nullptr, -1, &td);
+        if (r) return r;
+        sc_launch_maxsim((const float*)e->tok[0].p, a_qoff, (const float*)e->tok[1].p, a_doff, a_keep, a_pq, a_pd, P, W, a_out, s);
+        SC_HIP(hipGetLastError());
+        SC_HIP(hipMemcpyAsync(out_scores, a_out, (size_t)P * 4, hipMemcpyDeviceToHost, s));
+        return SC_OK;
+    };
+    st = run();
+    if (st) {
+        hipStreamSynchronize(s);  // uploads from the caller's arrays and the slots may be in flight
+        return st;
+    }
+    SC_HIP(hipStreamSynchronize(s));  // the one synchronisation of the call: the token vectors never left the device
     return SC_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "encoder_ops.h"
+#include "maxsim_rule.h"
 #include "sc_internal.h"
 
 namespace {
@@ -721,4 +722,54 @@ extern "C" sc_status sc_diag_score_head(sc_runtime* rt, const float* rows, int32
     sc_launch_score_head((const float*)dx.p, B, H, (const float*)dwd.p, (const float*)dbd.p, (const float*)dg.p, (const float*)db.p, h->norm_eps, (const float*)dwc.p,
                          (const float*)dbc.p, nl, (float*)dout.p, s);
     return download(dout.p, (size_t)B * nl * 4, out_logits, s);
+}
+
+// ------------------------------------------------------------------ late interaction: MaxSim alone
+// the arguments both forms take: offsets start at 0 and ascend, every query has 1 .. 128 tokens, every pair index is in range
+static sc_status maxsim_check(const char* who, const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const int32_t* pair_q,
+                              const int32_t* pair_d, int32_t P, int32_t W, const float* out) {
+    if (!Q || !q_off || !D || !d_off || !pair_q || !pair_d || !out) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (Bq < 1 || Bd < 1 || P < 1) return sc_fail(SC_ERR_INVALID, "%s: need Bq, Bd, P >= 1 (got %d, %d, %d)", who, Bq, Bd, P);
+    if (!maxsim_width_ok(W)) return sc_fail(SC_ERR_INVALID, "%s: W = %d must be a multiple of 16 within 16 .. 128", who, W);
+    if (q_off[0] != 0 || d_off[0] != 0) return sc_fail(SC_ERR_INVALID, "%s: offsets must start at 0", who);
+    for (int32_t i = 0; i < Bq; ++i)
+        if (q_off[i + 1] - q_off[i] < 1 || q_off[i + 1] - q_off[i] > MAXSIM_MAX_NQ)
+            return sc_fail(SC_ERR_INVALID, "%s: query %d has %d tokens (1 .. %d)", who, i, q_off[i + 1] - q_off[i], MAXSIM_MAX_NQ);
+    for (int32_t i = 0; i < Bd; ++i)
+        if (d_off[i + 1] - d_off[i] < 1) return sc_fail(SC_ERR_INVALID, "%s: document %d has %d tokens", who, i, d_off[i + 1] - d_off[i]);
+    for (int32_t p = 0; p < P; ++p)
+        if (pair_q[p] < 0 || pair_q[p] >= Bq || pair_d[p] < 0 || pair_d[p] >= Bd)
+            return sc_fail(SC_ERR_INVALID, "%s: pair %d = (%d, %d) outside the %d queries / %d documents", who, p, pair_q[p], pair_d[p], Bq, Bd);
+    return SC_OK;
+}
+
+// The rule on the CPU: the same header the kernel compiles (tests on a machine without a GPU).
+extern "C" sc_status sc_diag_maxsim_host(const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const uint8_t* keep,
+                                         const int32_t* pair_q, const int32_t* pair_d, int32_t P, int32_t W, float* out) {
+    SC_TRY(maxsim_check("sc_diag_maxsim_host", Q, q_off, Bq, D, d_off, Bd, pair_q, pair_d, P, W, out));
+    for (int32_t p = 0; p < P; ++p) {
+        const int32_t q0 = q_off[pair_q[p]], d0 = d_off[pair_d[p]];
+        out[p] = maxsim_score_seq(Q + (size_t)q0 * W, q_off[pair_q[p] + 1] - q0, D + (size_t)d0 * W, d_off[pair_d[p] + 1] - d0, keep ? keep + d0 : nullptr, W);
+    }
+    return SC_OK;
+}
+
+extern "C" sc_status sc_diag_maxsim(sc_runtime* rt, const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd,
+                                    const uint8_t* keep, const int32_t* pair_q, const int32_t* pair_d, int32_t P, int32_t W, float* out) {
+    if (!rt) return sc_fail(SC_ERR_INVALID, "sc_diag_maxsim: NULL argument");
+    SC_TRY(maxsim_check("sc_diag_maxsim", Q, q_off, Bq, D, d_off, Bd, pair_q, pair_d, P, W, out));
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf dq, dqo, dd, ddo, dk, dpq, dpd, dout;
+    SC_TRY(upload(Q, (size_t)q_off[Bq] * W * 4, dq, s));
+    SC_TRY(upload(q_off, ((size_t)Bq + 1) * 4, dqo, s));
+    SC_TRY(upload(D, (size_t)d_off[Bd] * W * 4, dd, s));
+    SC_TRY(upload(d_off, ((size_t)Bd + 1) * 4, ddo, s));
+    if (keep) SC_TRY(upload(keep, (size_t)d_off[Bd], dk, s));
+    SC_TRY(upload(pair_q, (size_t)P * 4, dpq, s));
+    SC_TRY(upload(pair_d, (size_t)P * 4, dpd, s));
+    SC_TRY(alloc_nan(dout, (size_t)P * 4, s));
+    sc_launch_maxsim((const float*)dq.p, (const int32_t*)dqo.p, (const float*)dd.p, (const int32_t*)ddo.p, (const uint8_t*)dk.p, (const int32_t*)dpq.p,
+                     (const int32_t*)dpd.p, P, W, (float*)dout.p, s);
+    return download(dout.p, (size_t)P * 4, out, s);
 }

@@ -718,6 +718,14 @@ def create_reranker(model: "str | None" = None, **kwargs: Any) -> Any:
         return None
     from . import reranker
 
+    kind = str(kwargs.pop("kind", None) or getattr(settings, "mi355x_reranker_kind", "auto") or "auto").lower()
+    if kind not in ("auto", "cross", "late"):
+        raise ValueError(f"mi355x_reranker_kind must be auto, cross or late, not {kind!r}")
+    from . import late
+
+    if kind == "late" or (kind == "auto" and late.is_late_dir(path)):  # a PyLate or Stanford ColBERT directory: token vectors and MaxSim
+        log.info("initializing_mi355x_late_reranker directory=%s", path)
+        return late.MI355XLateReranker(path, **kwargs)
     if Path(path).is_dir():  # a transformers directory: a ModernBERT or Qwen2 / Qwen3 reranker, its prompt and score tokens from the settings
         for key, name in (("instruction", "mi355x_reranker_instruction"), ("true_token", "mi355x_reranker_true_token"), ("false_token", "mi355x_reranker_false_token")):
             value = getattr(settings, name, None)

@@ -10,7 +10,7 @@ Backend-specific keys ride on the reference's extra="allow" (settings.py:36):
     mi355x_weights_path, mi355x_vocab_path, mi355x_allow_synthetic, mi355x_max_tokens, mi355x_store_path, mi355x_ingest_batch,
     mi355x_document_prefix, mi355x_query_prefix, mi355x_packed, mi355x_pooling, mi355x_lexical,
     mi355x_reranker_path, mi355x_reranker_vocab, mi355x_rerank_fetch_k, mi355x_tokenizer_json,
-    mi355x_reranker_instruction, mi355x_reranker_true_token, mi355x_reranker_false_token
+    mi355x_reranker_instruction, mi355x_reranker_true_token, mi355x_reranker_false_token, mi355x_reranker_kind
 """
 from __future__ import annotations
 
@@ -56,6 +56,7 @@ _DEFAULTS: dict[str, Any] = {
     "mi355x_pooling": "",             # "mean" | "cls" | "last" (Qwen2 models only); empty: what the weight file states (GGUF pooling_type, 1_Pooling/config.json), else mean
     "mi355x_lexical": False,          # keep a term row per chunk on the device for hybrid (BM25 + dense) search: MilvusVectorStore(lexical=...)
     "mi355x_reranker_path": None,     # .safetensors of a BertForSequenceClassification cross-encoder, or a transformers directory of a ModernBERT / Qwen2 / Qwen3 reranker (embeddings/reranker.py)
+    "mi355x_reranker_kind": "auto",   # "auto" | "cross" | "late": late = token vectors + MaxSim (embeddings/late.py); auto = late when the directory holds config_sentence_transformers.json or artifact.metadata
     "mi355x_reranker_vocab": None,    # its vocab.txt (default: mi355x_vocab_path)
     "mi355x_reranker_instruction": "",     # decoder rerankers: the task instruction of the prompt (empty: the template's own)
     "mi355x_reranker_true_token": "yes",   # causal-LM rerankers: the vocabulary entry whose logit says "relevant" ...
