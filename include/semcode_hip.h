@@ -914,6 +914,16 @@ sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, int32_t Q, i
  * not run.  *path = 4: list-major probing (R >= 2 and the gather merge holds nprobe k-lists: nprobe * k <= 8192); 3: per-query
  * probing; 0: neither has a plan -- the coarse stage is then not applicable either. */
 sc_status sc_diag_ivf_exact_path(int32_t ld, int32_t R, int32_t k, int32_t nprobe, int32_t cus, int32_t* path);
+/* The host plan of a packed encoder call, computed without a device or an encoder (tests): the rules of sc_encoder_embed_packed and, by
+ * kind, of its siblings on ids / offsets [B + 1] -- kind 0 texts, 1 pairs (first_lens [B]: sc_encoder_score_pairs), 2 sequences of
+ * sc_encoder_score_seqs, 3 a token call (expand_id as sc_encoder_embed_tokens; query != 0: the texts are the query side of
+ * sc_encoder_score_late, at most 128 tokens each with or without expansion) -- under a model stated by the sc_encoder_cfg fields of the same
+ * names, with the messages of those entry points; then every array the call would upload.  out as sc_diag_ivf_plan's, all int32: ids / pos
+ * [M], starts / lens [B], items [4 per item], nitems [3], types [M] / ones [B] (kind 1), dst [M] (kind 3), common (the bytes every kind lays
+ * out alike, uint32); int64 scalars rows, M (rows rounded up to 256), nrows (token vectors asked for), items_cap, plan_bytes, common_bytes. */
+sc_status sc_diag_encoder_plan(const int32_t* ids, const int64_t* offsets, int32_t B, int32_t kind, const int32_t* first_lens, int32_t expand_id,
+                               int32_t query, int32_t max_pos, int32_t pos_type, int32_t vocab, int32_t type_vocab, int32_t arch, int32_t global_every,
+                               int32_t local_window, void* out, int64_t cap_bytes, int64_t* need_bytes);
 
 /* Multi-GPU final step (one process per GPU): merge `lists` per-shard results
  * dist [lists,Q,k] / rows [lists,Q,k] (as produced by sc_index_search* on each shard and

@@ -15,7 +15,7 @@ profiles/encoder_split_ab.log; scripts/ab_encoder.sh drives it).  One process pe
 Encoders: BERT, jina (ALiBi + GEGLU), nomic (rotary + SwiGLU, rope_fused 0 and 1) x {hidden 256 / ffn 512 (foldable), hidden 128 /
 ffn 384 (128-tile path)} x normalize {0, 1} x (B, S) {(2, 32), (5, 256)} (256 and 1 280 token rows: either side of the 1 024-row
 pipeline switch) x set_path {auto, batch, small}.  Then every instantiation of the attention kernels on its own (attention_section,
-causal_section).
+causal_section), and the three architectures through every kind of packed call with seeded heads (forward_section).
 """
 import hashlib
 import sys
@@ -114,6 +114,105 @@ def causal_section(nv, rt, rng):
     return out
 
 
+def forward_section(nv, rt, rng):
+    """The host paths of the second split of the encoder host code (profiles/encoder_split2_ab.log) that the pooled lines above do not
+    reach: 2-layer synthetic models of the three architectures through every kind of packed call, with seeded heads.  Packed lens
+    [1, 33, 129, 257, 300] (1 024 token rows) and the same twice plus [512] (2 304): either side of the 1 024-row switch, each under
+    set_path auto / batch / small.  arch 1: global_every 1 and 3, mean and [CLS]; arch 2: head_dim 64 with and without qk_norm and 128,
+    kv_heads < heads, mean and last token; arch 0: [CLS] with cls_prune 0 and 1, rectangle and packed; score_pairs (arch 0, with and
+    without pooler), score_seqs (arch 1 pooling 0 and 1, arch 2), embed_tokens (documents, expanded queries) and score_late (with and
+    without d_keep) on arch 0 (foldable and not) and arch 1."""
+    out = []
+    f = lambda *s: (0.05 * rng.standard_normal(s)).astype(np.float32)
+    small = [1, 33, 129, 257, 300]
+    packs = {}
+    for name, lens in (("1024", small), ("2304", small + small + [512])):
+        offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        packs[name] = (rng.integers(1, 1000, size=int(offsets[-1])).astype(np.int32), offsets, np.array(lens))
+    rect = (rng.integers(1, 1000, size=(5, 256)).astype(np.int32), np.array([256, 1, 33, 129, 200], np.int32))
+    q_lens = [1, 33, 100, 128]
+    q_off = np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int64)
+    q_ids = rng.integers(1, 1000, size=int(q_off[-1])).astype(np.int32)
+
+    def each_path(enc, tag, call):
+        for path in ("auto", "batch", "small"):
+            enc.set_path(path)
+            for name, a in call().items():
+                out.append(line(f"{tag} path={path} {name}", a))
+        enc.set_path("auto")
+
+    def embeds(enc, tag):
+        each_path(enc, f"{tag} rect", lambda: {"pooled": enc.embed_ids(*rect)})
+        for pname, (ids, offsets, _) in packs.items():
+            each_path(enc, f"{tag} packed {pname}", lambda: {"pooled": enc.embed_packed(ids, offsets)})
+
+    def tokens(enc, tag):
+        enc.set_token_head(f(64, enc.hidden))
+        for pname, (ids, offsets, lens) in packs.items():
+            keep = (rng.integers(0, 4, size=ids.size) > 0).astype(np.uint8)
+            keep[offsets[:-1]] = 1  # every document keeps a token
+            pq, pd = np.array([0, 1, 2, 3, 3], np.int32), np.array([0, len(lens) - 1, 2, 1, 4], np.int32)
+            each_path(enc, f"{tag} tokens {pname}", lambda: {
+                "docs": enc.embed_tokens(ids, offsets)[0], "queries": enc.embed_tokens(q_ids, q_off, expand_id=103)[0],
+                "late": enc.score_late(q_ids, q_off, ids, offsets, pq, pd, expand_id=103),
+                "late keep": enc.score_late(q_ids, q_off, ids, offsets, pq, pd, expand_id=103, d_keep=keep),
+                "late plain": enc.score_late(q_ids, q_off, ids, offsets, pq, pd)})
+
+    arch0 = {"h256": dict(hidden=256, heads=4, ffn=512), "h128": dict(hidden=128, heads=2, ffn=384)}
+    for shape, dims in arch0.items():
+        cfg = dict(nv.BERT_BASE, vocab=1000, layers=2, max_pos=512, **dims)
+        for normalize in (0, 1):
+            enc = nv.Encoder(rt, cfg, weights=None, normalize=bool(normalize), synth_seed=5)
+            embeds(enc, f"fwd arch0 {shape} norm={normalize} mean")
+            enc.pooling = "cls"
+            for prune in (0, 1):
+                nv.diag_set_option("cls_prune", prune)
+                embeds(enc, f"fwd arch0 {shape} norm={normalize} cls prune={prune}")
+            nv.diag_set_option("cls_prune", -1)
+            enc.pooling = "mean"
+            if normalize:
+                H = enc.hidden
+                for pooler in (False, True):
+                    enc.set_pair_head(f(2, H), f(2), *((f(H, H), f(H)) if pooler else ()))
+                    for pname, (ids, offsets, lens) in packs.items():
+                        first = np.maximum(1, lens // 3).astype(np.int32)
+                        pairs = lens >= 2  # (a pair has at least two tokens: the text of one token is left out)
+                        p_off = np.concatenate([[0], np.cumsum(lens[pairs])]).astype(np.int64)
+                        p_ids = np.concatenate([ids[a:b] for a, b, k in zip(offsets[:-1], offsets[1:], pairs) if k])
+                        each_path(enc, f"fwd arch0 {shape} pairs pooler={pooler} {pname}",
+                                  lambda: dict(zip(("logits", "cls"), enc.score_pairs(p_ids, p_off, first[pairs], want_cls=True))))
+                tokens(enc, f"fwd arch0 {shape}")
+            enc.close()
+
+    modern = dict(vocab=1000, hidden=256, layers=2, heads=4, ffn=512, max_pos=512, type_vocab=1, ln_eps=1e-5, rotary=True, geglu=True, modernbert=True,
+                  local_window=128, rope_theta=160000.0, rope_theta_local=10000.0)
+    for ge in (1, 3):
+        enc = nv.Encoder(rt, dict(modern, global_every=ge), weights=None, normalize=True, synth_seed=6)
+        H = enc.hidden
+        for pooling in ("mean", "cls"):
+            enc.pooling = pooling
+            embeds(enc, f"fwd arch1 ge={ge} {pooling}")
+            enc.set_score_head(dict(kind=1, pooling=pooling, dense_w=f(H, H), dense_b=f(H), norm_g=1 + f(H), norm_b=f(H), norm_eps=1e-5, cls_w=f(1, H), cls_b=f(1)))
+            for pname, (ids, offsets, _) in packs.items():
+                each_path(enc, f"fwd arch1 ge={ge} seqs head={pooling} {pname}", lambda: dict(zip(("logits", "rows"), enc.score_seqs(ids, offsets, want_rows=True))))
+        enc.pooling = "mean"
+        tokens(enc, f"fwd arch1 ge={ge}")
+        enc.close()
+
+    causal = dict(vocab=1000, hidden=256, layers=2, ffn=512, max_pos=512, type_vocab=1, ln_eps=1e-6, rotary=True, swiglu=True, qwen2=True, rope_theta=1000000.0)
+    widths = {"hd64": dict(heads=4, kv_heads=2), "hd64 qk_norm": dict(heads=4, kv_heads=2, qk_norm=True), "hd128": dict(heads=4, kv_heads=2, head_dim=128, qk_norm=True)}
+    for wname, dims in widths.items():
+        enc = nv.Encoder(rt, dict(causal, **dims), weights=None, normalize=True, synth_seed=7)
+        for pooling in ("mean", "last"):
+            enc.pooling = pooling
+            embeds(enc, f"fwd arch2 {wname} {pooling}")
+        enc.set_score_head(dict(kind=2, cls_w=f(2, enc.hidden), cls_b=f(2)))
+        for pname, (ids, offsets, _) in packs.items():
+            each_path(enc, f"fwd arch2 {wname} seqs {pname}", lambda: dict(zip(("logits", "rows"), enc.score_seqs(ids, offsets, want_rows=True))))
+        enc.close()
+    return out
+
+
 def dump(lib_path, out_path):
     nv = use_library(lib_path)
     rt = nv.Runtime()
@@ -185,6 +284,7 @@ def dump(lib_path, out_path):
     out.append(line("embed ln", nv.diag_embed(rt, ids, wemb, None, temb, 64, ln=(gamma, beta, 1e-12))))
     out += attention_section(nv, rt, np.random.default_rng(7))
     out += causal_section(nv, rt, np.random.default_rng(8))
+    out += forward_section(nv, rt, np.random.default_rng(9))
     rt.close()
     Path(out_path).write_text("\n".join(out) + "\n")
     print(f"{len(out)} arrays -> {out_path}")

@@ -203,6 +203,8 @@ SIGNATURES = {
     "sc_diag_ivf_plan": (C.c_int32, [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_int64, C.POINTER(C.c_int64)]),
     "sc_diag_ivf_exact_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "sc_diag_encoder_plan": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_int32] * 8 + [C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64)]),
     "sc_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_size_t]),
     "sc_comm_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "sc_comm_destroy": (C.c_int32, [C.c_void_p]),
@@ -1153,11 +1155,16 @@ def diag_ivf_plan(path: str, probes, list_off, k: int, ld: int, cus: int, wide: 
     list_off = np.ascontiguousarray(list_off, np.int64)
     if probes.ndim != 2 or list_off.ndim != 1 or list_off.size < 2:
         raise ValueError("diag_ivf_plan: probes must be [Q, nprobe], list_off [nlist + 1]")
-    need = C.c_int64()
     args = (path.encode(), _ptr(probes), probes.shape[0], probes.shape[1], _ptr(list_off), list_off.size - 1, int(k), int(ld), int(cus), 1 if wide else 0)
-    _check(lib().sc_diag_ivf_plan(*args, None, 0, C.byref(need)))
+    return _diag_records(lib().sc_diag_ivf_plan, args)
+
+
+def _diag_records(fn, args) -> "dict[str, np.ndarray]":
+    """Calls a host-plan diag entry twice (size, then data) and cuts its named records apart."""
+    need = C.c_int64()
+    _check(fn(*args, None, 0, C.byref(need)))
     blob = np.empty(need.value, np.uint8)
-    _check(lib().sc_diag_ivf_plan(*args, _ptr(blob), blob.size, C.byref(need)))
+    _check(fn(*args, _ptr(blob), blob.size, C.byref(need)))
     out, at, kinds = {}, 0, (np.dtype("<i4"), np.dtype("<i8"), np.dtype("<u4"), IVF_ITEM_DTYPE)
     while at < blob.size:
         name = blob[at:at + 16].tobytes().split(b"\0")[0].decode()
@@ -1174,6 +1181,19 @@ def diag_ivf_exact_path(ld: int, R: int, k: int, nprobe: int, cus: int) -> str:
     path = C.c_int32()
     _check(lib().sc_diag_ivf_exact_path(int(ld), int(R), int(k), int(nprobe), int(cus), C.byref(path)))
     return {0: "none", 3: "ivf", 4: "ivf_listmajor"}[path.value]
+
+
+def diag_encoder_plan(ids, offsets, kind: str = "texts", first_lens=None, expand_id: int = -1, query: bool = False, *, max_pos: int = 2048, pos_type: int = 0,
+                      vocab: int = 30522, type_vocab: int = 2, arch: int = 0, global_every: int = 0, local_window: int = 0) -> "dict[str, np.ndarray]":
+    """The host plan of a packed encoder call (sc_diag_encoder_plan; no device, no encoder): kind "texts", "pairs" (first_lens), "scored" or
+    "tokens" (expand_id; query: the query side of score_late), the model's bounds as keywords.  The checks of the entry points run first
+    (ScError with their messages); then every array the call would upload, by name; scalars as arrays of one."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    fl = None if first_lens is None else np.ascontiguousarray(first_lens, np.int32)
+    args = (_ptr(ids), _ptr(offsets), offsets.size - 1, ("texts", "pairs", "scored", "tokens").index(kind), _ptr(fl), int(expand_id),
+            1 if query else 0, int(max_pos), int(pos_type), int(vocab), int(type_vocab), int(arch), int(global_every), int(local_window))
+    return _diag_records(lib().sc_diag_encoder_plan, args)
 
 
 def diag_set_option(name: str, value: int) -> None:

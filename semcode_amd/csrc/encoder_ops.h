@@ -1,5 +1,5 @@
 // encoder_ops.h -- the encoder's device entry points: what gemm_bf16.hip and encoder_ops.hip define and the encoder host files
-// (sc_encoder.cpp, sc_encoder_diag.cpp) call.  Defaults of optional arguments live here only; the .hip files include this header,
+// (sc_encoder_*.cpp) call.  Defaults of optional arguments live here only; the .hip files include this header,
 // so a definition that drifts from its prototype does not compile.  All launchers enqueue on `s` and never synchronise.
 #pragma once
 #include <vector>
@@ -142,16 +142,10 @@ void sc_launch_cls_gather(const void* x, const int32_t* starts, int B, int S, in
 void sc_launch_attention_cls(const void* qkv, const int32_t* starts, const int32_t* lens, int B, int S, int M, int H, int head_dim, const float* slopes, void* ctx,
                              int rows_pad, hipStream_t s);
 
-// ---- sc_encoder.cpp: the attention work items of packed sequences (host): per sequence one item for every 8 query blocks of 32 rows
-// (class 0) or one item (classes 1, 2), written as {start, len, first query block, 0} in class order.  items must hold
-// sc_packed_items_cap(rows, B) items.
-inline int64_t sc_packed_items_cap(int64_t rows, int64_t B) { return B + rows / 256; }
-void sc_packed_items(const int32_t* starts, const int32_t* lens, int64_t B, int32_t* items, int nitems[3]);
-
-// ---- sc_encoder.cpp: the rules of a score head, with sc_fail's message under `who`.  arch: the encoder's (0 is refused), or -1 for the kernels
+// ---- sc_encoder_heads.cpp: the rules of a score head, with sc_fail's message under `who`.  arch: the encoder's (0 is refused), or -1 for the kernels
 // alone (sc_diag_score_head: any kind, pooling not read)
 sc_status sc_score_head_check(const sc_score_head* h, int arch, int H, const char* who);
 
-// ---- sc_encoder.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
+// ---- sc_encoder_model.cpp: the rotary tables those kernels read.  [positions][32] cos, then [positions][32] sin: rotate-half (GPT-NeoX)
 // angles p * theta^(-2 i / 64), i < 32, computed in double; theta <= 0 means 10000.  head_dim 128: [positions][64] each, p * theta^(-2 i / 128)
 std::vector<float> sc_rope_table(int64_t positions, float theta, int head_dim = 64);

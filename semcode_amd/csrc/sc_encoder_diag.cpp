@@ -2,12 +2,15 @@
 //
 // The pattern of every harness: host f32 in (activations rounded to bf16 by f32_to_bf16_kernel), THE PRODUCT LAUNCHER, result widened
 // to f32 and copied back, synchronous.  Output buffers are pre-filled with 0xFF bytes (NaN as bf16 and as f32), so that an element a
-// kernel does not write shows in the result.  (sc_diag_encoder_read, which needs the encoder handle, is in sc_encoder.cpp.)
+// kernel does not write shows in the result.  (sc_diag_encoder_read, which needs the encoder handle, is in sc_encoder_embed.cpp.)
+// sc_diag_encoder_plan, at the end, touches no device: the host plan of a packed call (sc_encoder_plan.h).
 #include <cstring>
 #include <vector>
 
 #include "encoder_ops.h"
 #include "maxsim_rule.h"
+#include "sc_diag_blob.h"
+#include "sc_encoder_plan.h"
 #include "sc_internal.h"
 
 namespace {
@@ -772,4 +775,36 @@ extern "C" sc_status sc_diag_maxsim(sc_runtime* rt, const float* Q, const int32_
     sc_launch_maxsim((const float*)dq.p, (const int32_t*)dqo.p, (const float*)dd.p, (const int32_t*)ddo.p, (const uint8_t*)dk.p, (const int32_t*)dpq.p,
                      (const int32_t*)dpd.p, P, W, (float*)dout.p, s);
     return download(dout.p, (size_t)P * 4, out, s);
+}
+
+// The plan of a packed call without a device or a handle: the rules of its kind (kind = PackedCall::Kind: 0 texts, 1 pairs, 2 scored,
+// 3 tokens) under the model bounds given as plain values, then the filler into a buffer sized by PlanOffsets; out as sc_diag_ivf_plan's.
+extern "C" sc_status sc_diag_encoder_plan(const int32_t* ids, const int64_t* offsets, int32_t B, int32_t kind, const int32_t* first_lens, int32_t expand_id,
+                                          int32_t query, int32_t max_pos, int32_t pos_type, int32_t vocab, int32_t type_vocab, int32_t arch, int32_t global_every,
+                                          int32_t local_window, void* out, int64_t cap_bytes, int64_t* need_bytes) {
+    const char* who = "sc_diag_encoder_plan";
+    if (!ids || !need_bytes || kind < 0 || kind > 3 || (kind == 1 && !first_lens)) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    const PlanBounds mb{max_pos, pos_type, vocab, type_vocab, arch, global_every, local_window, MAXSIM_MAX_NQ};
+    int64_t used = 0, nrows = B;
+    if (kind == PackedCall::TOKENS) SC_TRY(sc_plan_check_tokens(offsets, B, expand_id, query != 0, mb, who, &used, &nrows));
+    else SC_TRY(sc_plan_check_offsets(offsets, B, mb, who, &used));
+    if (kind == PackedCall::PAIRS) SC_TRY(sc_plan_check_pairs(offsets, first_lens, B, mb, who));
+    PackedCall call = kind == PackedCall::PAIRS ? PackedCall::pairs(first_lens) : kind == PackedCall::TOKENS ? PackedCall::tokens(expand_id, nullptr) : PackedCall{};
+    call.kind = (PackedCall::Kind)kind;
+    const int64_t M = ceil256(used);
+    const PlanOffsets po((size_t)M, (size_t)B, call.kind);
+    std::vector<char> buf(po.total, (char)0xCD);
+    int nitems[3];
+    const int64_t rows = sc_plan_fill(ids, offsets, B, call, po, M, buf.data(), nitems);
+    DiagBlob bl;
+    bl.put("ids", 0, buf.data() + po.ids, (size_t)M, 4), bl.put("pos", 0, buf.data() + po.pos, (size_t)M, 4);
+    bl.put("starts", 0, buf.data() + po.starts, (size_t)B, 4), bl.put("lens", 0, buf.data() + po.lens, (size_t)B, 4);
+    bl.put("items", 0, buf.data() + po.items, (size_t)(nitems[0] + nitems[1] + nitems[2]) * 4, 4), bl.put("nitems", 0, nitems, 3, 4);
+    if (kind == PackedCall::PAIRS) bl.put("types", 0, buf.data() + po.types, (size_t)M, 4), bl.put("ones", 0, buf.data() + po.ones, (size_t)B, 4);
+    if (kind == PackedCall::TOKENS) bl.put("dst", 0, buf.data() + po.dst, (size_t)M, 4);
+    bl.num("rows", rows), bl.num("M", M), bl.num("nrows", nrows), bl.num("items_cap", sc_packed_items_cap(M, B)), bl.num("plan_bytes", (int64_t)po.total);
+    bl.num("common_bytes", (int64_t)PlanOffsets((size_t)M, (size_t)B).total);
+    bl.put("common", 2, buf.data(), PlanOffsets((size_t)M, (size_t)B).total / 4, 4);
+    bl.give(out, cap_bytes, need_bytes);
+    return SC_OK;
 }

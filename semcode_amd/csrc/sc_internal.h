@@ -316,5 +316,5 @@ void sc_set_group_width0(int v);       // sc_grouped.cpp
 void sc_set_group_width1(int v);
 void sc_set_mmr_chunk_q(int v);        // sc_mmr.cpp
 void sc_set_lex_chunk_q(int v);        // sc_lexical.cpp
-void sc_encoder_set_rope_fused(int v); // sc_encoder.cpp
-void sc_encoder_set_cls_prune(int v);  // sc_encoder.cpp
+void sc_encoder_set_rope_fused(int v); // sc_encoder_forward.cpp
+void sc_encoder_set_cls_prune(int v);  // sc_encoder_forward.cpp

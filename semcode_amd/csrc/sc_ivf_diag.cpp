@@ -1,32 +1,11 @@
 // sc_ivf_diag.cpp -- sc_diag_ivf_plan: the host planners of IVF probing (sc_ivf_plan.cpp) on caller-given probe tables and list offsets,
 // fed through sc_ivf_plan_params like the searches; no device is touched (tests/test_ivf_plan_host.py).
-#include <cstring>
 #include <string>
 #include <vector>
 
+#include "sc_diag_blob.h"
 #include "sc_internal.h"
 #include "sc_ivf_plan.h"
-
-namespace {
-// out = records of {char name[16]; int32 kind (0 i32, 1 i64, 2 u32, 3 IvfCoarseItem); int32 0; int64 count; data padded to 8 bytes}
-struct Blob {
-    std::vector<char> bytes;
-    void put(const char* name, int kind, const void* data, size_t count, size_t elem) {
-        char head[32] = {0};
-        strncpy(head, name, 15);
-        const int32_t kd = kind;
-        const int64_t n = (int64_t)count;
-        memcpy(head + 16, &kd, 4);
-        memcpy(head + 24, &n, 8);
-        bytes.insert(bytes.end(), head, head + 32);
-        if (count) bytes.insert(bytes.end(), (const char*)data, (const char*)data + count * elem);
-        bytes.resize((bytes.size() + 7) & ~(size_t)7, 0);
-    }
-    void i32(const char* name, const std::vector<int32_t>& v) { put(name, 0, v.data(), v.size(), 4); }
-    void i64(const char* name, const std::vector<int64_t>& v) { put(name, 1, v.data(), v.size(), 8); }
-    void num(const char* name, int64_t v) { put(name, 1, &v, 1, 8); }
-};
-}  // namespace
 
 extern "C" sc_status sc_diag_ivf_exact_path(int32_t ld, int32_t R, int32_t k, int32_t nprobe, int32_t cus, int32_t* path) {
     if (!path || cus < 1) return sc_fail(SC_ERR_INVALID, "sc_diag_ivf_exact_path: bad argument");
@@ -43,7 +22,7 @@ extern "C" sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, i
     IvfPlanParams pp;
     const bool lm_ok = sc_ivf_plan_params(ld, k, nprobe, cus, &pp);
     if (!wide) pp.wide_ok = false;
-    Blob bl;
+    DiagBlob bl;
     if (which == "listmajor") {
         if (!lm_ok) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_ivf_plan: k=%d / ld=%d / nprobe=%d not supported by the list-major probe", k, ld, nprobe);
         IvfListMajorPlan lm;
@@ -75,7 +54,6 @@ extern "C" sc_status sc_diag_ivf_plan(const char* path, const int64_t* probes, i
     } else {
         return sc_fail(SC_ERR_INVALID, "sc_diag_ivf_plan: path must be \"listmajor\" or \"coarse\"");
     }
-    *need_bytes = (int64_t)bl.bytes.size();
-    if (out && cap_bytes >= *need_bytes) memcpy(out, bl.bytes.data(), bl.bytes.size());
+    bl.give(out, cap_bytes, need_bytes);
     return SC_OK;
 }

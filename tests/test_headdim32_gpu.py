@@ -1,4 +1,4 @@
-"""GPU: head dimension 32 (Head32 / attention_qblock_core32 of attention_core.h as the policy of the attention kernels, the create rules of sc_encoder.cpp) through the C ABI.
+"""GPU: head dimension 32 (Head32 / attention_qblock_core32 of attention_core.h as the policy of the attention kernels, the create rules of sc_encoder_model.cpp) through the C ABI.
 
 Bounds.
   Single kernels against float64 numpy over bf16-rounded inputs with scale 1/sqrt(32): max <= 3e-2, median <= 3e-3, the bounds of

@@ -1,8 +1,9 @@
 """CPU: the host side of packed variable-length batches that needs no device.
 
-sc_encoder_packed_rows takes an encoder handle (the length bound is the model's max_pos), and an encoder needs a device: its row counts
-and argument errors are checked in tests/test_packed_gpu.py.  Here: the cutter the provider sizes its packed calls with, the flattening
-of a padded batch, the ABI entries and the setting."""
+The plan of a packed call -- the rules of its offsets, the row count, every array it uploads -- is host arithmetic of plain values
+(semcode_amd/csrc/sc_encoder_plan.cpp) and is checked through diag_encoder_plan in tests/test_encoder_plan_host.py; sc_encoder_packed_rows
+itself takes an encoder handle, which needs a device (tests/test_packed_gpu.py).  Here: the cutter the provider sizes its packed calls with,
+the flattening of a padded batch, the ABI entries and the setting."""
 import numpy as np
 import pytest
 
@@ -11,9 +12,20 @@ from semcode_amd.embeddings.providers import cut_packed, flatten_ids
 
 def rows_of(lens):
     """Stand-in for Encoder.packed_rows in the cutter tests -- the library's rule (include/semcode_hip.h): ceil32 per text, the total
-    rounded up to 256.  The library's own count is checked in tests/test_packed_gpu.py::test_packed_rows."""
+    rounded up to 256.  test_rows_of_is_the_librarys_count holds it against the library's plan."""
     used = int(((np.asarray(lens, np.int64) + 31) // 32 * 32).sum())
     return (used + 255) // 256 * 256
+
+
+def test_rows_of_is_the_librarys_count():
+    from semcode_amd._native import diag_encoder_plan
+
+    rng = np.random.default_rng(0)  # the lens of test_cutter_groups_are_consecutive_and_within_budget, seed 0
+    lens = np.concatenate([rng.integers(1, 300, size=200), [2048, 1, 2048, 2048, 31, 33], rng.integers(1, 2049, size=50)])
+    rng.shuffle(lens)
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    plan = diag_encoder_plan(np.zeros(int(offsets[-1]), np.int32), offsets)
+    assert int(plan["M"][0]) == rows_of(lens)
 
 
 @pytest.mark.parametrize("budget", [256, 1024, 4096, 65536])
