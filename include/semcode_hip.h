@@ -139,7 +139,28 @@ sc_status sc_synth_fill_dev(sc_runtime* rt, float* out, int64_t rows, int32_t di
  *   the columns (j, j + head_dim / 2) of a head with the angle p * rope_theta^(-2j / head_dim).  qk_norm 1: Q and K get an RMSNorm over each
  *   head's head_dim columns BEFORE the rotation (f32 statistics, eps = ln_eps, one gamma [head_dim] for Q and one for K per layer), at either
  *   head width.  Any other head_dim is SC_ERR_UNSUPPORTED, any other qk_norm SC_ERR_INVALID; a non-zero head_dim or qk_norm on arch 0 or 1 is
- *   SC_ERR_UNSUPPORTED.  Out of scope: heads of 128 on arch 0 / 1, hidden above 2 048 (Qwen3-Embedding-4B / 8B, the 7B models), sliding windows. */
+ *   SC_ERR_UNSUPPORTED.  Out of scope: heads of 128 on arch 0 / 1, hidden above 2 048 (Qwen3-Embedding-4B / 8B, the 7B models), sliding windows.
+ *
+ * arch 3 (the T5 ENCODER behind Salesforce/codet5p-110m-embedding = 32100 / 768 / 12 layers / 12 heads / 3072 ReLU, sentence-transformers/gtr-t5-*,
+ *   sentence-t5-* and the instructor backbones; eps 1e-6): h = tok_emb[id] (no embedding norm, no position and no type table);  per layer
+ *   h += Wo Attn(RMS(h)),  h += W2 act(W1 RMS(h));  pooled from RMS_final(h), RMS as on arch 2.  Positions enter through a bucketed relative
+ *   bias only (pos_type 3): scores are q.k + rel_bias[bucket(j - i)][head] over the real keys j < len, with NO 1/sqrt(d) scaling, one
+ *   learned table [rel_buckets, heads] for all layers.  Bucket rule (transformers' bidirectional one), nb = rel_buckets / 2, me = nb / 2,
+ *   n = |j - i|:  b = (j > i) ? nb : 0;  b += n if n < me, else b += min(nb - 1, me + trunc(log(n / me) / log(rel_max_distance / me) * (nb - me))),
+ *   evaluated in float32 as transformers does (sc_diag_rel_buckets returns the integers).  ffn_type 3 = Linear-ReLU-Linear (T5 v1.0, CodeT5+);
+ *   ffn_type 4 = gated tanh-GELU ("gelu_new": 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))); T5 v1.1, flan, sentence-T5), W1 [2*ffn, H] with
+ *   the wi_0 (activated) rows first, then wi_1.  arch 3 requires pos_type 3, ffn_type 3 or 4, rel_buckets even (32 in released models) and
+ *   rel_max_distance (128), head dimension 64 -- head_dim 0 = hidden / heads, which must be 64; 64 stated: the attention width AW = heads * 64
+ *   may differ from hidden as on arch 2 (t5-v1.1-small: 512 hidden, 6 heads) -- AW a multiple of 128, kv_heads, qk_norm, local_window all 0,
+ *   max_pos <= 2048, next to the hidden % 128, ffn % 128 and hidden <= 2048 rules; anything else is SC_ERR_UNSUPPORTED or SC_ERR_INVALID with a
+ *   message naming the field.  pos_type 3, ffn_type 3 / 4, rel_buckets and rel_max_distance on arch 0 - 2 are SC_ERR_UNSUPPORTED.  Pooling:
+ *   sc_encoder_set_pooling 0 (masked mean of RMS_final(h)) or 1 (the first token's row, RMS_final in f32 inside the pooling kernel; the whole
+ *   last layer runs); 2 is SC_ERR_INVALID.  sc_encoder_score_pairs, sc_encoder_set_score_head, sc_encoder_score_seqs and
+ *   sc_encoder_set_token_head are SC_ERR_UNSUPPORTED.  The forward is the stand-alone-norm pipeline of arch 1 / 2 for every batch size.
+ *   The projection behind the pooling of these models (CodeT5+'s proj, the Dense module of sentence-T5 / GTR) is sc_encoder_set_output_proj.
+ *   Out of scope: the T5 decoder and seq2seq rerankers (monoT5), d_kv 128 and hidden above 2 048 (t5-3b / 11b, the xl / xxl sentence
+ *   models), Instructor's instruction-masked pooling, .bin checkpoints, GGUF, the LayerNorm-folded pipeline and the pruned first-token layer
+ *   for arch 3, texts beyond 2 048 tokens. */
 typedef struct sc_encoder_cfg {
     int32_t vocab, hidden, layers, heads, ffn, max_pos, type_vocab;
     float ln_eps;
@@ -148,10 +169,12 @@ typedef struct sc_encoder_cfg {
     int32_t pos_type;     /* 0 = learned absolute position table (BERT); 1 = ALiBi: no table, scores get
                              -slope_h * |i - j| (jina-embeddings-v2 family named in the reference README);
                              2 = rotary (nomic-bert): no table, Q and K rotated by position ("rotate-half" pairing
-                             (j, j + 32) of a head, angle p * rope_theta^(-2j/64)); max_pos bounds the sequence length */
+                             (j, j + 32) of a head, angle p * rope_theta^(-2j/64)); max_pos bounds the sequence length;
+                             3 = the bucketed relative position bias of arch 3 (above): no table, no rotation */
     int32_t ffn_type;     /* 0 = Linear-GELU-Linear (BERT); 1 = GEGLU: W1 is [2*ffn, H] (gate rows first, then up
                              rows), hidden = gelu(gate) * up, b1 is [2*ffn] (zeros for bias-free models);
-                             2 = SwiGLU (nomic-bert): the same layout, hidden = silu(gate) * up                */
+                             2 = SwiGLU (nomic-bert): the same layout, hidden = silu(gate) * up;
+                             3 = Linear-ReLU-Linear, 4 = gated tanh-GELU in the layout of 1 (both arch 3 only, above) */
     float rope_theta;     /* pos_type 2: rotary base (1000 for nomic-embed-text); 0 = 10000                   */
     /* appended; all zero = the behaviour of the struct without them */
     int32_t arch;           /* 0 = post-LN BERT family; 1 = pre-LN ModernBERT; 2 = pre-norm causal decoder, Qwen2 family (above) */
@@ -161,6 +184,8 @@ typedef struct sc_encoder_cfg {
     int32_t kv_heads;       /* arch 2: K / V heads of the grouped-query attention, a divisor of heads; 0 = heads.  Must be 0 on arch 0, 1 */
     int32_t head_dim;       /* arch 2: 0 = hidden / heads (must be 64), 64, or 128 (stated; hidden need not be heads * 128).  Must be 0 on arch 0, 1 */
     int32_t qk_norm;        /* arch 2: 1 = per-head RMSNorm of Q and K before the rotation (Qwen3); 0 = none.  Must be 0 on arch 0, 1 */
+    int32_t rel_buckets;      /* arch 3 (pos_type 3): buckets of the relative position bias, even (32 in released models).  Must be 0 on arch 0 - 2 */
+    int32_t rel_max_distance; /* arch 3 (pos_type 3): distance from which on every position shares the last bucket (128).  Must be 0 on arch 0 - 2 */
 } sc_encoder_cfg;
 
 /* Size in bytes of the f32 weight blob sc_encoder_create expects for cfg.  Blob order (all f32,
@@ -182,7 +207,12 @@ typedef struct sc_encoder_cfg {
  * arch 2 with head_dim 128 (or 64 stated), AW = heads * head_dim, KV = kv_heads * head_dim: Wq [AW,H], bq [AW], Wk [KV,H], bk [KV], Wv [KV,H],
  * bv [KV], Wo [H,AW], bo [H], the rest as above; with qk_norm, q_norm_gamma [head_dim] and k_norm_gamma [head_dim] follow each layer's ln2_beta.
  * The fused projection stays in 64-column blocks, N = AW + 2 KV: a 128-wide head is two consecutive blocks.  sc_encoder_info reports the
- * head_dim in use on arch 2 (64 or 128, never 0). */
+ * head_dim in use on arch 2 (64 or 128, never 0).
+ * arch 3, AW = heads * 64: word_emb [vocab,H], rel_bias [rel_buckets, heads] (transformers' layout of relative_attention_bias.weight), then
+ * the arch 2 per-layer order without the QK-norm vectors -- Wq [AW,H], bq, Wk, bk, Wv, bv, Wo [H,AW], bo, ln1_gamma (layer.0.layer_norm),
+ * ln1_beta, W1 ([ffn,H] = wi at ffn_type 3; [2*ffn,H] = wi_0 rows, then wi_1 rows at ffn_type 4), b1, W2 [H,ffn] (= wo), b2, ln2_gamma
+ * (layer.1.layer_norm), ln2_beta -- then final_norm_gamma [H], final_norm_beta [H].  Bias slots hold zeros for released models and are
+ * honoured by the GEMM epilogues; the beta slots are present and never read. */
 sc_status sc_encoder_blob_bytes(const sc_encoder_cfg* cfg, int64_t* out);
 /* Replaces EmbeddingProviderFactory.create() loading a model (providers.py:69-100): uploads the
  * weights (converted to bf16 on device).  weights_blob == NULL: synthetic weights 0.02*N(0,1) from
@@ -208,9 +238,19 @@ sc_status sc_encoder_set_path(sc_encoder* enc, int32_t path);
  * pooling 2 = the row of the text's last real token (row start + len - 1 of a rectangle or of packed rows): the vector of causal
  * embedding models.  Accepted on arch 2 only (on arch 0 and 1 it is SC_ERR_INVALID like any unknown value): the row gets RMS_final in
  * f32 and is L2-normalised by the rule above.  On arch 2 pooling 1 is SC_ERR_INVALID (a causal first token sees only itself) and
- * pooling 0 takes RMS_final over all rows, then the mean kernels. */
+ * pooling 0 takes RMS_final over all rows, then the mean kernels.  On arch 3 pooling 1 is the first token's row with RMS_final in f32. */
 sc_status sc_encoder_set_pooling(sc_encoder* enc, int32_t pooling);
 sc_status sc_encoder_get_pooling(sc_encoder* enc, int32_t* out);
+/* The output projection behind the pooling of an embedding model: CodeT5+ (first token -> Linear(768, 256) -> L2), sentence-T5 / GTR (mean ->
+ * Dense(768, 768, no bias) -> L2).  W [E,H] f32 host, torch.nn.Linear layout; b [E] or NULL; E a multiple of 16, 16 <= E <= 2048 (else
+ * SC_ERR_INVALID); W == NULL removes it.  Accepted on every arch, for the pooled embedding calls only: pair, score and token calls do not read
+ * it.  With a projection installed the pooled row is taken UN-normalised, out = W pooled + b, then x / max(|x|, 1e-12) when cfg.normalize;
+ * every embedding entry point -- sc_encoder_embed_ids, _dev, _into, _into_async, sc_encoder_embed_packed, _into, _into_async -- writes [B, E],
+ * and the _into forms require an index of dimension E.  A text's vector is the same bits whichever batch-mates it has (output_proj_kernel:
+ * f32 MFMA, 16 rows a workgroup, every sum in an order that depends on (H, E) only).  The call drains the stream and lets go of the workspace.
+ * sc_encoder_out_dim: the width of what the embedding entry points return now (E, or hidden). */
+sc_status sc_encoder_set_output_proj(sc_encoder* enc, const float* W, const float* b, int32_t E);
+sc_status sc_encoder_out_dim(sc_encoder* enc, int32_t* out);
 /* Replaces Embeddings.embed_documents / embed_query after tokenisation (indexer.py:150,
  * pipeline.py:171-175): ids [B,S] int32 (S in {32,64,128,256,512}, padded by the caller), lens [B] =
  * number of real tokens per row (keys >= len are masked, pooling = mean over the first len tokens),
@@ -446,6 +486,23 @@ sc_status sc_diag_set_option(const char* name, int32_t value);
  * position r % S, S a power of two; theta <= 0 = 10000).  sc_diag_swiglu: h [rows, 2F] f32 (gate | up) -> out [rows, F] =
  * silu(gate) * up through the SwiGLU kernel (F a multiple of 8). */
 sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta);
+/* The T5 encoder's kernels on their own (arch 3).
+ * sc_diag_rel_buckets: the bucket rule of sc_encoder_cfg's comment, the function that builds the device table: out[d + span - 1] =
+ *   bucket(d) for d = key - query in -(span - 1) .. span - 1.  Host arithmetic only: no runtime, no device.
+ * sc_diag_attention_bias / sc_diag_attention_bias_packed: sc_diag_attention_ex / sc_diag_attention_packed with heads of 64 and the scores
+ *   q.k + rel_bias[bucket(key - query)][head] (NO 1/8), rel_bias [buckets][heads] f32; positions count from the start of each sequence.
+ * sc_diag_ffn_act: kind 3 = the ReLU pass on h [rows, F] (rounded to bf16) -> out [rows, F]; kind 4 = the tanh-GELU gate on h [rows, 2F]
+ *   (gate | up) -> out [rows, F] = gelu_new(gate) * up.  F a multiple of 8. */
+sc_status sc_diag_rel_buckets(int32_t rel_buckets, int32_t max_distance, int32_t span, int32_t* out);
+sc_status sc_diag_attention_bias(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                                 const float* rel_bias, int32_t buckets, int32_t max_distance, float* out);
+sc_status sc_diag_attention_bias_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                        int32_t blocked_rows, const float* rel_bias, int32_t buckets, int32_t max_distance, float* out);
+sc_status sc_diag_ffn_act(sc_runtime* rt, int32_t kind, const float* h, int32_t rows, int32_t F, float* out);
+/* sc_diag_output_proj: output_proj_kernel on its own.  x [B,H] f32 (taken as it is: pooled rows are f32), W [E,H], bias [E] or NULL ->
+ * out [B,E] = W x + bias, L2-normalised by x / max(|x|, 1e-12) when normalize.  H, E multiples of 16 within 16 .. 2048. */
+sc_status sc_diag_output_proj(sc_runtime* rt, const float* x, int32_t B, int32_t H, const float* W, const float* bias, int32_t E, int32_t normalize,
+                              float* out);
 sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out);
 /* qkv [B*S, 3*heads*64] rows = [Q | K | V]; lens [B]; out [B*S, heads*64] = softmax(QK^T/8 + mask) V. */
 sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out);

@@ -47,7 +47,7 @@ def kernels(lib):
                 if name is None or not line.startswith("\t") and not line.startswith(" "):
                     continue
                 ins = re.sub(r"\s*//.*$", "", line).strip()
-                if ins:
+                if ins and ins != "...":  # "...": zero padding objdump skips behind a function, no instruction
                     lines.append(re.sub(r"\s+", " ", ins))
             if name is not None:
                 out[name] = lines

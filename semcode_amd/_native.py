@@ -43,13 +43,26 @@ class EncoderCfg(C.Structure):
     # The fields above are sc_encoder_cfg as it stood when kv_heads was appended; what later models append lives in EncoderCfgFull, the
     # whole struct.  The library reads and writes sizeof(sc_encoder_cfg) bytes through every sc_encoder_cfg pointer (sc_encoder_info
     # fills all of it), so an object of the shorter layout must never reach it: constructing EncoderCfg gives the whole struct.
+    # The declared fields end where the struct ended when qk_norm was appended; the object always owns all of sizeof(sc_encoder_cfg) bytes,
+    # zeroed (EncoderCfgFull.CFG_BYTES: all-zero tail fields mean the behaviour without them).
     def __new__(cls, *args, **kw):
-        return super().__new__(EncoderCfgFull if cls is EncoderCfg else cls, *args, **kw)
+        real = EncoderCfgFull if cls is EncoderCfg else cls
+        return real.from_buffer(bytearray(real.CFG_BYTES))
 
 
 class EncoderCfgFull(EncoderCfg):
-    """sc_encoder_cfg in full: EncoderCfg's fields, then head_dim and qk_norm (arch 2: Qwen3-Embedding, Qwen2.5-1.5B)."""
+    """sc_encoder_cfg: EncoderCfg's fields, then head_dim and qk_norm (arch 2: Qwen3-Embedding, Qwen2.5-1.5B).  The two fields the T5
+    encoder appended (arch 3: rel_buckets, rel_max_distance) lie behind the declared ones, in the object's own CFG_BYTES buffer, and are
+    read and written through the properties below; keyword arguments reach them as they reach a declared field."""
     _fields_ = [("head_dim", C.c_int32), ("qk_norm", C.c_int32)]
+    TAIL_FIELDS = ("rel_buckets", "rel_max_distance")  # int32 each, behind qk_norm in include/semcode_hip.h (tests/test_t5.py checks both against it)
+    CFG_BYTES = 88 + 4 * len(TAIL_FIELDS)  # sizeof(sc_encoder_cfg)
+
+    def _tail(self, name):
+        return C.c_int32.from_address(C.addressof(self) + 88 + 4 * self.TAIL_FIELDS.index(name))
+
+    rel_buckets = property(lambda self: self._tail("rel_buckets").value, lambda self, v: setattr(self._tail("rel_buckets"), "value", int(v)))
+    rel_max_distance = property(lambda self: self._tail("rel_max_distance").value, lambda self, v: setattr(self._tail("rel_max_distance"), "value", int(v)))
 
 
 class ScoreHead(C.Structure):
@@ -91,6 +104,9 @@ SIGNATURES = {
     "sc_encoder_wait": (C.c_int32, [C.c_void_p]),
     "sc_encoder_packed_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "sc_encoder_embed_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sc_encoder_set_output_proj": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "sc_encoder_out_dim": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "sc_diag_output_proj": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_encoder_set_pair_head": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32]),
     "sc_encoder_score_pairs": (C.c_int32, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_encoder_set_score_head": (C.c_int32, [C.c_void_p, C.POINTER(ScoreHead)]),
@@ -121,6 +137,11 @@ SIGNATURES = {
     "sc_diag_attention": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     "sc_diag_swiglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_rel_buckets": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_attention_bias": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_attention_bias_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p]),
+    "sc_diag_ffn_act": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_fold_ln": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "sc_diag_gemm_strip": (C.c_int32, [C.c_int32] * 4),
     "sc_diag_gemm_lna": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -822,6 +843,7 @@ class Comm:
 BERT_BASE = dict(vocab=30522, hidden=768, layers=12, heads=12, ffn=3072, max_pos=512, type_vocab=2, ln_eps=1e-12)
 SEQ_BUCKETS = (32, 64, 128, 256, 512, 1024, 2048)  # > 512: ALiBi or rotary encoders (no position table), or a position table that long
 POOLINGS = {"mean": 0, "cls": 1}  # sc_encoder_set_pooling
+POOLINGS_T5 = {"mean": 0, "first": 1}  # ... of a T5 encoder (arch 3): "first" = the first token's row (CodeT5+)
 POOLINGS_QWEN2 = {"mean": 0, "last": 2}  # ... of a qwen2 encoder (arch 2): "last" = the last real token's row; no "cls" there
 
 
@@ -829,8 +851,16 @@ def encoder_cfg(c: dict, normalize: bool = False, synth_seed: int = 0) -> Encode
     """sc_encoder_cfg of a complete configuration dict (the keys of BERT_BASE plus the architecture switches alibi / rotary / geglu /
     swiglu / rope_theta and, for the pre-LN ModernBERT family, modernbert / local_window / global_every / rope_theta_local; for the causal
     Qwen2 / Qwen3 family, qwen2 / kv_heads / head_dim (0, 64 or 128: heads of 128 are stated, never derived) / qk_norm)."""
-    if c.get("modernbert") and c.get("qwen2"):
-        raise ValueError("encoder configuration: modernbert and qwen2 are two architectures, pick one")
+    if sum(1 for k in ("modernbert", "qwen2", "t5") if c.get(k)) > 1:
+        raise ValueError("encoder configuration: modernbert, qwen2 and t5 are architectures, pick one")
+    if c.get("t5"):  # the T5 encoder (arch 3): relative position bias (pos_type 3), ffn "relu" (3) or "gated-gelu" (4)
+        ffn = {"relu": 3, "gated-gelu": 4}.get(c.get("t5_ffn"))
+        if ffn is None:
+            raise ValueError(f"encoder configuration: t5_ffn must be 'relu' or 'gated-gelu', got {c.get('t5_ffn')!r}")
+        return EncoderCfg(vocab=c["vocab"], hidden=c["hidden"], layers=c["layers"], heads=c["heads"], ffn=c["ffn"], max_pos=c["max_pos"],
+                          type_vocab=c.get("type_vocab") or 1, ln_eps=c["ln_eps"], normalize=1 if normalize else 0, synth_seed=synth_seed, pos_type=3,
+                          ffn_type=ffn, arch=3, head_dim=int(c.get("head_dim") or 0), rel_buckets=int(c.get("rel_buckets") or 0),
+                          rel_max_distance=int(c.get("rel_max_distance") or 0))
     if c.get("rotary") and c.get("alibi"):
         raise ValueError("encoder configuration: rotary and alibi are two position schemes, pick one")
     if c.get("swiglu") and c.get("geglu"):
@@ -879,7 +909,7 @@ class Encoder:
     @property
     def poolings(self) -> dict:
         """The pooling modes of this encoder's architecture: name -> sc_encoder_set_pooling value."""
-        return POOLINGS_QWEN2 if self.cfg.arch == 2 else POOLINGS
+        return POOLINGS_QWEN2 if self.cfg.arch == 2 else POOLINGS_T5 if self.cfg.arch == 3 else POOLINGS
 
     @property
     def pooling(self) -> str:
@@ -911,6 +941,27 @@ class Encoder:
             raise RuntimeError("encoder is closed")
         return self._h
 
+    @property
+    def out_dim(self) -> int:
+        """Width of the vectors the embedding calls return: hidden, or E of the installed output projection (sc_encoder_out_dim)."""
+        v = C.c_int32()
+        _check(lib().sc_encoder_out_dim(self.handle, C.byref(v)))
+        return v.value
+
+    def set_output_proj(self, W=None, b=None) -> None:
+        """Install the output projection behind the pooling (sc_encoder_set_output_proj): W [E, hidden], b [E] or None; the embedding calls
+        then return [B, E] = W pooled + b, L2-normalised when the encoder normalises.  W None removes it."""
+        if W is None:
+            _check(lib().sc_encoder_set_output_proj(self.handle, None, None, 0))
+            return
+        W = np.ascontiguousarray(W, np.float32)
+        if W.ndim != 2 or W.shape[1] != self.hidden:
+            raise ValueError(f"output projection must be [E, {self.hidden}], got {W.shape}")
+        b = None if b is None else np.ascontiguousarray(b, np.float32).reshape(-1)
+        if b is not None and b.shape != (W.shape[0],):
+            raise ValueError("output projection bias must be [E]")
+        _check(lib().sc_encoder_set_output_proj(self.handle, W.ctypes.data_as(C.c_void_p), None if b is None else b.ctypes.data_as(C.c_void_p), W.shape[0]))
+
     def set_path(self, path: str) -> None:
         """'auto' | 'batch' (LayerNorm-folded 256-tile pipeline for every size) | 'small' (split-K + LayerNorm kernels)."""
         _check(lib().sc_encoder_set_path(self.handle, {"auto": 0, "batch": 1, "small": 2}[path]))
@@ -922,7 +973,7 @@ class Encoder:
         if ids.ndim != 2 or lens.shape != (ids.shape[0],):
             raise ValueError("ids must be [B, S] and lens [B]")
         B, S = ids.shape
-        out = np.empty((B, self.hidden), dtype=np.float32)
+        out = np.empty((B, self.out_dim), dtype=np.float32)
         _check(lib().sc_encoder_embed_ids(self.handle, ids.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S,
                                           out.ctypes.data_as(C.c_void_p)))
         return out
@@ -942,7 +993,7 @@ class Encoder:
             _check(lib().sc_encoder_embed_ids_into_async(self.handle, ids.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S,
                                                          index.handle, rows.ctypes.data_as(C.c_void_p)))
             return None
-        out = np.empty((B, self.hidden), dtype=np.float32) if want_host else None
+        out = np.empty((B, self.out_dim), dtype=np.float32) if want_host else None
         _check(lib().sc_encoder_embed_ids_into(self.handle, ids.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S, index.handle,
                                                rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p) if want_host else None))
         return out
@@ -972,7 +1023,7 @@ class Encoder:
     def embed_packed(self, ids_flat, offsets) -> np.ndarray:
         """embed_ids without padding: text i = ids_flat[offsets[i]:offsets[i + 1]] -> [B, hidden] f32."""
         ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
-        out = np.empty((B, self.hidden), dtype=np.float32)
+        out = np.empty((B, self.out_dim), dtype=np.float32)
         _check(lib().sc_encoder_embed_packed(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B,
                                              out.ctypes.data_as(C.c_void_p)))
         return out
@@ -987,7 +1038,7 @@ class Encoder:
             _check(lib().sc_encoder_embed_packed_into_async(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B,
                                                             index.handle, rows.ctypes.data_as(C.c_void_p)))
             return None
-        out = np.empty((B, self.hidden), dtype=np.float32) if want_host else None
+        out = np.empty((B, self.out_dim), dtype=np.float32) if want_host else None
         _check(lib().sc_encoder_embed_packed_into(self.handle, ids_flat.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p), B, index.handle,
                                                   rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p) if want_host else None))
         return out
@@ -1245,6 +1296,67 @@ def diag_rope(rt: Runtime, qk, S: int, heads: int, theta: float) -> np.ndarray:
     if out.shape != (rows, heads * 64):
         raise ValueError("qk must be [rows, heads * 64]")
     _check(lib().sc_diag_rope(rt.handle, out.ctypes.data_as(C.c_void_p), rows, int(S), int(heads), float(theta)))
+    return out
+
+
+def diag_rel_buckets(rel_buckets: int, max_distance: int, span: int) -> np.ndarray:
+    """T5's bucket rule as the library evaluates it: [2 span - 1] int32, entry d + span - 1 = bucket(d), d = key - query.  No device."""
+    out = np.empty(max(2 * int(span) - 1, 1), np.int32)  # (a span below 1 is the library's to refuse)
+    _check(lib().sc_diag_rel_buckets(int(rel_buckets), int(max_distance), int(span), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def diag_ffn_act(rt: Runtime, kind: int, h) -> np.ndarray:
+    """kind 3: the ReLU pass on h [rows, F]; kind 4: the tanh-GELU gate on h [rows, 2F] (gate | up).  bf16-rounded, [rows, F]."""
+    h = np.ascontiguousarray(h, np.float32)
+    rows, F = h.shape[0], h.shape[1] // (2 if kind == 4 else 1)
+    out = np.empty((rows, F), np.float32)
+    _check(lib().sc_diag_ffn_act(rt.handle, int(kind), h.ctypes.data_as(C.c_void_p), rows, F, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def diag_attention_bias(rt: Runtime, qkv, lens, B: int, S: int, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
+    """sc_launch_attention_rel as the T5 forward calls it: diag_attention_ex with rel_bias [buckets, heads] in place of slopes."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    lens = np.ascontiguousarray(lens, np.int32)
+    rb = np.ascontiguousarray(rel_bias, np.float32)
+    H = heads * 64
+    if blocked_rows:
+        pad = np.zeros((blocked_rows, 3 * H), np.float32)
+        pad[: B * S] = qkv
+        qkv = block64(pad)
+    out = np.empty((B * S, H), np.float32)
+    _check(lib().sc_diag_attention_bias(rt.handle, qkv.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S, heads, int(blocked_rows),
+                                        rb.ctypes.data_as(C.c_void_p), rb.shape[0], int(max_distance), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def diag_attention_bias_packed(rt: Runtime, qkv, starts, lens, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
+    """The packed form: diag_attention_packed with rel_bias [buckets, heads] in place of slopes."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    starts = np.ascontiguousarray(starts, np.int32)
+    lens = np.ascontiguousarray(lens, np.int32)
+    rb = np.ascontiguousarray(rel_bias, np.float32)
+    H = heads * 64
+    R = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
+    if qkv.shape != (R, 3 * H) or starts.shape != lens.shape:
+        raise ValueError(f"diag_attention_bias_packed: qkv must be [{R}, {3 * H}], starts and lens [B]")
+    if blocked_rows:
+        qkv = block64(qkv)
+    out = np.empty((R, H), np.float32)
+    _check(lib().sc_diag_attention_bias_packed(rt.handle, qkv.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
+                                               len(lens), heads, int(blocked_rows), rb.ctypes.data_as(C.c_void_p), rb.shape[0], int(max_distance),
+                                               out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def diag_output_proj(rt: Runtime, x, W, b=None, normalize: bool = True) -> np.ndarray:
+    """output_proj_kernel on its own: x [B, H] f32, W [E, H], b [E] or None -> [B, E] = W x + b, L2-normalised if asked."""
+    x, W = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(W, np.float32)
+    b = None if b is None else np.ascontiguousarray(b, np.float32)
+    out = np.empty((x.shape[0], W.shape[0]), np.float32)
+    _check(lib().sc_diag_output_proj(rt.handle, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], W.ctypes.data_as(C.c_void_p),
+                                     None if b is None else b.ctypes.data_as(C.c_void_p), W.shape[0], 1 if normalize else 0, out.ctypes.data_as(C.c_void_p)))
     return out
 
 

@@ -4,7 +4,8 @@
 //                (AttnState / attention_qblock_core / attn_state_store), the band fold of local attention (attention_qblock_window),
 //                the causal fold for heads of 64 and of 128 (AttnStateCausal<NB> / attention_qblock_causal<NB, KT>, NB blocks of 64
 //                columns a head; at 128 K and V are two 64-wide images each)
-//   head width : Head64<ALIBI> and Head32 name state, init, fold and store of a width; the kernels are templates on one of them.
+//   head width : Head64<ALIBI>, Head64Rel (a table of the distance: T5) and Head32 name state, init, fold and store of a width and its
+//                additive bias; the kernels are templates on one of them.
 //                Head dimension 32: the LDS images hold a PAIR of heads, AttnState32 / attention_qblock_core32 / attn_state32_store
 //                run the softmax once per head of the pair
 //   the shell  : what a kernel does around the math (LDS carve-up, operand addressing, the two staging loops, the Q load, wait +
@@ -36,14 +37,19 @@ static __device__ __forceinline__ void attn_state_init(AttnState& a) {
 }
 // One segment of keys (the KT tiles in Kl / Vl = keys key0 .. key0 + 32 KT of the sequence; len / nkt count inside the segment)
 // folded into the state.  first: the state is fresh (no rescale of O before the first group).
-template <int KT, bool FULL, bool ALIBI, int GKMAX = 4>
+// BIAS: 0 plain scores q.k / 8; 1 ALiBi, q.k / 8 - slope |query - key|; 2 a table of the distance (Head64Rel below): q.k + tbw[key - query],
+// NO 1/sqrt(d), tbw = the LDS image of the head's distance table, placed so that the score of the segment's key kr and this block's query
+// l31 reads tbw[kr - l31].  The bias is what the score accumulator STARTS from -- the MFMAs add q.k on top in f32 -- so it costs one LDS read
+// per score and no arithmetic; the scale of the exp2 domain is then the policy's own constant log2(e) where the plain arm has log2(e) / 8
+template <int KT, bool FULL, int BIAS, int GKMAX = 4>
 static __device__ __forceinline__ void attention_qblock_core(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane,
-                                                             int qbase, float slope2, AttnState& S_, bool first, int key0) {
+                                                             int qbase, float slope2, AttnState& S_, bool first, int key0, const float* tbw = nullptr) {
     constexpr int GK = KT < GKMAX ? KT : GKMAX;   // key tiles per group
     constexpr int NG = (KT + GK - 1) / GK;
     const int l31 = lane & 31, hh = lane >> 5;
     const float sl2 = 0.125f * 1.44269504088896340736f;  // 1/sqrt(64) * log2(e)
     const int tail = len & 31;                           // != 0: the last real key tile is partially masked
+    const float* tl = BIAS == 2 ? tbw + (4 * hh - l31) : nullptr;  // the lane's part of a bias address in ONE register; tile and r are immediates
     float m_run = S_.m_run, l_run = S_.l_run;
     f32x16 o0 = S_.o0, o1 = S_.o1;
 #pragma unroll
@@ -57,7 +63,7 @@ static __device__ __forceinline__ void attention_qblock_core(const bf16x8 (&qf)[
             if (FULL || t < nkt) {
                 f32x16 acc;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+                for (int r = 0; r < 16; ++r) acc[r] = BIAS == 2 ? tl[32 * t + (r & 3) + 8 * (r >> 2)] : 0.f;
                 const int krow = 32 * t + l31;
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) {
@@ -65,7 +71,7 @@ static __device__ __forceinline__ void attention_qblock_core(const bf16x8 (&qf)[
                     const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kl + krow * 128 + ((c ^ ((krow >> 1) & 7)) << 4));
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
                 }
-                if (ALIBI) {  // work in the exp2 domain from here on: v = s * sl2 - slope2 * |q - key|
+                if (BIAS == 1) {  // work in the exp2 domain from here on: v = s * sl2 - slope2 * |q - key|
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float dist = (float)(key0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hh - (qbase + l31));
@@ -75,7 +81,7 @@ static __device__ __forceinline__ void attention_qblock_core(const bf16x8 (&qf)[
                 st[i] = acc;
             }
         }
-        const float sc2 = ALIBI ? 1.0f : sl2;  // scores already scaled when ALIBI
+        const float sc2 = BIAS == 2 ? 1.44269504088896340736f : BIAS == 1 ? 1.0f : sl2;  // ALiBi scores are scaled already; the table's are q.k + bias, scale 1
         float mx = m_run;
 #pragma unroll
         for (int i = 0; i < GK; ++i) {
@@ -688,6 +694,9 @@ template <bool ALIBI>
 struct Head64 {
     typedef AttnState State;
     typedef const float* __restrict__ Extra;  // [heads] ALiBi slopes (device), NULL without ALIBI
+    typedef float Bias;                       // what the fold gets per head: the slope in the exp2 domain
+    static constexpr bool TABLE = false;      // no LDS table behind the staging areas
+    static constexpr int table_bytes(int, int) { return 0; }
     static __device__ __forceinline__ void init(State& st) { attn_state_init(st); }
     static __device__ __forceinline__ float slope2(Extra slopes, int head) { return ALIBI ? slopes[head] * 1.44269504088896340736f : 0.f; }
     template <int KT, bool FULL, int GKMAX>
@@ -702,6 +711,9 @@ struct Head64 {
 struct Head32 {
     typedef AttnState32 State;
     struct Extra {};
+    typedef float Bias;
+    static constexpr bool TABLE = false;
+    static constexpr int table_bytes(int, int) { return 0; }
     static __device__ __forceinline__ void init(State& st) { attn_state32_init(st); }
     static __device__ __forceinline__ float slope2(Extra, int) { return 0.f; }
     template <int KT, bool FULL, int GKMAX>
@@ -712,6 +724,63 @@ struct Head32 {
         attn_state32_store(st, xch, ostg, obase, H, lane);
     }
 };
+
+// Heads of 64 with a bucketed relative position bias (T5, cfg.pos_type 3): score = q.k + bias[head][bucket(key - query)], no 1/sqrt(d).
+// The host expands the model's [buckets][heads] table through the bucket rule (rel_bucket_rule.h) into a DISTANCE table per head,
+// tbl[head][d + span - 1] for d = key - query in -(span - 1) .. span - 1.  A workgroup stages the slice its queries
+// (QW of them from qlo) and the staged keys (SEG of them from key0) can reach behind the staging areas of the shell -- entry j holds the
+// distance key0 - qlo - (QW - 1) + j, SEG + QW - 1 entries -- and the fold starts each score accumulator from tbw[kr - l31]: one LDS read per
+// score, no transcendental, no global load, no arithmetic beside the MFMAs.  key0 and qbase enter through the staging exactly as ALiBi uses
+// them: segments of the long kernel, positions relative to the text's start in packed rows.
+struct RelBias {
+    const float* tbl;  // [heads][2 span - 1] f32 (device)
+    int span;          // cfg.max_pos
+};
+struct Head64Rel {
+    typedef AttnState State;
+    typedef RelBias Extra;
+    typedef const float* Bias;  // tbw of attention_qblock_core
+    static constexpr bool TABLE = true;
+    static constexpr int table_bytes(int seg, int qw) { return (seg + qw) * 4; }
+    static __device__ __forceinline__ void init(State& st) { attn_state_init(st); }
+    // entries d0 .. d0 + n - 1 of the head's table -> tb[0 .. n); a distance no (query, key) of a text can have is clamped into the table
+    static __device__ __forceinline__ void stage(Extra ex, int head, float* tb, int d0, int n, int tid, int nthreads) {
+        const int last = 2 * ex.span - 2;
+        const float* src = ex.tbl + (size_t)head * (last + 1);
+        for (int j = tid; j < n; j += nthreads) {
+            int g = d0 + j + ex.span - 1;
+            g = g < 0 ? 0 : (g > last ? last : g);
+            tb[j] = src[g];
+        }
+    }
+    // the wave's view of the staged slice: its query block starts `qoff` = (QW - 1) - (qbase - qlo) entries in
+    static __device__ __forceinline__ Bias bias(const float* tb, int qoff) { return tb + qoff; }
+    template <int KT, bool FULL, int GKMAX>
+    static __device__ __forceinline__ void fold(const bf16x8 (&qf)[4], const char* Kl, const char* Vl, float* xch, int len, int nkt, int lane, int qbase, Bias tbw, State& st, bool first,
+                                                int key0) {
+        // segments of 16 tiles fold in groups of TWO: with four, the bias reads in flight on top of 64 live scores put attention_kernel<.., 16, 8>
+        // (one workgroup per CU by its LDS, 256 registers a lane) 7 registers into scratch; with two it has none
+        attention_qblock_core<KT, FULL, 2, (KT >= 16 && GKMAX > 2 ? 2 : GKMAX)>(qf, Kl, Vl, xch, len, nkt, lane, qbase, 0.f, st, first, key0, tbw);
+    }
+    static __device__ __forceinline__ void store(const State& st, float* xch, char* ostg, bf16_t* obase, int H, int lane) {
+        attn_state_store(st, xch, ostg, obase, H, lane);
+    }
+};
+// What a shell hands the fold per head: the slope (Head64, Head32) or the wave's view of the staged table (Head64Rel)
+template <class HEAD>
+static __device__ __forceinline__ typename HEAD::Bias attn_bias_arg(typename HEAD::Extra extra, int head, const float* tb, int qoff) {
+    if constexpr (HEAD::TABLE) return HEAD::bias(tb, qoff);
+    else return HEAD::slope2(extra, head);
+}
+
+// The lane id for the store behind a segment loop.  The table policy's loop kernels sit at the 256 registers of their launch bounds, and the
+// compiler kept lane & 7 -- needed by the store only -- alive across the loop in scratch (4 bytes, 8 allocated) instead of recomputing it;
+// read afresh from the hardware behind the loop, nothing of it lives across.  The other policies keep their `lane`.
+template <class HEAD>
+static __device__ __forceinline__ int attn_store_lane(int lane) {
+    if constexpr (HEAD::TABLE) return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    else return lane;
+}
 
 // ------------------------------------------------------------------ launching
 // Raises KERNEL's dynamic-LDS limit to LDS bytes once per instantiation and device, then launches it with that much.

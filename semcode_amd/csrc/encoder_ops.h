@@ -45,6 +45,14 @@ void sc_launch_attention(const void* qkv, const int32_t* lens, int B, int S, int
                          int head_dim = 64);
 void sc_launch_geglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
 void sc_launch_swiglu(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+// T5 (cfg.arch 3).  geglu_tanh: the gate with the tanh-GELU ("gelu_new"), layout of the two above.  relu: in place on h [n] bf16, n a multiple of 8.
+// attention_rel / _rel_packed: sc_launch_attention / _packed for heads of 64 with scores q.k + tbl[head][key - query + span - 1] and NO 1/sqrt(d):
+// tbl [H / 64][2 span - 1] f32 on the device (sc_rel_bias_table); H = the attention width, heads * 64.
+void sc_launch_geglu_tanh(const void* h, int64_t tokens, int F, void* out, hipStream_t s);
+void sc_launch_relu(void* h, int64_t n, hipStream_t s);
+void sc_launch_attention_rel(const void* qkv, const int32_t* lens, int B, int S, int H, const float* tbl, int span, void* ctx, hipStream_t s, int blocked = 0);
+void sc_launch_attention_rel_packed(const void* qkv, const int32_t* items, const int* nitems, int H, const float* tbl, int span, void* ctx, hipStream_t s,
+                                    int blocked = 0);
 // rotary positions: in-place rotation of the first `nblocks` 64-column blocks (Q and K heads) of a blocked buffer [blocks][M][64];
 // cos / sin [>= S][32] f32, row r is position r % S
 void sc_launch_rope_qk(void* qkv, int64_t M, int nblocks, int S, const float* cos_t, const float* sin_t, hipStream_t s);
@@ -141,6 +149,11 @@ void sc_launch_cls_gather(const void* x, const int32_t* starts, int B, int S, in
                           hipStream_t s);
 void sc_launch_attention_cls(const void* qkv, const int32_t* starts, const int32_t* lens, int B, int S, int M, int H, int head_dim, const float* slopes, void* ctx,
                              int rows_pad, hipStream_t s);
+
+// ---- encoder_proj.hip: the output projection behind the pooling.  x [B,H] f32 (un-normalised pooled rows), W [E,H], bias [E] or NULL, f32 on
+// the device, 16-byte aligned -> out [B,E] = W x + bias, L2-normalised (x / max(|x|, 1e-12)) when normalize.  H, E multiples of 16, 16 .. 2048.
+bool sc_output_proj_supported(int H, int E);
+void sc_launch_output_proj(const float* x, int B, int H, const float* W, const float* bias, int E, int normalize, float* out, hipStream_t s);
 
 // ---- sc_encoder_heads.cpp: the rules of a score head, with sc_fail's message under `who`.  arch: the encoder's (0 is refused), or -1 for the kernels
 // alone (sc_diag_score_head: any kind, pooling not read)

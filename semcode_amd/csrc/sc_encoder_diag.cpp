@@ -9,6 +9,7 @@
 
 #include "encoder_ops.h"
 #include "maxsim_rule.h"
+#include "rel_bucket_rule.h"
 #include "sc_diag_blob.h"
 #include "sc_encoder_plan.h"
 #include "sc_internal.h"
@@ -47,6 +48,20 @@ sc_status download(const void* dev, size_t bytes, void* host, hipStream_t s) {
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
+    return SC_OK;
+}
+// T5's bias for the attention harnesses: rel_bias [buckets][heads] -> the distance table of a 2 048-token span on the device
+struct RelBiasArg {
+    const float* rel_bias = nullptr;
+    int buckets = 0, max_distance = 0;
+};
+const int DIAG_REL_SPAN = 2048;
+sc_status upload_rel_table(const char* who, const RelBiasArg& rb, int heads, sc_devbuf& out, hipStream_t s) {
+    if (!sc_rel_buckets_valid(rb.buckets, rb.max_distance))
+        return sc_fail(SC_ERR_INVALID, "%s: buckets must be even, 4 .. 256, and max_distance beyond buckets / 4, got %d / %d", who, rb.buckets, rb.max_distance);
+    const std::vector<float> tbl = sc_rel_bias_table(rb.rel_bias, rb.buckets, heads, rb.max_distance, DIAG_REL_SPAN);
+    SC_TRY(upload(tbl.data(), tbl.size() * 4, out, s));
+    SC_HIP(hipStreamSynchronize(s));  // tbl goes out of scope
     return SC_OK;
 }
 // device bf16 [n] -> host f32 [n]; synchronises
@@ -289,7 +304,7 @@ extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const flo
 // the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.  head_dim 64, or 32 (an even
 // number of heads, no slopes): H = heads * head_dim, the blocks stay 64 columns wide.
 static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                const float* slopes, float* out, int32_t head_dim = 64) {
+                                const float* slopes, float* out, int32_t head_dim = 64, RelBiasArg rb = RelBiasArg()) {
     if (!rt || !qkv || !lens || !out || B < 1 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
     const int H = heads * head_dim;
     if (!sc_attention_supported(S, H, heads, head_dim))
@@ -304,8 +319,19 @@ static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qk
     SC_TRY(upload(lens, (size_t)B * 4, dl, s));
     if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
     SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
-    sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
+    if (rb.rel_bias) {
+        SC_TRY(upload_rel_table(who, rb, heads, dsl, s));
+        sc_launch_attention_rel(dq.p, (const int32_t*)dl.p, B, S, H, (const float*)dsl.p, DIAG_REL_SPAN, dc.p, s, blocked_rows);
+    } else {
+        sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
+    }
     return download_bf16(dc.p, tokens * H, out, s);
+}
+// sc_launch_attention_rel: heads of 64, scores q.k + rel_bias[bucket(key - query)][head], no 1/sqrt(d)
+extern "C" sc_status sc_diag_attention_bias(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
+                                            const float* rel_bias, int32_t buckets, int32_t max_distance, float* out) {
+    if (!rel_bias) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_bias: rel_bias is NULL");
+    return diag_attention("sc_diag_attention_bias", rt, qkv, lens, B, S, heads, blocked_rows, nullptr, out, 64, RelBiasArg{rel_bias, buckets, max_distance});
 }
 extern "C" sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
                                           int32_t blocked_rows, const float* slopes, float* out) {
@@ -344,7 +370,7 @@ extern "C" sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, con
 
 // sc_launch_attention_packed as the packed forward calls it: the work items come from sc_packed_items, as there.
 static sc_status diag_attention_packed(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                       int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out) {
+                                       int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out, RelBiasArg rb = RelBiasArg()) {
     if (!rt || !qkv || !starts || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
     if (head_dim != 64 && !(head_dim == 32 && heads % 2 == 0 && !slopes))
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads and no ALiBi slopes (got %d, %d heads)", who, head_dim, heads);
@@ -369,8 +395,28 @@ static sc_status diag_attention_packed(const char* who, sc_runtime* rt, const fl
     SC_TRY(upload(items.data(), items.size() * 4, di, s));
     if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
     SC_TRY(alloc_nan(dc, (size_t)R * H * 2, s));
-    sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
+    if (rb.rel_bias) {
+        SC_TRY(upload_rel_table(who, rb, heads, dsl, s));
+        sc_launch_attention_rel_packed(dq.p, (const int32_t*)di.p, nitems, H, (const float*)dsl.p, DIAG_REL_SPAN, dc.p, s, blocked_rows);
+    } else {
+        sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
+    }
     return download_bf16(dc.p, R * H, out, s);  // synchronises: items may go
+}
+extern "C" sc_status sc_diag_attention_bias_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
+                                                   int32_t blocked_rows, const float* rel_bias, int32_t buckets, int32_t max_distance, float* out) {
+    if (!rel_bias) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_bias_packed: rel_bias is NULL");
+    return diag_attention_packed("sc_diag_attention_bias_packed", rt, qkv, starts, lens, B, heads, 64, blocked_rows, nullptr, out,
+                                 RelBiasArg{rel_bias, buckets, max_distance});
+}
+// The bucket rule alone: host arithmetic, no runtime (rel_bucket_rule.h, what builds the device table)
+extern "C" sc_status sc_diag_rel_buckets(int32_t rel_buckets, int32_t max_distance, int32_t span, int32_t* out) {
+    if (!out || span < 1 || span > (1 << 20)) return sc_fail(SC_ERR_INVALID, "sc_diag_rel_buckets: bad argument (span 1 .. 2^20)");
+    if (!sc_rel_buckets_valid(rel_buckets, max_distance))
+        return sc_fail(SC_ERR_INVALID, "sc_diag_rel_buckets: rel_buckets must be even, 4 .. 256, and max_distance beyond rel_buckets / 4, got %d / %d", rel_buckets,
+                       max_distance);
+    sc_rel_buckets(rel_buckets, max_distance, span, out);
+    return SC_OK;
 }
 extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
                                               int32_t blocked_rows, const float* slopes, float* out) {
@@ -611,6 +657,43 @@ static sc_status diag_gate(const char* who, bool swiglu, sc_runtime* rt, const f
 extern "C" sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_geglu", false, rt, h, rows, F, out); }
 // swiglu_kernel: silu(gate) * up
 extern "C" sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_swiglu", true, rt, h, rows, F, out); }
+
+// The activations of the T5 feed-forwards.  kind 3: relu_kernel, in place on the bf16-rounded h [rows, F] -> out [rows, F]; kind 4:
+// glu_kernel<ActGeluTanh> on h [rows, 2F] (gate | up) -> out [rows, F] = gelu_new(gate) * up
+extern "C" sc_status sc_diag_ffn_act(sc_runtime* rt, int32_t kind, const float* h, int32_t rows, int32_t F, float* out) {
+    const char* who = "sc_diag_ffn_act";
+    if (kind != 3 && kind != 4) return sc_fail(SC_ERR_INVALID, "%s: kind must be 3 (ReLU) or 4 (tanh-GELU gate), got %d", who, kind);
+    if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "%s: bad argument (F must be a multiple of 8)", who);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf fh, dh, dc;
+    if (kind == 3) {
+        SC_TRY(upload_bf16(h, (int64_t)rows * F, fh, dh, s));
+        sc_launch_relu(dh.p, (int64_t)rows * F, s);
+        return download_bf16(dh.p, (int64_t)rows * F, out, s);
+    }
+    SC_TRY(upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s));
+    SC_TRY(alloc_nan(dc, (size_t)rows * F * 2, s));
+    sc_launch_geglu_tanh(dh.p, rows, F, dc.p, s);
+    return download_bf16(dc.p, (int64_t)rows * F, out, s);
+}
+
+// output_proj_kernel on its own: x [B,H] f32 as it is (the pooled rows are f32), W [E,H], bias [E] or NULL -> out [B,E]
+extern "C" sc_status sc_diag_output_proj(sc_runtime* rt, const float* x, int32_t B, int32_t H, const float* W, const float* bias, int32_t E, int32_t normalize,
+                                         float* out) {
+    const char* who = "sc_diag_output_proj";
+    if (!rt || !x || !W || !out || B < 1 || B > 65536 * 16) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    if (!sc_output_proj_supported(H, E)) return sc_fail(SC_ERR_INVALID, "%s: H and E must be multiples of 16 within 16 .. 2048, got %d, %d", who, H, E);
+    SC_HIP(hipSetDevice(rt->device));
+    hipStream_t s = rt->stream;
+    sc_devbuf dx, dw, db, dout;
+    SC_TRY(upload(x, (size_t)B * H * 4, dx, s));
+    SC_TRY(upload(W, (size_t)E * H * 4, dw, s));
+    if (bias) SC_TRY(upload(bias, (size_t)E * 4, db, s));
+    SC_TRY(alloc_nan(dout, (size_t)B * E * 4, s));
+    sc_launch_output_proj((const float*)dx.p, B, H, (const float*)dw.p, bias ? (const float*)db.p : nullptr, E, normalize, (float*)dout.p, s);
+    return download(dout.p, (size_t)B * E * 4, out, s);
+}
 
 // The embedding kernels.  ln == 0: embed_raw_kernel -> rows [tokens_pad,H] + stats [slots][tokens_pad][2]; ln != 0: embed_ln_kernel ->
 // rows [tokens,H] (tokens_pad, slots, stats unused).  ids [tokens] (tokens = B*S, position = token % S), wemb [vocab,H], pemb [max_pos,H] or

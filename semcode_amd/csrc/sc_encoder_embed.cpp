@@ -10,8 +10,8 @@
 static sc_status check_embed_args(sc_encoder* e, const void* ids, const void* lens, int32_t B, int32_t S, const void* out) {
     if (!e || !ids || !lens || !out) return sc_fail(SC_ERR_INVALID, "embed: NULL argument");
     if (B < 1 || B > 65536) return sc_fail(SC_ERR_INVALID, "embed: batch %d out of range", B);
-    // (arch 2: the head width is the configuration's, hidden need not be heads * head_dim -- only the rule for S is asked for)
-    if (e->cfg.arch == 2 ? !sc_attention_supported(S, 64, 1, 64) : !sc_attention_supported(S, e->cfg.hidden, e->cfg.heads, e->cfg.hidden / e->cfg.heads))
+    // (arch 2, 3: the head width is the configuration's, hidden need not be heads * head_dim -- only the rule for S is asked for)
+    if (e->cfg.arch >= 2 ? !sc_attention_supported(S, 64, 1, 64) : !sc_attention_supported(S, e->cfg.hidden, e->cfg.heads, e->cfg.hidden / e->cfg.heads))
         return sc_fail(SC_ERR_UNSUPPORTED, "embed: sequence length %d not in {32,64,128,256,512,1024,2048} (pad on the host)", S);
     if (S > e->cfg.max_pos && e->cfg.pos_type != 1) return sc_fail(SC_ERR_INVALID, "embed: sequence length %d exceeds max_pos %d", S, e->cfg.max_pos);
     return SC_OK;
@@ -20,7 +20,8 @@ static sc_status check_embed_args(sc_encoder* e, const void* ids, const void* le
 // the index of an _into call (`who`) takes this encoder's rows
 static sc_status check_index(sc_encoder* e, sc_index* ix, const char* who) {
     if (ix->rt != e->rt) return sc_fail(SC_ERR_INVALID, "%s: encoder and index belong to different runtimes", who);
-    if (ix->dim != e->cfg.hidden) return sc_fail(SC_ERR_INVALID, "%s: index dim %d != encoder hidden %d", who, ix->dim, e->cfg.hidden);
+    if (ix->dim != out_width(e))
+        return sc_fail(SC_ERR_INVALID, "%s: index dim %d != encoder %s %d", who, ix->dim, e->proj.mem ? "output projection width" : "hidden", out_width(e));
     return SC_OK;
 }
 
@@ -42,14 +43,26 @@ static sc_status embed_host_locked(sc_encoder* e, const void* ids, const void* l
     return forward_locked(e, e->ids, e->lens, B, S, e->pooled);
 }
 
-// e->pooled into the index rows `rows`; lock order: encoder, then index (nothing takes them the other way round)
-static sc_status store_pooled_locked(sc_encoder* e, sc_index* ix, const int64_t* rows, int32_t B, const char* who) {
-    std::lock_guard<std::mutex> gi(ix->mu);
-    return sc_index_put_rows_locked(ix, e->pooled, true, rows, B, who);
+// What an embedding call returns for the B rows in e->pooled: the rows themselves, or -- an output projection is installed, the forward left
+// them un-normalised (out_normalize) -- their projection [B, E], normalised by the kernel, in `dst` (NULL: e->projected).  Enqueued, not synchronised.
+static const float* finished_rows(sc_encoder* e, int32_t B, float* dst = nullptr) {
+    if (!e->proj.mem) return e->pooled;
+    if (!dst) dst = e->projected;
+    sc_launch_output_proj(e->pooled, B, e->cfg.hidden, e->proj.w, e->proj.b, e->proj.E, e->cfg.normalize, dst, e->rt->stream);
+    return dst;
 }
-// ... and to the host (asynchronously)
-static sc_status pooled_to_host(sc_encoder* e, float* out, int32_t B) {
-    SC_HIP(hipMemcpyAsync(out, e->pooled, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, e->rt->stream));
+// the finished rows into the index rows `rows`; lock order: encoder, then index (nothing takes them the other way round)
+static sc_status store_pooled_locked(sc_encoder* e, sc_index* ix, const int64_t* rows, int32_t B, const char* who, const float** done = nullptr) {
+    const float* v = finished_rows(e, B);
+    if (done) *done = v;
+    std::lock_guard<std::mutex> gi(ix->mu);
+    return sc_index_put_rows_locked(ix, v, true, rows, B, who);
+}
+// ... and to the host (asynchronously); `v`: rows that are finished already
+static sc_status pooled_to_host(sc_encoder* e, float* out, int32_t B, const float* v = nullptr) {
+    if (!v) v = finished_rows(e, B);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(out, v, (size_t)B * out_width(e) * 4, hipMemcpyDeviceToHost, e->rt->stream));
     return SC_OK;
 }
 
@@ -61,7 +74,12 @@ extern "C" sc_status sc_encoder_embed_ids_dev(sc_encoder* e, const int32_t* ids_
     SC_HIP(hipSetDevice(e->rt->device));
     st = ensure_ws(e, (int64_t)B * S, B);
     if (st) return st;
-    return forward_locked(e, ids_dev, lens_dev, B, S, out_dev);
+    if (!e->proj.mem) return forward_locked(e, ids_dev, lens_dev, B, S, out_dev);
+    st = forward_locked(e, ids_dev, lens_dev, B, S, e->pooled);
+    if (st) return st;
+    finished_rows(e, B, out_dev);
+    SC_HIP(hipGetLastError());
+    return SC_OK;
 }
 
 extern "C" sc_status sc_encoder_embed_ids(sc_encoder* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t S, float* out) {
@@ -72,7 +90,8 @@ extern "C" sc_status sc_encoder_embed_ids(sc_encoder* e, const int32_t* ids, con
     st = embed_host_locked(e, ids, lens, B, S);
     if (st) return st;
     hipStream_t s = e->rt->stream;
-    SC_HIP(hipMemcpyAsync(out, e->pooled, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, s));
+    st = pooled_to_host(e, out, B);
+    if (st) return st;
     SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }
@@ -86,12 +105,13 @@ extern "C" sc_status sc_encoder_embed_ids_into(sc_encoder* e, const int32_t* ids
     st = embed_host_locked(e, ids, lens, B, S);
     if (st) return st;
     hipStream_t s = e->rt->stream;
-    st = store_pooled_locked(e, ix, rows, B, "sc_encoder_embed_ids_into");
+    const float* done = nullptr;
+    st = store_pooled_locked(e, ix, rows, B, "sc_encoder_embed_ids_into", &done);
     if (st) {
         hipStreamSynchronize(s);  // drain the stream before the upsert error is reported
         return st;
     }
-    if (out) SC_HIP(hipMemcpyAsync(out, e->pooled, (size_t)B * e->cfg.hidden * 4, hipMemcpyDeviceToHost, s));
+    if (out) SC_HIP(hipMemcpyAsync(out, done, (size_t)B * out_width(e) * 4, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }
@@ -214,8 +234,9 @@ extern "C" sc_status sc_encoder_embed_packed_into(sc_encoder* e, const int32_t* 
     if (st) return st;
     std::lock_guard<std::mutex> g(e->mu);
     return packed_call_locked(e, ids, offsets, B, used, PackedCall{}, rows, false, [&](const int64_t* h_rows) {
-        sc_status r = store_pooled_locked(e, ix, h_rows, B, who);
-        return r || !out ? r : pooled_to_host(e, out, B);
+        const float* done = nullptr;
+        sc_status r = store_pooled_locked(e, ix, h_rows, B, who, &done);
+        return r || !out ? r : pooled_to_host(e, out, B, done);
     });
 }
 

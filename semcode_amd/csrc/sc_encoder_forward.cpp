@@ -4,12 +4,13 @@
 //   -> X1 = LN(Y) -> Hm = gelu(X1 W1^T + b1) -> Y2 = Hm W2^T + b2 + X1 -> X = LN(Y2); pooled = masked mean, or (sc_encoder_set_pooling 1)
 //   the [CLS] row -- the last layer then runs on the [CLS] rows only from its attention on (cls_last_layer, encoder_cls.hip).
 //   forward_locked is its small-batch form, forward_folded_locked the batch form with every LayerNorm folded into its neighbours.
-// Pre-norm models (cfg.arch 1, ModernBERT) and causal decoders (cfg.arch 2, the Qwen2 family) share forward_raw_locked: h += Attn(N(h)),
+// Pre-norm models (cfg.arch 1, ModernBERT), causal decoders (cfg.arch 2, the Qwen2 family) and T5 encoders (cfg.arch 3) share forward_raw_locked: h += Attn(N(h)),
 //   h += MLP(N(h)) on a raw residual stream.  What a packed batch is (PackedCall, sc_encoder_plan.h) decides the two ends of each.
 #include "sc_encoder_state.h"
 
 static void launch_gate(const sc_encoder_cfg& c, const void* h, int64_t tokens, int F, void* out, hipStream_t s) {
     if (c.ffn_type == 2) sc_launch_swiglu(h, tokens, F, out, s);
+    else if (c.ffn_type == 4) sc_launch_geglu_tanh(h, tokens, F, out, s);
     else sc_launch_geglu(h, tokens, F, out, s);
 }
 // batch pipeline of rotary models ("rope_fused" of sc_diag_set_option): -1 = default, 0 = rope_qk_kernel after the QKV GEMM,
@@ -41,15 +42,16 @@ static void launch_attention(sc_encoder* e, const int32_t* lens_dev, int B, int 
     else sc_launch_attention(e->qkv, lens_dev, B, S, e->cfg.hidden, e->slopes, e->ctx, s, M, hd);
 }
 // The three steps in which the layers of the raw-stream forward (arch 1, arch 2) differ.
-// norm: LayerNorm with beta (arch 1) or RMSNorm (arch 2, b unused)
+// norm: LayerNorm with beta (arch 1) or RMSNorm (arch 2 and 3, b unused)
 static void launch_norm(const sc_encoder_cfg& c, const void* in, int tokens, const float* g, const float* b, void* out, hipStream_t s) {
-    if (c.arch == 2) sc_launch_rmsnorm(in, tokens, c.hidden, g, c.ln_eps, out, s);
+    if (c.arch >= 2) sc_launch_rmsnorm(in, tokens, c.hidden, g, c.ln_eps, out, s);
     else sc_launch_layernorm(in, tokens, c.hidden, g, b, c.ln_eps, out, s);
 }
 // rotation of layer l: arch 1 with the table of the layer's kind; arch 2 at head_dim 128 or with qk_norm by qknorm_rope_kernel -- the per-head
 // RMSNorm of Q and K and the rotation in one pass -- while the 64-wide model without it keeps rope_qk_kernel
 static void launch_layer_rotation(sc_encoder* e, const LayerW& w, int l, int M, int S, const PackedLayout* pk, hipStream_t s) {
     const sc_encoder_cfg& c = e->cfg;
+    if (c.arch == 3) return;  // T5 has no rotation: positions enter through the attention's bias table
     if (c.arch == 2 && (head_width(c) == 128 || c.qk_norm))
         sc_launch_qknorm_rope(e->qkv, M, c.heads, c.kv_heads, head_width(c), S, pk ? pk->pos : nullptr, c.max_pos, e->rope_cos, e->rope_sin, w.qng, w.kng, c.ln_eps, s);
     else launch_rope(e, M, S, pk, s, layer_is_local(c, l));
@@ -60,6 +62,9 @@ static void launch_layer_attention(sc_encoder* e, int l, const int32_t* lens_dev
     if (c.arch == 2) {
         if (pk) sc_launch_attention_causal_packed(e->qkv, pk->items, pk->nitems, c.heads, c.kv_heads, head_width(c), e->ctx, s, M);
         else sc_launch_attention_causal(e->qkv, lens_dev, B, S, c.heads, c.kv_heads, head_width(c), e->ctx, s, M);
+    } else if (c.arch == 3) {  // the one table serves every layer
+        if (pk) sc_launch_attention_rel_packed(e->qkv, pk->items, pk->nitems, (int)attn_width(c), e->rel_tbl, c.max_pos, e->ctx, s, M);
+        else sc_launch_attention_rel(e->qkv, lens_dev, B, S, (int)attn_width(c), e->rel_tbl, c.max_pos, e->ctx, s, M);
     } else if (layer_is_local(c, l)) {
         if (pk) sc_launch_attention_window_packed(e->qkv, pk->items, pk->nitems, c.hidden, c.local_window, e->ctx, s, M);
         else sc_launch_attention_window(e->qkv, lens_dev, B, S, c.hidden, c.local_window, e->ctx, s, M);
@@ -115,13 +120,13 @@ static sc_status cls_last_layer(sc_encoder* e, const LayerW& w, const int32_t* l
         ffn_in = e->hg;
     }
     sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, F, w.w2, F, w.b2, e->x1, H, e->y, H, Mc, H, F, s, sk, skb); });
-    sc_launch_cls_pool(e->y, nullptr, B, 1, H, w.ln2g, w.ln2b, c.ln_eps, c.normalize, out_dev, s);  // compact rows: text i's row is i
+    sc_launch_cls_pool(e->y, nullptr, B, 1, H, w.ln2g, w.ln2b, c.ln_eps, out_normalize(e, pk), out_dev, s);  // compact rows: text i's row is i
     SC_HIP(hipGetLastError());
     return SC_OK;
 }
 static void launch_mean_pool(sc_encoder* e, const void* x, const int32_t* lens_dev, int B, int S, const PackedLayout* pk, float* out_dev, hipStream_t s) {
     if (pk) sc_launch_mean_pool_packed(x, pk->starts, lens_dev, B, e->cfg.hidden, out_normalize(e, pk), out_dev, s);
-    else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, e->cfg.normalize, out_dev, s);
+    else sc_launch_mean_pool(x, lens_dev, B, S, e->cfg.hidden, out_normalize(e, pk), out_dev, s);
 }
 
 // The batch pipeline with every LayerNorm folded into its neighbours (no layernorm_kernel launch, no LayerNorm round trip
@@ -194,7 +199,7 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
         return launch_token_head(e, e->x1, pk, s);
     }
     if (cls) {  // the last LayerNorm on B rows, inside the pooling kernel
-        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, last.ln2g, last.ln2b, c.ln_eps, c.normalize, out_dev, s);
+        sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, last.ln2g, last.ln2b, c.ln_eps, out_normalize(e, pk), out_dev, s);
     } else if (out_normalize(e, pk)) {  // L2-normalised output: the plain pooling kernel does it; give it the normalised rows
         sc_launch_layernorm(e->x, tokens, H, last.ln2g, last.ln2b, c.ln_eps, e->x1, s);
         launch_mean_pool(e, e->x1, lens_dev, B, S, pk, out_dev, s);
@@ -228,12 +233,17 @@ static sc_status forward_folded_locked(sc_encoder* e, const int32_t* ids_dev, co
 //                 row (in f32, inside the pooling kernel; never pruned:      | pooling kernel), or the masked mean of RMS_final(h)
 //                 cls_last_layer is the post-LN layer); a token call: the    | (never a token call: the heads refuse arch 2)
 //                 token head on final_norm(h)                                |
+// T5 encoders (cfg.arch 3) are the third column: h at first and N as arch 2 (raw embedding kernels, RMSNorm in every layer); widths AW = KV =
+// heads * 64 (H unless head_dim 64 is stated); NO rotation; attention = the global kernels on Head64Rel (scores q.k + the bias table of the
+// distance, one table for all layers, no 1/8); feed-forward act = ReLU as a pass of its own over FFN1's [M, F] output (ffn_type 3) or the
+// tanh-GELU gate (ffn_type 4); pooled = the masked mean of RMS_final(h), or RMS_final of the FIRST token's row in f32 (the last-token kernel
+// under lengths of 1); never a scored or a token call (the heads refuse arch 3).
 static sc_status forward_raw_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* lens_dev, int32_t B, int32_t S, float* out_dev,
                                     const PackedLayout* pk) {
     const sc_encoder_cfg& c = e->cfg;
     sc_runtime* rt = e->rt;
     hipStream_t s = rt->stream;
-    const bool causal = c.arch == 2;
+    const bool causal = c.arch == 2, raw_emb = c.arch >= 2;  // arch 2 and 3: h starts as the token embedding itself, RMSNorm in every layer
     const int H = c.hidden, F = c.ffn, AW = (int)attn_width(c), QN = AW + 2 * (int)kv_width(c);
     const int tokens = pk ? pk->rows : B * S;
     const int M = (int)ceil256(tokens);
@@ -241,14 +251,14 @@ static sc_status forward_raw_locked(sc_encoder* e, const int32_t* ids_dev, const
     void* sk;
     size_t skb;
     if (sc_status st = splitk_scratch(e, M, scored || token_call(pk), &sk, &skb)) return st;
-    if (causal && pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
-    else if (causal) sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
+    if (raw_emb && pk) sc_launch_embed_raw_packed(ids_dev, pk->pos, tokens, M, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
+    else if (raw_emb) sc_launch_embed_raw(ids_dev, tokens, M, S, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->x, nullptr, 0, s);
     else if (pk) sc_launch_embed_ln_packed(ids_dev, pk->pos, tokens, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     else sc_launch_embed_ln(ids_dev, tokens, S, H, c.vocab, c.max_pos, e->wemb, nullptr, e->temb, e->embg, e->embb, c.ln_eps, e->x, s);
     for (int l = 0; l < c.layers; ++l) {
         const LayerW& w = e->layers[l];
         const void* a = e->x;
-        if (causal || l > 0) {
+        if (raw_emb || l > 0) {
             launch_norm(c, e->x, tokens, w.ln1g, w.ln1b, e->x1, s);
             a = e->x1;
         }
@@ -257,13 +267,22 @@ static sc_status forward_raw_locked(sc_encoder* e, const int32_t* ids_dev, const
         sc_with_prof(rt, SC_PROF_ATTN, [&] { launch_layer_attention(e, l, lens_dev, B, S, M, pk, s); });
         sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->ctx, AW, w.wo, AW, w.bo, e->x, H, e->y, H, M, H, AW, s, sk, skb); });
         launch_norm(c, e->y, tokens, w.ln2g, w.ln2b, e->x1, s);
-        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
-        launch_gate(c, e->hm, M, F, e->hg, s);
-        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, e->hg, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
+        const void* ffn_in = e->hg;
+        if (c.ffn_type == 3) {  // Linear-ReLU-Linear (T5 v1.0): the ReLU as a pass of its own over FFN1's output, no gate
+            sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, F, M, F, H, s, sk, skb); });
+            sc_launch_relu(e->hm, (int64_t)M * F, s);
+            ffn_in = e->hm;
+        } else {
+            sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS, e->x1, H, w.w1, H, w.b1, nullptr, 0, e->hm, 2 * F, M, 2 * F, H, s, sk, skb); });
+            launch_gate(c, e->hm, M, F, e->hg, s);
+        }
+        sc_with_prof(rt, SC_PROF_GEMM, [&] { sc_launch_gemm_bf16(EPI_BIAS_RES, ffn_in, F, w.w2, F, w.b2, e->y, H, e->x, H, M, H, F, s, sk, skb); });
     }
     const int32_t* starts = pk ? pk->starts : nullptr;
     if (causal && (scored || e->pooling == 2)) {
         sc_launch_last_pool(e->x, starts, lens_dev, B, S, H, e->fing, c.ln_eps, out_normalize(e, pk), out_dev, s);
+    } else if (c.arch == 3 && cls_pooling(e, pk)) {  // T5, first token: the last-token kernel under lengths of 1 -- RMS_final in f32 on B rows
+        sc_launch_last_pool(e->x, starts, e->ones, B, S, H, e->fing, c.ln_eps, out_normalize(e, pk), out_dev, s);
     } else if (!causal && (scored ? pk->call.head_pool == 1 : cls_pooling(e, pk))) {
         sc_launch_cls_pool(e->x, starts, B, S, H, e->fing, e->finb, c.ln_eps, out_normalize(e, pk), out_dev, s);
     } else {
@@ -329,7 +348,7 @@ sc_status forward_locked(sc_encoder* e, const int32_t* ids_dev, const int32_t* l
         sc_launch_layernorm(e->y, tokens, H, w.ln2g, w.ln2b, c.ln_eps, e->x, s);
     }
     if (tok) return launch_token_head(e, e->x, pk, s);
-    if (cls) sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, nullptr, nullptr, c.ln_eps, c.normalize, out_dev, s);
+    if (cls) sc_launch_cls_pool(e->x, pk ? pk->starts : nullptr, B, S, H, nullptr, nullptr, c.ln_eps, out_normalize(e, pk), out_dev, s);
     else launch_mean_pool(e, e->x, lens_dev, B, S, pk, out_dev, s);
     SC_HIP(hipGetLastError());
     return SC_OK;

@@ -22,9 +22,10 @@ struct HeadPart {
 // Measures over an Arena, allocates, places, uploads while keeping the first error -- a bf16 array through an f32 staging copy, rounded once on
 // device as every encoder weight -- and synchronises: the caller's arrays are free on return and nothing still reads the head that goes.
 // On failure the fresh allocation is freed and *installed stays; on success the old one is freed.  No parts: the head is removed.
-// Takes e->mu.
+// Takes e->mu; `swapped`, if given, runs behind the exchange under the same hold (the stream is drained by then).
 template <class Head>
-static sc_status install_head(sc_encoder* e, Head* installed, Head* fresh, const std::vector<HeadPart>& parts, const char* what) {
+static sc_status install_head(sc_encoder* e, Head* installed, Head* fresh, const std::vector<HeadPart>& parts, const char* what,
+                              void (*swapped)(sc_encoder*) = nullptr) {
     std::lock_guard<std::mutex> g(e->mu);
     SC_HIP(hipSetDevice(e->rt->device));
     hipStream_t s = e->rt->stream;
@@ -69,6 +70,7 @@ static sc_status install_head(sc_encoder* e, Head* installed, Head* fresh, const
     }
     hipFree(installed->mem);
     *installed = *fresh;
+    if (swapped) swapped(e);
     return SC_OK;
 }
 
@@ -108,6 +110,7 @@ extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, c
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 1 (pre-LN) models have no pair head: their classifier is not pooler + linear", who);
     if (e->cfg.arch == 2)  // no segment ids, no [CLS] row, no pooler: rerankers of this family are out of scope
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models do not score pairs: the family has no [CLS] row and no pair head", who);
+    if (e->cfg.arch == 3) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 3 (T5 encoder) models are embedding models only here: no pair, score or token head (seq2seq rerankers are out of scope)", who);
     int64_t used = 0;
     sc_status st = check_packed_offsets(e, offsets, B, who, &used);
     if (!st) st = sc_plan_check_pairs(offsets, first_lens, B, plan_bounds(e), who);
@@ -121,11 +124,42 @@ extern "C" sc_status sc_encoder_score_pairs(sc_encoder* e, const int32_t* ids, c
     });
 }
 
+// ------------------------------------------------------------------ the output projection behind the pooling (every arch; embedding calls only)
+extern "C" sc_status sc_encoder_set_output_proj(sc_encoder* e, const float* W, const float* b, int32_t E) {
+    const char* who = "sc_encoder_set_output_proj";
+    if (!e) return sc_fail(SC_ERR_INVALID, "%s: NULL encoder", who);
+    const size_t H = (size_t)e->cfg.hidden;
+    OutProj fresh;
+    std::vector<HeadPart> parts;
+    if (W) {
+        if (E < 16 || E > 2048 || (E % 16)) return sc_fail(SC_ERR_INVALID, "%s: E = %d must be a multiple of 16 within 16 .. 2048", who, E);
+        if (!sc_output_proj_supported((int)H, E)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: hidden %d must be a multiple of 16, at most 2048", who, (int)H);
+        fresh.E = E;
+        parts = {{&fresh.w, W, (size_t)E * H}, {&fresh.b, b, (size_t)E}};
+    }
+    // the workspace holds the projected rows of a batch: dropped in the lock hold that exchanges the projection, so that no call sees one laid
+    // out for the other; the next call lays it out again, with or without them
+    return install_head(e, &e->proj, &fresh, parts, "output projection", [](sc_encoder* enc) {
+        hipFree(enc->ws);
+        enc->ws = nullptr;
+        enc->projected = nullptr;
+        enc->ws_tokens = 0;
+        enc->ws_batch = 0;
+    });
+}
+extern "C" sc_status sc_encoder_out_dim(sc_encoder* e, int32_t* out) {
+    if (!e || !out) return sc_fail(SC_ERR_INVALID, "sc_encoder_out_dim: NULL argument");
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = out_width(e);
+    return SC_OK;
+}
+
 // ------------------------------------------------------------------ score heads of the arch 1 / arch 2 rerankers
 // arch: the encoder's, or -1 (sc_diag_score_head: the kernels alone, any kind, pooling not read)
 sc_status sc_score_head_check(const sc_score_head* h, int arch, int H, const char* who) {
     if (arch == 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 0 (post-LN BERT family) models take the pooler + linear head of sc_encoder_set_pair_head / sc_encoder_score_pairs", who);
+    if (arch == 3) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 3 (T5 encoder) models are embedding models only here: no pair, score or token head (seq2seq rerankers are out of scope)", who);
     if (h->kind != 1 && h->kind != 2)
         return sc_fail(SC_ERR_INVALID, "%s: unknown kind %d (1 = prediction head of the pre-norm family, 2 = linear head on the last token)", who, h->kind);
     if (arch > 0 && h->kind != arch)
@@ -167,6 +201,7 @@ extern "C" sc_status sc_encoder_score_seqs(sc_encoder* e, const int32_t* ids, co
     if (!e || !ids || !offsets || !out_logits) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
     if (e->cfg.arch == 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 0 (post-LN BERT family) models score pairs through sc_encoder_set_pair_head / sc_encoder_score_pairs", who);
+    if (e->cfg.arch == 3) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 3 (T5 encoder) models are embedding models only here: no pair, score or token head (seq2seq rerankers are out of scope)", who);
     int64_t used = 0;
     sc_status st = check_packed_offsets(e, offsets, B, who, &used);
     if (st) return st;
@@ -184,6 +219,7 @@ extern "C" sc_status sc_encoder_set_token_head(sc_encoder* e, const float* w, in
     const char* who = "sc_encoder_set_token_head";
     if (!e) return sc_fail(SC_ERR_INVALID, "%s: NULL encoder", who);
     if (e->cfg.arch == 2) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models have no token head: late interaction needs bidirectional token rows", who);
+    if (e->cfg.arch == 3) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 3 (T5 encoder) models are embedding models only here: no pair, score or token head (seq2seq rerankers are out of scope)", who);
     const size_t H = (size_t)e->cfg.hidden;
     if (w && !sc_token_head_supported((int)H, W)) return sc_fail(SC_ERR_INVALID, "%s: W = %d must be a multiple of 16 within 16 .. 128", who, W);
     TokenHead fresh;

@@ -7,13 +7,15 @@
 #include <cmath>
 #include <new>
 
+#include "rel_bucket_rule.h"
 #include "sc_encoder_state.h"
 
 // number of f32 values in the weight blob, in blob order (see include/semcode_hip.h)
 static int64_t blob_floats(const sc_encoder_cfg& c) {
     const int64_t H = c.hidden, F = c.ffn, F1 = ffn_gated(c) ? 2 * F : F;
     const int64_t KV = kv_width(c), AW = attn_width(c);
-    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch != 0 ? 0 : (int64_t)c.type_vocab * H) + (c.arch == 2 ? 0 : 2 * H);
+    int64_t n = (int64_t)c.vocab * H + (c.pos_type != 0 ? 0 : (int64_t)c.max_pos * H) + (c.arch != 0 ? 0 : (int64_t)c.type_vocab * H) + (c.arch >= 2 ? 0 : 2 * H);
+    if (c.pos_type == 3) n += (int64_t)c.rel_buckets * c.heads;  // rel_bias [rel_buckets, heads] behind word_emb
     n += (int64_t)c.layers * ((AW * H + AW) + (H * AW + H) + 2 * (KV * H + KV) + 2 * H + (F1 * H + F1) + (H * F + H) + 2 * H);
     if (c.arch == 2 && c.qk_norm) n += (int64_t)c.layers * 2 * head_width(c);  // q_norm, k_norm gammas behind each layer's ln2_beta
     if (c.arch != 0) n += 2 * H;  // final_norm
@@ -29,21 +31,30 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
     if (c.vocab < 1 || c.hidden < 1 || c.layers < 1 || c.heads < 1 || c.ffn < 1 || c.max_pos < 1 || c.type_vocab < 1)
         return sc_fail(SC_ERR_INVALID, "sc_encoder_create: non-positive model dimension");
     const bool wide = c.arch == 2 && c.head_dim == 128;  // heads of 128 are stated, never derived: hidden need not be heads * 128
-    if (!wide && c.hidden != c.heads * 64 && c.hidden != c.heads * 32)
+    if (!wide && !t5_stated_heads(c) && c.hidden != c.heads * 64 && c.hidden != c.heads * 32)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension must be 64 or 32 (hidden=%d heads=%d)", c.hidden, c.heads);
     if (c.hidden % 128 || c.ffn % 128 || c.hidden > 2048)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: hidden (<=2048) and ffn must be multiples of 128 (got %d, %d)", c.hidden, c.ffn);
     if (!(c.ln_eps > 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: ln_eps must be > 0");
-    if (c.pos_type < 0 || c.pos_type > 2 || c.ffn_type < 0 || c.ffn_type > 2) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown pos_type / ffn_type");
+    if (c.pos_type < 0 || c.pos_type > 3 || c.ffn_type < 0 || c.ffn_type > 4) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown pos_type / ffn_type");
     if (c.hidden == c.heads * 32 && c.pos_type != 0)  // the rotary kernels pair columns (j, j + 32) of a 64-wide head; no 32-wide ALiBi kernel
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head dimension 32 runs with learned positions only (pos_type 0), not pos_type %d (%s)", c.pos_type,
                        c.pos_type == 1 ? "ALiBi" : "rotary");
     if (c.pos_type == 2 && !(c.rope_theta >= 0.f)) return sc_fail(SC_ERR_INVALID, "sc_encoder_create: rope_theta must be >= 0 (0 = 10000)");
-    if (c.arch < 0 || c.arch > 2)
-        return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT, 2 = causal Qwen2 decoder)", c.arch);
+    if (c.arch < 0 || c.arch > 3)
+        return sc_fail(SC_ERR_INVALID, "sc_encoder_create: unknown arch %d (0 = post-LN BERT family, 1 = pre-LN ModernBERT, 2 = causal Qwen2 decoder, 3 = T5 encoder)", c.arch);
+    if (c.arch == 3 && !sc_rel_buckets_valid(c.rel_buckets, c.rel_max_distance))  // (first: an arch 3 configuration without its table is no model at all)
+        return sc_fail(SC_ERR_INVALID, "sc_encoder_create: arch 3 needs rel_buckets even, 4 .. 256, and rel_max_distance beyond rel_buckets / 4, got %d / %d",
+                       c.rel_buckets, c.rel_max_distance);
+    if (c.arch != 3) {  // what the T5 encoder brought along exists in its pipeline only
+        if (c.pos_type == 3) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: pos_type 3 (bucketed relative position bias) needs arch 3, not arch %d", c.arch);
+        if (c.ffn_type > 2) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: ffn_type %d (3 = ReLU, 4 = tanh-GELU gate) needs arch 3, not arch %d", c.ffn_type, c.arch);
+        if (c.rel_buckets != 0 || c.rel_max_distance != 0)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: rel_buckets %d / rel_max_distance %d need arch 3 (0 elsewhere)", c.rel_buckets, c.rel_max_distance);
+    }
     if (c.arch != 2 && c.kv_heads != 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: kv_heads %d needs arch 2 (grouped-query attention exists in the causal pipeline only)", c.kv_heads);
-    if (c.arch != 2 && c.head_dim != 0)
+    if (c.arch != 2 && c.arch != 3 && c.head_dim != 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim %d needs arch 2 (a stated head dimension exists in the causal pipeline only; 0 elsewhere)", c.head_dim);
     if (c.arch != 2 && c.qk_norm != 0)
         return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: qk_norm %d needs arch 2 (the per-head RMSNorm of Q and K exists in the causal pipeline only)", c.qk_norm);
@@ -63,6 +74,24 @@ static sc_status check_cfg(const sc_encoder_cfg& c) {
                            c.heads);
         if (c.local_window != 0 || c.global_every > 1)
             return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window %d / global_every %d need arch 1 (arch 2 attends causally in every layer)", c.local_window,
+                           c.global_every);
+        return SC_OK;
+    }
+    if (c.arch == 3) {
+        // the T5 encoder: heads of 64 (Head64Rel), the bias table instead of positions, ReLU or the tanh-GELU gate
+        if (c.head_dim != 0 && c.head_dim != 64)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: head_dim must be 0 (hidden / heads, which must be 64) or 64 on arch 3, got %d", c.head_dim);
+        if (c.head_dim == 0 && c.hidden != c.heads * 64)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 3 needs head dimension 64 (hidden=%d heads=%d; head_dim 64 states it when hidden differs)", c.hidden,
+                           c.heads);
+        if ((c.heads * 64) % 128 || c.heads * 64 > 2048)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 3 needs heads * 64 (the attention width) a multiple of 128, at most 2048, got heads %d", c.heads);
+        if (c.pos_type != 3) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 3 runs with the relative position bias only (pos_type 3), not pos_type %d", c.pos_type);
+        if (c.ffn_type != 3 && c.ffn_type != 4)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 3 runs with ffn_type 3 (ReLU) or 4 (tanh-GELU gate), not ffn_type %d", c.ffn_type);
+        if (c.max_pos > 2048) return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: arch 3 needs max_pos <= 2048 (the distance table's span), got %d", c.max_pos);
+        if (c.local_window != 0 || c.global_every > 1)
+            return sc_fail(SC_ERR_UNSUPPORTED, "sc_encoder_create: local_window %d / global_every %d need arch 1 (arch 3 attends globally in every layer)", c.local_window,
                            c.global_every);
         return SC_OK;
     }
@@ -127,6 +156,7 @@ static void layout_params(sc_encoder* e, Arena& a) {
     e->rope_sin = e->rope_cos ? e->rope_cos + rope_n : nullptr;
     e->rope_cos_l = c.arch == 1 ? a.f32(2 * rope_n) : nullptr;
     e->rope_sin_l = e->rope_cos_l ? e->rope_cos_l + rope_n : nullptr;
+    e->rel_tbl = c.pos_type == 3 ? a.f32((size_t)c.heads * (2 * (size_t)c.max_pos - 1)) : nullptr;
     e->temb = a.f32(c.arch != 0 ? H : (size_t)c.type_vocab * H);  // arch 1, 2 have no type table: one row of zeros for the embedding kernels
     e->fing = c.arch != 0 ? a.f32(H) : nullptr;
     e->finb = c.arch != 0 ? a.f32(H) : nullptr;
@@ -220,9 +250,17 @@ extern "C" sc_status sc_encoder_create(sc_runtime* rt, const sc_encoder_cfg* cfg
     if (e->slopes) put_host(e->slopes, alibi_slopes(cfg->heads));
     if (e->rope_cos) put_host(e->rope_cos, sc_rope_table(cfg->max_pos, cfg->rope_theta, (int)HD));
     if (e->rope_cos_l) put_host(e->rope_cos_l, sc_rope_table(cfg->max_pos, cfg->rope_theta_local));
+    if (e->rel_tbl) {  // rel_bias [rel_buckets, heads] of the blob (synthetic: the 0.02 N(0,1) values) -> the distance table, expanded on the host
+        const int64_t nb = (int64_t)cfg->rel_buckets * cfg->heads;
+        std::vector<float> rb((size_t)nb);
+        he = hipMemcpyAsync(rb.data(), take(nb), (size_t)nb * 4, hipMemcpyDeviceToHost, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        if (he != hipSuccess) return fail(sc_fail(SC_ERR_HIP, "relative bias download failed: %s", hipGetErrorString(he)));
+        put_host(e->rel_tbl, sc_rel_bias_table(rb.data(), cfg->rel_buckets, cfg->heads, cfg->rel_max_distance, cfg->max_pos));
+    }
     if (cfg->arch != 0) hipMemsetAsync(e->temb, 0, (size_t)H * 4, s);
     else put_f32(e->temb, take((int64_t)cfg->type_vocab * H), (int64_t)cfg->type_vocab * H, COPY);
-    if (cfg->arch != 2) {  // arch 2 has no embedding norm
+    if (cfg->arch < 2) {  // arch 2 and 3 have no embedding norm
         put_f32(e->embg, take(H), H, ONES);
         put_f32(e->embb, take(H), H, ZEROS);
     }
@@ -283,6 +321,7 @@ extern "C" sc_status sc_encoder_destroy(sc_encoder* e) {
     hipFree(e->ws);
     hipFree(e->splitk);
     hipFree(e->pair.mem);
+    hipFree(e->proj.mem);
     hipFree(e->score.mem);
     hipFree(e->token.mem);
     hipFree(e->tok[0].p);
@@ -311,8 +350,10 @@ static void layout_ws(sc_encoder* e, Arena& a, size_t tokens, size_t nb) {
     e->hg = ffn_gated(e->cfg) ? a.bf16(tokens * F) : nullptr;
     e->ids = (int32_t*)a.take(tokens * 4);
     e->lens = (int32_t*)a.take(nb * 4);
+    e->ones = e->cfg.arch == 3 ? (int32_t*)a.take(nb * 4) : nullptr;
     e->plan = (char*)a.take(PlanOffsets(tokens, nb, PackedCall::PAIRS).total);
     e->pooled = a.f32(nb * H);
+    e->projected = e->proj.mem ? a.f32(nb * (size_t)e->proj.E) : nullptr;
     e->logits = a.f32(nb * 2);
     e->stat_a = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
     e->stat_b = e->foldable ? a.f32(slots * tokens * 2) : nullptr;
@@ -335,6 +376,7 @@ sc_status ensure_ws(sc_encoder* e, int64_t rows, int64_t B) {
     SC_HIP(hipMemsetAsync(e->ws, 0, arena.used, e->rt->stream));  // padded rows must hold finite values
     arena = Arena{e->ws};
     layout_ws(e, arena, (size_t)tokens, (size_t)B);  // place
+    if (e->ones) SC_HIP(hipMemsetD32Async((hipDeviceptr_t)e->ones, 1, (size_t)B, e->rt->stream));
     e->ws_tokens = tokens;
     e->ws_batch = B;
     return SC_OK;

@@ -49,6 +49,12 @@ struct TokenHead {  // late interaction (sc_encoder_set_token_head): the project
     int W = 0;
 };
 
+struct OutProj {  // the output projection behind the pooling (sc_encoder_set_output_proj): W [E,H] | b [E], f32; b NULL = none
+    char* mem = nullptr;
+    float *w = nullptr, *b = nullptr;
+    int E = 0;
+};
+
 struct sc_encoder {
     sc_runtime* rt = nullptr;
     sc_encoder_cfg cfg{};
@@ -58,6 +64,7 @@ struct sc_encoder {
     float *rope_cos = nullptr, *rope_sin = nullptr;  // rotary positions: [max_pos][32] f32 each (device) or NULL; arch 2 at head_dim 128: [max_pos][64]
     float *rope_cos_l = nullptr, *rope_sin_l = nullptr;  // arch 1: the table of the local layers (base rope_theta_local); the one above is the global layers'
     float *fing = nullptr, *finb = nullptr;              // arch 1: final_norm gamma / beta
+    float* rel_tbl = nullptr;  // pos_type 3 (T5): the distance table of the bias attention, [heads][2 max_pos - 1] f32 (sc_rel_bias_table), one for all layers
     std::vector<LayerW> layers;
     // workspace for `ws_tokens` (multiple of 256) tokens
     int64_t ws_tokens = 0;
@@ -65,6 +72,7 @@ struct sc_encoder {
     void *x = nullptr, *x1 = nullptr, *y = nullptr, *qkv = nullptr, *ctx = nullptr, *hm = nullptr, *hg = nullptr;
     int32_t* ids = nullptr;
     int32_t* lens = nullptr;
+    int32_t* ones = nullptr;  // arch 3: [ws_batch] lengths of 1, under which the last-token pooling kernel takes every text's FIRST row
     // packed batches: padded ids | positions | starts | lens | attention items (PlanOffsets), one upload per call.  Part of every
     // workspace, rectangle callers' too: 8 bytes per token row + 24 per sequence next to the 17-29 KiB a row's activations take
     char* plan = nullptr;
@@ -75,7 +83,7 @@ struct sc_encoder {
     float *fin_a = nullptr, *fin_b = nullptr;    // [ws_tokens][2] their finalised (mu, rs)
     bool foldable = false;                       // shapes allow the folded pipeline (256-tile GEMMs, K % 256 == 0)
     int path = 0;                                // sc_encoder_set_path: 0 auto, 1 batch pipeline always, 2 small-batch pipeline always
-    int pooling = 0;                             // sc_encoder_set_pooling: 0 masked mean, 1 the [CLS] row, 2 the last real token's row (arch 2)
+    int pooling = 0;                             // sc_encoder_set_pooling: 0 masked mean, 1 the [CLS] / first row, 2 the last real token's row (arch 2)
     void* splitk = nullptr;  // f32 partial products of the split-K GEMMs, allocated on first use (splitk_scratch)
     static constexpr size_t SPLITK_BYTES = 64u << 20;
     // pinned host staging: the plan of one packed batch, or ids | lens | rows of one asynchronous rectangle batch, per slot
@@ -87,6 +95,8 @@ struct sc_encoder {
     } pin[2];
     int pin_next = 0;
     PairHead pair;
+    OutProj proj;
+    float* projected = nullptr;  // [ws_batch][proj.E] in the workspace: what the embedding entry points return when a projection is installed
     ScoreHead score;
     TokenHead token;
     // token vectors of sc_encoder_embed_tokens / sc_encoder_score_late: the queries' (0) and the documents' (1) [rows][W] f32, and the
@@ -113,7 +123,12 @@ static inline bool token_call(const PackedLayout* pk) { return pk && pk->call.ki
 // [CLS] pooling applies to texts only: pairs take their [CLS] row whatever the mode, a scored call pools as its head says, a token call pools nothing
 static inline bool cls_pooling(const sc_encoder* e, const PackedLayout* pk) { return e->pooling == 1 && (!pk || pk->call.kind == PackedCall::TEXTS); }
 // the rows of a pair call and of a scored call are never L2-normalised
-static inline int out_normalize(const sc_encoder* e, const PackedLayout* pk) { return pair_call(pk) || scored_call(pk) ? 0 : e->cfg.normalize; }
+// ... and neither is the pooled row of a text when an output projection follows it: the projection kernel normalises its own output
+static inline int out_normalize(const sc_encoder* e, const PackedLayout* pk) {
+    return pair_call(pk) || scored_call(pk) || (e->proj.mem && (!pk || pk->call.kind == PackedCall::TEXTS)) ? 0 : e->cfg.normalize;
+}
+// the width of what an embedding entry point returns
+static inline int out_width(const sc_encoder* e) { return e->proj.mem ? e->proj.E : e->cfg.hidden; }
 
 // Lays the buffers of one device allocation out, each 256-byte aligned.  The layout code runs twice: over an arena without a base
 // it only measures (every buffer comes back NULL, `used` is the size to allocate), over the allocation it hands out the pointers.
@@ -125,13 +140,15 @@ struct Arena {
     void* bf16(size_t n) { return take(n * 2); }
 };
 
-// ffn_type 1 (GEGLU) and 2 (SwiGLU): W1 holds gate and up rows, an element-wise kernel sits between the two FFN GEMMs
-static inline bool ffn_gated(const sc_encoder_cfg& c) { return c.ffn_type == 1 || c.ffn_type == 2; }
+// ffn_type 1 (GEGLU), 2 (SwiGLU) and 4 (tanh-GELU gate, T5 v1.1): W1 holds gate and up rows, an element-wise kernel sits between the two FFN GEMMs
+static inline bool ffn_gated(const sc_encoder_cfg& c) { return c.ffn_type == 1 || c.ffn_type == 2 || c.ffn_type == 4; }
+// arch 3 (T5) with head_dim 64 stated: heads of 64 whatever hidden / heads is (t5-v1.1-small: 512 hidden, 6 heads)
+static inline bool t5_stated_heads(const sc_encoder_cfg& c) { return c.arch == 3 && c.head_dim == 64; }
 // arch 2: heads of 64, or of 128 when cfg.head_dim says so; K and V have kv_heads of them (0 = heads), Q has heads of them -- the attention
 // width AW, which need not be hidden at 128.  Every other model projects Q, K and V to hidden columns
 static inline int head_width(const sc_encoder_cfg& c) { return c.arch == 2 && c.head_dim == 128 ? 128 : 64; }
-static inline int64_t kv_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)(c.kv_heads > 0 ? c.kv_heads : c.heads) * head_width(c) : (int64_t)c.hidden; }
-static inline int64_t attn_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)c.heads * head_width(c) : (int64_t)c.hidden; }
+static inline int64_t attn_width(const sc_encoder_cfg& c) { return c.arch == 2 || t5_stated_heads(c) ? (int64_t)c.heads * head_width(c) : (int64_t)c.hidden; }
+static inline int64_t kv_width(const sc_encoder_cfg& c) { return c.arch == 2 ? (int64_t)(c.kv_heads > 0 ? c.kv_heads : c.heads) * head_width(c) : attn_width(c); }
 // arch 1: layer l attends globally iff l % global_every == 0 (global_every 0 counts as 1: every layer global)
 static inline bool layer_is_local(const sc_encoder_cfg& c, int l) { return c.arch == 1 && c.global_every > 1 && (l % c.global_every) != 0; }
 static inline PlanBounds plan_bounds(const sc_encoder* e) {

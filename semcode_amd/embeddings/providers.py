@@ -253,6 +253,165 @@ def _qwen_common(c: dict) -> dict:
                 swiglu=True, qwen2=True, rope_theta=float(rp.get("rope_theta", c.get("rope_theta", 10000.0))))
 
 
+def t5_config(config: "str | Path | dict") -> dict:
+    """The encoder configuration of a transformers T5 `config.json` (path or parsed dict; model_type `t5`, or `codet5p_embedding`, whose
+    `embed_dim` -- the width of the projection behind its first-token pooling -- is reported as "embed_dim"): `d_model`, `num_heads`,
+    `num_layers`, `d_ff`, the buckets of the relative position bias, `layer_norm_epsilon`, and `feed_forward_proj` "relu" or "gated-gelu"
+    (anything else is refused by name).  `d_kv` must be 64: heads of 64 are stated to the library when d_model / num_heads is not 64
+    (t5-v1.1-small).  max_pos is the 2 048 tokens a text may have here: T5 has no position table, the cap sizes the bias table."""
+    if not isinstance(config, dict):
+        import json
+
+        config = json.loads(Path(config).read_text())
+    c = config
+    if c.get("model_type") not in (None, "t5", "codet5p_embedding"):
+        raise ValueError(f"not a T5 configuration (model_type {c.get('model_type')!r})")
+    if int(c.get("d_kv", 64)) != 64:
+        raise ValueError(f"T5 config: d_kv {c.get('d_kv')} is not supported (heads of 64 only)")
+    ffn = c.get("feed_forward_proj", "relu")
+    if ffn not in ("relu", "gated-gelu"):
+        raise ValueError(f"T5 config: feed_forward_proj {ffn!r} is not supported ('relu' or 'gated-gelu')")
+    hidden, heads = int(c["d_model"]), int(c["num_heads"])
+    out = dict(vocab=int(c["vocab_size"]), hidden=hidden, layers=int(c["num_layers"]), heads=heads, ffn=int(c["d_ff"]), max_pos=2048, type_vocab=1,
+               ln_eps=float(c.get("layer_norm_epsilon", 1e-6)), t5=True, t5_ffn=ffn, rel_buckets=int(c.get("relative_attention_num_buckets", 32)),
+               rel_max_distance=int(c.get("relative_attention_max_distance", 128)))
+    if hidden != heads * 64:
+        out["head_dim"] = 64
+    if c.get("model_type") == "codet5p_embedding":
+        out["embed_dim"] = int(c["embed_dim"])
+    return out
+
+
+def t5_model_dir(weights: "str | Path | None") -> Optional[Path]:
+    """The directory of a T5 encoder model -- `weights` is that directory or its model.safetensors, and the config.json in it says
+    model_type t5 or codet5p_embedding -- else None."""
+    if not isinstance(weights, (str, Path)):
+        return None
+    path = Path(weights)
+    d = path if path.is_dir() else path.parent if path.suffix.lower() == ".safetensors" else None
+    if d is None or not (d / "config.json").is_file():
+        return None
+    import json
+
+    try:
+        c = json.loads((d / "config.json").read_text())
+    except (OSError, ValueError):
+        return None
+    return d if c.get("model_type") in ("t5", "codet5p_embedding") else None
+
+
+# transformers' T5EncoderModel / T5Model / CodeT5p_Embedding names -> the arch 3 blob of include/semcode_hip.h; decoder tensors are ignored.
+# Checked against T5EncoderModel on seeded weights (tests/test_t5.py); no released checkpoint exists offline, so parity for real files is unpinned.
+def _t5_blob(path, tensors: dict, cfg: dict) -> np.ndarray:
+    def find(*names: str):
+        for name in names:
+            if name in tensors:
+                return np.asarray(tensors[name], dtype=np.float32)
+        return None
+
+    def get(*names: str) -> np.ndarray:
+        t = find(*names)
+        if t is None:
+            raise KeyError(f"{path}: tensor {names[0]!r} not found")
+        return t
+
+    H, F, heads, layers = int(cfg["hidden"]), int(cfg["ffn"]), int(cfg["heads"]), int(cfg["layers"])
+    AW = heads * 64
+    gated = cfg["t5_ffn"] == "gated-gelu"
+    emb = get("shared.weight", "encoder.embed_tokens.weight")
+    rel = get("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight")
+    if emb.shape != (int(cfg["vocab"]), H) or rel.shape != (int(cfg["rel_buckets"]), heads):
+        raise ValueError(f"{path}: embedding table {emb.shape} / relative_attention_bias {rel.shape}, the configuration says "
+                         f"[{cfg['vocab']}, {H}] and [{cfg['rel_buckets']}, {heads}]")
+    zH, zA = np.zeros(H, np.float32), np.zeros(AW, np.float32)
+    parts = [emb.reshape(-1), rel.reshape(-1)]
+    for l in range(layers):
+        q = f"encoder.block.{l}.layer."
+        wq, wk, wv, wo = (get(q + f"0.SelfAttention.{n}.weight") for n in "qkvo")
+        if wq.shape != (AW, H) or wk.shape != (AW, H) or wv.shape != (AW, H) or wo.shape != (H, AW):
+            raise ValueError(f"{path}: {q}0.SelfAttention q / k / v / o are {wq.shape} / {wk.shape} / {wv.shape} / {wo.shape}, expected three [{AW}, {H}] and [{H}, {AW}]")
+        if gated:
+            w1 = np.concatenate([get(q + "1.DenseReluDense.wi_0.weight"), get(q + "1.DenseReluDense.wi_1.weight")])
+        else:
+            w1 = get(q + "1.DenseReluDense.wi.weight")
+        w2 = get(q + "1.DenseReluDense.wo.weight")
+        if w1.shape != ((2 * F if gated else F), H) or w2.shape != (H, F):
+            raise ValueError(f"{path}: {q}1.DenseReluDense weights are {w1.shape} / {w2.shape}, the configuration says ffn {F} ({cfg['t5_ffn']})")
+        parts += [wq.reshape(-1), zA, wk.reshape(-1), zA, wv.reshape(-1), zA, wo.reshape(-1), zH, get(q + "0.layer_norm.weight"), zH,
+                  w1.reshape(-1), np.zeros(w1.shape[0], np.float32), w2.reshape(-1), zH, get(q + "1.layer_norm.weight"), zH]
+    parts += [get("encoder.final_layer_norm.weight"), zH]
+    return np.concatenate(parts)
+
+
+def t5_projection(model_dir: "str | Path", tensors: Optional[dict] = None) -> "tuple[Optional[np.ndarray], Optional[np.ndarray]]":
+    """(W [E, H], b [E] or None) of the projection behind a T5 model's pooling, (None, None) when it has none: `proj.weight` / `proj.bias` of
+    the model file (CodeT5+), else the sentence-transformers module `2_Dense/model.safetensors` (`linear.weight`, `linear.bias` if any), whose
+    `2_Dense/config.json` must state an Identity activation -- any other is refused: the device applies none."""
+    d = Path(model_dir)
+    if tensors is None:
+        from safetensors.numpy import load_file
+
+        tensors = load_file(str(d / "model.safetensors"))
+    if "proj.weight" in tensors:
+        b = tensors.get("proj.bias")
+        return np.asarray(tensors["proj.weight"], np.float32), None if b is None else np.asarray(b, np.float32)
+    dense = d / "2_Dense"
+    if not (dense / "model.safetensors").is_file():
+        return None, None
+    import json
+
+    from safetensors.numpy import load_file
+
+    act = str(json.loads((dense / "config.json").read_text()).get("activation_function", "")) if (dense / "config.json").is_file() else ""
+    if not act.endswith("Identity"):
+        raise ValueError(f"{dense}: activation_function {act!r} is not supported (the Dense module must be linear: torch.nn.modules.linear.Identity)")
+    t = load_file(str(dense / "model.safetensors"))
+    if "linear.weight" not in t:
+        raise KeyError(f"{dense / 'model.safetensors'}: tensor 'linear.weight' not found")
+    b = t.get("linear.bias")
+    return np.asarray(t["linear.weight"], np.float32), None if b is None else np.asarray(b, np.float32)
+
+
+def t5_pooling(model_dir: "str | Path", pooling: Optional[str] = None) -> str:
+    """"first" or "mean" for a T5 directory: the argument ("cls" counts as "first"); else first for a codet5p_embedding model; else what
+    1_Pooling/config.json states (pooling_mode_cls_token -> first); else mean."""
+    if pooling:
+        mode = {"cls": "first"}.get(str(pooling).strip().lower(), str(pooling).strip().lower())
+        if mode not in ("first", "mean"):
+            raise ValueError(f"pooling of a T5 encoder must be 'first' or 'mean', got {pooling!r}")
+        return mode
+    import json
+
+    d = Path(model_dir)
+    if json.loads((d / "config.json").read_text()).get("model_type") == "codet5p_embedding":
+        return "first"
+    conf = d / "1_Pooling" / "config.json"
+    if conf.is_file() and bool(json.loads(conf.read_text()).get("pooling_mode_cls_token")):
+        return "first"
+    return "mean"
+
+
+def load_t5_directory(model_dir: "str | Path", pooling: Optional[str] = None) -> dict:
+    """Everything MI355XEmbeddings needs of a T5 encoder directory: cfg (t5_config of its config.json), blob (arch 3 order), proj (W, b) or
+    (None, None), pooling, and tokenizer_json -- the directory's tokenizer.json (T5's Unigram and CodeT5's byte-level BPE alike go through
+    HFTokenizer).  A directory with only the sentencepiece file is refused: convert it to a tokenizer.json first."""
+    from safetensors.numpy import load_file
+
+    d = Path(model_dir)
+    if not (d / "tokenizer.json").is_file():
+        if (d / "spiece.model").is_file():
+            raise ValueError(f"{d} has spiece.model but no tokenizer.json: the sentencepiece file is not read here; write the fast tokenizer's "
+                             "tokenizer.json (AutoTokenizer.from_pretrained(dir).save_pretrained(dir)) next to it")
+        raise ValueError(f"{d} has no tokenizer.json")
+    if not (d / "model.safetensors").is_file():
+        raise ValueError(f"{d} has no model.safetensors (.bin checkpoints are not read)")
+    cfg = t5_config(d / "config.json")
+    cfg.pop("embed_dim", None)
+    tensors = load_file(str(d / "model.safetensors"))
+    return dict(cfg=cfg, blob=_t5_blob(d / "model.safetensors", tensors, cfg), proj=t5_projection(d, tensors), pooling=t5_pooling(d, pooling),
+                tokenizer_json=d / "tokenizer.json")
+
+
 def qwen3_config(config: "str | Path | dict") -> dict:
     """The encoder configuration of a transformers Qwen3 `config.json` (Qwen3-Embedding-0.6B): qwen2_config's fields, `head_dim` from the
     file (hidden_size / num_attention_heads without it; the 0.6B model states 128 at hidden 1 024), qk_norm=True -- the per-head RMSNorm of Q
@@ -492,6 +651,16 @@ class MI355XEmbeddings:
         self._cfg = dict(_native.BERT_BASE)
         self._vocab_tmp = None
         file_pooling = None
+        # a T5 encoder directory (CodeT5+, GTR, sentence-T5; `weights` = the directory or its model.safetensors): config.json, the weights,
+        # the projection behind the pooling, the pooling and tokenizer.json all come from it (load_t5_directory)
+        t5 = None
+        t5_dir = t5_model_dir(weights)
+        if t5_dir is not None:
+            t5 = load_t5_directory(t5_dir, pooling or getattr(settings, "mi355x_pooling", None))
+            self._cfg = dict(t5["cfg"])
+            weights = t5["blob"]
+            if tokenizer_json is None and getattr(settings, "mi355x_tokenizer_json", None) is None:
+                tokenizer_json = t5["tokenizer_json"]
         if gguf_path is not None:  # the file states its own architecture, and carries the WordPiece vocabulary
             from .gguf import gguf_config, gguf_vocab, read_gguf
 
@@ -536,7 +705,7 @@ class MI355XEmbeddings:
         self._fast_tokenizer: Any = None
         self._owns_runtime = False  # an explicit runtime is the caller's; the default one is shared with the vector store
         self._runtime = runtime or _native.shared_runtime(int(device if device is not None else getattr(settings, "mi355x_device", 0)))
-        self.pooling = resolve_pooling(pooling, getattr(settings, "mi355x_pooling", None), weights, file_pooling)
+        self.pooling = t5["pooling"] if t5 else resolve_pooling(pooling, getattr(settings, "mi355x_pooling", None), weights, file_pooling)
         if isinstance(weights, (str, Path)):
             weights = load_weight_blob(weights, self._cfg["layers"], self._cfg)
         if weights is None:
@@ -551,7 +720,9 @@ class MI355XEmbeddings:
             self.tokenizer = WordPieceTokenizer(vocab)
             if isinstance(vocab, (str, Path)):  # the C++ tokenizer (ASCII fast path + full Unicode normalisation, multi-threaded)
                 self._fast_tokenizer = _native.NativeTokenizer(vocab)
-        self.dimension = self._cfg["hidden"]
+        if t5 and t5["proj"][0] is not None:
+            self._encoder.set_output_proj(*t5["proj"])
+        self.dimension = self._encoder.out_dim  # hidden, or the width of the model's output projection: what a store is created with
         # Texts that reached max_tokens lost their tail.  The reference's default chunker emits up to 200 lines / 6 000 characters
         # (tree_sitter_chunker.py:64-65: 1.5-2k word pieces) and only shrinks chunks for llamacpp / lmstudio (ingestion/manager.py:68-79),
         # so with a 512-position BERT most real chunks are cut: counted here and logged (once per power of two), never silent.
