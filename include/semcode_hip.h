@@ -416,7 +416,9 @@ sc_status sc_encoder_score_seqs(sc_encoder* enc, const int32_t* ids, const int64
  * sc_diag_maxsim runs the kernel alone on uploaded arrays, sc_diag_maxsim_host the rule on the CPU (no GPU involved): Q / D [.., W] f32 token
  * vectors, text i's at rows [off[i], off[i + 1]) (int32 offsets from 0), keep NULL or one byte per document token.  A document without a
  * kept token scores nq * -inf = -inf there.
- * Out of scope: arch 2; _dev / asynchronous forms; storing token vectors in the index (a multi-vector collection); query lengths above
+ * Storing token vectors in the index (a multi-vector collection) and scoring from them without a passage forward: sc_index_put_tokens,
+ * sc_index_rerank_late and sc_index_search_late, below.
+ * Out of scope: arch 2; _dev / asynchronous forms; a device-to-device hand-over of token vectors to an index; query lengths above
  * 128; XLM-R backbones (jina-colbert-v2); a projection with a bias. */
 sc_status sc_encoder_set_token_head(sc_encoder* enc, const float* w /*[W,H] or NULL*/, int32_t W);
 sc_status sc_encoder_embed_tokens(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, int32_t expand_id, float* out /*[sum n_i,W]*/,
@@ -895,6 +897,66 @@ sc_status sc_diag_lex_score_host(const uint16_t* terms, int64_t n, int32_t T, co
                                  float avgdl, float* out_score, uint8_t* out_hit);
 sc_status sc_diag_rrf_host(const int64_t* dense_rows, const int64_t* lex_rows, int32_t F, int32_t k, int32_t c, float wd, float wl, float* out_score,
                            int64_t* out_rows);
+
+/* The token store: late interaction (ColBERT, above) with the documents encoded ONCE, at ingest.  Every row of an index may carry
+ * 0 .. 2 048 token vectors of W floats (W a multiple of 16 within 16 .. 128, the rule of maxsim_rule.h), parked on the device next to
+ * the rows like the group labels and the term rows -- caller data, not scratch (sc_index_release_scratch keeps it), not persisted by
+ * the library -- but keyed by LOCAL ROW NUMBER through a table, wherever an IVF layout put the row's vector.
+ *   layout   a pool of token vectors, appended to, and a table (int64 start, int32 len) per row, 16 bytes, on the device with a host
+ *            mirror.  fmt 0 stores the f32 bits; fmt 1 stores bf16: every float rounded to nearest-even on its upper 16 bits once, at
+ *            install, and widened back exactly when read -- the stored value is one f32 bit pattern (sc_diag_round_bf16 of the input),
+ *            every score below is the MaxSim rule on those values, and no bf16 arithmetic happens anywhere.  W and fmt are fixed by
+ *            the first install; another W or fmt later is SC_ERR_INVALID (sc_index_drop_tokens first).
+ *   dead     a put appends the new vectors and repoints the row; what the row pointed to before is dead.  sc_index_compact_tokens
+ *            gathers the live tokens in row order into a fresh pool (one kernel), after which dead = 0; it also runs by itself at the
+ *            end of a put or a delete that leaves dead > live (skipped when it cannot allocate).  Results of every call are the same
+ *            bits before and after.
+ *   rows     rows that never got tokens have none; the table follows the index's row count (rows appended later have none).
+ *            sc_index_put_rows / _overwrite / _add leave a row's tokens alone -- replacing them is the caller's second call.
+ *            sc_index_delete_rows renumbers the table with the rows: survivors keep their tokens, the deleted rows' become dead
+ *            (group labels and term rows are still dropped by a delete).
+ * sc_index_put_tokens: rows [n] distinct local row numbers in [0, rows), counts [n] in 0 .. 2 048 (0 removes the row's tokens), vecs
+ * [sum counts, W] f32 (host) row after row.  Everything is validated before anything changes; SC_ERR_NOMEM leaves the store as it
+ * was.  Synchronises.  sc_index_reserve_tokens pre-sizes the pool (before the first install: remembered until the format is known);
+ * otherwise it grows geometrically, contents kept.  sc_index_get_tokens: out_counts [n] and, unless out_vecs is NULL, the rows' vectors
+ * one after the other as f32 (widened as stored), at most cap_tokens of them (more: SC_ERR_INVALID, nothing written) -- it serves a
+ * save.  sc_index_token_stats: rows that have tokens, live and dead tokens, W and fmt (0, 0: nothing installed), the pool's bytes.
+ * sc_index_drop_tokens frees the store. */
+sc_status sc_index_put_tokens(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs /*[sum counts,W]*/, int32_t W, int32_t fmt);
+sc_status sc_index_reserve_tokens(sc_index* ix, int64_t tokens);
+sc_status sc_index_compact_tokens(sc_index* ix);
+sc_status sc_index_get_tokens(sc_index* ix, const int64_t* rows, int64_t n, int32_t* out_counts, float* out_vecs /*or NULL*/, int64_t cap_tokens);
+sc_status sc_index_token_stats(sc_index* ix, int64_t* rows_with_tokens, int64_t* live, int64_t* dead, int32_t* W, int32_t* fmt, int64_t* pool_bytes);
+sc_status sc_index_drop_tokens(sc_index* ix);
+/* Scoring from the store.  Questions: Q [q_off[Bq], W] f32 token vectors (what sc_encoder_embed_tokens returns for the query side),
+ * question q's at rows [q_off[q], q_off[q + 1]), 1 .. 128 of them; 1 <= Bq <= 65 536.  Score of (question, row) =
+ * maxsim_score_seq(Q_q, nq, D_row, len_row, NULL, W) of maxsim_rule.h on the stored values: bit-identical to sc_diag_maxsim_host, and at
+ * fmt 0 to what sc_encoder_score_late gives for the same texts (a text's token vectors do not depend on its batch-mates).
+ * sc_index_rerank_late (late_rerank_kernel, one workgroup per pair, the tile code of maxsim_kernel reading through the table): cand
+ * [Bq, C] holds what the searches return, row_base + local row, -1 = padding; 1 <= C <= 1 024; out_scores [Bq, C] in candidate order
+ * (the caller sorts); a padding entry or a row without tokens scores -inf.  No passage forward runs.
+ * sc_index_search_late (late_scan_kernel): the exact, exhaustive MaxSim top-k over every row that has tokens, 1 <= k <= 128.  allow ==
+ * NULL (allow_words 0): every row; else the bitset of sc_index_search_masked over local row numbers, tested before any of a row's
+ * tokens is read.  Larger score first under the order of the score key (-0 < +0), ties to the lower row; out_rows = row_base + row;
+ * padded with -1 and -inf.  The same on FLAT and trained IVF_FLAT: the store is in row-number order.  How: one launch per question, its
+ * token vectors resident in LDS in MFMA fragment order; a wave takes one document at a time in tiles of 16 tokens straight from
+ * global memory against every question tile (v_mfma_f32_16x16x4_f32, two chains at a time), one running maximum key per question
+ * tile, the ordered sum per document, per-wave sorted key lists, sc_topk_merge's tree merge.  Rows are dealt in fixed blocks of 4, in
+ * row order, by one integer work counter (documents differ too much in length for a static split); the counter decides which wave
+ * scores a row and nothing else: keys are distinct and the merge exact, so the result is bit-identical to sc_diag_late_search_host
+ * whatever the partition.
+ * SC_ERR_INVALID before anything changes: no tokens installed, a NULL pointer, Bq / C / k out of range, q_off[0] != 0, a question with 0
+ * or more than 128 vectors, a candidate that is neither -1 nor a row, a short allow.  Host pointers; both synchronise.
+ * Out of scope: sharded collections, _dev / asynchronous forms, several questions per pass, a bf16-MFMA coarse pass with exact re-score.
+ * sc_diag_late_search_host is the search on the CPU over D [d_off[n], W] f32 (row r's vectors at [d_off[r], d_off[r + 1]), int64), rows
+ * reported without a row_base; sc_diag_round_bf16 the install-time rounding of fmt 1 (out = the value stored for in).  No GPU involved. */
+sc_status sc_index_rerank_late(sc_index* ix, const float* Q, const int32_t* q_off /*[Bq+1]*/, int32_t Bq, const int64_t* cand /*[Bq,C]*/, int32_t C,
+                               float* out_scores /*[Bq,C]*/);
+sc_status sc_index_search_late(sc_index* ix, const float* Q, const int32_t* q_off /*[Bq+1]*/, int32_t Bq, int32_t k, const uint32_t* allow, int64_t allow_words,
+                               float* out_score /*[Bq,k]*/, int64_t* out_rows /*[Bq,k]*/);
+sc_status sc_diag_late_search_host(const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int64_t* d_off /*[n+1]*/, int64_t n, int32_t W, int32_t k,
+                                   const uint32_t* allow, int64_t allow_words, float* out_score, int64_t* out_rows);
+sc_status sc_diag_round_bf16(const float* in, int64_t n, float* out);
 
 /* Replaces Collection.create_index(IVF_FLAT, nlist) + load() (milvus_store.py:76-84) for an index created with
  * SC_INDEX_IVF_FLAT: deterministic k-means (niter Lloyd iterations on <= 256*nlist sampled rows), assignment of

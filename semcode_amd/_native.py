@@ -208,6 +208,18 @@ SIGNATURES = {
     "sc_index_last_lex_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "sc_diag_lex_score_host": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "sc_diag_rrf_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "sc_index_put_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "sc_index_reserve_tokens": (C.c_int32, [C.c_void_p, C.c_int64]),
+    "sc_index_compact_tokens": (C.c_int32, [C.c_void_p]),
+    "sc_index_get_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "sc_index_token_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64)]),
+    "sc_index_drop_tokens": (C.c_int32, [C.c_void_p]),
+    "sc_index_rerank_late": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sc_index_search_late": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sc_diag_late_search_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p]),
+    "sc_diag_round_bf16": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p]),
     "sc_index_train": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
     "sc_index_ivf_assignments": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "sc_index_set_ivf": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
@@ -340,6 +352,68 @@ def diag_rrf_host(dense_rows, lex_rows, k: int, c: int = 60, dense_weight: float
     _check(lib().sc_diag_rrf_host(d.ctypes.data_as(C.c_void_p), l.ctypes.data_as(C.c_void_p), d.shape[0], int(k), int(c), float(dense_weight), float(lexical_weight),
                                   score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
     return score, rows
+
+
+TOKEN_FORMATS = {"f32": 0, "bf16": 1}  # storage of the token store (csrc/late_rule.h)
+
+
+def pack_token_lists(token_vectors) -> "tuple[np.ndarray, np.ndarray]":
+    """Ragged token vectors as (counts [n] int32, vecs [sum counts, W] f32): a pair (counts, vecs) is checked and passed on, a sequence of
+    [n_i, W] arrays (None or empty: no tokens) is concatenated."""
+    if isinstance(token_vectors, tuple) and len(token_vectors) == 2 and np.ndim(token_vectors[0]) == 1 and np.ndim(token_vectors[1]) == 2:
+        counts = np.ascontiguousarray(token_vectors[0], dtype=np.int32)
+        vecs = np.ascontiguousarray(token_vectors[1], dtype=np.float32)
+        if int(counts.sum()) != vecs.shape[0]:
+            raise ValueError(f"counts sum to {int(counts.sum())}, vecs has {vecs.shape[0]} rows")
+        return counts, vecs
+    parts = [None if t is None else np.ascontiguousarray(t, dtype=np.float32) for t in token_vectors]
+    real = [p for p in parts if p is not None and p.size]
+    if any(p.ndim != 2 for p in real) or len({p.shape[1] for p in real}) > 1:
+        raise ValueError("every entry must be a [n_i, W] float array of one W")
+    counts = np.array([0 if p is None or not p.size else p.shape[0] for p in parts], dtype=np.int32)
+    vecs = np.concatenate(real, axis=0) if real else np.empty((0, 0), dtype=np.float32)
+    return counts, np.ascontiguousarray(vecs)
+
+
+def pack_questions(questions) -> "tuple[np.ndarray, np.ndarray]":
+    """(Q [sum nq, W] f32, q_off [Bq + 1] int32) of a batch of questions' token vectors (see pack_token_lists for the forms; a pair is
+    (Q, q_off) here)."""
+    if isinstance(questions, tuple) and len(questions) == 2 and np.ndim(questions[0]) == 2 and np.ndim(questions[1]) == 1:
+        return np.ascontiguousarray(questions[0], dtype=np.float32), np.ascontiguousarray(questions[1], dtype=np.int32)
+    counts, vecs = pack_token_lists(list(questions))
+    q_off = np.zeros(counts.shape[0] + 1, dtype=np.int32)
+    np.cumsum(counts, out=q_off[1:])
+    return vecs, q_off
+
+
+def diag_late_search_host(questions, docs, k: int, allow=None) -> "tuple[np.ndarray, np.ndarray]":
+    """sc_index_search_late on the CPU (sc_diag_late_search_host; no GPU): docs as Index.put_tokens takes them -> (score [Bq, k],
+    rows [Bq, k]), rows without a row_base."""
+    Q, q_off = pack_questions(questions)
+    counts, D = pack_token_lists(docs)
+    n = counts.shape[0]
+    d_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=d_off[1:])
+    W = Q.shape[1]
+    if D.shape[0] and D.shape[1] != W:
+        raise ValueError("questions and documents must have one W")
+    Bq = q_off.shape[0] - 1
+    score, rows = _result_arrays(Bq, k)
+    words = None if allow is None else pack_allow(allow, n)
+    if words is not None and words.size == 0:
+        words = np.zeros(1, dtype=np.uint32)
+    _check(lib().sc_diag_late_search_host(Q.ctypes.data_as(C.c_void_p), q_off.ctypes.data_as(C.c_void_p), Bq, D.ctypes.data_as(C.c_void_p) if D.shape[0] else None,
+                                          d_off.ctypes.data_as(C.c_void_p), n, W, int(k), None if words is None else words.ctypes.data_as(C.c_void_p),
+                                          0 if words is None else words.shape[0], score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+    return score, rows
+
+
+def diag_round_bf16(x) -> np.ndarray:
+    """What the token store keeps for x at fmt 'bf16': every float rounded to nearest-even on its upper 16 bits (sc_diag_round_bf16)."""
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(a)
+    _check(lib().sc_diag_round_bf16(a.ctypes.data_as(C.c_void_p), a.size, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def _as_f32(a, shape_last: int | None = None) -> np.ndarray:
@@ -689,6 +763,85 @@ class Index:
         r, by, p = C.c_int64(), C.c_int64(), C.c_int32()
         _check(lib().sc_index_last_lex_stats(self.handle, C.byref(r), C.byref(by), C.byref(p)))
         return {"rows_scanned": int(r.value), "bytes_per_pass": int(by.value), "passes": int(p.value)}
+
+    # ---- the token store (late interaction): sc_index_put_tokens and the calls that score from it
+    def put_tokens(self, rows, token_vectors, fmt: str = "f32") -> None:
+        """Store the token vectors of `rows` (distinct local row numbers): token_vectors is one [n_i, W] f32 array per row (n_i 0 .. 2 048;
+        0 or None removes the row's tokens), or a pair (counts [n], vecs [sum counts, W]).  W and fmt ('f32' | 'bf16': rounded to
+        nearest-even once, here) are fixed by the first call.  A row's previous tokens become dead (compact_tokens)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        counts, vecs = pack_token_lists(token_vectors)
+        if counts.shape[0] != r.shape[0]:
+            raise ValueError("token_vectors must have one entry per row")
+        if vecs.shape[0] == 0:
+            st = self.token_stats()
+            if not st["W"]:
+                raise ValueError("no token vectors given and none installed: W is unknown")
+            vecs = np.empty((0, st["W"]), dtype=np.float32)
+        _check(lib().sc_index_put_tokens(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], counts.ctypes.data_as(C.c_void_p), vecs.ctypes.data_as(C.c_void_p),
+                                         vecs.shape[1], TOKEN_FORMATS[fmt]))
+
+    def reserve_tokens(self, tokens: int) -> None:
+        """Pre-size the token pool (sc_index_reserve_tokens)."""
+        _check(lib().sc_index_reserve_tokens(self.handle, int(tokens)))
+
+    def compact_tokens(self) -> None:
+        """Gather the live tokens in row order into a fresh pool: dead = 0 afterwards (sc_index_compact_tokens)."""
+        _check(lib().sc_index_compact_tokens(self.handle))
+
+    def drop_tokens(self) -> None:
+        _check(lib().sc_index_drop_tokens(self.handle))
+
+    def token_stats(self) -> dict:
+        """rows_with_tokens, live and dead tokens, W, fmt ('f32' | 'bf16'; W 0: nothing installed), pool_bytes (sc_index_token_stats)."""
+        rw, live, dead, pool = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        W, fmt = C.c_int32(), C.c_int32()
+        _check(lib().sc_index_token_stats(self.handle, C.byref(rw), C.byref(live), C.byref(dead), C.byref(W), C.byref(fmt), C.byref(pool)))
+        return {"rows_with_tokens": int(rw.value), "live": int(live.value), "dead": int(dead.value), "W": int(W.value), "fmt": "bf16" if fmt.value == 1 else "f32",
+                "pool_bytes": int(pool.value)}
+
+    def token_counts(self, rows) -> np.ndarray:
+        """Tokens stored for each of `rows` (int32 [n]; no vectors are copied)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        counts = np.empty(r.shape[0], dtype=np.int32)
+        _check(lib().sc_index_get_tokens(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], counts.ctypes.data_as(C.c_void_p), None, 0))
+        return counts
+
+    def get_tokens(self, rows) -> "tuple[np.ndarray, np.ndarray]":
+        """(counts [n] int32, vecs [sum counts, W] f32): the rows' stored token vectors, widened as stored (sc_index_get_tokens)."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        counts = np.empty(r.shape[0], dtype=np.int32)
+        _check(lib().sc_index_get_tokens(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], counts.ctypes.data_as(C.c_void_p), None, 0))
+        total = int(counts.sum())
+        vecs = np.empty((total, self.token_stats()["W"]), dtype=np.float32)
+        if total:
+            _check(lib().sc_index_get_tokens(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], counts.ctypes.data_as(C.c_void_p), vecs.ctypes.data_as(C.c_void_p), total))
+        return counts, vecs
+
+    def rerank_late(self, questions, cand) -> np.ndarray:
+        """MaxSim scores of every question against its candidates from the stored token vectors (sc_index_rerank_late): questions = one
+        [nq, W] f32 array per question (1 <= nq <= 128) or a pair (Q [sum nq, W], q_off [Bq + 1]); cand [Bq, C] = row_base + local row as
+        the searches return them, -1 = padding.  -> scores [Bq, C] f32 in candidate order; padding and rows without tokens: -inf."""
+        Q, q_off = pack_questions(questions)
+        c = np.ascontiguousarray(cand, dtype=np.int64)
+        if c.ndim != 2 or c.shape[0] != q_off.shape[0] - 1:
+            raise ValueError(f"cand must be [Bq, C] with one row per question, got shape {c.shape}")
+        out = np.empty(c.shape, dtype=np.float32)
+        _check(lib().sc_index_rerank_late(self.handle, Q.ctypes.data_as(C.c_void_p), q_off.ctypes.data_as(C.c_void_p), c.shape[0], c.ctypes.data_as(C.c_void_p), c.shape[1],
+                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def search_late(self, questions, k: int = 10, allow=None) -> "tuple[np.ndarray, np.ndarray]":
+        """The exact, exhaustive MaxSim top-k over the rows that have tokens (sc_index_search_late): questions as rerank_late; allow as
+        for search_masked, or None.  -> (score [Bq, k] f32, rows [Bq, k] i64), larger score first, ties to the lower row, padded
+        with -1 / -inf."""
+        Q, q_off = pack_questions(questions)
+        Bq = q_off.shape[0] - 1
+        score, rows = _result_arrays(Bq, k)
+        allow_ptr, allow_words, _keep = self._allow_args(allow)
+        _check(lib().sc_index_search_late(self.handle, Q.ctypes.data_as(C.c_void_p), q_off.ctypes.data_as(C.c_void_p), Bq, int(k), allow_ptr, allow_words,
+                                          score.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p)))
+        return score, rows
 
     def train(self, niter: int = 10, seed: int = 0) -> None:
         """IVF_FLAT: k-means + list build (sc_index_train)."""

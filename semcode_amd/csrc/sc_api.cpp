@@ -259,6 +259,7 @@ extern "C" sc_status sc_index_destroy(sc_index* ix) {
     hipFree(ix->list_off);
     for (const sc_index_buf& b : SC_INDEX_BUFS) sc_buf_free(ix->*b.buf);
     for (sc_shadow* sh : ix->shadows) sc_shadow_release(*sh);
+    sc_tok_free_locked(ix);
     if (ix->quant) sc_index_destroy(ix->quant);
     sc_runtime* rt = ix->rt;
     delete ix;

@@ -215,6 +215,19 @@ void sc_launch_lex_scan(const uint16_t* terms, int64_t n, int T, const uint32_t*
 void sc_launch_lex_stats(const uint16_t* terms, int64_t n, int T, uint32_t* df, unsigned long long* sum_dl, hipStream_t s);
 void sc_launch_lex_fuse(const int64_t* dense_rows, const int64_t* lex_rows, int F, int Q, int k, int32_t c, float wd, float wl, float* out_score, int64_t* out_rows,
                         hipStream_t s);
+// scan_late.hip: late interaction over the token store of an index (sc_tokens.cpp; rules: maxsim_rule.h, late_rule.h).  pool: token
+// vectors of W elements, f32 (fmt 0) or bf16 (fmt 1); table [n]: a row's tokens are pool[start, start + len).
+// late_rerank: out [Bq][C] = the MaxSim score of question q (rows [q_off[q], q_off[q + 1]) of Q [.., W]) against row cand[q][c] (local
+// row number; -1 or a row without tokens: -inf).  late_scan: ONE question Q [nq <= 128][W] over every row that has tokens (allow NULL or
+// a bitset over rows) -> partial [nwg * 4][k] sorted late_hit_key lists for sc_launch_topk_merge (SC_METRIC_IP, groups 1, lists nwg * 4,
+// qt 1); nwg from sc_late_scan_workgroups; next_block: one device word the caller zeroes before the launch (the work counter).  late_gather: the live tokens of every row from old_pool (old_tab) to new_pool (new_tab).
+struct sc_tok_entry;
+int sc_late_scan_workgroups(int64_t n, int nq, int W, int k, int cus);
+void sc_launch_late_rerank(const float* Q, const int32_t* q_off, int Bq, const void* pool, int fmt, const sc_tok_entry* table, const int64_t* cand, int C, int W,
+                           float* out, hipStream_t s);
+void sc_launch_late_scan(const float* Q, int nq, const void* pool, int fmt, const sc_tok_entry* table, int64_t n, const uint32_t* allow, int W, int k, int nwg,
+                         uint64_t* partial, unsigned* next_block, hipStream_t s);
+void sc_launch_late_gather(const sc_tok_entry* old_tab, const sc_tok_entry* new_tab, int64_t n, const void* old_pool, void* new_pool, int tok_bytes, int cus, hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

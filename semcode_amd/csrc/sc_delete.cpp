@@ -83,6 +83,7 @@ extern "C" sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int
         ix->last_del_rows_moved = ix->last_del_bytes_moved = 0;
         ix->last_del_kept = 0;
         ix->last_del_dropped = valid_before;
+        if (ix->tok) sc_tok_delete_locked(ix, ids);
         return SC_OK;
     }
     // stored positions of the deleted rows, ascending
@@ -218,5 +219,6 @@ extern "C" sc_status sc_index_delete_rows(sc_index* ix, const int64_t* rows, int
     ix->last_del_kept = valid_before;
     ix->last_del_dropped = 0;
     SC_HIP(hipStreamSynchronize(s));  // the delete list and the host tables behind asynchronous copies go out of scope
+    if (ix->tok) sc_tok_delete_locked(ix, ids);  // the token store's table is renumbered with the rows (sc_tokens.cpp)
     return SC_OK;
 }

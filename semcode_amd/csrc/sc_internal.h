@@ -84,6 +84,8 @@ struct sc_shadow {
     int stat_bit = 0;              // 1 | 2 | 4 in sc_index_last_delete_stats
 };
 
+struct sc_token_store;
+
 struct sc_index {
     sc_runtime* rt = nullptr;
     int dim = 0, ld = 0;
@@ -142,6 +144,11 @@ struct sc_index {
     bool lex_stat_dirty = true;
     int64_t last_lex_rows = 0, last_lex_bytes = 0;  // sc_index_last_lex_stats
     int last_lex_passes = 0;
+    // late interaction (sc_tokens.cpp): the caller's token vectors per row -- a ragged pool and a (start, len) table in local
+    // row-number order, NULL until the first sc_index_put_tokens / sc_index_reserve_tokens; not scratch, kept across deletes.
+    // late_scratch: the partial lists of a search
+    sc_token_store* tok = nullptr;
+    sc_buf late_scratch;
     // IVF_FLAT (after sc_index_train): X / xnorm are stored list-major
     sc_index* quant = nullptr;                    // flat index over the nlist centroids (coarse quantizer)
     uint32_t* perm = nullptr;                     // device [ivf_rows]: stored position -> row id (insertion order)
@@ -190,7 +197,7 @@ inline constexpr sc_index_buf SC_INDEX_BUFS[] = {
     {&sc_index::stage, true},   {&sc_index::partial, true},     {&sc_index::bscratch, true},     {&sc_index::fb, true},
     {&sc_index::fb2, true},     {&sc_index::tailbuf, true},     {&sc_index::ivf_scratch, true},  {&sc_index::ivfc_scratch, true},
     {&sc_index::mask_words, true}, {&sc_index::mask_cnt, true}, {&sc_index::mask_sel, true}, {&sc_index::group_scratch, true},
-    {&sc_index::mmr_scratch, true}, {&sc_index::lex_scratch, true},
+    {&sc_index::mmr_scratch, true}, {&sc_index::lex_scratch, true}, {&sc_index::late_scratch, true},
     {&sc_index::qpad, false},   {&sc_index::qnorm, false},      {&sc_index::io, false},          {&sc_index::groups, false},
     {&sc_index::mmr_stat, false},   {&sc_index::terms, false},      {&sc_index::lex_stat, false},
 };
@@ -290,6 +297,10 @@ bool sc_ivf_applicable(const sc_index* ix, int Q, int nprobe);
 sc_status sc_search_masked_locked(sc_index* ix, const float* q_dev, int32_t Q, int32_t k, const uint32_t* allow_dev, float* out_dist, int64_t* out_rows);
 // sc_lexical.cpp: forget the term rows (sc_index_delete_rows renumbers the rows; sc_index_drop_terms)
 void sc_lex_drop_locked(sc_index* ix);
+// sc_tokens.cpp: the token store follows a delete -- the table is renumbered with the rows (del: the deleted row numbers, ascending),
+// survivors keep their tokens, the deleted rows' tokens become dead (and are compacted away once dead > live); the store is freed
+void sc_tok_delete_locked(sc_index* ix, const std::vector<int64_t>& del);
+void sc_tok_free_locked(sc_index* ix);
 // sc_ivf_probe.cpp.  The nprobe nearest centroids of every query under the INDEX metric (the quantizer's own search; takes qz->mu):
 // distances and list ids at the head of ix->ivf_scratch, grown to hold `extra_bytes` more behind them; `host`: the ids there too
 // (synchronises).

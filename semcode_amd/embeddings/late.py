@@ -203,10 +203,24 @@ class MI355XLateReranker:
         vec, counts = self._encoder.embed_tokens(ids, off, expand_id=self.mask_id)
         return np.split(vec, np.cumsum(counts)[:-1])
 
-    def embed_document_tokens(self, texts: Sequence[str]) -> "list[np.ndarray]":
-        ids, off = _flatten([self.document_ids(t) for t in texts])
-        vec, counts = self._encoder.embed_tokens(ids, off, expand_id=-1)
-        return np.split(vec, np.cumsum(counts)[:-1])
+    def embed_document_tokens(self, texts: Sequence[str], kept_only: bool = False) -> "list[np.ndarray]":
+        """One [n_i, W] array per text.  kept_only: without the tokens whose keep flag is 0 (punctuation) -- what a token store keeps,
+        since score_pairs leaves exactly those out of every maximum.  Batches follow rows_budget, as score_pairs' do."""
+        rows = [self.document_ids(t) for t in texts]
+        out: "list[np.ndarray]" = []
+        rows_of = lambda l: self._encoder.packed_rows(np.concatenate(([0], np.cumsum(l))))  # noqa: E731
+        window = max(1, 524288 // max(self.document_length, 32) // 2)
+        lens = np.asarray([len(r) for r in rows], np.int64)
+        for start in range(0, len(rows), window):
+            for a, b in cut_packed(lens[start:start + window], self.rows_budget, rows_of):
+                ids, off = _flatten(rows[start + a:start + b])
+                vec, counts = self._encoder.embed_tokens(ids, off, expand_id=-1)
+                parts = np.split(vec, np.cumsum(counts)[:-1])
+                if kept_only:
+                    keep = self.keep_flags(ids).astype(bool)
+                    parts = [p[keep[off[i]:off[i + 1]]] for i, p in enumerate(parts)]
+                out += parts
+        return out
 
     # ---- scores
     def score_pairs(self, questions: Sequence[str], passages: Sequence[str]) -> np.ndarray:

@@ -77,7 +77,7 @@ def build_payloads(repo_name: str, repo_path: Path, chunks: Sequence[Any], embed
 def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedding_client: Any, vector_store: Any,
                   embed_progress: Optional[Callable[[int, int], None]] = None,
                   upsert_progress: Optional[Callable[[int, int], None]] = None, batch_size: Optional[int] = None,
-                  prune: bool = False) -> int:
+                  prune: bool = False, token_vectors: Optional[Sequence[Any]] = None) -> int:
     """`_build_payloads` + `upsert_embeddings` (indexer.py:94-114) as one pipelined pass for the MI355X backend.
 
     What differs from the reference's two loops, and only in speed: (1) no `list[float]` is ever built -- a batch goes
@@ -95,6 +95,9 @@ def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedd
     md5(repo:path:start:end), so an edit that shifts line numbers, a removed or a renamed file leave rows behind that no
     chunk of the new tree maps to; the reference never removes them (its re-index only upserts).  Nothing is pruned if the
     ingest raises.  The default keeps the reference's behaviour: upsert only.
+
+    A store that keeps late-interaction token vectors (MilvusVectorStore(late=..., late_format=...)) stores every chunk's with its row
+    in the same pass: its own reranker encodes the batch's texts, or token_vectors (one [n_i, W] array per chunk) is handed through.
     """
     total = len(chunks)
     for cb in (embed_progress, upsert_progress):
@@ -135,7 +138,8 @@ def ingest_chunks(repo_name: str, repo_path: Path, chunks: Sequence[Any], embedd
             idx, (tok, lens) = item
             metas = [{"repo": repo_name, "path": str(Path(chunks[i].path).relative_to(repo_path)), "language": chunks[i].language,
                       "start_line": chunks[i].start_line, "end_line": chunks[i].end_line, "symbol": chunks[i].symbol} for i in idx]
-            vector_store.upsert_encoded([ids[i] for i in idx], tok, lens, [chunks[i].content for i in idx], metas, embedding_client, wait=False)
+            extra = {} if token_vectors is None else {"token_vectors": [token_vectors[i] for i in idx]}
+            vector_store.upsert_encoded([ids[i] for i in idx], tok, lens, [chunks[i].content for i in idx], metas, embedding_client, wait=False, **extra)
             done += len(idx)
             if done == len(keep):
                 embedding_client.wait()  # the last report means "stored"

@@ -113,8 +113,58 @@ class Retriever:
             raise ValueError("rerank=True needs a reranker: Retriever(embedding_client, vector_store, reranker=...)")
         return True
 
-    def _rerank(self, questions: Sequence[str], per_question: List[List[Dict[str, Any]]], top_k: int) -> List[List[Dict[str, Any]]]:
-        """All (question, snippet) pairs of all questions in one score_pairs call (shared packed batches), then _apply_scores each."""
+    def _check_late(self, late: Any, rerank: Any, group_by: Any, mmr: Any, hybrid: Any) -> bool:
+        """Argument errors of late=, raised before anything runs."""
+        if not late:
+            return False
+        for name, value in (("mmr", mmr), ("group_by", group_by), ("hybrid", hybrid if hybrid is not False else None), ("rerank", rerank or None)):
+            if value is not None:
+                raise ValueError(f"late together with {name} is not supported: the MaxSim search is the whole retrieval")
+        if self.reranker is None or not hasattr(self.reranker, "embed_query_tokens"):
+            raise ValueError("late=True needs a late-interaction reranker: Retriever(embedding_client, vector_store, reranker=MI355XLateReranker(...))")
+        if not hasattr(self.vector_store, "search_late"):
+            raise ValueError(f"late=True needs a store with search_late: {type(self.vector_store).__name__} has none")
+        return True
+
+    def _retrieve_late(self, questions: Sequence[str], repos: Any, languages: Any) -> List[List[Dict[str, Any]]]:
+        """The MaxSim search as the first stage: the questions' forward, then one exhaustive search over the stored token vectors."""
+        if not self._ensure_connected():
+            return [[] for _ in questions]
+        try:
+            dist, rows = self.vector_store.search_late(self.reranker.embed_query_tokens(list(questions)), _top_k(), **self._filter_kwargs(repos, languages))
+            results = self.vector_store.hits_for(dist, rows)
+        except Exception as exc:
+            log.error("late_search_failed error=%s", exc)
+            self.last_error = exc
+            return [[] for _ in questions]
+        self.last_error = None if results else ValueError("no_results")
+        return [[doc for doc in (hit_to_document(hit) for hit in hits) if doc] for hits in results]
+
+    def _rerank_from_store(self, questions: Sequence[str], per_question: List[List[Dict[str, Any]]], rows: List[List[Any]],
+                           top_k: int) -> Optional[List[List[Dict[str, Any]]]]:
+        """The stored token vectors score the candidates when the reranker is a late-interaction one and the store holds tokens for
+        EVERY candidate row: the questions' forward only.  None: not possible here, score_pairs does it."""
+        store, rr = self.vector_store, self.reranker
+        if not (hasattr(rr, "embed_query_tokens") and hasattr(store, "rerank_late") and hasattr(store, "has_late_tokens")):
+            return None
+        flat = [r for rs in rows for r in rs]
+        if not flat or any(r is None for r in flat) or not store.has_late_tokens(flat):
+            return None
+        width = max(len(rs) for rs in rows)
+        cand = np.full((len(rows), width), -1, dtype=np.int64)
+        for i, rs in enumerate(rows):
+            cand[i, :len(rs)] = rs
+        scores = store.rerank_late(rr.embed_query_tokens(list(questions)), cand)
+        return [_apply_scores(docs, scores[i, :len(docs)], top_k) for i, docs in enumerate(per_question)]
+
+    def _rerank(self, questions: Sequence[str], per_question: List[List[Dict[str, Any]]], top_k: int,
+                rows: Optional[List[List[Any]]] = None) -> List[List[Dict[str, Any]]]:
+        """All (question, snippet) pairs of all questions in one score_pairs call (shared packed batches), then _apply_scores each.
+        rows (the candidates' row numbers, one per document): tried first against the store's token vectors (_rerank_from_store)."""
+        if rows is not None:
+            done = self._rerank_from_store(questions, per_question, rows, top_k)
+            if done is not None:
+                return done
         qs = [q for q, docs in zip(questions, per_question) for _ in docs]
         ps = [doc["snippet"] for docs in per_question for doc in docs]
         scores = self.reranker.score_pairs(qs, ps) if qs else []
@@ -125,7 +175,7 @@ class Retriever:
         return out
 
     def retrieve(self, question: str, *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                 mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None) -> List[Dict[str, Any]]:
+                 mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None, late: Any = None) -> List[Dict[str, Any]]:
         """pipeline.py:93-129, one question.  repos / languages restrict the search itself (MilvusVectorStore.search), where the
         reference front ends drop hits from an unfiltered top-k afterwards.  group_by ("path" | "repo"): at most one document per
         file / per repo, so rag_max_context_sources buys that many different sources.  mmr (in [0, 1]) / fetch_k: maximal marginal
@@ -134,7 +184,13 @@ class Retriever:
         with the dense ones, so a question that names an identifier finds the chunk that defines it.  rerank=True: the store is asked
         for fetch_k hits (default settings.mi355x_rerank_fetch_k, at least top_k; filters, group_by and hybrid apply to that search), the
         reranker scores every (question, snippet) pair, and the top_k by that score come back -- ties by retrieval rank, `score` the
-        reranker's, `retrieval_score` the store's.  Not together with mmr (ValueError); a reranker failure yields [] and last_error."""
+        reranker's, `retrieval_score` the store's.  Not together with mmr (ValueError); a reranker failure yields [] and last_error.
+        With a late-interaction reranker and a store that keeps token vectors for every candidate row (MilvusVectorStore(late=...)) the
+        scores come from the stored vectors -- the question's forward only, the same bits as score_pairs; otherwise score_pairs runs.
+        late=True: the exact MaxSim search over the stored token vectors IS the retrieval (the question's token vectors, no dense
+        search); repos / languages apply; with mmr, group_by, hybrid or rerank it raises ValueError before anything runs."""
+        if self._check_late(late, rerank, group_by, mmr, hybrid):
+            return self._retrieve_late([question], repos, languages)[0]
         reranking = self._check_rerank(rerank, mmr)
         if not self._ensure_connected():
             return []
@@ -157,10 +213,11 @@ class Retriever:
             return []
         except TypeError:  # not iterable: taken as the hits themselves, as the reference does
             hits = results
-        documents = [doc for doc in (hit_to_document(hit) for hit in hits) if doc]
+        pairs = [(doc, getattr(hit, "row", None)) for hit, doc in ((hit, hit_to_document(hit)) for hit in hits) if doc]
+        documents = [doc for doc, _ in pairs]
         if reranking:
             try:
-                documents = self._rerank([question], [documents], top_k)[0]
+                documents = self._rerank([question], [documents], top_k, rows=[[row for _, row in pairs]])[0]
             except Exception as exc:
                 log.error("rerank_failed error=%s", exc)
                 self.last_error = exc
@@ -169,13 +226,16 @@ class Retriever:
         return documents
 
     def retrieve_batch(self, questions: Sequence[str], *, repos: Any = None, languages: Any = None, group_by: Optional[str] = None,
-                       mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None) -> List[List[Dict[str, Any]]]:
+                       mmr: Optional[float] = None, fetch_k: Optional[int] = None, hybrid: Any = None, rerank: Any = None,
+                       late: Any = None) -> List[List[Dict[str, Any]]]:
         """Many questions at once: one encoder batch (`embed_documents_array`) and one batched search (`search_batch`) when the
         seams offer them, else `retrieve` per question.  Per question the result is what `retrieve` returns for it (a store
         that returns no hit for a question yields [] for that question).  repos / languages / group_by / mmr / fetch_k / hybrid: one setting
         for the whole batch, as in `retrieve`.  rerank=True: as in `retrieve`, with the pairs of ALL questions scored in shared
-        packed batches."""
+        packed batches (or, as in `retrieve`, from the store's token vectors).  late=True: as in `retrieve`, one search for all."""
         questions = list(questions)
+        if self._check_late(late, rerank, group_by, mmr, hybrid):
+            return self._retrieve_late(questions, repos, languages) if questions else []
         reranking = self._check_rerank(rerank, mmr)
         if not questions:
             return []
@@ -196,10 +256,11 @@ class Retriever:
             log.error("milvus_search_failed error=%s", exc)
             self.last_error = exc
             return [[] for _ in questions]
-        out = [[doc for doc in (hit_to_document(hit) for hit in hits) if doc] for hits in results]
+        pairs = [[(doc, getattr(hit, "row", None)) for hit, doc in ((hit, hit_to_document(hit)) for hit in hits) if doc] for hits in results]
+        out = [[doc for doc, _ in ps] for ps in pairs]
         if reranking:
             try:
-                out = self._rerank(questions, out, top_k)
+                out = self._rerank(questions, out, top_k, rows=[[row for _, row in ps] for ps in pairs])
             except Exception as exc:
                 log.error("rerank_failed error=%s", exc)
                 self.last_error = exc

@@ -18,6 +18,11 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
                                                    hashed code terms, on device (needs MilvusVectorStore(lexical=True))
     .delete(ids) / .delete_where(repo=, path=, language=)
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
+    MilvusVectorStore(late=reranker, late_format="f32" | "bf16")
+                                                -> a multi-vector collection: every chunk's late-interaction token vectors are kept on the
+                                                   device next to its row at upsert; .rerank_late(question_vectors, rows) scores candidates
+                                                   from them without a passage forward, .search_late(question_vectors, top_k) is the exact
+                                                   MaxSim search over them
 
 What lives where: vectors and their norms in HBM (sc_index); the scalar columns of the reference
 schema (id, repo, path, language, text, metadata; milvus_store.py:59-74) and the md5 -> row map in
@@ -104,7 +109,7 @@ class MilvusVectorStore:
     def __init__(self, collection_name: str = "semcode_chunks", dim: Optional[int] = None, *, metric: Optional[str] = None,
                  index_type: Optional[str] = None, nlist: Optional[int] = None, nprobe: Optional[int] = None,
                  device: Optional[int] = None, runtime: Any = None, index_factory: Optional[Callable[..., Any]] = None,
-                 lexical: Optional[bool] = None, lex_slots: int = 128) -> None:
+                 lexical: Optional[bool] = None, lex_slots: int = 128, late: Any = None, late_format: Optional[str] = None) -> None:
         settings = _resolve_settings()
         self.collection_name = collection_name
         self.dim = dim or settings.embedding_dimension
@@ -155,6 +160,16 @@ class MilvusVectorStore:
         self._terms = np.zeros((0, self.lex_slots), dtype=np.uint16)
         self._terms_on_device = -1
         self._lex_stats: Optional[tuple] = None  # (idf [65536] f32, avgdl f32)
+        # late interaction (late=<MI355XLateReranker>, or SEMCODE_MI355X_LATE_STORE=f32|bf16 with the reranker of the settings): every
+        # chunk's token vectors, without those of punctuation, go to the device index with its row (Index.put_tokens) and follow it
+        # through deletes; late_format None = no token store
+        fmt = str(late_format if late_format is not None else getattr(settings, "mi355x_late_store", "off") or "off").lower()
+        if late is not None and late_format is None and fmt == "off":
+            fmt = "f32"
+        if fmt not in ("off", "f32", "bf16"):
+            raise ValueError(f"late_format / mi355x_late_store must be off, f32 or bf16, got {fmt!r}")
+        self.late = late
+        self.late_format: Optional[str] = None if fmt == "off" else fmt
 
     # ------------------------------------------------------------------ lifecycle
     def connect(self) -> None:
@@ -165,6 +180,11 @@ class MilvusVectorStore:
             if self._collection is not None:
                 return
             self._collection = self._ensure_collection()
+            if self.late_format is not None and self.late is None and getattr(settings, "mi355x_reranker_path", None):
+                # a format without a reranker object: the late-interaction reranker of the settings (none there: every upsert brings token_vectors=)
+                from ..embeddings.late import MI355XLateReranker
+
+                self.late = MI355XLateReranker(runtime=self._runtime)
             store_path = getattr(settings, "mi355x_store_path", None)
             if store_path and (Path(store_path) / "manifest.json").exists() and not self._ids:
                 self.load(store_path)  # utility.has_collection(...) -> Collection(name).load() of the reference (milvus_store.py:51-54)
@@ -193,8 +213,10 @@ class MilvusVectorStore:
         return len(self._ids)
 
     # ------------------------------------------------------------------ upsert
-    def upsert_embeddings(self, payloads: Sequence[EmbeddingPayload], progress: Optional[Callable[[int, int], None]] = None) -> None:
-        """Insert or update embeddings (replace by primary key), reference milvus_store.py:87-133."""
+    def upsert_embeddings(self, payloads: Sequence[EmbeddingPayload], progress: Optional[Callable[[int, int], None]] = None,
+                          token_vectors: Optional[Sequence[Any]] = None) -> None:
+        """Insert or update embeddings (replace by primary key), reference milvus_store.py:87-133.  token_vectors (a store with a
+        late format only): one [n_i, W] array per payload instead of the late reranker's own embed_document_tokens."""
         if self._collection is None:
             raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
 
@@ -212,12 +234,12 @@ class MilvusVectorStore:
         for start in range(0, total, batch_size):
             batch = payload_list[start:start + batch_size]
             with self._lock:
-                self._upsert_batch(batch)
+                self._upsert_batch(batch, None if token_vectors is None else token_vectors[start:start + batch_size])
             inserted += len(batch)
             if progress:
                 progress(inserted, total)
 
-    def _upsert_batch(self, batch: Sequence[EmbeddingPayload]) -> None:
+    def _upsert_batch(self, batch: Sequence[EmbeddingPayload], token_vectors: Optional[Sequence[Any]] = None) -> None:
         vectors = np.asarray([p.vector for p in batch], dtype=np.float32)
         if vectors.ndim != 2 or vectors.shape[1] != self.dim:
             raise ValueError(f"embedding dimension mismatch: collection dim={self.dim}, got array of shape {vectors.shape}")
@@ -228,7 +250,8 @@ class MilvusVectorStore:
         # one native call per batch: it validates that every row is an existing row or the next free one, so a drift between
         # the device index and the host columns fails loudly; the columns are committed only after it has succeeded
         self._put_rows(vectors[keep], rows)
-        self.commit_rows(ids, rows, [batch[i].text for i in keep], [batch[i].metadata for i in keep])
+        self.commit_rows(ids, rows, [batch[i].text for i in keep], [batch[i].metadata for i in keep],
+                         token_vectors=None if token_vectors is None else [token_vectors[i] for i in keep])
 
     def _put_rows(self, vectors: np.ndarray, rows: np.ndarray) -> None:
         ix = self._collection
@@ -259,8 +282,13 @@ class MilvusVectorStore:
             rows[i] = row
         return rows
 
-    def commit_rows(self, ids: Sequence[str], rows: np.ndarray, texts: Sequence[str], metadatas: Sequence[dict]) -> None:
-        """Scalar columns + primary-key map for rows whose vectors have just been written (same mapping as _upsert_batch)."""
+    def commit_rows(self, ids: Sequence[str], rows: np.ndarray, texts: Sequence[str], metadatas: Sequence[dict],
+                    token_vectors: Optional[Sequence[Any]] = None) -> None:
+        """Scalar columns + primary-key map for rows whose vectors have just been written (same mapping as _upsert_batch).  A store
+        with a late format also stores every row's token vectors (token_vectors, or the late reranker's for `texts`): a replaced
+        primary key replaces its row's tokens."""
+        if self.late_format is not None and len(rows):
+            self._commit_tokens(rows, texts, token_vectors)  # (first: a failure leaves the columns as they were)
         self._mask_cache.clear()
         self._groups_installed = None
         for pk, row, text, meta in zip(ids, rows.tolist(), texts, metadatas):
@@ -281,6 +309,49 @@ class MilvusVectorStore:
         if self.lexical and len(rows):
             self._commit_terms(rows, texts)
         self._note_growth()
+
+    # ------------------------------------------------------------------ token vectors of the late-interaction store
+    def _commit_tokens(self, rows: np.ndarray, texts: Sequence[str], token_vectors: Optional[Sequence[Any]]) -> None:
+        ix = self._collection
+        if not hasattr(ix, "put_tokens"):
+            raise NotImplementedError(f"{type(ix).__name__} has no put_tokens(rows, token_vectors, fmt): this vector index cannot keep token vectors")
+        if token_vectors is None:
+            if self.late is None:
+                raise ValueError("a store with a late format needs token vectors: construct it with late=<MI355XLateReranker> or pass token_vectors=")
+            token_vectors = self.late.embed_document_tokens(list(texts), kept_only=True)
+        if len(token_vectors) != len(rows):
+            raise ValueError(f"{len(rows)} rows but {len(token_vectors)} token arrays")
+        ix.put_tokens(np.asarray(rows, dtype=np.int64), list(token_vectors), fmt=self.late_format)
+
+    def has_late_tokens(self, rows: Any) -> bool:
+        """True when the store keeps token vectors and every one of these rows (-1 entries aside) has some."""
+        ix = self._collection
+        if self.late_format is None or ix is None or not hasattr(ix, "token_counts"):
+            return False
+        r = np.asarray(rows, dtype=np.int64).reshape(-1)
+        r = r[r >= 0]
+        with self._lock:
+            return bool(r.size == 0 or (ix.token_counts(r) > 0).all())
+
+    def rerank_late(self, question_vectors: Any, rows: Any) -> np.ndarray:
+        """MaxSim scores [Bq, C] of every question (one [nq, W] array each, as MI355XLateReranker.embed_query_tokens returns them)
+        against the rows [Bq, C] a search returned (-1 = padding: -inf), read from the stored token vectors: no passage forward."""
+        if self._collection is None:
+            raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
+        with self._lock:
+            return self._collection.rerank_late(question_vectors, np.asarray(rows, dtype=np.int64))
+
+    def search_late(self, question_vectors: Any, top_k: int = 10, *, repos: Any = None, languages: Any = None) -> "tuple[np.ndarray, np.ndarray]":
+        """The exact MaxSim search over the stored token vectors: (score [Bq, k], rows [Bq, k]; -1 = no hit), best first, ties to the
+        lower row.  repos / languages as in search_batch.  top_k <= 128."""
+        if self._collection is None:
+            raise RuntimeError("Milvus collection is not initialized. Call connect() first.")
+        if self.late_format is None:
+            raise ValueError("search_late needs the token store: construct the store with late=... / late_format=... (or set SEMCODE_MI355X_LATE_STORE)")
+        with self._lock:
+            flt = self._filter(repos, languages)
+            allow = None if flt is None or flt[1] else flt[0]
+            return self._collection.search_late(question_vectors, k=int(top_k), allow=allow)
 
     # ------------------------------------------------------------------ term rows of the hybrid search
     @staticmethod
@@ -338,7 +409,7 @@ class MilvusVectorStore:
             self._needs_train = True
 
     def upsert_arrays(self, ids: Sequence[str], vectors: Any, texts: Sequence[str], metadatas: Sequence[dict],
-                      progress: Optional[Callable[[int, int], None]] = None) -> None:
+                      progress: Optional[Callable[[int, int], None]] = None, token_vectors: Optional[Sequence[Any]] = None) -> None:
         """upsert_embeddings without EmbeddingPayload / list[float] boxing: vectors is one [n, dim] float array.  Same
         progress protocol and batch size (settings.milvus_upsert_batch_size), same replace-by-primary-key result."""
         if self._collection is None:
@@ -363,13 +434,14 @@ class MilvusVectorStore:
             with self._lock:
                 rows = self.plan_rows(b_ids)
                 self._put_rows(vec[keep], rows)
-                self.commit_rows(b_ids, rows, [texts[i] for i in keep], [metadatas[i] for i in keep])
+                self.commit_rows(b_ids, rows, [texts[i] for i in keep], [metadatas[i] for i in keep],
+                                 token_vectors=None if token_vectors is None else [token_vectors[i] for i in keep])
             done = stop
             if progress:
                 progress(done, total)
 
     def upsert_encoded(self, ids: Sequence[str], token_ids: np.ndarray, lens: np.ndarray, texts: Sequence[str], metadatas: Sequence[dict],
-                       embedding_client: Any, wait: bool = True) -> None:
+                       embedding_client: Any, wait: bool = True, token_vectors: Optional[Sequence[Any]] = None) -> None:
         """One batch, embed + upsert fused: the encoder output goes from its device buffer straight into the index rows.
         wait=False: the device work is only enqueued (embedding_client.wait() completes it); searches issued afterwards are
         ordered behind it on the device stream either way."""
@@ -381,7 +453,7 @@ class MilvusVectorStore:
             # work is reported by embedding_client.wait() (services.ingest_chunks calls it before it returns) -- the rows of
             # that batch then hold undefined vectors and the caller must upsert them again
             embedding_client.embed_ids_into(self, token_ids, lens, rows, wait=wait)
-            self.commit_rows(ids, rows, texts, metadatas)
+            self.commit_rows(ids, rows, texts, metadatas, token_vectors=token_vectors)
 
     # ------------------------------------------------------------------ delete (Collection.delete(expr) of pymilvus)
     def delete(self, ids: Sequence[str]) -> int:
@@ -719,6 +791,20 @@ class MilvusVectorStore:
                 np.ascontiguousarray(ivf["centroids"], dtype="<f4").tofile(tmp / "ivf_centroids.f32")
                 np.ascontiguousarray(self._collection.ivf_assignments(), dtype="<i4").tofile(tmp / "ivf_assign.i32")
                 manifest["ivf_trained_nlist"] = int(ivf["nlist"])
+            st = self._collection.token_stats() if self.late_format is not None and hasattr(self._collection, "token_stats") else None
+            if st and st["W"]:  # tokens.f32 | tokens.bf16 ([tokens, W], row after row) + token_counts.i32 ([rows])
+                counts_all = []
+                with open(tmp / f"tokens.{st['fmt']}", "wb") as f:
+                    for start in range(0, n, 16384):
+                        counts, vecs = self._collection.get_tokens(np.arange(start, min(n, start + 16384)))
+                        counts_all.append(counts)
+                        if st["fmt"] == "bf16":  # the stored values have no lower half: the file holds the upper one
+                            (np.ascontiguousarray(vecs).view(np.uint32) >> 16).astype("<u2").tofile(f)
+                        else:
+                            np.ascontiguousarray(vecs, dtype="<f4").tofile(f)
+                counts_all = np.concatenate(counts_all) if counts_all else np.zeros(0, np.int32)
+                counts_all.astype("<i4").tofile(tmp / "token_counts.i32")
+                manifest.update(late_format=st["fmt"], late_width=int(st["W"]), late_tokens=int(counts_all.sum()))
             (tmp / "manifest.json").write_text(json.dumps(manifest, indent=1))
         if path.exists():
             shutil.rmtree(path)
@@ -760,6 +846,8 @@ class MilvusVectorStore:
             if self.lexical:  # (the term rows are not persisted: rebuilt from the saved texts)
                 self._terms = self._lex_terms(self._texts, self.lex_slots) if n else np.zeros((0, self.lex_slots), dtype=np.uint16)
                 self._upload_all_terms()
+            if manifest.get("late_format") in ("f32", "bf16") and n > 0:
+                self._load_tokens(path, manifest, n)
             self._needs_train = True
             # the saved lists are reused as they are (no k-means) when they fit this collection's index parameters
             tn = int(manifest.get("ivf_trained_nlist", 0))
@@ -771,6 +859,23 @@ class MilvusVectorStore:
                     self._collection.set_ivf(cent.reshape(tn, self.dim), assign)
                     self._needs_train = False
                     self._trained_rows = n
+
+    def _load_tokens(self, path: Path, manifest: dict, n: int) -> None:
+        """The saved token vectors back into the device index, in the saved format (which becomes the store's).  Caller holds the lock."""
+        fmt, W, total = manifest["late_format"], int(manifest["late_width"]), int(manifest["late_tokens"])
+        counts = np.fromfile(path / "token_counts.i32", dtype="<i4")
+        if counts.size != n or int(counts.sum()) != total:
+            raise ValueError(f"{path}: token_counts.i32 holds {counts.size} rows / {int(counts.sum())} tokens, manifest says {n} / {total}")
+        data = np.memmap(path / f"tokens.{fmt}", dtype="<u2" if fmt == "bf16" else "<f4", mode="r", shape=(total, W)) if total else None
+        self.late_format = fmt
+        off = np.concatenate(([0], np.cumsum(counts, dtype=np.int64)))
+        for start in range(0, n, 16384):
+            stop = min(n, start + 16384)
+            if off[stop] == off[start]:
+                continue
+            block = np.asarray(data[off[start]:off[stop]])
+            vecs = (block.astype(np.uint32) << 16).view(np.float32) if fmt == "bf16" else block.astype(np.float32)
+            self._collection.put_tokens(np.arange(start, stop), (counts[start:stop].astype(np.int32), vecs), fmt=fmt)
 
     def __iter__(self) -> Iterator:  # pragma: no cover - convenience
         return iter(self._ids)
