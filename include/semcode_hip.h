@@ -418,14 +418,32 @@ sc_status sc_encoder_score_seqs(sc_encoder* enc, const int32_t* ids, const int64
  * kept token scores nq * -inf = -inf there.
  * Storing token vectors in the index (a multi-vector collection) and scoring from them without a passage forward: sc_index_put_tokens,
  * sc_index_rerank_late and sc_index_search_late, below.
- * Out of scope: arch 2; _dev / asynchronous forms; a device-to-device hand-over of token vectors to an index; query lengths above
- * 128; XLM-R backbones (jina-colbert-v2); a projection with a bias. */
+ * sc_encoder_embed_tokens_into: the hand-over at ingest.  The document-side call of sc_encoder_embed_tokens (expand_id < 0; the same
+ * pipeline rules, so the same bits) whose token head writes straight into the token pool of `ix`: text i's KEPT token vectors become the
+ * tokens of local row rows[i], with the semantics of sc_index_put_tokens(ix, rows, B, kept counts, .., W, fmt) below -- appended, the rows
+ * repointed, their old tokens dead, the automatic compaction at the end.  keep: one byte per input token in ids order, as d_keep above,
+ * 0 = the token is not stored (it is still attended), NULL = every token is stored; a text without a kept token gets count 0, which
+ * removes the row's tokens.  The flags enter the host plan: a dropped token's packed row maps to no output row, the kept ones are numbered
+ * compactly, text after text (sc_diag_encoder_plan_keep shows that plan without a device).  fmt 0 stores the head's f32 bits; fmt 1 rounds
+ * them in the kernel's epilogue by the rule of the store (sc_diag_round_bf16), 8-byte stores: the stored bits are those the host path
+ * (sc_encoder_embed_tokens, drop, sc_index_put_tokens) stores.  out_counts [B] or NULL receives the kept counts.  No token vector crosses
+ * to the host; the call synchronises once, at its end (and where the pool has to grow).  Order: everything validated; room made (the
+ * table follows the rows, the pool grows -- SC_ERR_NOMEM leaves the store as it was); the forward into pool[used ...); only then the
+ * table repointed and used advanced -- a failed forward leaves the store unchanged, nothing points at the tail it wrote.  Takes the
+ * encoder's mutex, then the index's, as sc_encoder_embed_packed_into.  With nothing launched and nothing changed -- SC_ERR_INVALID: a NULL
+ * pointer (keep and out_counts aside), no token head installed, fmt outside 0 / 1, the head's W or fmt differing from an installed
+ * store's, encoder and index on different runtimes, rows out of range or not distinct, every refusal of sc_encoder_embed_tokens;
+ * SC_ERR_UNSUPPORTED: an arch 2 encoder, more than SC_ENCODER_PACKED_MAX_ROWS token rows.
+ * Out of scope: arch 2; an asynchronous form of the hand-over (pool growth reallocates and must synchronise; the late model shares the
+ * dense encoder's stream); query lengths above 128; XLM-R backbones (jina-colbert-v2); a projection with a bias. */
 sc_status sc_encoder_set_token_head(sc_encoder* enc, const float* w /*[W,H] or NULL*/, int32_t W);
 sc_status sc_encoder_embed_tokens(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, int32_t expand_id, float* out /*[sum n_i,W]*/,
                                   int32_t* out_counts /*[B]*/);
 sc_status sc_encoder_score_late(sc_encoder* enc, const int32_t* q_ids, const int64_t* q_offsets, int32_t Bq, int32_t expand_id, const int32_t* d_ids,
                                 const int64_t* d_offsets, int32_t Bd, const uint8_t* d_keep /*or NULL*/, const int32_t* pair_q, const int32_t* pair_d, int32_t P,
                                 float* out_scores /*[P]*/);
+sc_status sc_encoder_embed_tokens_into(sc_encoder* enc, const int32_t* ids, const int64_t* offsets, int32_t B, const uint8_t* keep /*[offsets[B]] or NULL*/,
+                                       sc_index* ix, const int64_t* rows /*[B]*/, int32_t fmt, int32_t* out_counts /*[B] or NULL*/);
 sc_status sc_diag_maxsim(sc_runtime* rt, const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const uint8_t* keep,
                          const int32_t* pair_q, const int32_t* pair_d, int32_t P, int32_t W, float* out);
 sc_status sc_diag_maxsim_host(const float* Q, const int32_t* q_off, int32_t Bq, const float* D, const int32_t* d_off, int32_t Bd, const uint8_t* keep,
@@ -921,8 +939,17 @@ sc_status sc_diag_rrf_host(const int64_t* dense_rows, const int64_t* lex_rows, i
  * otherwise it grows geometrically, contents kept.  sc_index_get_tokens: out_counts [n] and, unless out_vecs is NULL, the rows' vectors
  * one after the other as f32 (widened as stored), at most cap_tokens of them (more: SC_ERR_INVALID, nothing written) -- it serves a
  * save.  sc_index_token_stats: rows that have tokens, live and dead tokens, W and fmt (0, 0: nothing installed), the pool's bytes.
- * sc_index_drop_tokens frees the store. */
+ * sc_index_drop_tokens frees the store.
+ * sc_index_put_tokens_dev is sc_index_put_tokens with the vectors on the device: vecs_dev [.., W] f32 (DEVICE), src [sum counts] (host)
+ * or NULL.  Stored token j (in stored order: row after row of `rows`) is vecs_dev[src[j]], or vecs_dev[j] without a list -- a gather list
+ * of 4 bytes a token, so a caller drops or reorders tokens without moving a vector; its entries must be >= 0 (SC_ERR_INVALID) and name
+ * tokens the caller's array holds (not checked: the array's length is the caller's).  late_install_kernel copies (fmt 0) or rounds
+ * (fmt 1, the rule above) into pool[used ...) before the table is repointed.  The same checks, the same order of work, the same
+ * semantics; synchronises once, at its end.  sc_encoder_embed_tokens_into (above) is the third form: the encoder's token head writes
+ * the pool's tail itself. */
 sc_status sc_index_put_tokens(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs /*[sum counts,W]*/, int32_t W, int32_t fmt);
+sc_status sc_index_put_tokens_dev(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs_dev /*[..,W] f32, device*/,
+                                  const int32_t* src /*[sum counts] host, or NULL*/, int32_t W, int32_t fmt);
 sc_status sc_index_reserve_tokens(sc_index* ix, int64_t tokens);
 sc_status sc_index_compact_tokens(sc_index* ix);
 sc_status sc_index_get_tokens(sc_index* ix, const int64_t* rows, int64_t n, int32_t* out_counts, float* out_vecs /*or NULL*/, int64_t cap_tokens);
@@ -947,7 +974,8 @@ sc_status sc_index_drop_tokens(sc_index* ix);
  * whatever the partition.
  * SC_ERR_INVALID before anything changes: no tokens installed, a NULL pointer, Bq / C / k out of range, q_off[0] != 0, a question with 0
  * or more than 128 vectors, a candidate that is neither -1 nor a row, a short allow.  Host pointers; both synchronise.
- * Out of scope: sharded collections, _dev / asynchronous forms, several questions per pass, a bf16-MFMA coarse pass with exact re-score.
+ * Out of scope: sharded collections, _dev / asynchronous forms of the two scoring calls, several questions per pass, a bf16-MFMA coarse
+ * pass with exact re-score.
  * sc_diag_late_search_host is the search on the CPU over D [d_off[n], W] f32 (row r's vectors at [d_off[r], d_off[r + 1]), int64), rows
  * reported without a row_base; sc_diag_round_bf16 the install-time rounding of fmt 1 (out = the value stored for in).  No GPU involved. */
 sc_status sc_index_rerank_late(sc_index* ix, const float* Q, const int32_t* q_off /*[Bq+1]*/, int32_t Bq, const int64_t* cand /*[Bq,C]*/, int32_t C,
@@ -1043,6 +1071,11 @@ sc_status sc_diag_ivf_exact_path(int32_t ld, int32_t R, int32_t k, int32_t nprob
 sc_status sc_diag_encoder_plan(const int32_t* ids, const int64_t* offsets, int32_t B, int32_t kind, const int32_t* first_lens, int32_t expand_id,
                                int32_t query, int32_t max_pos, int32_t pos_type, int32_t vocab, int32_t type_vocab, int32_t arch, int32_t global_every,
                                int32_t local_window, void* out, int64_t cap_bytes, int64_t* need_bytes);
+/* The same for the documents' token call under keep flags (sc_encoder_embed_tokens_into): keep [offsets[B]] one byte per token or NULL.
+ * out: ids / pos / dst [M], starts / lens / counts [B] int32 -- dst is -1 on a dropped token's row, on alignment rows and on the tail, the
+ * kept rows count up from 0 text after text; counts the kept tokens per text -- and int64 scalars rows, M, nrows (tokens given), kept. */
+sc_status sc_diag_encoder_plan_keep(const int32_t* ids, const int64_t* offsets, int32_t B, const uint8_t* keep, int32_t max_pos, int32_t pos_type, int32_t vocab,
+                                    void* out, int64_t cap_bytes, int64_t* need_bytes);
 
 /* Multi-GPU final step (one process per GPU): merge `lists` per-shard results
  * dist [lists,Q,k] / rows [lists,Q,k] (as produced by sc_index_search* on each shard and

@@ -113,6 +113,7 @@ SIGNATURES = {
     "sc_encoder_score_seqs": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_encoder_set_token_head": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32]),
     "sc_encoder_embed_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sc_encoder_embed_tokens_into": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "sc_encoder_score_late": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
                               + [C.c_int32, C.c_void_p]),
     "sc_diag_maxsim": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
@@ -209,6 +210,7 @@ SIGNATURES = {
     "sc_diag_lex_score_host": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "sc_diag_rrf_host": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "sc_index_put_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "sc_index_put_tokens_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "sc_index_reserve_tokens": (C.c_int32, [C.c_void_p, C.c_int64]),
     "sc_index_compact_tokens": (C.c_int32, [C.c_void_p]),
     "sc_index_get_tokens": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -238,6 +240,8 @@ SIGNATURES = {
     "sc_diag_ivf_exact_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "sc_diag_encoder_plan": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_int32] * 8 + [C.c_void_p, C.c_int64,
                                          C.POINTER(C.c_int64)]),
+    "sc_diag_encoder_plan_keep": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                              C.POINTER(C.c_int64)]),
     "sc_comm_unique_id": (C.c_int32, [C.c_void_p, C.c_size_t]),
     "sc_comm_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "sc_comm_destroy": (C.c_int32, [C.c_void_p]),
@@ -781,6 +785,20 @@ class Index:
         _check(lib().sc_index_put_tokens(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], counts.ctypes.data_as(C.c_void_p), vecs.ctypes.data_as(C.c_void_p),
                                          vecs.shape[1], TOKEN_FORMATS[fmt]))
 
+    def put_tokens_dev(self, rows, counts, vecs_ptr: int, src, W: int, fmt: str = "f32") -> None:
+        """put_tokens with the vectors on the device (sc_index_put_tokens_dev): vecs_ptr = device address of [.., W] f32, counts [n] the
+        tokens of each row, src = the source token of every stored token in stored order (int32 [sum counts], a gather list) or None:
+        the first sum(counts) tokens in order.  Copied (f32) or rounded (bf16) on the device into the pool."""
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if c.shape[0] != r.shape[0]:
+            raise ValueError("counts must have one entry per row")
+        s = None if src is None else np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        if s is not None and s.shape[0] != int(c.sum()):
+            raise ValueError("src must name one source token per stored token")
+        _check(lib().sc_index_put_tokens_dev(self.handle, r.ctypes.data_as(C.c_void_p), r.shape[0], c.ctypes.data_as(C.c_void_p), C.c_void_p(int(vecs_ptr)) if vecs_ptr else None,
+                                             None if s is None else s.ctypes.data_as(C.c_void_p), int(W), TOKEN_FORMATS[fmt]))
+
     def reserve_tokens(self, tokens: int) -> None:
         """Pre-size the token pool (sc_index_reserve_tokens)."""
         _check(lib().sc_index_reserve_tokens(self.handle, int(tokens)))
@@ -1271,6 +1289,22 @@ class Encoder:
         _check(lib().sc_encoder_embed_tokens(self.handle, _ptr(ids_flat), _ptr(offsets), B, int(expand_id), _ptr(out), _ptr(counts)))
         return out, counts
 
+    def embed_tokens_into(self, ids_flat, offsets, keep, index: "Index", rows, fmt: str = "f32") -> np.ndarray:
+        """Packed documents -> their kept token vectors as the tokens of `rows` of `index`, written by the token head straight into the
+        index's token pool (sc_encoder_embed_tokens_into): what embed_tokens, dropping the tokens whose keep flag is 0 and
+        Index.put_tokens store, without a vector crossing to the host.  keep: one uint8 per token or None (all kept).  -> kept counts [B]."""
+        ids_flat, offsets, B = self._packed_args(ids_flat, offsets)
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8)
+            if keep.shape != ids_flat.shape:
+                raise ValueError("keep must hold one flag per token")
+        r = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if r.shape[0] != B:
+            raise ValueError("rows must hold one row number per text")
+        counts = np.empty(B, dtype=np.int32)
+        _check(lib().sc_encoder_embed_tokens_into(self.handle, _ptr(ids_flat), _ptr(offsets), B, _ptr(keep), index.handle, _ptr(r), TOKEN_FORMATS[fmt], _ptr(counts)))
+        return counts
+
     def score_late(self, q_ids, q_offsets, d_ids, d_offsets, pair_q, pair_d, expand_id: int = -1, d_keep=None) -> np.ndarray:
         """MaxSim scores [P] of the pairs (pair_q[p], pair_d[p]) over the token vectors of the packed queries and documents; the vectors
         stay on the device.  d_keep: one uint8 per document token, 0 = left out of every maximum (punctuation); None = all kept."""
@@ -1398,6 +1432,17 @@ def diag_encoder_plan(ids, offsets, kind: str = "texts", first_lens=None, expand
     args = (_ptr(ids), _ptr(offsets), offsets.size - 1, ("texts", "pairs", "scored", "tokens").index(kind), _ptr(fl), int(expand_id),
             1 if query else 0, int(max_pos), int(pos_type), int(vocab), int(type_vocab), int(arch), int(global_every), int(local_window))
     return _diag_records(lib().sc_diag_encoder_plan, args)
+
+
+def diag_encoder_plan_keep(ids, offsets, keep=None, *, max_pos: int = 2048, pos_type: int = 0, vocab: int = 30522) -> "dict[str, np.ndarray]":
+    """The host plan of the documents' token call under keep flags (sc_diag_encoder_plan_keep; no device, no encoder): dst [M] is -1 on
+    dropped, alignment and tail rows and counts the kept rows up text after text; counts [B] the kept tokens per text."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    kp = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    if kp is not None and kp.shape != ids.shape:
+        raise ValueError("keep must hold one flag per token")
+    return _diag_records(lib().sc_diag_encoder_plan_keep, (_ptr(ids), _ptr(offsets), offsets.size - 1, _ptr(kp), int(max_pos), int(pos_type), int(vocab)))
 
 
 def diag_set_option(name: str, value: int) -> None:

@@ -131,10 +131,11 @@ void sc_launch_score_head(const float* r, int B, int H, const float* Wd, const f
 
 // ---- encoder_tokens.hip: late interaction.  token_head: x [rows, H] bf16 (rows a multiple of 32), w [W, H] bf16, dst [rows] = the compact output
 // row of every packed row or -1 -> out[dst][W] f32 = the L2-normalised projection (the pooling kernels' 1e-12 rule).  W % 16 == 0, 16 .. 128;
-// H % 32 == 0.  maxsim: the rule of maxsim_rule.h over P pairs: Q [.., W] / D [.., W] f32 token vectors, text i's at rows [off[i], off[i + 1]),
+// H % 32 == 0.  fmt 1: out[dst][W] bf16 instead, every component of that f32 vector rounded once by late_round_bf16 (the token pool of an
+// index at fmt 1).  maxsim: the rule of maxsim_rule.h over P pairs: Q [.., W] / D [.., W] f32 token vectors, text i's at rows [off[i], off[i + 1]),
 // keep NULL or one byte per document token, pair_q / pair_d [P] -> out [P].  A query has at most 128 tokens.  All device pointers.
 bool sc_token_head_supported(int H, int W);
-void sc_launch_token_head(const void* x, int rows, int H, const void* w, int W, const int32_t* dst, float* out, hipStream_t s);
+void sc_launch_token_head(const void* x, int rows, int H, const void* w, int W, const int32_t* dst, void* out, int fmt, hipStream_t s);
 void sc_launch_maxsim(const float* Q, const int32_t* q_off, const float* D, const int32_t* d_off, const uint8_t* keep, const int32_t* pair_q, const int32_t* pair_d,
                       int P, int W, float* out, hipStream_t s);
 

@@ -18,6 +18,8 @@
 //                        values: every lane of a row ends with the same bits).  scale = 1 / max(sqrt(|v|^2), 1e-12), the pooling
 //                        kernels' rule; one 16-byte store per tile.  A column of the MFMA depends on no other column: a row's vector
 //                        is the same bits whatever rows stand next to it.  No LDS, no atomics.
+// token_head_bf16_kernel<NT>  the same up to the scale; writes the vectors as bf16 (late_round_bf16 of each f32 component, 8-byte stores) so
+//                        that sc_encoder_embed_tokens_into can aim it at the tail of an index's bf16 token pool.
 // maxsim_kernel          one workgroup (4 waves) per pair.  Wave w takes the document tiles w, w + 4, ... of 16 tokens; the query tiles of
 //                        16 are the outer loop.  Per tile pair one v_mfma_f32_16x16x4_f32 chain over W / 4 steps fed as mmr_gram_kernel
 //                        feeds it -- lane (r16, g) supplies floats 16 t + 4 g + c of document token 16 dt + r16 (A) and of query token
@@ -28,7 +30,7 @@
 //                        the LDS, and lane 0 adds m_t in ascending t with __fadd_rn.  Integer maxima: no order matters.  No atomics.
 // Registers and scratch: at the launchers.
 #include "encoder_ops.h"
-#include "maxsim_rule.h"
+#include "late_rule.h"
 
 template <int NT>
 __global__ __launch_bounds__(256) void token_head_kernel(const bf16_t* __restrict__ x, int rows, int H, const bf16_t* __restrict__ w, const int32_t* __restrict__ dst,
@@ -63,6 +65,49 @@ __global__ __launch_bounds__(256) void token_head_kernel(const bf16_t* __restric
     float* o = out + (size_t)d * (16 * NT) + 4 * g;
 #pragma unroll
     for (int n = 0; n < NT; ++n) *reinterpret_cast<f32x4*>(o + 16 * n) = f32x4{acc[n][0] * scale, acc[n][1] * scale, acc[n][2] * scale, acc[n][3] * scale};
+}
+
+// The sibling of token_head_kernel that writes into a bf16 token pool (sc_encoder_embed_tokens_into at fmt 1; that kernel is untouched, as
+// late_rerank_kernel leaves maxsim_kernel): the same loads, the same MFMA chains, the same |v|^2 and scale in f32; then each of the lane's
+// four consecutive columns rounded once by late_round_bf16 -- what sc_index_put_tokens does to the f32 vector on the host, so the stored
+// bits are the same -- and one 8-byte store per column tile where the f32 form stores 16.
+template <int NT>
+__global__ __launch_bounds__(256) void token_head_bf16_kernel(const bf16_t* __restrict__ x, int rows, int H, const bf16_t* __restrict__ w, const int32_t* __restrict__ dst,
+                                                               uint16_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63, r16 = lane & 15, g = lane >> 4;
+    const int r0 = 16 * (blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (r0 >= rows) return;  // (wave-uniform; rows is a multiple of 32)
+    const int row = r0 + r16;
+    const int d = dst[row];
+    if (!__any(d >= 0)) return;
+    const bf16_t* xr = x + (size_t)row * H + 8 * g;
+    const bf16_t* wr = w + (size_t)r16 * H + 8 * g;
+    f32x4 acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int steps = H >> 5;
+    for (int s = 0; s < steps; ++s) {
+        const bf16x8 b = *reinterpret_cast<const bf16x8*>(xr + 32 * s);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8*>(wr + (size_t)(16 * n) * H + 32 * s);
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[n], 0, 0, 0);
+        }
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) ss += (acc[n][0] * acc[n][0] + acc[n][1] * acc[n][1]) + (acc[n][2] * acc[n][2] + acc[n][3] * acc[n][3]);
+    ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    const float scale = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    if (d < 0) return;
+    uint16_t* o = out + (size_t)d * (16 * NT) + 4 * g;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const uint32_t h0 = late_round_bf16(acc[n][0] * scale), h1 = late_round_bf16(acc[n][1] * scale);
+        const uint32_t h2 = late_round_bf16(acc[n][2] * scale), h3 = late_round_bf16(acc[n][3] * scale);
+        *reinterpret_cast<uint2*>(o + 16 * n) = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+    }
 }
 
 __global__ __launch_bounds__(256) void maxsim_kernel(const float* __restrict__ Q, const int32_t* __restrict__ q_off, const float* __restrict__ D,
@@ -118,15 +163,19 @@ __global__ __launch_bounds__(256) void maxsim_kernel(const float* __restrict__ Q
 
 bool sc_token_head_supported(int H, int W) { return maxsim_width_ok(W) && H >= 32 && (H % 32) == 0; }
 
-// Registers / scratch (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): profiles/late_kernels.log
-void sc_launch_token_head(const void* x, int rows, int H, const void* w, int W, const int32_t* dst, float* out, hipStream_t s) {
-    if (rows < 1 || !sc_token_head_supported(H, W)) return;  // (the host checks these before it plans a call)
+// Registers / scratch (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): profiles/late_kernels.log; the bf16 sibling and the
+// comparison of the f32 instantiations with their earlier text: profiles/late_ingest_kernels.log
+void sc_launch_token_head(const void* x, int rows, int H, const void* w, int W, const int32_t* dst, void* out, int fmt, hipStream_t s) {
+    if (rows < 1 || !sc_token_head_supported(H, W) || (fmt != 0 && fmt != 1)) return;  // (the host checks these before it plans a call)
     const dim3 grid((unsigned)((rows + 63) / 64)), block(256);
     const bf16_t* xp = (const bf16_t*)x;
     const bf16_t* wp = (const bf16_t*)w;
     switch (W / 16) {
-#define TOKEN_HEAD_CASE(NT) \
-    case NT: hipLaunchKernelGGL((token_head_kernel<NT>), grid, block, 0, s, xp, rows, H, wp, dst, out); break;
+#define TOKEN_HEAD_CASE(NT)                                                                                                       \
+    case NT:                                                                                                                      \
+        if (fmt == 0) hipLaunchKernelGGL((token_head_kernel<NT>), grid, block, 0, s, xp, rows, H, wp, dst, (float*)out);          \
+        else hipLaunchKernelGGL((token_head_bf16_kernel<NT>), grid, block, 0, s, xp, rows, H, wp, dst, (uint16_t*)out);           \
+        break;
         TOKEN_HEAD_CASE(1) TOKEN_HEAD_CASE(2) TOKEN_HEAD_CASE(3) TOKEN_HEAD_CASE(4) TOKEN_HEAD_CASE(5) TOKEN_HEAD_CASE(6) TOKEN_HEAD_CASE(7) TOKEN_HEAD_CASE(8)
 #undef TOKEN_HEAD_CASE
     }

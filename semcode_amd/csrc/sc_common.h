@@ -228,6 +228,9 @@ void sc_launch_late_rerank(const float* Q, const int32_t* q_off, int Bq, const v
 void sc_launch_late_scan(const float* Q, int nq, const void* pool, int fmt, const sc_tok_entry* table, int64_t n, const uint32_t* allow, int W, int k, int nwg,
                          uint64_t* partial, unsigned* next_block, hipStream_t s);
 void sc_launch_late_gather(const sc_tok_entry* old_tab, const sc_tok_entry* new_tab, int64_t n, const void* old_pool, void* new_pool, int tok_bytes, int cus, hipStream_t s);
+// late_install: vecs [.., W] f32 (device), src [total] source token of each stored token (device) or NULL (0 .. total - 1) -> dst, `total`
+// tokens of W elements in the pool's format (fmt 1: rounded by late_round_bf16)
+void sc_launch_late_install(const float* vecs, const int32_t* src, int64_t total, int W, int fmt, void* dst, int cus, hipStream_t s);
 // partial [groups][lists][qt][k] sorted keys -> out_dist [Q,k], out_rows [Q,k]
 // more lists than one LDS tree merge holds (2 * lists * k keys > 128 KiB) are merged in levels whose intermediate k-lists live right
 // behind the partial lists: that many extra bytes (included in ScanPlan::partial_bytes)

@@ -3,7 +3,7 @@
 // The pattern of every harness: host f32 in (activations rounded to bf16 by f32_to_bf16_kernel), THE PRODUCT LAUNCHER, result widened
 // to f32 and copied back, synchronous.  Output buffers are pre-filled with 0xFF bytes (NaN as bf16 and as f32), so that an element a
 // kernel does not write shows in the result.  (sc_diag_encoder_read, which needs the encoder handle, is in sc_encoder_embed.cpp.)
-// sc_diag_encoder_plan, at the end, touches no device: the host plan of a packed call (sc_encoder_plan.h).
+// sc_diag_encoder_plan and sc_diag_encoder_plan_keep, at the end, touch no device: the host plan of a packed call (sc_encoder_plan.h).
 #include <cstring>
 #include <vector>
 
@@ -888,6 +888,32 @@ extern "C" sc_status sc_diag_encoder_plan(const int32_t* ids, const int64_t* off
     bl.num("rows", rows), bl.num("M", M), bl.num("nrows", nrows), bl.num("items_cap", sc_packed_items_cap(M, B)), bl.num("plan_bytes", (int64_t)po.total);
     bl.num("common_bytes", (int64_t)PlanOffsets((size_t)M, (size_t)B).total);
     bl.put("common", 2, buf.data(), PlanOffsets((size_t)M, (size_t)B).total / 4, 4);
+    bl.give(out, cap_bytes, need_bytes);
+    return SC_OK;
+}
+
+// The plan of the documents' token call under keep flags (sc_encoder_embed_tokens_into), without a device or a handle: the rules of a
+// document-side token call, the kept counts, then the filler.  keep NULL: every token is kept.  out as sc_diag_encoder_plan's.
+extern "C" sc_status sc_diag_encoder_plan_keep(const int32_t* ids, const int64_t* offsets, int32_t B, const uint8_t* keep, int32_t max_pos, int32_t pos_type,
+                                               int32_t vocab, void* out, int64_t cap_bytes, int64_t* need_bytes) {
+    const char* who = "sc_diag_encoder_plan_keep";
+    if (!ids || !need_bytes) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    const PlanBounds mb{max_pos, pos_type, vocab, 2, 0, 0, 0, MAXSIM_MAX_NQ};
+    int64_t used = 0, nrows = 0;
+    SC_TRY(sc_plan_check_tokens(offsets, B, -1, false, mb, who, &used, &nrows));
+    std::vector<int32_t> counts((size_t)B);
+    const int64_t kept = sc_plan_kept_counts(offsets, B, keep, counts.data());
+    const PackedCall call = PackedCall::kept_tokens(keep, nullptr, 0);
+    const int64_t M = ceil256(used);
+    const PlanOffsets po((size_t)M, (size_t)B, call.kind);
+    std::vector<char> buf(po.total, (char)0xCD);
+    int nitems[3];
+    const int64_t rows = sc_plan_fill(ids, offsets, B, call, po, M, buf.data(), nitems);
+    DiagBlob bl;
+    bl.put("ids", 0, buf.data() + po.ids, (size_t)M, 4), bl.put("pos", 0, buf.data() + po.pos, (size_t)M, 4);
+    bl.put("starts", 0, buf.data() + po.starts, (size_t)B, 4), bl.put("lens", 0, buf.data() + po.lens, (size_t)B, 4);
+    bl.put("dst", 0, buf.data() + po.dst, (size_t)M, 4), bl.i32("counts", counts);
+    bl.num("rows", rows), bl.num("M", M), bl.num("nrows", nrows), bl.num("kept", kept);
     bl.give(out, cap_bytes, need_bytes);
     return SC_OK;
 }

@@ -74,7 +74,7 @@ static void launch_layer_attention(sc_encoder* e, int l, const int32_t* lens_dev
 }
 // the token head on the rows `x` after the model's last norm, in place of a pooling kernel
 static sc_status launch_token_head(sc_encoder* e, const void* x, const PackedLayout* pk, hipStream_t s) {
-    sc_launch_token_head(x, pk->rows, e->cfg.hidden, e->token.w, e->token.W, pk->per_row, pk->call.tok_out, s);
+    sc_launch_token_head(x, pk->rows, e->cfg.hidden, e->token.w, e->token.W, pk->per_row, pk->call.tok_out, pk->call.tok_fmt, s);
     SC_HIP(hipGetLastError());
     return SC_OK;
 }

@@ -1,8 +1,8 @@
 // sc_encoder_heads.cpp -- what runs behind the packed forward instead of plain pooling: the three heads of a handle and their calls.
 // Pairs of a cross-encoder (set_pair_head / score_pairs, arch 0; encoder_pairs.hip), sequences of the other two families' rerankers
 // (set_score_head / score_seqs: [CLS] or masked mean of final_norm on arch 1, RMS_final of the last token on arch 2; encoder_heads.hip) and
-// late interaction (set_token_head / embed_tokens / score_late: the token head on every row asked for, MaxSim over those vectors;
-// encoder_tokens.hip).  What each call's batch is travels to the forward as a PackedCall (sc_encoder_plan.h).
+// late interaction (set_token_head / embed_tokens / embed_tokens_into / score_late: the token head on every row asked for -- to the host, or
+// straight into the token pool of an index --, MaxSim over those vectors; encoder_tokens.hip).  What each call's batch is travels to the forward as a PackedCall (sc_encoder_plan.h).
 #include <vector>
 
 #include "sc_encoder_state.h"
@@ -268,6 +268,57 @@ extern "C" sc_status sc_encoder_embed_tokens(sc_encoder* e, const int32_t* ids, 
         const int64_t len = offsets[i + 1] - offsets[i];
         out_counts[i] = (int32_t)(expand_id >= 0 ? ceil32(len) : len);
     }
+    return SC_OK;
+}
+
+// The documents' token call with the token head aimed at the tail of the index's token pool: the put of sc_tokens.cpp (sc_tok_put_*) whose
+// step 3 is the forward.  The keep flags enter the plan (a dropped token's row maps to -1, the kept ones count up text after text), so the
+// head writes exactly the vectors the host path would upload, in the pool's format, where the table is about to point.  Lock order:
+// encoder, then index, as store_pooled_locked (sc_encoder_embed.cpp) takes them; both are held to the end -- the pool may not move
+// under the forward.
+extern "C" sc_status sc_encoder_embed_tokens_into(sc_encoder* e, const int32_t* ids, const int64_t* offsets, int32_t B, const uint8_t* keep, sc_index* ix,
+                                                  const int64_t* rows, int32_t fmt, int32_t* out_counts) {
+    const char* who = "sc_encoder_embed_tokens_into";
+    if (!e || !ids || !offsets || !ix || !rows) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (e->cfg.arch == 2) return sc_fail(SC_ERR_UNSUPPORTED, "%s: arch 2 (causal decoder) models have no token head", who);
+    int64_t used = 0, nrows = 0;
+    sc_status st = sc_plan_check_tokens(offsets, B, -1, false, plan_bounds(e), who, &used, &nrows);
+    if (st) return st;
+    if (ix->rt != e->rt) return sc_fail(SC_ERR_INVALID, "%s: encoder and index belong to different runtimes", who);
+    std::vector<int32_t> counts((size_t)B);
+    const int64_t total = sc_plan_kept_counts(offsets, B, keep, counts.data());  // (a text has at most 2 048 tokens: so has a row)
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->token.mem) return sc_fail(SC_ERR_INVALID, "%s: no token head installed (sc_encoder_set_token_head)", who);
+    const int W = e->token.W;
+    st = sc_tok_check_format(W, fmt, who);
+    if (st) return st;
+    std::lock_guard<std::mutex> gi(ix->mu);
+    sc_tok_put put;
+    st = sc_tok_put_check_locked(ix, rows, B, W, fmt, who, &put);
+    if (st) return st;
+    SC_HIP(hipSetDevice(e->rt->device));
+    void* tail = nullptr;
+    st = sc_tok_put_room_locked(ix, W, fmt, total, who, &put, &tail);
+    if (st) return st;
+    bool committed = false;
+    auto commit = [&](const int64_t*) {
+        committed = true;
+        return sc_tok_put_commit_locked(ix, rows, B, counts.data(), put);
+    };
+    if (total > 0) {
+        st = packed_call_locked(e, ids, offsets, B, used, PackedCall::kept_tokens(keep, tail, fmt), nullptr, false, commit);  // the one synchronisation is its last step
+    } else {  // nothing is kept: the rows lose their tokens, no forward runs
+        st = commit(nullptr);
+        hipStream_t s = e->rt->stream;
+        if (!st) SC_HIP(hipStreamSynchronize(s));
+    }
+    if (st) {
+        if (!committed) sc_tok_put_abandon_locked(ix, put);  // (the stream is drained: nothing points at what the forward wrote)
+        return st;
+    }
+    sc_tok_put_done_locked(ix);
+    if (out_counts)
+        for (int32_t i = 0; i < B; ++i) out_counts[i] = counts[(size_t)i];
     return SC_OK;
 }
 

@@ -66,6 +66,19 @@ sc_status sc_plan_check_tokens(const int64_t* offsets, int32_t B, int32_t expand
     return SC_OK;
 }
 
+int64_t sc_plan_kept_counts(const int64_t* offsets, int32_t B, const uint8_t* keep, int32_t* counts) {
+    int64_t total = 0;
+    for (int32_t i = 0; i < B; ++i) {
+        int32_t n = 0;
+        if (!keep) n = (int32_t)(offsets[i + 1] - offsets[i]);
+        else
+            for (int64_t j = offsets[i]; j < offsets[i + 1]; ++j) n += keep[j] != 0;
+        counts[i] = n;
+        total += n;
+    }
+    return total;
+}
+
 int64_t sc_plan_fill(const int32_t* ids, const int64_t* offsets, int32_t B, const PackedCall& call, const PlanOffsets& po, int64_t M, char* buf, int nitems[3]) {
     int32_t* h_ids = (int32_t*)(buf + po.ids);
     int32_t* h_pos = (int32_t*)(buf + po.pos);
@@ -98,7 +111,9 @@ int64_t sc_plan_fill(const int32_t* ids, const int64_t* offsets, int32_t B, cons
         for (int32_t i = 0; i < B; ++i) {
             const int32_t n = call.expand_id >= 0 ? (int32_t)ceil32(h_lens[i]) : h_lens[i];
             for (int32_t j = h_lens[i]; j < n; ++j) h_ids[h_starts[i] + j] = call.expand_id;
-            for (int32_t j = 0; j < n; ++j) h_dst[h_starts[i] + j] = at++;
+            const uint8_t* kp = call.expand_id < 0 && call.keep ? call.keep + offsets[i] : nullptr;  // (flags belong to documents)
+            for (int32_t j = 0; j < n; ++j)
+                if (!kp || kp[j]) h_dst[h_starts[i] + j] = at++;
         }
     }
     sc_packed_items(h_starts, h_lens, B, (int32_t*)(buf + po.items), nitems);

@@ -27,15 +27,21 @@ struct PackedCall {
                  // token) instead of the encoder's mode; never L2-normalised
         TOKENS   // a token call (sc_encoder_embed_tokens, sc_encoder_score_late): nothing is pooled, the last layer is never pruned; the token
                  // head writes tok_out [.., W] f32 (device) compactly and in text order.  expand_id >= 0: queries -- every row of a text's
-                 // 32-row span is asked for and its alignment rows carry that token instead of token 0; < 0: documents -- the len_i real rows
+                 // 32-row span is asked for and its alignment rows carry that token instead of token 0; < 0: documents -- the len_i real rows,
+                 // or (keep given) those of them whose keep flag is not 0: a dropped token's row is attended like any other and its
+                 // vector never stored.  tok_fmt 1: tok_out takes the vectors rounded to bf16 (late_rule.h), 2 W bytes each
     } kind = TEXTS;
     const int32_t* first_lens = nullptr;  // PAIRS: host [B], validated
     int head_pool = -1;                   // SCORED
     int32_t expand_id = -1;               // TOKENS
-    float* tok_out = nullptr;             // TOKENS
+    void* tok_out = nullptr;              // TOKENS
+    int tok_fmt = 0;                      // TOKENS
+    const uint8_t* keep = nullptr;        // TOKENS, documents: host [offsets[B]] in ids order, validated; NULL = every token is asked for
     static PackedCall pairs(const int32_t* first_lens) { PackedCall c; c.kind = PAIRS; c.first_lens = first_lens; return c; }
     static PackedCall scored(int head_pool) { PackedCall c; c.kind = SCORED; c.head_pool = head_pool; return c; }
-    static PackedCall tokens(int32_t expand_id, float* out) { PackedCall c; c.kind = TOKENS; c.expand_id = expand_id; c.tok_out = out; return c; }
+    static PackedCall tokens(int32_t expand_id, void* out) { PackedCall c; c.kind = TOKENS; c.expand_id = expand_id; c.tok_out = out; return c; }
+    // the documents of sc_encoder_embed_tokens_into: the kept tokens' vectors, numbered compactly text after text, at `out` in format `fmt`
+    static PackedCall kept_tokens(const uint8_t* keep, void* out, int fmt) { PackedCall c = tokens(-1, out); c.keep = keep; c.tok_fmt = fmt; return c; }
 };
 
 // The attention work items of packed sequences: per sequence one item for every 8 query blocks of 32 rows (class 0) or one item
@@ -82,7 +88,12 @@ sc_status sc_plan_check_pairs(const int64_t* offsets, const int32_t* first_lens,
 sc_status sc_plan_check_tokens(const int64_t* offsets, int32_t B, int32_t expand_id, bool query, const PlanBounds& mb, const char* who, int64_t* used,
                                int64_t* nrows);
 
+// The token vectors a document-side token call under keep flags stores for each text: counts[i] = the tokens of text i whose flag is not 0
+// (keep NULL: len_i); returns their sum.  sc_plan_fill numbers exactly these rows.
+int64_t sc_plan_kept_counts(const int64_t* offsets, int32_t B, const uint8_t* keep, int32_t* counts);
+
 // Fills `buf`, laid out by po = PlanOffsets(M, B, call.kind) with M = ceil256(rows), from host ids / validated offsets: ids (0 on alignment
 // rows and the tail, or expand_id on a query's alignment rows), pos (0 .. span - 1 per text, 0 on the tail), starts, lens, items and, by kind,
-// types / ones or dst (-1 for a row that is not asked for).  Returns the token rows in use.
+// types / ones or dst (-1 for a row that is not asked for: alignment rows, the tail, a document token whose keep flag is 0; the others count up
+// from 0, text after text).  Returns the token rows in use.
 int64_t sc_plan_fill(const int32_t* ids, const int64_t* offsets, int32_t B, const PackedCall& call, const PlanOffsets& po, int64_t M, char* buf, int nitems[3]);

@@ -301,6 +301,21 @@ void sc_lex_drop_locked(sc_index* ix);
 // survivors keep their tokens, the deleted rows' tokens become dead (and are compacted away once dead > live); the store is freed
 void sc_tok_delete_locked(sc_index* ix, const std::vector<int64_t>& del);
 void sc_tok_free_locked(sc_index* ix);
+// ... and the steps of a put (the comment at their definitions has the order): the checks that need no lock, then, under ix->mu with the
+// device set, rows / format against the store, room (*tail = where `total` tokens of the store's format go), abandon (the store as it was
+// before room; the stream is idle), commit (table repointed and uploaded, not synchronised), done (the automatic compaction)
+struct sc_tok_put {
+    std::vector<int64_t> sorted;  // the rows, ascending
+    bool fresh = false;           // room created the store
+    int W_before = 0, fmt_before = 0;
+};
+sc_status sc_tok_check_format(int32_t W, int32_t fmt, const char* who);
+sc_status sc_tok_check_counts(const int32_t* counts, int64_t n, const char* who, int64_t* total);
+sc_status sc_tok_put_check_locked(sc_index* ix, const int64_t* rows, int64_t n, int32_t W, int32_t fmt, const char* who, sc_tok_put* put);
+sc_status sc_tok_put_room_locked(sc_index* ix, int32_t W, int32_t fmt, int64_t total, const char* who, sc_tok_put* put, void** tail);
+void sc_tok_put_abandon_locked(sc_index* ix, const sc_tok_put& put);
+sc_status sc_tok_put_commit_locked(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const sc_tok_put& put);
+void sc_tok_put_done_locked(sc_index* ix);
 // sc_ivf_probe.cpp.  The nprobe nearest centroids of every query under the INDEX metric (the quantizer's own search; takes qz->mu):
 // distances and list ids at the head of ix->ivf_scratch, grown to hold `extra_bytes` more behind them; `host`: the ids there too
 // (synchronises).

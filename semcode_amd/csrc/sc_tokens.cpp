@@ -1,8 +1,10 @@
 // sc_tokens.cpp -- the multi-vector collection of the C ABI: the token store of an index (sc_index_put_tokens, _reserve_tokens,
-// _compact_tokens, _get_tokens, _token_stats, _drop_tokens) and the two calls that score from it (sc_index_rerank_late,
+// _put_tokens_dev, _compact_tokens, _get_tokens, _token_stats, _drop_tokens) and the two calls that score from it (sc_index_rerank_late,
 // sc_index_search_late; kernels: scan_late.hip, rules: maxsim_rule.h, late_rule.h).  The token vectors are the caller's data parked on
 // the device next to the rows, as the group labels and the term rows are, but keyed by local row number through a table, so that a
-// delete renumbers them instead of dropping them (sc_tok_delete_locked, called by sc_index_delete_rows).
+// delete renumbers them instead of dropping them (sc_tok_delete_locked, called by sc_index_delete_rows).  A put has three forms -- vectors
+// from the host, vectors on the device (sc_index_put_tokens_dev, late_install_kernel) and vectors the encoder's token head writes straight
+// into the pool (sc_encoder_embed_tokens_into) -- over one set of steps (sc_tok_put_*).
 //
 // Layout: pool = token vectors of W elements (f32 or bf16), appended to; table[row] = (start, len) in tokens, on the device with a
 // host mirror that is the truth.  A put appends the new vectors and repoints the rows; what a row pointed to before is dead until a
@@ -163,54 +165,73 @@ void sc_tok_delete_locked(sc_index* ix, const std::vector<int64_t>& del) {
 
 static sc_status no_store(const char* who) { return sc_fail(SC_ERR_INVALID, "%s: the index holds no token vectors (sc_index_put_tokens)", who); }
 
-extern "C" sc_status sc_index_put_tokens(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs, int32_t W, int32_t fmt) {
-    const char* who = "sc_index_put_tokens";
-    if (!ix || n < 0 || (n > 0 && (!rows || !counts))) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+// ---- a put, in the steps its three forms share (sc_index_put_tokens: vectors from the host; sc_index_put_tokens_dev: vectors on the device;
+// sc_encoder_embed_tokens_into, sc_encoder_heads.cpp: vectors the token head writes).  One copy of every rule:
+//   1. sc_tok_check_format / sc_tok_check_counts (no lock), sc_tok_put_check_locked: everything is validated before anything changes
+//   2. sc_tok_put_room_locked: the table follows the rows, the pool holds used + total tokens -- the only step that may fail once work has
+//      begun (SC_ERR_NOMEM), and it leaves the store as it was.  *tail = pool[used ...), where the caller's device work puts the vectors
+//   3. the caller's copies or kernels into the tail: nothing points at it yet, so a failure there (sc_tok_put_abandon_locked) changes nothing
+//   4. sc_tok_put_commit_locked: the rows' entries repointed, their runs uploaded, used advanced; the caller synchronises (the uploads read
+//      the host table) and ends with sc_tok_put_done_locked, the automatic compaction
+sc_status sc_tok_check_format(int32_t W, int32_t fmt, const char* who) {
     if (!maxsim_width_ok(W)) return sc_fail(SC_ERR_INVALID, "%s: W = %d must be a multiple of 16 within 16 .. %d", who, W, MAXSIM_MAX_W);
     if (fmt != 0 && fmt != 1) return sc_fail(SC_ERR_INVALID, "%s: fmt must be 0 (f32) or 1 (bf16), got %d", who, fmt);
-    int64_t total = 0;
+    return SC_OK;
+}
+
+sc_status sc_tok_check_counts(const int32_t* counts, int64_t n, const char* who, int64_t* total) {
+    *total = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (counts[i] < 0 || counts[i] > LATE_MAX_TOKENS) return sc_fail(SC_ERR_INVALID, "%s: counts[%lld] = %d outside 0 .. %d", who, (long long)i, counts[i], LATE_MAX_TOKENS);
-        total += counts[i];
+        *total += counts[i];
     }
-    if (total > 0 && !vecs) return sc_fail(SC_ERR_INVALID, "%s: vecs is NULL", who);
-    std::lock_guard<std::mutex> g(ix->mu);
+    return SC_OK;
+}
+
+sc_status sc_tok_put_check_locked(sc_index* ix, const int64_t* rows, int64_t n, int32_t W, int32_t fmt, const char* who, sc_tok_put* put) {
     for (int64_t i = 0; i < n; ++i)
         if (rows[i] < 0 || rows[i] >= ix->n) return sc_fail(SC_ERR_INVALID, "%s: rows[%lld] = %lld out of range [0,%lld)", who, (long long)i, (long long)rows[i], (long long)ix->n);
-    std::vector<int64_t> sorted(rows, rows + n);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return sc_fail(SC_ERR_INVALID, "%s: row numbers must be distinct", who);
+    put->sorted.assign(rows, rows + n);
+    std::sort(put->sorted.begin(), put->sorted.end());
+    if (std::adjacent_find(put->sorted.begin(), put->sorted.end()) != put->sorted.end()) return sc_fail(SC_ERR_INVALID, "%s: row numbers must be distinct", who);
     if (ix->tok && ix->tok->W != 0 && (ix->tok->W != W || ix->tok->fmt != fmt))
         return sc_fail(SC_ERR_INVALID, "%s: W=%d fmt=%d, the index holds tokens of W=%d fmt=%d (sc_index_drop_tokens first)", who, W, fmt, ix->tok->W, ix->tok->fmt);
-    if (n == 0) return SC_OK;
-    SC_HIP(hipSetDevice(ix->rt->device));
-    hipStream_t s = ix->rt->stream;
-    const bool fresh = !ix->tok;
-    if (fresh) ix->tok = new sc_token_store();
+    return SC_OK;
+}
+
+// (the caller has set the device)
+sc_status sc_tok_put_room_locked(sc_index* ix, int32_t W, int32_t fmt, int64_t total, const char* who, sc_tok_put* put, void** tail) {
+    put->fresh = !ix->tok;
+    if (put->fresh) ix->tok = new sc_token_store();
     sc_token_store* ts = ix->tok;
-    const int W_before = ts->W, fmt_before = ts->fmt;
+    put->W_before = ts->W;
+    put->fmt_before = ts->fmt;
     ts->W = W;
     ts->fmt = fmt;
-    // ---- room first: from here to the uploads nothing can fail but the allocations, which leave the store as it was
     sc_status st = tok_follow_rows(ix, who);
-    if (!st) st = tok_grow_pool(ix, std::max(ts->used + total, W_before == 0 ? ts->reserve : 0), true, who);
+    if (!st) st = tok_grow_pool(ix, std::max(ts->used + total, put->W_before == 0 ? ts->reserve : 0), true, who);
     if (st) {
-        if (fresh) sc_tok_free_locked(ix);
-        else { ts->W = W_before; ts->fmt = fmt_before; }
+        sc_tok_put_abandon_locked(ix, *put);
         return st;
     }
-    // ---- the vectors behind the pool's contents
-    std::vector<uint16_t> half;
-    if (total > 0) {
-        const void* src = vecs;
-        if (fmt == 1) {
-            half.resize((size_t)total * W);
-            for (size_t i = 0; i < half.size(); ++i) half[i] = late_round_bf16(vecs[i]);
-            src = half.data();
-        }
-        SC_HIP(hipMemcpyAsync(ts->pool.as<char>() + (size_t)ts->used * tok_bytes(ts), src, (size_t)total * tok_bytes(ts), hipMemcpyHostToDevice, s));
+    *tail = ts->pool.as<char>() + (size_t)ts->used * tok_bytes(ts);
+    return SC_OK;
+}
+
+// the store as it was before sc_tok_put_room_locked (the pool may have grown: its contents are the same).  The stream is idle.
+void sc_tok_put_abandon_locked(sc_index* ix, const sc_tok_put& put) {
+    if (put.fresh) {
+        sc_tok_free_locked(ix);
+        return;
     }
-    // ---- the table: the rows' entries repointed, what they pointed to is dead
+    ix->tok->W = put.W_before;
+    ix->tok->fmt = put.fmt_before;
+}
+
+// the table: the rows' entries repointed at the tail, what they pointed to is dead
+sc_status sc_tok_put_commit_locked(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const sc_tok_put& put) {
+    sc_token_store* ts = ix->tok;
+    hipStream_t s = ix->rt->stream;
     int64_t at = ts->used;
     for (int64_t i = 0; i < n; ++i) {
         sc_tok_entry& e = ts->tab[(size_t)rows[i]];
@@ -220,14 +241,101 @@ extern "C" sc_status sc_index_put_tokens(sc_index* ix, const int64_t* rows, int6
         at += counts[i];
     }
     ts->used = at;
+    const std::vector<int64_t>& sorted = put.sorted;
     for (size_t i = 0; i < sorted.size();) {  // one copy per run of consecutive rows
         size_t j = i + 1;
         while (j < sorted.size() && sorted[j] == sorted[j - 1] + 1) ++j;
         SC_HIP(hipMemcpyAsync(ts->table.as<sc_tok_entry>() + sorted[i], ts->tab.data() + sorted[i], (j - i) * sizeof(sc_tok_entry), hipMemcpyHostToDevice, s));
         i = j;
     }
+    return SC_OK;
+}
+
+void sc_tok_put_done_locked(sc_index* ix) { tok_auto_compact(ix); }
+
+extern "C" sc_status sc_index_put_tokens(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs, int32_t W, int32_t fmt) {
+    const char* who = "sc_index_put_tokens";
+    if (!ix || n < 0 || (n > 0 && (!rows || !counts))) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    sc_status st = sc_tok_check_format(W, fmt, who);
+    int64_t total = 0;
+    if (!st) st = sc_tok_check_counts(counts, n, who, &total);
+    if (st) return st;
+    if (total > 0 && !vecs) return sc_fail(SC_ERR_INVALID, "%s: vecs is NULL", who);
+    std::lock_guard<std::mutex> g(ix->mu);
+    sc_tok_put put;
+    st = sc_tok_put_check_locked(ix, rows, n, W, fmt, who, &put);
+    if (st) return st;
+    if (n == 0) return SC_OK;
+    SC_HIP(hipSetDevice(ix->rt->device));
+    hipStream_t s = ix->rt->stream;
+    // ---- room first: from here to the uploads nothing can fail but the allocations, which leave the store as it was
+    void* tail = nullptr;
+    st = sc_tok_put_room_locked(ix, W, fmt, total, who, &put, &tail);
+    if (st) return st;
+    // ---- the vectors behind the pool's contents
+    std::vector<uint16_t> half;
+    if (total > 0) {
+        const void* src = vecs;
+        if (fmt == 1) {
+            half.resize((size_t)total * W);
+            for (size_t i = 0; i < half.size(); ++i) half[i] = late_round_bf16(vecs[i]);
+            src = half.data();
+        }
+        SC_HIP(hipMemcpyAsync(tail, src, (size_t)total * tok_bytes(ix->tok), hipMemcpyHostToDevice, s));
+    }
+    st = sc_tok_put_commit_locked(ix, rows, n, counts, put);
+    if (st) return st;
     SC_HIP(hipStreamSynchronize(s));  // (the caller's arrays may go once this returns)
-    tok_auto_compact(ix);
+    sc_tok_put_done_locked(ix);
+    return SC_OK;
+}
+
+extern "C" sc_status sc_index_put_tokens_dev(sc_index* ix, const int64_t* rows, int64_t n, const int32_t* counts, const float* vecs_dev, const int32_t* src, int32_t W,
+                                             int32_t fmt) {
+    const char* who = "sc_index_put_tokens_dev";
+    if (!ix || n < 0 || (n > 0 && (!rows || !counts))) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
+    sc_status st = sc_tok_check_format(W, fmt, who);
+    int64_t total = 0;
+    if (!st) st = sc_tok_check_counts(counts, n, who, &total);
+    if (st) return st;
+    if (total > 0 && !vecs_dev) return sc_fail(SC_ERR_INVALID, "%s: vecs_dev is NULL", who);
+    if (src)
+        for (int64_t j = 0; j < total; ++j)
+            if (src[j] < 0) return sc_fail(SC_ERR_INVALID, "%s: src[%lld] = %d is not a token of vecs_dev", who, (long long)j, src[j]);
+    std::lock_guard<std::mutex> g(ix->mu);
+    sc_tok_put put;
+    st = sc_tok_put_check_locked(ix, rows, n, W, fmt, who, &put);
+    if (st) return st;
+    if (n == 0) return SC_OK;
+    SC_HIP(hipSetDevice(ix->rt->device));
+    hipStream_t s = ix->rt->stream;
+    void* tail = nullptr;
+    st = sc_tok_put_room_locked(ix, W, fmt, total, who, &put, &tail);
+    if (st) return st;
+    auto run = [&]() -> sc_status {  // the gather list behind the searches' scratch, the vectors into the tail, the table
+        if (total > 0) {
+            const int32_t* src_dev = nullptr;
+            if (src) {
+                const sc_status r = sc_grow(ix, ix->late_scratch, (size_t)total * 4);
+                if (r) return r;
+                SC_HIP(hipMemcpyAsync(ix->late_scratch.p, src, (size_t)total * 4, hipMemcpyHostToDevice, s));
+                src_dev = ix->late_scratch.as<int32_t>();
+            }
+            sc_with_prof(ix->rt, SC_PROF_SCAN, [&] { sc_launch_late_install(vecs_dev, src_dev, total, W, fmt, tail, ix->rt->cus, s); });
+            SC_HIP(hipGetLastError());
+        }
+        return SC_OK;
+    };
+    st = run();
+    if (st) {
+        hipStreamSynchronize(s);
+        sc_tok_put_abandon_locked(ix, put);
+        return st;
+    }
+    st = sc_tok_put_commit_locked(ix, rows, n, counts, put);
+    if (st) return st;
+    SC_HIP(hipStreamSynchronize(s));  // (the caller's arrays may go once this returns)
+    sc_tok_put_done_locked(ix);
     return SC_OK;
 }
 

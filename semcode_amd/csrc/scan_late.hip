@@ -32,7 +32,11 @@
 //                           Keys are distinct (the row is part of them) and sc_launch_topk_merge is exact, so the result does not
 //                           depend on the partition of rows over waves.  No atomic touches a score or a list.
 // late_gather_kernel        one wave per row: the row's len W elements from the old pool to its place in the new one, 16 bytes per lane.
-// Registers and scratch: profiles/late_store_kernels.log.
+// late_install_kernel<FMT>  the put whose vectors are on the device already (sc_index_put_tokens_dev): f32 token vectors, in order or through
+//                           a gather list, to the pool's tail -- copied at FMT 0, rounded by late_round_bf16 at FMT 1.  16-byte loads,
+//                           16- or 8-byte stores, a grid-stride loop over a grid capped by the CU count.  HBM-bound: 4 W bytes read and
+//                           4 W or 2 W written per token.  No atomics, no LDS.
+// Registers and scratch: profiles/late_store_kernels.log, profiles/late_ingest_kernels.log.
 #include "sc_common.h"  // (first: the HIP runtime header, whose bit casts maxsim_rule.h uses)
 #include "late_rule.h"
 
@@ -340,4 +344,33 @@ void sc_launch_late_gather(const sc_tok_entry* old_tab, const sc_tok_entry* new_
     const int64_t want = (n + 3) / 4, cap = (int64_t)cus * 8;
     hipLaunchKernelGGL(late_gather_kernel, dim3((unsigned)(want > cap ? cap : want)), dim3(256), 0, s, old_tab, new_tab, n, (const unsigned char*)old_pool,
                        (unsigned char*)new_pool, tok_bytes);
+}
+
+// token j of the put: the f32 vector vecs[src ? src[j] : j] -> dst + j W elements in the pool's format.  A lane moves one piece of four
+// consecutive floats: the pieces of the `total` tokens form one flat range, so a wave's 64 loads (and stores) are contiguous wherever
+// src is ascending, whatever W.  FMT 1 rounds each float once by late_round_bf16, the rule sc_index_put_tokens applies on the host.
+template <int FMT>
+__global__ __launch_bounds__(256) void late_install_kernel(const float* __restrict__ vecs, const int32_t* __restrict__ src, int64_t total, int W, void* __restrict__ dst) {
+    const int ppt = W >> 2;  // pieces per token
+    const int64_t pieces = total * ppt, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pieces; i += stride) {
+        const int64_t j = i / ppt;
+        const int p = (int)(i - j * ppt);
+        const int64_t from = src ? (int64_t)src[j] : j;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(vecs + from * W + 4 * p);
+        if constexpr (FMT == 0) {
+            reinterpret_cast<f32x4*>(dst)[i] = v;
+        } else {
+            const uint32_t h0 = late_round_bf16(v[0]), h1 = late_round_bf16(v[1]), h2 = late_round_bf16(v[2]), h3 = late_round_bf16(v[3]);
+            reinterpret_cast<uint2*>(dst)[i] = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
+        }
+    }
+}
+
+void sc_launch_late_install(const float* vecs, const int32_t* src, int64_t total, int W, int fmt, void* dst, int cus, hipStream_t s) {
+    if (total < 1 || !maxsim_width_ok(W) || (fmt != 0 && fmt != 1)) return;  // (the host checks these first)
+    const int64_t want = (total * (W >> 2) + 255) / 256, cap = (int64_t)cus * 8;
+    const dim3 grid((unsigned)(want > cap ? cap : want)), block(256);
+    if (fmt == 0) hipLaunchKernelGGL(late_install_kernel<0>, grid, block, 0, s, vecs, src, total, W, dst);
+    else hipLaunchKernelGGL(late_install_kernel<1>, grid, block, 0, s, vecs, src, total, W, dst);
 }

@@ -222,6 +222,29 @@ class MI355XLateReranker:
                 out += parts
         return out
 
+    def shares_runtime(self, index: Any) -> bool:
+        """True when the device encoder and `index` live on one runtime: store_document_tokens can write into that index."""
+        rt = getattr(self._encoder, "rt", None)
+        return rt is not None and rt is getattr(index, "rt", None) and hasattr(self._encoder, "embed_tokens_into")
+
+    def store_document_tokens(self, texts: Sequence[str], index: Any, rows: Any, fmt: str = "f32") -> np.ndarray:
+        """The texts' kept token vectors as the tokens of `rows` of the device index, handed over on the device (Encoder.embed_tokens_into):
+        what index.put_tokens(rows, embed_document_tokens(texts, kept_only=True), fmt) stores, bit for bit, without the vectors' trip
+        through the host.  Same ids, same keep flags, same batches under rows_budget.  -> the kept counts [n] int32."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if len(rows) != len(texts):
+            raise ValueError(f"{len(texts)} texts but {len(rows)} rows")
+        docs = [self.document_ids(t) for t in texts]
+        counts = np.zeros(len(docs), np.int32)
+        rows_of = lambda l: self._encoder.packed_rows(np.concatenate(([0], np.cumsum(l))))  # noqa: E731
+        window = max(1, 524288 // max(self.document_length, 32) // 2)
+        lens = np.asarray([len(r) for r in docs], np.int64)
+        for start in range(0, len(docs), window):
+            for a, b in cut_packed(lens[start:start + window], self.rows_budget, rows_of):
+                ids, off = _flatten(docs[start + a:start + b])
+                counts[start + a:start + b] = self._encoder.embed_tokens_into(ids, off, self.keep_flags(ids), index, rows[start + a:start + b], fmt)
+        return counts
+
     # ---- scores
     def score_pairs(self, questions: Sequence[str], passages: Sequence[str]) -> np.ndarray:
         """(question i, passage i) -> MaxSim scores [n] f32 (higher = more relevant).  Every distinct question and passage is encoded once

@@ -10,7 +10,8 @@ Backend-specific keys ride on the reference's extra="allow" (settings.py:36):
     mi355x_weights_path, mi355x_vocab_path, mi355x_allow_synthetic, mi355x_max_tokens, mi355x_store_path, mi355x_ingest_batch,
     mi355x_document_prefix, mi355x_query_prefix, mi355x_packed, mi355x_pooling, mi355x_lexical,
     mi355x_reranker_path, mi355x_reranker_vocab, mi355x_rerank_fetch_k, mi355x_tokenizer_json,
-    mi355x_reranker_instruction, mi355x_reranker_true_token, mi355x_reranker_false_token, mi355x_reranker_kind, mi355x_late_store
+    mi355x_reranker_instruction, mi355x_reranker_true_token, mi355x_reranker_false_token, mi355x_reranker_kind, mi355x_late_store,
+    mi355x_late_handover
 """
 from __future__ import annotations
 
@@ -63,6 +64,7 @@ _DEFAULTS: dict[str, Any] = {
     "mi355x_reranker_false_token": "no",   # ... and the one that says "not": score = logit_true - logit_false
     "mi355x_rerank_fetch_k": 40,      # hits the store is asked for when Retriever.retrieve(rerank=True) re-orders them
     "mi355x_late_store": "off",       # "off" | "f32" | "bf16": keep every chunk's token vectors of the late-interaction reranker next to its row (MilvusVectorStore(late=..., late_format=...))
+    "mi355x_late_handover": True,     # with a late store: the reranker's token head writes a chunk's vectors straight into the index's token pool; off = download, drop punctuation on the host, upload (the same stored bits)
 }
 
 

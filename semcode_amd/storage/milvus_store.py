@@ -20,7 +20,8 @@ progress protocol and error behaviour, so IndexerService (src/semcode/services/i
                                                 -> Collection.delete(expr): rows removed, survivors renumbered densely
     MilvusVectorStore(late=reranker, late_format="f32" | "bf16")
                                                 -> a multi-vector collection: every chunk's late-interaction token vectors are kept on the
-                                                   device next to its row at upsert; .rerank_late(question_vectors, rows) scores candidates
+                                                   device next to its row at upsert (written there by the reranker's own token head when
+                                                   both share a runtime; late_handover=False: through the host); .rerank_late(question_vectors, rows) scores candidates
                                                    from them without a passage forward, .search_late(question_vectors, top_k) is the exact
                                                    MaxSim search over them
 
@@ -109,7 +110,8 @@ class MilvusVectorStore:
     def __init__(self, collection_name: str = "semcode_chunks", dim: Optional[int] = None, *, metric: Optional[str] = None,
                  index_type: Optional[str] = None, nlist: Optional[int] = None, nprobe: Optional[int] = None,
                  device: Optional[int] = None, runtime: Any = None, index_factory: Optional[Callable[..., Any]] = None,
-                 lexical: Optional[bool] = None, lex_slots: int = 128, late: Any = None, late_format: Optional[str] = None) -> None:
+                 lexical: Optional[bool] = None, lex_slots: int = 128, late: Any = None, late_format: Optional[str] = None,
+                 late_handover: Optional[bool] = None) -> None:
         settings = _resolve_settings()
         self.collection_name = collection_name
         self.dim = dim or settings.embedding_dimension
@@ -170,6 +172,9 @@ class MilvusVectorStore:
             raise ValueError(f"late_format / mi355x_late_store must be off, f32 or bf16, got {fmt!r}")
         self.late = late
         self.late_format: Optional[str] = None if fmt == "off" else fmt
+        # the hand-over at ingest (late_handover=, or SEMCODE_MI355X_LATE_HANDOVER): the late reranker's token head writes a chunk's vectors
+        # straight into the index's token pool (store_document_tokens) instead of handing them over through the host; the stored bits are the same
+        self.late_handover = bool(getattr(settings, "mi355x_late_handover", True) if late_handover is None else late_handover)
 
     # ------------------------------------------------------------------ lifecycle
     def connect(self) -> None:
@@ -318,10 +323,24 @@ class MilvusVectorStore:
         if token_vectors is None:
             if self.late is None:
                 raise ValueError("a store with a late format needs token vectors: construct it with late=<MI355XLateReranker> or pass token_vectors=")
+            if self._hands_over(ix):
+                if len(texts) != len(rows):
+                    raise ValueError(f"{len(rows)} rows but {len(texts)} texts")
+                self.late.store_document_tokens(list(texts), ix, np.asarray(rows, dtype=np.int64), self.late_format)
+                return
             token_vectors = self.late.embed_document_tokens(list(texts), kept_only=True)
         if len(token_vectors) != len(rows):
             raise ValueError(f"{len(rows)} rows but {len(token_vectors)} token arrays")
         ix.put_tokens(np.asarray(rows, dtype=np.int64), list(token_vectors), fmt=self.late_format)
+
+    def _hands_over(self, ix: Any) -> bool:
+        """The late reranker can write its token vectors into this index on the device: the setting is on, the reranker has
+        store_document_tokens, and its encoder lives on the index's runtime.  Anything else takes the path through the host."""
+        late = self.late
+        if not self.late_handover or not hasattr(late, "store_document_tokens"):
+            return False
+        shares = getattr(late, "shares_runtime", None)
+        return bool(shares is not None and shares(ix))
 
     def has_late_tokens(self, rows: Any) -> bool:
         """True when the store keeps token vectors and every one of these rows (-1 entries aside) has some."""
