@@ -503,29 +503,51 @@ sc_status sc_diag_set_option(const char* name, int32_t value);
 /* "rope_fused" of sc_diag_set_option: how the batch pipeline of a rotary encoder rotates Q and K (-1 = default, 0 = the stand-alone
  * kernel after the QKV projection, 1 = inside that projection's epilogue); the two agree to bf16 rounding, not bit for bit.
  * sc_diag_rope: the stand-alone rotation kernel on qk [rows, heads*64] f32, in place (rounded to bf16 on device first; row r is
- * position r % S, S a power of two; theta <= 0 = 10000).  sc_diag_swiglu: h [rows, 2F] f32 (gate | up) -> out [rows, F] =
- * silu(gate) * up through the SwiGLU kernel (F a multiple of 8). */
+ * position r % S, S a power of two; theta <= 0 = 10000). */
 sc_status sc_diag_rope(sc_runtime* rt, float* qk, int32_t rows, int32_t S, int32_t heads, float theta);
-/* The T5 encoder's kernels on their own (arch 3).
- * sc_diag_rel_buckets: the bucket rule of sc_encoder_cfg's comment, the function that builds the device table: out[d + span - 1] =
+/* sc_diag_rel_buckets: T5's bucket rule of sc_encoder_cfg's comment, the function that builds the device table: out[d + span - 1] =
  *   bucket(d) for d = key - query in -(span - 1) .. span - 1.  Host arithmetic only: no runtime, no device.
- * sc_diag_attention_bias / sc_diag_attention_bias_packed: sc_diag_attention_ex / sc_diag_attention_packed with heads of 64 and the scores
- *   q.k + rel_bias[bucket(key - query)][head] (NO 1/8), rel_bias [buckets][heads] f32; positions count from the start of each sequence.
- * sc_diag_ffn_act: kind 3 = the ReLU pass on h [rows, F] (rounded to bf16) -> out [rows, F]; kind 4 = the tanh-GELU gate on h [rows, 2F]
- *   (gate | up) -> out [rows, F] = gelu_new(gate) * up.  F a multiple of 8. */
+ * sc_diag_ffn_act: the kernel between the two FFN GEMMs, kind = the model's ffn_type.  1 GEGLU, 2 SwiGLU, 4 the tanh-GELU gate: h [rows, 2F]
+ *   (gate | up) -> out [rows, F] = gelu / silu / gelu_new (gate) * up.  3 = the ReLU pass on h [rows, F] (rounded to bf16) -> out [rows, F].
+ *   F a multiple of 8. */
 sc_status sc_diag_rel_buckets(int32_t rel_buckets, int32_t max_distance, int32_t span, int32_t* out);
-sc_status sc_diag_attention_bias(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                 const float* rel_bias, int32_t buckets, int32_t max_distance, float* out);
-sc_status sc_diag_attention_bias_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                        int32_t blocked_rows, const float* rel_bias, int32_t buckets, int32_t max_distance, float* out);
 sc_status sc_diag_ffn_act(sc_runtime* rt, int32_t kind, const float* h, int32_t rows, int32_t F, float* out);
 /* sc_diag_output_proj: output_proj_kernel on its own.  x [B,H] f32 (taken as it is: pooled rows are f32), W [E,H], bias [E] or NULL ->
  * out [B,E] = W x + bias, L2-normalised by x / max(|x|, 1e-12) when normalize.  H, E multiples of 16 within 16 .. 2048. */
 sc_status sc_diag_output_proj(sc_runtime* rt, const float* x, int32_t B, int32_t H, const float* W, const float* bias, int32_t E, int32_t normalize,
                               float* out);
-sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out);
-/* qkv [B*S, 3*heads*64] rows = [Q | K | V]; lens [B]; out [B*S, heads*64] = softmax(QK^T/8 + mask) V. */
-sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out);
+/* sc_diag_attention_run: ONE launch of a product attention launcher, whichever the descriptor names.  The descriptor is validated and its
+ * geometry derived by host arithmetic before rt is looked at.  d = head_dim, H = heads * d, kvh = kv_heads under the causal mask (query
+ * head h reads K / V head h / (heads / kv_heads)), else heads; kv_heads is then 0 or heads.  qkv rows are [Q (heads) | K (kvh) | V (kvh)] x d.
+ * mask: FULL    out = softmax over the keys j < len of QK^T / sqrt(d), times V.  d 64, or 32 (an even number of heads: a 64-column block holds
+ *                 heads 2j and 2j+1).  slopes [heads]: the ALiBi bias of the product (d 64).  rel_bias [rel_buckets][heads] f32: T5, the scores
+ *                 are q.k + rel_bias[bucket(key - query)][head] with NO 1 / sqrt(d), positions from the start of each sequence (d 64).
+ *       WINDOW  the keys j < len with |i - j| <= local_window / 2 (even, 2 .. 128); a row that sees no key is zero.  d 64.
+ *       CAUSAL  the keys j <= i, j < len.  d 64 or 128, 1 <= kv_heads <= heads <= 2048 / d, heads % kv_heads == 0.
+ *       CLS     FULL for the first row of each text only, slopes with either d: out [B, H].  A row-major rectangle with S 1 .. 2048 (the
+ *                 harness lays it out in 64-column blocks of ceil256(B*S) rows, as the QKV projection writes it).
+ * Rows, starts == NULL: a rectangle of B texts of S rows (S one of 32, 64, 128, 256, 512, 1024, 2048), lens [B] clamped to 1 .. S, R = B*S
+ *   rows in and out.  Every row is finite (rows at or beyond len are queries too).
+ * Rows, starts != NULL: packed, S is not read; sequence b owns the rows starts[b] .. starts[b] + ceil32(lens[b]) (starts multiples of 32, lens
+ *   1 .. 2048), R = the end of the last sequence rounded up to 256 rows in and out.  Every row of a sequence is finite, rows outside every
+ *   sequence stay NaN.
+ * blocked_rows == 0: qkv is [R][columns] row-major.  > 0: qkv is in 64-column blocks [columns / 64][blocked_rows][64], the layout the QKV
+ *   projections write; a rectangle needs blocked_rows >= B*S (that GEMM's M) and still returns B*S rows, packed rows have R = blocked_rows >=
+ *   the last sequence's end.  out [rows, H] is row-major; both forms give the same bits.
+ * B 1 .. 65536, H <= 2048.  A head_dim, kv_heads or local_window no kernel has, and a combination no launcher serves (slopes with WINDOW,
+ * CAUSAL, rel_bias or -- outside CLS -- d 32; rel_bias or WINDOW with d != 64; rel_bias with another mask than FULL; CLS with starts or
+ * blocked_rows) are SC_ERR_UNSUPPORTED with a message naming the fields; anything else out of range is SC_ERR_INVALID. */
+enum { SC_DIAG_ATTN_FULL = 0, SC_DIAG_ATTN_WINDOW = 1, SC_DIAG_ATTN_CAUSAL = 2, SC_DIAG_ATTN_CLS = 3 };
+typedef struct sc_diag_attn {
+    int32_t mask; /* SC_DIAG_ATTN_* */
+    int32_t B, S, heads, kv_heads, head_dim, blocked_rows, local_window;
+    const int32_t* starts;  /* NULL = the rectangle form, else [B] */
+    const int32_t* lens;    /* [B] */
+    const float* slopes;    /* NULL or [heads] */
+    const float* rel_bias;  /* NULL = no T5 bias, else [rel_buckets][heads] */
+    int32_t rel_buckets, rel_max_distance;
+} sc_diag_attn;
+sc_status sc_diag_attention_run(sc_runtime* rt, const sc_diag_attn* a, const float* qkv, float* out);
 
 /* Single-kernel diagnostics of the LayerNorm-folded batch pipeline and of the stand-alone encoder kernels (tests/test_fold_kernels_gpu.py).
  * Same pattern as above: host f32 in, activations rounded to bf16 on the device, ONE launch through the product's own launcher, the
@@ -545,9 +567,7 @@ sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* len
  * sc_diag_gemm_resln: EPI_RESLN_STATS: C [M,N] = A W^T + bias + (R - mu) rs gam with (mu, rs) = fin [M][2] of the raw residual R [M,N]
  *   (bias already holds + beta); stats_out [N/256][M][2] = (sum, sum of squares) of the bf16 C per 256-column tile.  flags bit 0: A is
  *   given in 64-column blocks [K/64][M][64].
- * sc_diag_attention_ex: sc_diag_attention with the product's layout and bias: blocked_rows > 0 = qkv is [3 heads][blocked_rows][64]
- *   (blocked_rows >= B*S: the rows of the projection that wrote it), 0 = row-major; slopes = NULL or [heads] ALiBi slopes.
- * sc_diag_layernorm: x [tokens,H] -> LayerNorm rows (H a multiple of 8, <= 2048).  sc_diag_geglu: h [rows,2F] (gate | up) -> gelu(gate) up.
+ * sc_diag_layernorm: x [tokens,H] -> LayerNorm rows (H a multiple of 8, <= 2048).
  * sc_diag_mean_pool: x [B*S,H] -> out [B,H] f32, masked mean over the first lens[b] rows (lens clamped to 1..S); normalize 0 = the
  *   sliced kernel, 1 = the one-workgroup kernel with L2 normalisation.  sc_diag_mean_pool_ln: the same of LayerNorm(y) from raw rows
  *   y [tokens_pad,H] and their partial statistics stats [slots][tokens_pad][2].
@@ -565,49 +585,8 @@ sc_status sc_diag_gemm_lna(sc_runtime* rt, int32_t epi, int32_t flags, const flo
 int32_t sc_diag_gemm_strip(int32_t M, int32_t N, int32_t K, int32_t cus);
 sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const float* A, const float* W, const float* bias, const float* gam, const float* R,
                              const float* fin, float eps, int32_t M, int32_t N, int32_t K, float* C, float* stats_out);
-sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                               const float* slopes, float* out);
-/* sc_diag_attention_packed: the packed attention kernel on its own, conventions of sc_diag_attention_ex.  Sequence b owns the rows
- * starts[b] .. starts[b] + ceil32(lens[b]) (starts multiples of 32, lens 1 .. 2048); R = blocked_rows
- * if > 0 (qkv is [3 heads][R][64]), else the end of the last sequence rounded up to 256 (qkv is [R][3*heads*64] row-major).
- * out [R, heads*64]: rows of a sequence at or beyond its length are finite, rows outside every sequence stay NaN. */
-sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                   int32_t blocked_rows, const float* slopes, float* out);
-/* sc_diag_attention_hd / sc_diag_attention_packed_hd: sc_diag_attention_ex / sc_diag_attention_packed for a head dimension of 64 or 32:
- * qkv is [rows][3*heads*head_dim] row-major, or -- blocked -- [3*heads*head_dim/64][blocked_rows][64]; out [rows, heads*head_dim].
- * head_dim 32 needs an even number of heads (a 64-column block holds heads 2j and 2j+1) and slopes == NULL. */
-sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                               int32_t blocked_rows, const float* slopes, float* out);
-sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                      int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out);
 /* "cls_prune" of sc_diag_set_option: the last layer of a [CLS]-pooled forward (-1 = default: pruned, 0 = the full last layer over every
- * token row, 1 = on the [CLS] rows only).
- * sc_diag_attention_cls: attention_cls_kernel on its own, rectangle form.  qkv [B*S][3*heads*head_dim] row-major f32 (the harness lays it
- * out in 64-column blocks, as the QKV projection does), lens [B] clamped to 1 .. S, S <= 2048, head_dim 64 or 32 (an even number of
- * heads), alibi NULL or [heads] slopes (both head widths) -> out [B, heads*head_dim] = softmax(q_0 K^T / sqrt(head_dim) - slope_h j) V of
- * each text's first row. */
-sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                                const float* alibi, float* out);
-/* sc_diag_attention_window: the windowed attention kernels (encoder_window.hip) on their own, head dimension 64, conventions of
- * sc_diag_attention_ex / sc_diag_attention_packed: out = softmax over the keys j < len with |i - j| <= local_window / 2 of QK^T/8, times V.
- * starts == NULL: a rectangle, qkv [B*S][3*heads*64] (or blocked), lens clamped to 1 .. S, out [B*S, heads*64]; a row that sees no key
- * (beyond len + local_window / 2) is zero.  starts != NULL: packed rows, S is not read, R and out as sc_diag_attention_packed (rows
- * outside every sequence stay NaN).  local_window even, 2 .. 128, else SC_ERR_UNSUPPORTED. */
-sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                   int32_t local_window, int32_t blocked_rows, float* out);
-/* sc_diag_attention_causal: the causal grouped-query attention kernels (encoder_causal.hip) on their own, head dimension 64, conventions of
- * sc_diag_attention_window: out = softmax over the keys j <= i, j < len of QK^T/8, times V; query head h reads K/V head h / (heads / kv_heads).
- * qkv is [rows][(heads + 2 kv_heads) * 64] as [Q | K | V], or (blocked_rows > 0) in 64-column blocks [(heads + 2 kv_heads)][blocked_rows][64].
- * starts == NULL: a rectangle [B*S rows], lens clamped to 1 .. S, out [B*S, heads*64], every row finite (rows at or beyond len are queries
- * too).  starts != NULL: packed rows, S is not read, R and out as sc_diag_attention_packed: rows outside every sequence stay NaN, every
- * row of a sequence is finite.  1 <= kv_heads <= heads <= 32 with heads % kv_heads == 0, else SC_ERR_UNSUPPORTED. */
-sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                   int32_t kv_heads, int32_t blocked_rows, float* out);
-/* sc_diag_attention_causal_hd: the same with the head dimension stated: 64 (the kernels above) or 128 (attention_causal_kernel<2, ..> and its
- * packed form: scores QK^T/sqrt(128), a head two consecutive 64-column blocks).  Columns are x head_dim instead of x 64 throughout; heads *
- * head_dim <= 2048, else SC_ERR_UNSUPPORTED. */
-sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                      int32_t kv_heads, int32_t head_dim, int32_t blocked_rows, float* out);
+ * token row, 1 = on the [CLS] rows only). */
 /* sc_diag_qknorm_rope: qknorm_rope_kernel (pos NULL: position = row % S, S a power of two <= 65536) or its packed form (pos [rows], clamped to
  * max_pos - 1; S then is the table's length, max_pos) on their own.  x [rows, (heads + 2 kv_heads) * head_dim] f32 as [Q | K | V] is rounded to
  * bf16, laid out in 64-column blocks, processed in place and returned widened in the same row-major form: the first heads + kv_heads heads
@@ -621,7 +600,6 @@ sc_status sc_diag_rmsnorm(sc_runtime* rt, const float* x, int32_t tokens, int32_
 sc_status sc_diag_mean_pool(sc_runtime* rt, const float* x, const int32_t* lens, int32_t B, int32_t S, int32_t H, int32_t normalize, float* out);
 sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const float* stats, int32_t slots, int32_t tokens_pad, const float* gamma,
                                const float* beta, float eps, const int32_t* lens, int32_t B, int32_t S, int32_t H, float* out);
-sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out);
 sc_status sc_diag_embed(sc_runtime* rt, int32_t ln, const int32_t* ids, int32_t tokens, int32_t S, int32_t H, int32_t vocab, int32_t max_pos,
                         const float* wemb, const float* pemb, const float* temb, const float* gamma, const float* beta, float eps,
                         int32_t tokens_pad, int32_t slots, float* rows, float* stats);

@@ -135,36 +135,22 @@ SIGNATURES = {
     "sc_diag_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "sc_diag_gemm_i8": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_encoder_read": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t]),
-    "sc_diag_attention": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_attention_run": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),  # (rt, DiagAttn*, qkv, out)
     "sc_diag_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
-    "sc_diag_swiglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_rel_buckets": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "sc_diag_attention_bias": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
-    "sc_diag_attention_bias_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                                  C.c_void_p]),
     "sc_diag_ffn_act": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_fold_ln": (C.c_int32, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "sc_diag_gemm_strip": (C.c_int32, [C.c_int32] * 4),
     "sc_diag_gemm_lna": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_gemm_resln": (C.c_int32, [C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "sc_diag_attention_ex": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "sc_diag_attention_packed": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "sc_diag_attention_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "sc_diag_attention_cls": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "sc_diag_attention_window": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "sc_diag_attention_packed_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_diag_layernorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
-    "sc_diag_attention_causal": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "sc_diag_attention_causal_hd": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                                 C.c_void_p]),
     "sc_diag_qknorm_rope": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_float]),
     "sc_diag_rmsnorm": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p]),
     "sc_diag_mean_pool": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_mean_pool_ln": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "sc_diag_geglu": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "sc_diag_embed": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 +
                                  [C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sc_index_create": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]),
@@ -1476,17 +1462,6 @@ def diag_gemm_i8(rt: Runtime, A, W) -> np.ndarray:
     return out
 
 
-def diag_attention(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, blocked_rows: int = 0) -> np.ndarray:
-    if head_dim != 64 or blocked_rows:
-        return diag_attention_ex(rt, qkv, lens, B, S, heads, blocked_rows=blocked_rows, head_dim=head_dim)
-    qkv = np.ascontiguousarray(qkv, np.float32)
-    lens = np.ascontiguousarray(lens, np.int32)
-    out = np.empty((B * S, heads * 64), np.float32)
-    _check(lib().sc_diag_attention(rt.handle, qkv.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S, heads,
-                                   out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
 def diag_rope(rt: Runtime, qk, S: int, heads: int, theta: float) -> np.ndarray:
     """The stand-alone rotary kernel on qk [rows, heads * 64] (row r = position r % S): the rotated values, bf16-rounded."""
     out = np.array(qk, dtype=np.float32, order="C")
@@ -1504,50 +1479,6 @@ def diag_rel_buckets(rel_buckets: int, max_distance: int, span: int) -> np.ndarr
     return out
 
 
-def diag_ffn_act(rt: Runtime, kind: int, h) -> np.ndarray:
-    """kind 3: the ReLU pass on h [rows, F]; kind 4: the tanh-GELU gate on h [rows, 2F] (gate | up).  bf16-rounded, [rows, F]."""
-    h = np.ascontiguousarray(h, np.float32)
-    rows, F = h.shape[0], h.shape[1] // (2 if kind == 4 else 1)
-    out = np.empty((rows, F), np.float32)
-    _check(lib().sc_diag_ffn_act(rt.handle, int(kind), h.ctypes.data_as(C.c_void_p), rows, F, out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
-def diag_attention_bias(rt: Runtime, qkv, lens, B: int, S: int, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
-    """sc_launch_attention_rel as the T5 forward calls it: diag_attention_ex with rel_bias [buckets, heads] in place of slopes."""
-    qkv = np.ascontiguousarray(qkv, np.float32)
-    lens = np.ascontiguousarray(lens, np.int32)
-    rb = np.ascontiguousarray(rel_bias, np.float32)
-    H = heads * 64
-    if blocked_rows:
-        pad = np.zeros((blocked_rows, 3 * H), np.float32)
-        pad[: B * S] = qkv
-        qkv = block64(pad)
-    out = np.empty((B * S, H), np.float32)
-    _check(lib().sc_diag_attention_bias(rt.handle, qkv.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), B, S, heads, int(blocked_rows),
-                                        rb.ctypes.data_as(C.c_void_p), rb.shape[0], int(max_distance), out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
-def diag_attention_bias_packed(rt: Runtime, qkv, starts, lens, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
-    """The packed form: diag_attention_packed with rel_bias [buckets, heads] in place of slopes."""
-    qkv = np.ascontiguousarray(qkv, np.float32)
-    starts = np.ascontiguousarray(starts, np.int32)
-    lens = np.ascontiguousarray(lens, np.int32)
-    rb = np.ascontiguousarray(rel_bias, np.float32)
-    H = heads * 64
-    R = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
-    if qkv.shape != (R, 3 * H) or starts.shape != lens.shape:
-        raise ValueError(f"diag_attention_bias_packed: qkv must be [{R}, {3 * H}], starts and lens [B]")
-    if blocked_rows:
-        qkv = block64(qkv)
-    out = np.empty((R, H), np.float32)
-    _check(lib().sc_diag_attention_bias_packed(rt.handle, qkv.ctypes.data_as(C.c_void_p), starts.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
-                                               len(lens), heads, int(blocked_rows), rb.ctypes.data_as(C.c_void_p), rb.shape[0], int(max_distance),
-                                               out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
 def diag_output_proj(rt: Runtime, x, W, b=None, normalize: bool = True) -> np.ndarray:
     """output_proj_kernel on its own: x [B, H] f32, W [E, H], b [E] or None -> [B, E] = W x + b, L2-normalised if asked."""
     x, W = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(W, np.float32)
@@ -1555,15 +1486,6 @@ def diag_output_proj(rt: Runtime, x, W, b=None, normalize: bool = True) -> np.nd
     out = np.empty((x.shape[0], W.shape[0]), np.float32)
     _check(lib().sc_diag_output_proj(rt.handle, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], W.ctypes.data_as(C.c_void_p),
                                      None if b is None else b.ctypes.data_as(C.c_void_p), W.shape[0], 1 if normalize else 0, out.ctypes.data_as(C.c_void_p)))
-    return out
-
-
-def diag_swiglu(rt: Runtime, h) -> np.ndarray:
-    """The SwiGLU kernel on h [rows, 2F] (gate | up): silu(gate) * up, bf16-rounded, [rows, F]."""
-    h = np.ascontiguousarray(h, np.float32)
-    rows, F = h.shape[0], h.shape[1] // 2
-    out = np.empty((rows, F), np.float32)
-    _check(lib().sc_diag_swiglu(rt.handle, h.ctypes.data_as(C.c_void_p), rows, F, out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -1588,6 +1510,111 @@ def block64(a: np.ndarray) -> np.ndarray:
 def unblock64(a: np.ndarray, M: int, N: int) -> np.ndarray:
     """Inverse of block64."""
     return np.ascontiguousarray(np.asarray(a).reshape(N // 64, M, 64).transpose(1, 0, 2).reshape(M, N))
+
+
+ATTN_FULL, ATTN_WINDOW, ATTN_CAUSAL, ATTN_CLS = range(4)
+
+
+class DiagAttn(C.Structure):
+    """sc_diag_attn of include/semcode_hip.h."""
+    _fields_ = [(n, C.c_int32) for n in ("mask", "B", "S", "heads", "kv_heads", "head_dim", "blocked_rows", "local_window")] + \
+               [(n, C.c_void_p) for n in ("starts", "lens", "slopes", "rel_bias")] + [("rel_buckets", C.c_int32), ("rel_max_distance", C.c_int32)]
+
+
+def _diag_attention_rows(starts, lens, S: int = 0, blocked_rows: int = 0) -> int:
+    """Rows of qkv one attention launch reads: blocked_rows if given, else B * S (starts None) or the last sequence's end rounded up to 256."""
+    if blocked_rows:
+        return int(blocked_rows)
+    return len(lens) * int(S) if starts is None else (int((np.asarray(starts) + (np.asarray(lens) + 31) // 32 * 32).max()) + 255) // 256 * 256
+
+
+def _diag_attention(rt, mask: int, qkv, lens, heads: int, B=None, S: int = 0, starts=None, kv_heads: int = 0, head_dim: int = 64, blocked_rows: int = 0,
+                    local_window: int = 0, slopes=None, rel_bias=None, max_distance: int = 0) -> np.ndarray:
+    """One sc_diag_attention_run call.  qkv [R, (heads + 2 kv_heads) * head_dim] row-major as [Q | K | V] (kv_heads = heads but under the causal
+    mask), R = _diag_attention_rows; a rectangle may come as its B * S rows alone and is padded with zero rows.  blocked_rows > 0 hands it over
+    in 64-column blocks.  -> [B, H] (CLS), [B * S, H] (rectangle) or [R, H] (packed), H = heads * head_dim."""
+    qkv, lens = _f32(qkv), np.ascontiguousarray(lens, np.int32)
+    starts = None if starts is None else np.ascontiguousarray(starts, np.int32)
+    sl, rb = (None if a is None else _f32(a) for a in (slopes, rel_bias))
+    B, S, heads, head_dim = len(lens) if B is None else int(B), int(S), int(heads), int(head_dim)
+    H, cols = heads * head_dim, (heads + 2 * (int(kv_heads) if mask == ATTN_CAUSAL else heads)) * head_dim
+    R = _diag_attention_rows(starts, lens[:B], S, blocked_rows)
+    if starts is None and qkv.shape == (B * S, cols) and R > B * S:
+        qkv = np.concatenate([qkv, np.zeros((R - B * S, cols), np.float32)])
+    if qkv.shape != (R, cols) or lens.ndim != 1 or len(lens) < B or (starts is not None and starts.shape != lens.shape):
+        raise ValueError(f"diag_attention: qkv must be [{R}, {cols}], lens (and starts, if given) [B]")
+    if blocked_rows:
+        qkv = block64(qkv)
+    out = np.empty((B if mask == ATTN_CLS else B * S if starts is None else R, H), np.float32)
+    addr = lambda a: None if a is None else a.ctypes.data
+    desc = DiagAttn(mask, B, S, heads, int(kv_heads), head_dim, int(blocked_rows), int(local_window), addr(starts), addr(lens), addr(sl), addr(rb),
+                    0 if rb is None else rb.shape[0], int(max_distance))
+    _check(lib().sc_diag_attention_run(None if rt is None else rt.handle, C.addressof(desc), _ptr(qkv), _ptr(out)))
+    return out
+
+
+def diag_attention(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, blocked_rows: int = 0) -> np.ndarray:
+    return _diag_attention(rt, ATTN_FULL, qkv, lens, heads, B=B, S=S, head_dim=head_dim, blocked_rows=blocked_rows)
+
+
+def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
+    """sc_launch_attention as the pipelines call it: blocked_rows > 0 lays qkv [B*S, 3H] out as [3H/64][blocked_rows][64] (rows beyond
+    B*S zero); slopes [heads] = ALiBi; head_dim 64 or 32 (H = heads * head_dim)."""
+    return _diag_attention(rt, ATTN_FULL, qkv, lens, heads, B=B, S=S, head_dim=head_dim, blocked_rows=blocked_rows, slopes=slopes)
+
+
+def diag_attention_bias(rt: Runtime, qkv, lens, B: int, S: int, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
+    """sc_launch_attention_rel as the T5 forward calls it: diag_attention_ex with rel_bias [buckets, heads] in place of slopes."""
+    return _diag_attention(rt, ATTN_FULL, qkv, lens, heads, B=B, S=S, blocked_rows=blocked_rows, rel_bias=rel_bias, max_distance=max_distance)
+
+
+def diag_attention_cls(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, slopes=None) -> np.ndarray:
+    """attention_cls_kernel on its own: qkv [B*S, 3H] row-major, one query row per text (its first) -> [B, H], H = heads * head_dim."""
+    return _diag_attention(rt, ATTN_CLS, qkv, lens, heads, B=B, S=S, head_dim=head_dim, slopes=slopes)
+
+
+def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
+    """The packed attention kernel on its own: qkv [R, 3H] row-major, sequence b on the rows starts[b] .. starts[b] + ceil32(lens[b]);
+    R = blocked_rows (> 0: handed over as [3H/64][R][64]) or the last sequence's end rounded up to 256.  -> [R, H], H = heads * head_dim."""
+    return _diag_attention(rt, ATTN_FULL, qkv, lens, heads, starts=starts, head_dim=head_dim, blocked_rows=blocked_rows, slopes=slopes)
+
+
+def diag_attention_bias_packed(rt: Runtime, qkv, starts, lens, heads: int, rel_bias, max_distance: int, blocked_rows: int = 0) -> np.ndarray:
+    """The packed form: diag_attention_packed with rel_bias [buckets, heads] in place of slopes."""
+    return _diag_attention(rt, ATTN_FULL, qkv, lens, heads, starts=starts, blocked_rows=blocked_rows, rel_bias=rel_bias, max_distance=max_distance)
+
+
+def diag_attention_window(rt: Runtime, qkv, lens, heads: int, local_window: int, S: int = 0, starts=None, blocked_rows: int = 0) -> np.ndarray:
+    """The windowed attention kernels on their own (head dimension 64): a query sees the real keys with |i - j| <= local_window / 2.
+    starts None: a rectangle, qkv [B*S, 3H] -> [B*S, H].  Else packed rows as diag_attention_packed: qkv [R, 3H] -> [R, H]."""
+    return _diag_attention(rt, ATTN_WINDOW, qkv, lens, heads, S=S, starts=starts, blocked_rows=blocked_rows, local_window=local_window)
+
+
+def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: int = 0, starts=None, blocked_rows: int = 0, head_dim: int = 64) -> np.ndarray:
+    """The causal grouped-query attention kernels on their own (head dimension 64 or 128): a query sees the real keys at or before its own
+    position; query head h reads K / V head h // (heads // kv_heads).  qkv columns are [Q (heads) | K (kv_heads) | V (kv_heads)] x head_dim.
+    starts None: a rectangle, qkv [B*S, (heads + 2 kv_heads) * head_dim] -> [B*S, heads * head_dim].  Else packed rows as diag_attention_packed."""
+    return _diag_attention(rt, ATTN_CAUSAL, qkv, lens, heads, S=S, starts=starts, kv_heads=kv_heads, head_dim=head_dim, blocked_rows=blocked_rows)
+
+
+def diag_ffn_act(rt: Runtime, kind: int, h) -> np.ndarray:
+    """The kernel between the two FFN GEMMs, kind = ffn_type.  1 GEGLU, 2 SwiGLU, 4 the tanh-GELU gate: h [rows, 2F] (gate | up) -> act(gate) * up;
+    3: the ReLU pass on h [rows, F].  bf16-rounded, [rows, F]."""
+    h = _f32(h)
+    rows, F = h.shape[0], h.shape[1] // (1 if kind == 3 else 2)
+    out = np.empty((rows, F), np.float32)
+    _check(lib().sc_diag_ffn_act(rt.handle, int(kind), _ptr(h), rows, F, _ptr(out)))
+    return out
+
+
+def diag_geglu(rt: Runtime, h) -> np.ndarray:
+    """The GEGLU kernel on h [rows, 2F] (gate | up): gelu(gate) * up, bf16-rounded, [rows, F]."""
+    return diag_ffn_act(rt, 1, h)
+
+
+def diag_swiglu(rt: Runtime, h) -> np.ndarray:
+    """The SwiGLU kernel on h [rows, 2F] (gate | up): silu(gate) * up, bf16-rounded, [rows, F]."""
+    return diag_ffn_act(rt, 2, h)
 
 
 def diag_fold_ln(rt: Runtime, W, gamma, beta, bias=None):
@@ -1632,111 +1659,6 @@ def diag_gemm_resln(rt: Runtime, A, W, bias, gam, R, fin, eps: float, a_blocked:
     _check(lib().sc_diag_gemm_resln(rt.handle, 1 if a_blocked else 0, _ptr(Ad), _ptr(W), _ptr(bias), _ptr(gam), _ptr(R), _ptr(fin), float(eps), M, N, K,
                                     _ptr(Cc), _ptr(st)))
     return Cc, st
-
-
-def diag_attention_ex(rt: Runtime, qkv, lens, B: int, S: int, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
-    """sc_launch_attention as the pipelines call it: blocked_rows > 0 lays qkv [B*S, 3H] out as [3H/64][blocked_rows][64] (rows beyond
-    B*S zero); slopes [heads] = ALiBi; head_dim 64 or 32 (H = heads * head_dim)."""
-    qkv = _f32(qkv)
-    lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * head_dim
-    if blocked_rows:
-        pad = np.zeros((blocked_rows, 3 * H), np.float32)
-        pad[: B * S] = qkv
-        qkv = block64(pad)
-    sl = None if slopes is None else _f32(slopes)
-    out = np.empty((B * S, H), np.float32)
-    if head_dim != 64:
-        _check(lib().sc_diag_attention_hd(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(head_dim), int(blocked_rows), _ptr(sl), _ptr(out)))
-    else:
-        _check(lib().sc_diag_attention_ex(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(blocked_rows), _ptr(sl), _ptr(out)))
-    return out
-
-
-def diag_attention_cls(rt: Runtime, qkv, lens, B: int, S: int, heads: int, head_dim: int = 64, slopes=None) -> np.ndarray:
-    """attention_cls_kernel on its own: qkv [B*S, 3H] row-major, one query row per text (its first) -> [B, H], H = heads * head_dim."""
-    qkv = _f32(qkv)
-    lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * head_dim
-    if qkv.shape != (B * S, 3 * H) or lens.shape != (B,):
-        raise ValueError("qkv must be [B*S, 3*heads*head_dim] and lens [B]")
-    sl = None if slopes is None else _f32(slopes)
-    out = np.full((B, H), np.nan, np.float32)
-    _check(lib().sc_diag_attention_cls(rt.handle, _ptr(qkv), _ptr(lens), B, S, heads, int(head_dim), _ptr(sl), _ptr(out)))
-    return out
-
-
-def diag_attention_packed(rt: Runtime, qkv, starts, lens, heads: int, blocked_rows: int = 0, slopes=None, head_dim: int = 64) -> np.ndarray:
-    """The packed attention kernel on its own: qkv [R, 3H] row-major, sequence b on the rows starts[b] .. starts[b] + ceil32(lens[b]);
-    R = blocked_rows (> 0: handed over as [3H/64][R][64]) or the last sequence's end rounded up to 256.  -> [R, H], H = heads * head_dim."""
-    qkv = _f32(qkv)
-    starts = np.ascontiguousarray(starts, np.int32)
-    lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * head_dim
-    R = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
-    if qkv.shape != (R, 3 * H) or starts.shape != lens.shape:
-        raise ValueError(f"diag_attention_packed: qkv must be [{R}, {3 * H}], starts and lens [B]")
-    if blocked_rows:
-        qkv = block64(qkv)
-    sl = None if slopes is None else _f32(slopes)
-    out = np.empty((R, H), np.float32)
-    if head_dim != 64:
-        _check(lib().sc_diag_attention_packed_hd(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(head_dim), int(blocked_rows), _ptr(sl),
-                                                 _ptr(out)))
-    else:
-        _check(lib().sc_diag_attention_packed(rt.handle, _ptr(qkv), _ptr(starts), _ptr(lens), len(lens), heads, int(blocked_rows), _ptr(sl), _ptr(out)))
-    return out
-
-
-def diag_attention_window(rt: Runtime, qkv, lens, heads: int, local_window: int, S: int = 0, starts=None, blocked_rows: int = 0) -> np.ndarray:
-    """The windowed attention kernels on their own (head dimension 64): a query sees the real keys with |i - j| <= local_window / 2.
-    starts None: a rectangle, qkv [B*S, 3H] -> [B*S, H].  Else packed rows as diag_attention_packed: qkv [R, 3H] -> [R, H]."""
-    qkv = _f32(qkv)
-    lens = np.ascontiguousarray(lens, np.int32)
-    H = heads * 64
-    if starts is None:
-        rows = len(lens) * int(S)
-        R = int(blocked_rows) if blocked_rows else rows
-    else:
-        starts = np.ascontiguousarray(starts, np.int32)
-        R = rows = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
-    if qkv.shape != (R, 3 * H) or (starts is not None and starts.shape != lens.shape):
-        raise ValueError(f"diag_attention_window: qkv must be [{R}, {3 * H}], starts (if given) and lens [B]")
-    if blocked_rows:
-        qkv = block64(qkv)
-    out = np.empty((rows, H), np.float32)
-    _check(lib().sc_diag_attention_window(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
-                                          int(local_window), int(blocked_rows), _ptr(out)))
-    return out
-
-
-def diag_attention_causal(rt: Runtime, qkv, lens, heads: int, kv_heads: int, S: int = 0, starts=None, blocked_rows: int = 0, head_dim: int = 64) -> np.ndarray:
-    """The causal grouped-query attention kernels on their own (head dimension 64, or 128 through sc_diag_attention_causal_hd): a query sees
-    the real keys at or before its own position; query head h reads K / V head h // (heads // kv_heads).  qkv columns are
-    [Q (heads) | K (kv_heads) | V (kv_heads)] x head_dim.
-    starts None: a rectangle, qkv [B*S, (heads + 2 kv_heads) * head_dim] -> [B*S, heads * head_dim].  Else packed rows as diag_attention_packed."""
-    qkv = _f32(qkv)
-    lens = np.ascontiguousarray(lens, np.int32)
-    head_dim = int(head_dim)
-    H, QN = heads * head_dim, (heads + 2 * kv_heads) * head_dim
-    if starts is None:
-        rows = len(lens) * int(S)
-        R = int(blocked_rows) if blocked_rows else rows
-    else:
-        starts = np.ascontiguousarray(starts, np.int32)
-        R = rows = int(blocked_rows) if blocked_rows else (int((starts + (lens + 31) // 32 * 32).max()) + 255) // 256 * 256
-    if qkv.shape != (R, QN) or (starts is not None and starts.shape != lens.shape):
-        raise ValueError(f"diag_attention_causal: qkv must be [{R}, {QN}], starts (if given) and lens [B]")
-    if blocked_rows:
-        qkv = block64(qkv)
-    out = np.empty((rows, H), np.float32)
-    if head_dim != 64:
-        _check(lib().sc_diag_attention_causal_hd(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
-                                                 int(kv_heads), head_dim, int(blocked_rows), _ptr(out)))
-        return out
-    _check(lib().sc_diag_attention_causal(rt.handle, _ptr(qkv), None if starts is None else _ptr(starts), _ptr(lens), len(lens), int(S), heads,
-                                          int(kv_heads), int(blocked_rows), _ptr(out)))
-    return out
 
 
 def diag_qknorm_rope(rt: Runtime, x, heads: int, kv_heads: int, head_dim: int, S: int, theta: float, pos=None, gamma_q=None, gamma_k=None,
@@ -1794,15 +1716,6 @@ def diag_mean_pool_ln(rt: Runtime, y, stats, gamma, beta, eps: float, lens, S: i
     out = np.empty((B, H), np.float32)
     _check(lib().sc_diag_mean_pool_ln(rt.handle, _ptr(y), _ptr(stats), stats.shape[0], tp, _ptr(gamma), _ptr(beta), float(eps), _ptr(lens), B, int(S), H,
                                       _ptr(out)))
-    return out
-
-
-def diag_geglu(rt: Runtime, h) -> np.ndarray:
-    """The GEGLU kernel on h [rows, 2F] (gate | up): gelu(gate) * up, bf16-rounded, [rows, F]."""
-    h = _f32(h)
-    rows, F = h.shape[0], h.shape[1] // 2
-    out = np.empty((rows, F), np.float32)
-    _check(lib().sc_diag_geglu(rt.handle, _ptr(h), rows, F, _ptr(out)))
     return out
 
 

@@ -50,16 +50,10 @@ sc_status download(const void* dev, size_t bytes, void* host, hipStream_t s) {
     SC_HIP(hipStreamSynchronize(s));
     return SC_OK;
 }
-// T5's bias for the attention harnesses: rel_bias [buckets][heads] -> the distance table of a 2 048-token span on the device
-struct RelBiasArg {
-    const float* rel_bias = nullptr;
-    int buckets = 0, max_distance = 0;
-};
+// T5's bias for the attention harness: rel_bias [buckets][heads] (valid buckets / max_distance) -> the distance table of a 2 048-token span on the device
 const int DIAG_REL_SPAN = 2048;
-sc_status upload_rel_table(const char* who, const RelBiasArg& rb, int heads, sc_devbuf& out, hipStream_t s) {
-    if (!sc_rel_buckets_valid(rb.buckets, rb.max_distance))
-        return sc_fail(SC_ERR_INVALID, "%s: buckets must be even, 4 .. 256, and max_distance beyond buckets / 4, got %d / %d", who, rb.buckets, rb.max_distance);
-    const std::vector<float> tbl = sc_rel_bias_table(rb.rel_bias, rb.buckets, heads, rb.max_distance, DIAG_REL_SPAN);
+sc_status upload_rel_table(const float* rel_bias, int buckets, int heads, int max_distance, sc_devbuf& out, hipStream_t s) {
+    const std::vector<float> tbl = sc_rel_bias_table(rel_bias, buckets, heads, max_distance, DIAG_REL_SPAN);
     SC_TRY(upload(tbl.data(), tbl.size() * 4, out, s));
     SC_HIP(hipStreamSynchronize(s));  // tbl goes out of scope
     return SC_OK;
@@ -300,115 +294,132 @@ extern "C" sc_status sc_diag_gemm_resln(sc_runtime* rt, int32_t flags, const flo
     return download_bf16(dc.p, (int64_t)M * N, C, s);
 }
 
-// sc_launch_attention as the pipelines call it.  blocked_rows == 0: qkv [B*S][3H] row-major; > 0: qkv [3 heads][blocked_rows][64], the layout
-// the QKV projections write (blocked_rows >= B*S: that GEMM's M).  slopes: NULL or [heads] ALiBi slopes.  head_dim 64, or 32 (an even
-// number of heads, no slopes): H = heads * head_dim, the blocks stay 64 columns wide.
-static sc_status diag_attention(const char* who, sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                const float* slopes, float* out, int32_t head_dim = 64, RelBiasArg rb = RelBiasArg()) {
-    if (!rt || !qkv || !lens || !out || B < 1 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    const int H = heads * head_dim;
-    if (!sc_attention_supported(S, H, heads, head_dim))
-        return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048, head_dim 64 or 32 (an even number of heads)", who);
-    if (head_dim != 64 && slopes) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head dimension %d has no ALiBi kernel", who, head_dim);
-    const int64_t tokens = (int64_t)B * S;
-    if (blocked_rows && blocked_rows < tokens) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
-    SC_HIP(hipSetDevice(rt->device));
-    hipStream_t s = rt->stream;
-    sc_devbuf fq, dq, dl, dsl, dc;
-    SC_TRY(upload_bf16(qkv, (blocked_rows ? (int64_t)blocked_rows : tokens) * 3 * H, fq, dq, s));
-    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
-    if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
-    SC_TRY(alloc_nan(dc, (size_t)tokens * H * 2, s));
-    if (rb.rel_bias) {
-        SC_TRY(upload_rel_table(who, rb, heads, dsl, s));
-        sc_launch_attention_rel(dq.p, (const int32_t*)dl.p, B, S, H, (const float*)dsl.p, DIAG_REL_SPAN, dc.p, s, blocked_rows);
+// ------------------------------------------------------------------ attention: one harness over every product launcher
+// sc_diag_attention_run in three steps, each written once: the descriptor's rules, the geometry (both host arithmetic, before the runtime
+// is looked at), then stage / launch / download.  The layouts and the NaN contract are in include/semcode_hip.h.
+namespace {
+const char* const ATTN = "sc_diag_attention_run";
+
+sc_status attn_validate(const sc_diag_attn* a) {
+    const int heads = a->heads, hd = a->head_dim;
+    const bool window = a->mask == SC_DIAG_ATTN_WINDOW, causal = a->mask == SC_DIAG_ATTN_CAUSAL, cls = a->mask == SC_DIAG_ATTN_CLS;
+    if (a->mask < SC_DIAG_ATTN_FULL || a->mask > SC_DIAG_ATTN_CLS) return sc_fail(SC_ERR_INVALID, "%s: mask %d is none of 0 (full), 1 (window), 2 (causal), 3 (CLS rows)", ATTN, a->mask);
+    if (!a->lens || a->B < 1 || a->B > 65536 || a->blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument (lens, B 1 .. 65536, blocked_rows >= 0)", ATTN);
+    if (causal) {
+        if (!sc_attention_causal_supported(heads, a->kv_heads, hd))
+            return sc_fail(SC_ERR_UNSUPPORTED, "%s: mask causal needs head_dim 64 or 128 and 1 <= kv_heads <= heads <= 2048 / head_dim with heads %% kv_heads == 0, got heads %d, kv_heads %d, head_dim %d",
+                           ATTN, heads, a->kv_heads, hd);
     } else {
-        sc_launch_attention(dq.p, (const int32_t*)dl.p, B, S, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
+        if (heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument (heads %d)", ATTN, heads);
+        if (hd != 64 && !(hd == 32 && heads % 2 == 0))
+            return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads (got %d, %d heads)", ATTN, hd, heads);
+        if (heads > 2048 / hd) return sc_fail(SC_ERR_INVALID, "%s: bad argument (%d heads of %d: heads * head_dim beyond 2048)", ATTN, heads, hd);
+        if (a->kv_heads && a->kv_heads != heads) return sc_fail(SC_ERR_UNSUPPORTED, "%s: kv_heads %d of %d heads needs mask causal, got mask %d", ATTN, a->kv_heads, heads, a->mask);
     }
-    return download_bf16(dc.p, tokens * H, out, s);
-}
-// sc_launch_attention_rel: heads of 64, scores q.k + rel_bias[bucket(key - query)][head], no 1/sqrt(d)
-extern "C" sc_status sc_diag_attention_bias(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                            const float* rel_bias, int32_t buckets, int32_t max_distance, float* out) {
-    if (!rel_bias) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_bias: rel_bias is NULL");
-    return diag_attention("sc_diag_attention_bias", rt, qkv, lens, B, S, heads, blocked_rows, nullptr, out, 64, RelBiasArg{rel_bias, buckets, max_distance});
-}
-extern "C" sc_status sc_diag_attention_hd(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                                          int32_t blocked_rows, const float* slopes, float* out) {
-    return diag_attention("sc_diag_attention_hd", rt, qkv, lens, B, S, heads, blocked_rows, slopes, out, head_dim);
-}
-extern "C" sc_status sc_diag_attention_ex(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t blocked_rows,
-                                          const float* slopes, float* out) {
-    return diag_attention("sc_diag_attention_ex", rt, qkv, lens, B, S, heads, blocked_rows, slopes, out);
-}
-extern "C" sc_status sc_diag_attention(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, float* out) {
-    return diag_attention("sc_diag_attention", rt, qkv, lens, B, S, heads, 0, nullptr, out);
+    if (a->slopes && (window || causal)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: mask %d has no ALiBi kernel (slopes must be NULL)", ATTN, a->mask);
+    if (a->slopes && hd == 32 && !cls) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim 32 has no ALiBi kernel outside the CLS form (slopes must be NULL)", ATTN);
+    if (window) {
+        if (!sc_attention_window_supported(a->local_window)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: local_window must be even and within 2 .. 128, got %d", ATTN, a->local_window);
+        if (hd != 64) return sc_fail(SC_ERR_UNSUPPORTED, "%s: mask window (local_window) needs head_dim 64, got %d", ATTN, hd);
+    }
+    if (a->rel_bias) {
+        if (a->mask != SC_DIAG_ATTN_FULL) return sc_fail(SC_ERR_UNSUPPORTED, "%s: rel_bias needs mask full, got mask %d", ATTN, a->mask);
+        if (hd != 64) return sc_fail(SC_ERR_UNSUPPORTED, "%s: rel_bias needs head_dim 64, got %d", ATTN, hd);
+        if (a->slopes) return sc_fail(SC_ERR_UNSUPPORTED, "%s: rel_bias and slopes exclude each other", ATTN);
+        if (!sc_rel_buckets_valid(a->rel_buckets, a->rel_max_distance))
+            return sc_fail(SC_ERR_INVALID, "%s: rel_buckets must be even, 4 .. 256, and rel_max_distance beyond rel_buckets / 4, got %d / %d", ATTN, a->rel_buckets, a->rel_max_distance);
+    }
+    if (cls) {
+        if (a->starts || a->blocked_rows) return sc_fail(SC_ERR_UNSUPPORTED, "%s: mask CLS is a row-major rectangle: starts must be NULL and blocked_rows 0", ATTN);
+        if (a->S < 1 || a->S > 2048) return sc_fail(SC_ERR_INVALID, "%s: mask CLS: S must be within 1 .. 2048, got %d", ATTN, a->S);
+    }
+    return SC_OK;
 }
 
-// sc_launch_attention_cls, rectangle form.  The host lays qkv out in 64-column blocks of M = ceil256(B*S) rows, as the QKV projection writes it.
-extern "C" sc_status sc_diag_attention_cls(sc_runtime* rt, const float* qkv, const int32_t* lens, int32_t B, int32_t S, int32_t heads, int32_t head_dim,
-                                           const float* alibi, float* out) {
-    const char* who = "sc_diag_attention_cls";
-    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    if (head_dim != 64 && !(head_dim == 32 && heads % 2 == 0)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads", who);
-    const int H = heads * head_dim;
-    if (S < 1 || S > 2048 || H > 2048) return sc_fail(SC_ERR_INVALID, "%s: S and heads*head_dim must be at most 2048", who);
-    const int64_t tokens = (int64_t)B * S, M = (tokens + 255) / 256 * 256, nblk = 3 * H / 64;
-    std::vector<float> blocked((size_t)nblk * M * 64, 0.f);
-    for (int64_t r = 0; r < tokens; ++r)
-        for (int64_t cb = 0; cb < nblk; ++cb) memcpy(&blocked[(size_t)(cb * M + r) * 64], qkv + r * 3 * H + cb * 64, 64 * sizeof(float));
+// rows_in x qkv_cols is what the launcher reads, rows_out x out_cols what comes back; a packed call's work items as the packed forward builds them
+struct AttnGeom {
+    int64_t rows_in = 0, rows_out = 0;
+    int qkv_cols = 0, out_cols = 0;
+    std::vector<int32_t> items;
+    int nitems[3] = {0, 0, 0};
+};
+sc_status attn_geometry(const sc_diag_attn* a, AttnGeom& g) {
+    g.out_cols = a->heads * a->head_dim;
+    g.qkv_cols = (a->heads + 2 * (a->mask == SC_DIAG_ATTN_CAUSAL ? a->kv_heads : a->heads)) * a->head_dim;
+    const int64_t tokens = (int64_t)a->B * a->S;
+    if (a->mask == SC_DIAG_ATTN_CLS) {  // the harness blocks the rows itself, as the QKV projection writes them
+        g.rows_in = ceil256(tokens), g.rows_out = a->B;
+        return SC_OK;
+    }
+    if (!a->starts) {
+        if (!sc_attention_supported(a->S, 64, 1, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048, got %d", ATTN, a->S);
+        if (a->blocked_rows && a->blocked_rows < tokens) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", ATTN);
+        g.rows_in = a->blocked_rows ? (int64_t)a->blocked_rows : tokens, g.rows_out = tokens;
+        return SC_OK;
+    }
+    int64_t end = 0, used = 0;
+    for (int32_t b = 0; b < a->B; ++b) {
+        const int32_t start = a->starts[b], len = a->lens[b];
+        if (len < 1 || len > 2048 || start < 0 || (start % 32) || start > (1 << 24))
+            return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", ATTN, b, start, len);
+        used += ceil32(len);
+        if (start + ceil32(len) > end) end = start + ceil32(len);
+    }
+    const int64_t R = a->blocked_rows ? (int64_t)a->blocked_rows : ceil256(end);
+    if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", ATTN, a->blocked_rows, (long long)end);
+    g.rows_in = g.rows_out = R;
+    g.items.resize((size_t)sc_packed_items_cap(used, a->B) * 4);  // by the rows the sequences own: they may overlap here
+    sc_packed_items(a->starts, a->lens, a->B, g.items.data(), g.nitems);
+    return SC_OK;
+}
+}  // namespace
+
+extern "C" sc_status sc_diag_attention_run(sc_runtime* rt, const sc_diag_attn* a, const float* qkv, float* out) {
+    if (!a || !qkv || !out) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", ATTN);
+    SC_TRY(attn_validate(a));
+    AttnGeom g;
+    SC_TRY(attn_geometry(a, g));
+    if (!rt) return sc_fail(SC_ERR_INVALID, "%s: the runtime is NULL", ATTN);
+    const bool packed = a->starts != nullptr;
+    const int B = a->B, S = a->S, heads = a->heads, hd = a->head_dim, H = g.out_cols, blocked = a->blocked_rows;
+    std::vector<float> cls_rows;  // mask CLS: qkv [B*S][3H] laid out in 64-column blocks of rows_in rows, the padding rows zero
+    if (a->mask == SC_DIAG_ATTN_CLS) {
+        const int64_t nblk = g.qkv_cols / 64;
+        cls_rows.assign((size_t)(nblk * g.rows_in * 64), 0.f);
+        for (int64_t r = 0; r < (int64_t)B * S; ++r)
+            for (int64_t cb = 0; cb < nblk; ++cb) memcpy(&cls_rows[(size_t)(cb * g.rows_in + r) * 64], qkv + r * g.qkv_cols + cb * 64, 64 * sizeof(float));
+        qkv = cls_rows.data();
+    }
     SC_HIP(hipSetDevice(rt->device));
     hipStream_t s = rt->stream;
-    sc_devbuf fq, dq, dl, dsl, dc;
-    SC_TRY(upload_bf16(blocked.data(), nblk * M * 64, fq, dq, s));
-    SC_TRY(upload(lens, (size_t)B * 4, dl, s));
-    if (alibi) SC_TRY(upload(alibi, (size_t)heads * 4, dsl, s));
-    SC_TRY(alloc_nan(dc, (size_t)B * H * 2, s));
-    sc_launch_attention_cls(dq.p, nullptr, (const int32_t*)dl.p, B, S, (int)M, H, head_dim, alibi ? (const float*)dsl.p : nullptr, dc.p, B, s);
-    return download_bf16(dc.p, (int64_t)B * H, out, s);  // synchronises: `blocked` may go
+    sc_devbuf fq, dq, dseq, dex, dc;
+    SC_TRY(upload_bf16(qkv, g.rows_in * g.qkv_cols, fq, dq, s));
+    if (packed) SC_TRY(upload(g.items.data(), g.items.size() * 4, dseq, s));
+    else SC_TRY(upload(a->lens, (size_t)B * 4, dseq, s));
+    if (a->slopes) SC_TRY(upload(a->slopes, (size_t)heads * 4, dex, s));
+    SC_TRY(alloc_nan(dc, (size_t)g.rows_out * H * 2, s));
+    if (a->rel_bias) SC_TRY(upload_rel_table(a->rel_bias, a->rel_buckets, heads, a->rel_max_distance, dex, s));
+    const int32_t* seq = (const int32_t*)dseq.p;  // lens [B], or the packed items
+    const float* ex = (const float*)dex.p;        // slopes, the distance table, or NULL
+    switch (a->mask) {
+    case SC_DIAG_ATTN_CLS: sc_launch_attention_cls(dq.p, nullptr, seq, B, S, (int)g.rows_in, H, hd, ex, dc.p, B, s); break;
+    case SC_DIAG_ATTN_WINDOW:
+        if (packed) sc_launch_attention_window_packed(dq.p, seq, g.nitems, H, a->local_window, dc.p, s, blocked);
+        else sc_launch_attention_window(dq.p, seq, B, S, H, a->local_window, dc.p, s, blocked);
+        break;
+    case SC_DIAG_ATTN_CAUSAL:
+        if (packed) sc_launch_attention_causal_packed(dq.p, seq, g.nitems, heads, a->kv_heads, hd, dc.p, s, blocked);
+        else sc_launch_attention_causal(dq.p, seq, B, S, heads, a->kv_heads, hd, dc.p, s, blocked);
+        break;
+    default:
+        if (a->rel_bias && packed) sc_launch_attention_rel_packed(dq.p, seq, g.nitems, H, ex, DIAG_REL_SPAN, dc.p, s, blocked);
+        else if (a->rel_bias) sc_launch_attention_rel(dq.p, seq, B, S, H, ex, DIAG_REL_SPAN, dc.p, s, blocked);
+        else if (packed) sc_launch_attention_packed(dq.p, seq, g.nitems, H, ex, dc.p, s, blocked, hd);
+        else sc_launch_attention(dq.p, seq, B, S, H, ex, dc.p, s, blocked, hd);
+    }
+    return download_bf16(dc.p, g.rows_out * H, out, s);  // synchronises: cls_rows and the items may go
 }
 
-// sc_launch_attention_packed as the packed forward calls it: the work items come from sc_packed_items, as there.
-static sc_status diag_attention_packed(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                       int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out, RelBiasArg rb = RelBiasArg()) {
-    if (!rt || !qkv || !starts || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    if (head_dim != 64 && !(head_dim == 32 && heads % 2 == 0 && !slopes))
-        return sc_fail(SC_ERR_UNSUPPORTED, "%s: head_dim must be 64, or 32 with an even number of heads and no ALiBi slopes (got %d, %d heads)", who, head_dim, heads);
-    if (heads * head_dim > 2048) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    const int H = heads * head_dim;
-    int64_t end = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
-            return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
-        const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
-        if (e > end) end = e;
-    }
-    const int64_t R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
-    if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
-    SC_HIP(hipSetDevice(rt->device));
-    hipStream_t s = rt->stream;
-    std::vector<int32_t> items((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
-    int nitems[3];
-    sc_packed_items(starts, lens, B, items.data(), nitems);
-    sc_devbuf fq, dq, di, dsl, dc;
-    SC_TRY(upload_bf16(qkv, R * 3 * H, fq, dq, s));
-    SC_TRY(upload(items.data(), items.size() * 4, di, s));
-    if (slopes) SC_TRY(upload(slopes, (size_t)heads * 4, dsl, s));
-    SC_TRY(alloc_nan(dc, (size_t)R * H * 2, s));
-    if (rb.rel_bias) {
-        SC_TRY(upload_rel_table(who, rb, heads, dsl, s));
-        sc_launch_attention_rel_packed(dq.p, (const int32_t*)di.p, nitems, H, (const float*)dsl.p, DIAG_REL_SPAN, dc.p, s, blocked_rows);
-    } else {
-        sc_launch_attention_packed(dq.p, (const int32_t*)di.p, nitems, H, slopes ? (const float*)dsl.p : nullptr, dc.p, s, blocked_rows, head_dim);
-    }
-    return download_bf16(dc.p, R * H, out, s);  // synchronises: items may go
-}
-extern "C" sc_status sc_diag_attention_bias_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                                   int32_t blocked_rows, const float* rel_bias, int32_t buckets, int32_t max_distance, float* out) {
-    if (!rel_bias) return sc_fail(SC_ERR_INVALID, "sc_diag_attention_bias_packed: rel_bias is NULL");
-    return diag_attention_packed("sc_diag_attention_bias_packed", rt, qkv, starts, lens, B, heads, 64, blocked_rows, nullptr, out,
-                                 RelBiasArg{rel_bias, buckets, max_distance});
-}
 // The bucket rule alone: host arithmetic, no runtime (rel_bucket_rule.h, what builds the device table)
 extern "C" sc_status sc_diag_rel_buckets(int32_t rel_buckets, int32_t max_distance, int32_t span, int32_t* out) {
     if (!out || span < 1 || span > (1 << 20)) return sc_fail(SC_ERR_INVALID, "sc_diag_rel_buckets: bad argument (span 1 .. 2^20)");
@@ -417,109 +428,6 @@ extern "C" sc_status sc_diag_rel_buckets(int32_t rel_buckets, int32_t max_distan
                        max_distance);
     sc_rel_buckets(rel_buckets, max_distance, span, out);
     return SC_OK;
-}
-extern "C" sc_status sc_diag_attention_packed(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                              int32_t blocked_rows, const float* slopes, float* out) {
-    return diag_attention_packed("sc_diag_attention_packed", rt, qkv, starts, lens, B, heads, 64, blocked_rows, slopes, out);
-}
-extern "C" sc_status sc_diag_attention_packed_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t heads,
-                                                 int32_t head_dim, int32_t blocked_rows, const float* slopes, float* out) {
-    return diag_attention_packed("sc_diag_attention_packed_hd", rt, qkv, starts, lens, B, heads, head_dim, blocked_rows, slopes, out);
-}
-
-// sc_launch_attention_window / _packed as the pre-norm forward calls them (starts == NULL: the rectangle form)
-extern "C" sc_status sc_diag_attention_window(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                              int32_t local_window, int32_t blocked_rows, float* out) {
-    const char* who = "sc_diag_attention_window";
-    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0 || heads < 1 || heads * 64 > 2048) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    if (!sc_attention_window_supported(local_window)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: local_window must be even and within 2 .. 128, got %d", who, local_window);
-    const int H = heads * 64;
-    int64_t R = 0, rows_out = 0;
-    std::vector<int32_t> items;
-    int nitems[3] = {0, 0, 0};
-    if (starts) {
-        int64_t end = 0;
-        for (int32_t b = 0; b < B; ++b) {
-            if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
-                return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
-            const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
-            if (e > end) end = e;
-        }
-        R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
-        if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
-        rows_out = R;
-        items.resize((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
-        sc_packed_items(starts, lens, B, items.data(), nitems);
-    } else {
-        if (!sc_attention_supported(S, H, heads, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
-        rows_out = (int64_t)B * S;
-        if (blocked_rows && blocked_rows < rows_out) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
-        R = blocked_rows ? (int64_t)blocked_rows : rows_out;
-    }
-    SC_HIP(hipSetDevice(rt->device));
-    hipStream_t s = rt->stream;
-    sc_devbuf fq, dq, dl, dc;
-    SC_TRY(upload_bf16(qkv, R * 3 * H, fq, dq, s));
-    if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
-    else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
-    SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
-    if (starts) sc_launch_attention_window_packed(dq.p, (const int32_t*)dl.p, nitems, H, local_window, dc.p, s, blocked_rows);
-    else sc_launch_attention_window(dq.p, (const int32_t*)dl.p, B, S, H, local_window, dc.p, s, blocked_rows);
-    return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
-}
-
-// sc_launch_attention_causal / _packed as the causal forward calls them (starts == NULL: the rectangle form).  qkv rows are
-// [Q (heads) | K (kv_heads) | V (kv_heads)] x 64 columns; out [rows, heads * 64]
-static sc_status diag_attention_causal(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                       int32_t kv_heads, int32_t hd, int32_t blocked_rows, float* out);
-extern "C" sc_status sc_diag_attention_causal(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                              int32_t kv_heads, int32_t blocked_rows, float* out) {
-    return diag_attention_causal("sc_diag_attention_causal", rt, qkv, starts, lens, B, S, heads, kv_heads, 64, blocked_rows, out);
-}
-// ... with the head dimension stated: 64 or 128; columns x head_dim
-extern "C" sc_status sc_diag_attention_causal_hd(sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                                 int32_t kv_heads, int32_t head_dim, int32_t blocked_rows, float* out) {
-    return diag_attention_causal("sc_diag_attention_causal_hd", rt, qkv, starts, lens, B, S, heads, kv_heads, head_dim, blocked_rows, out);
-}
-static sc_status diag_attention_causal(const char* who, sc_runtime* rt, const float* qkv, const int32_t* starts, const int32_t* lens, int32_t B, int32_t S, int32_t heads,
-                                       int32_t kv_heads, int32_t hd, int32_t blocked_rows, float* out) {
-    if (!rt || !qkv || !lens || !out || B < 1 || B > 65536 || blocked_rows < 0) return sc_fail(SC_ERR_INVALID, "%s: bad argument", who);
-    if (!sc_attention_causal_supported(heads, kv_heads, hd))
-        return sc_fail(SC_ERR_UNSUPPORTED, "%s: need head_dim 64 or 128 and 1 <= kv_heads <= heads <= 2048 / head_dim with heads %% kv_heads == 0, got heads %d, kv_heads %d, head_dim %d",
-                       who, heads, kv_heads, hd);
-    const int H = heads * hd, QN = (heads + 2 * kv_heads) * hd;
-    int64_t R = 0, rows_out = 0;
-    std::vector<int32_t> items;
-    int nitems[3] = {0, 0, 0};
-    if (starts) {
-        int64_t end = 0;
-        for (int32_t b = 0; b < B; ++b) {
-            if (lens[b] < 1 || lens[b] > 2048 || starts[b] < 0 || (starts[b] % 32) || starts[b] > (1 << 24))
-                return sc_fail(SC_ERR_INVALID, "%s: sequence %d: start %d (multiple of 32) / length %d (1..2048) out of range", who, b, starts[b], lens[b]);
-            const int64_t e = (int64_t)starts[b] + (lens[b] + 31) / 32 * 32;
-            if (e > end) end = e;
-        }
-        R = blocked_rows ? (int64_t)blocked_rows : (end + 255) / 256 * 256;
-        if (R < end) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows %d < the last sequence's end %lld", who, blocked_rows, (long long)end);
-        rows_out = R;
-        items.resize((size_t)B * 8 * 4);  // at most 2048 / 256 items per sequence
-        sc_packed_items(starts, lens, B, items.data(), nitems);
-    } else {
-        if (!sc_attention_supported(S, 64, 1, 64)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: S must be one of 32,64,128,256,512,1024,2048", who);
-        rows_out = (int64_t)B * S;
-        if (blocked_rows && blocked_rows < rows_out) return sc_fail(SC_ERR_INVALID, "%s: blocked_rows < B*S", who);
-        R = blocked_rows ? (int64_t)blocked_rows : rows_out;
-    }
-    SC_HIP(hipSetDevice(rt->device));
-    hipStream_t s = rt->stream;
-    sc_devbuf fq, dq, dl, dc;
-    SC_TRY(upload_bf16(qkv, R * QN, fq, dq, s));
-    if (starts) SC_TRY(upload(items.data(), items.size() * 4, dl, s));
-    else SC_TRY(upload(lens, (size_t)B * 4, dl, s));
-    SC_TRY(alloc_nan(dc, (size_t)rows_out * H * 2, s));
-    if (starts) sc_launch_attention_causal_packed(dq.p, (const int32_t*)dl.p, nitems, heads, kv_heads, hd, dc.p, s, blocked_rows);
-    else sc_launch_attention_causal(dq.p, (const int32_t*)dl.p, B, S, heads, kv_heads, hd, dc.p, s, blocked_rows);
-    return download_bf16(dc.p, rows_out * H, out, s);  // synchronises: items may go
 }
 
 // qknorm_rope_kernel / qknorm_rope_packed_kernel on their own: x [rows, (heads + 2 kv_heads) * head_dim] f32 as [Q | K | V] -> bf16 in 64-column
@@ -641,40 +549,24 @@ extern "C" sc_status sc_diag_mean_pool_ln(sc_runtime* rt, const float* y, const 
     return download(dout.p, (size_t)B * H * 4, out, s);
 }
 
-// The gate kernels between the two FFN GEMMs: h [rows, 2F] (gate | up) -> out [rows, F] = act(gate) * up
-static sc_status diag_gate(const char* who, bool swiglu, sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) {
-    if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "%s: bad argument (F must be a multiple of 8)", who);
-    SC_HIP(hipSetDevice(rt->device));
-    hipStream_t s = rt->stream;
-    sc_devbuf fh, dh, dc;
-    SC_TRY(upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s));
-    SC_TRY(alloc_nan(dc, (size_t)rows * F * 2, s));
-    if (swiglu) sc_launch_swiglu(dh.p, rows, F, dc.p, s);
-    else sc_launch_geglu(dh.p, rows, F, dc.p, s);
-    return download_bf16(dc.p, (int64_t)rows * F, out, s);
-}
-// glu_kernel<ActGelu>: gelu(gate) * up
-extern "C" sc_status sc_diag_geglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_geglu", false, rt, h, rows, F, out); }
-// swiglu_kernel: silu(gate) * up
-extern "C" sc_status sc_diag_swiglu(sc_runtime* rt, const float* h, int32_t rows, int32_t F, float* out) { return diag_gate("sc_diag_swiglu", true, rt, h, rows, F, out); }
-
-// The activations of the T5 feed-forwards.  kind 3: relu_kernel, in place on the bf16-rounded h [rows, F] -> out [rows, F]; kind 4:
-// glu_kernel<ActGeluTanh> on h [rows, 2F] (gate | up) -> out [rows, F] = gelu_new(gate) * up
+// The kernels between the two FFN GEMMs, kind = the model's ffn_type.  The gates (1 glu_kernel<ActGelu>, 2 swiglu_kernel, 4
+// glu_kernel<ActGeluTanh>): h [rows, 2F] (gate | up) -> out [rows, F] = act(gate) * up; 3: relu_kernel, in place on the bf16-rounded h [rows, F]
 extern "C" sc_status sc_diag_ffn_act(sc_runtime* rt, int32_t kind, const float* h, int32_t rows, int32_t F, float* out) {
     const char* who = "sc_diag_ffn_act";
-    if (kind != 3 && kind != 4) return sc_fail(SC_ERR_INVALID, "%s: kind must be 3 (ReLU) or 4 (tanh-GELU gate), got %d", who, kind);
+    if (kind < 1 || kind > 4) return sc_fail(SC_ERR_INVALID, "%s: kind must be 1 (GEGLU), 2 (SwiGLU), 3 (ReLU) or 4 (tanh-GELU gate), got %d", who, kind);
     if (!rt || !h || !out || rows < 1 || F < 8 || (F % 8)) return sc_fail(SC_ERR_INVALID, "%s: bad argument (F must be a multiple of 8)", who);
     SC_HIP(hipSetDevice(rt->device));
     hipStream_t s = rt->stream;
     sc_devbuf fh, dh, dc;
+    SC_TRY(upload_bf16(h, (int64_t)rows * (kind == 3 ? 1 : 2) * F, fh, dh, s));
     if (kind == 3) {
-        SC_TRY(upload_bf16(h, (int64_t)rows * F, fh, dh, s));
         sc_launch_relu(dh.p, (int64_t)rows * F, s);
         return download_bf16(dh.p, (int64_t)rows * F, out, s);
     }
-    SC_TRY(upload_bf16(h, (int64_t)rows * 2 * F, fh, dh, s));
     SC_TRY(alloc_nan(dc, (size_t)rows * F * 2, s));
-    sc_launch_geglu_tanh(dh.p, rows, F, dc.p, s);
+    if (kind == 1) sc_launch_geglu(dh.p, rows, F, dc.p, s);
+    else if (kind == 2) sc_launch_swiglu(dh.p, rows, F, dc.p, s);
+    else sc_launch_geglu_tanh(dh.p, rows, F, dc.p, s);
     return download_bf16(dc.p, (int64_t)rows * F, out, s);
 }
 

@@ -201,7 +201,7 @@ def test_attention_cls_kernel(rt, S, hd, alibi):
     assert np.median(err) <= 3e-3
     if alibi and hd == 32:
         return  # the full kernels have no ALiBi form at head dimension 32
-    full = _native.diag_attention_ex(rt, qkv, lens, B, S, heads, slopes=slopes, head_dim=hd)  # sc_diag_attention_ex / sc_diag_attention_hd
+    full = _native.diag_attention_ex(rt, qkv, lens, B, S, heads, slopes=slopes, head_dim=hd)
     err = np.abs(got - full.reshape(B, S, H)[:, 0])
     print(f"  against row 0 of the full kernel: max {err.max():.3e}, median {np.median(err):.3e}")
     assert err.max() <= 3e-2 and np.median(err) <= 3e-3

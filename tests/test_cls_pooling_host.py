@@ -94,7 +94,7 @@ def test_new_symbols_are_declared_exported_and_bound():
 
     header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "semcode_hip.h").read_text(), flags=re.S)
     handle = ctypes.CDLL(str(build.build(verbose=False)))
-    for sym in ("sc_encoder_set_pooling", "sc_encoder_get_pooling", "sc_diag_attention_cls"):
+    for sym in ("sc_encoder_set_pooling", "sc_encoder_get_pooling", "sc_diag_attention_run"):
         assert re.search(rf"\b{sym}\s*\(", header), sym
         assert hasattr(handle, sym) and sym in _native.SIGNATURES, sym
     assert _native.POOLINGS == {"mean": 0, "cls": 1}

@@ -1,4 +1,4 @@
-"""GPU: packed variable-length batches (sc_encoder_embed_packed*, sc_diag_attention_packed) through the C ABI.
+"""GPU: packed variable-length batches (sc_encoder_embed_packed*, sc_diag_attention_run) through the C ABI.
 
 References: oracle/bert_oracle.py (learned positions; ALiBi + GEGLU) and tests/nomic_ref.py (rotary + SwiGLU), each text given ALONE and
 unpadded, so that nothing a neighbour or a padding row could leak is in them.  Bar: the project's whole-encoder bar of

@@ -67,7 +67,7 @@ def test_abi_has_the_packed_entries():
     from semcode_amd.csrc import build
 
     names = ["sc_encoder_packed_rows", "sc_encoder_embed_packed", "sc_encoder_embed_packed_into", "sc_encoder_embed_packed_into_async",
-             "sc_diag_attention_packed"]
+             "sc_diag_attention_run"]
     handle = ctypes.CDLL(str(build.build(verbose=False)))
     for n in names:
         assert n in _native.SIGNATURES and hasattr(handle, n), n

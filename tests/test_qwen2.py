@@ -200,6 +200,6 @@ def test_pooling_of_a_model_directory(tmp_path):
 
 def test_new_symbols_are_exported():
     lib = _native.lib()
-    for name in ("sc_diag_attention_causal", "sc_diag_rmsnorm"):
+    for name in ("sc_diag_attention_run", "sc_diag_rmsnorm"):
         assert name in _native.SIGNATURES and getattr(lib, name) is not None
     assert [f[0] for f in _native.EncoderCfg._fields_][-1] == "kv_heads"

@@ -167,7 +167,7 @@ def test_cfg_dict_forms():
         assert type(made) is _native.EncoderCfgFull and C.sizeof(made) == 88
     assert (_native.EncoderCfg(vocab=5, kv_heads=2, qk_norm=1).kv_heads, _native.EncoderCfg(head_dim=128).head_dim) == (2, 128)
     lib = _native.lib()
-    for name in ("sc_diag_attention_causal_hd", "sc_diag_qknorm_rope"):
+    for name in ("sc_diag_attention_run", "sc_diag_qknorm_rope"):
         assert name in _native.SIGNATURES and getattr(lib, name) is not None
 
 
