@@ -472,6 +472,24 @@ sc_status sc_tokenizer_encode(sc_tokenizer* tok, const char* bytes, const int64_
  * M, N multiples of 128, K multiple of 64. */
 sc_status sc_diag_gemm_bf16(sc_runtime* rt, int32_t epi, const float* A, const float* W, const float* bias, const float* R,
                             int32_t M, int32_t N, int32_t K, float* out);
+/* sc_diag_gemm_bf16_ex: the same launch (epi 0, 1 or 2, no "+ 16") in the forms the forward passes use.  flags bit 0: C is written and
+ *   returned in 64-column blocks [N/64][M][64]; bit 1: A is given as [K/64][M][64]; bit 2: the split-K scratch is offered (the launcher
+ *   splits where sc_diag_gemm_splitk says so); bit 3: the 128-tile kernel runs even where M and N divide by 256.  The arguments are
+ *   checked by host arithmetic before rt is looked at.  Blocked A is read by the per-tile 256-tile kernel only: with M or N not a
+ *   multiple of 256, with bit 2 or with bit 3 it is SC_ERR_UNSUPPORTED (the launcher itself launches nothing for such a call).
+ *   path (or NULL) [5] = what the launcher ran: {tile 128 / 256, K slices (1 = no split-K), walk order word, ring depth of the main loop
+ *   (0 = one barrier per K-tile), non-temporal C stores 0 / 1}.  The 128-tile kernel reports order 0, depth 0, nt 0 (it has none of
+ *   them), the split-K pair order 1 (row-major, no XCD remap), depth 0, nt 0.
+ * sc_diag_gemm_path: M > 0: the path an [M,K] x [N,K] launch would take under the current options ("gemm_order", "gemm_pp", "gemm_nt")
+ *   on a device with `cus` compute units (<= 0: the current device's), with the split-K scratch offered or not; host arithmetic only.
+ *   M == 0: the path of the most recent plain launch of this process.
+ * sc_diag_gemm_splitk: the K slices of the split-K rule alone (1 = no split) for `cus` compute units (<= 0: the current device's).
+ * "gemm_order" of sc_diag_set_option: tile walk of the plain 256-tile launches (-1 = default: by shape, 0 below 8 MiB of weights and
+ *   16 from there; else the order word: bit 0 = no XCD remap, word >> 1 = G > 1: column-major inside groups of G row panels). */
+sc_status sc_diag_gemm_bf16_ex(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* W, const float* bias, const float* R,
+                               int32_t M, int32_t N, int32_t K, float* out, int32_t* path);
+sc_status sc_diag_gemm_path(int32_t M, int32_t N, int32_t K, int32_t cus, int32_t splitk_scratch, int32_t* path);
+int32_t sc_diag_gemm_splitk(int32_t M, int32_t N, int32_t K, int32_t cus);
 /* Times `iters` launches of one GEMM shape on device-resident synthetic data (kernel tuning; variant 0 =
  * the product kernel, other values = diagnostic ablations whose outputs are meaningless). */
 sc_status sc_diag_gemm_bench(sc_runtime* rt, int32_t epi, int32_t M, int32_t N, int32_t K, int32_t iters, int32_t variant,

@@ -130,6 +130,10 @@ SIGNATURES = {
     "sc_tokenizer_info": (C.c_int32, [C.c_void_p] + [C.POINTER(C.c_int32)] * 5),
     "sc_tokenizer_encode": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "sc_diag_gemm_bf16": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "sc_diag_gemm_bf16_ex": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p]),
+    "sc_diag_gemm_path": (C.c_int32, [C.c_int32] * 5 + [C.c_void_p]),
+    "sc_diag_gemm_splitk": (C.c_int32, [C.c_int32] * 4),
     "sc_diag_gemm_bench": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "sc_diag_gemm_trace": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "sc_diag_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
@@ -1659,6 +1663,41 @@ def diag_gemm_resln(rt: Runtime, A, W, bias, gam, R, fin, eps: float, a_blocked:
     _check(lib().sc_diag_gemm_resln(rt.handle, 1 if a_blocked else 0, _ptr(Ad), _ptr(W), _ptr(bias), _ptr(gam), _ptr(R), _ptr(fin), float(eps), M, N, K,
                                     _ptr(Cc), _ptr(st)))
     return Cc, st
+
+
+GEMM_PATH_FIELDS = ("tile", "splitk", "order", "pp", "nt")
+
+
+def diag_gemm_bf16_ex(rt: Runtime, A, W, bias, R=None, epi: int = 0, c_blocked: bool = False, a_blocked: bool = False, splitk: bool = False,
+                      tile128: bool = False):
+    """One plain GEMM launch in the forms the forward passes use: (out [M,N], path).  c_blocked: C written in 64-column blocks (un-blocked
+    here); a_blocked: A handed over in 64-column blocks; splitk: the split-K scratch is offered; tile128: the 128-tile kernel is forced.
+    path = what the launcher ran, by GEMM_PATH_FIELDS.  The library checks the arguments before it looks at rt (None reaches them)."""
+    A, W, bias = _f32(A), _f32(W), _f32(bias)
+    R = None if R is None else _f32(R)
+    M, K = A.shape
+    N = W.shape[0]
+    if W.shape != (N, K) or bias.shape != (N,) or (R is not None and R.shape != (M, N)):
+        raise ValueError("diag_gemm_bf16_ex: shapes")
+    Ad = block64(A) if a_blocked and K % 64 == 0 else A
+    out, path = np.empty((M, N), np.float32), np.zeros(5, np.int32)
+    flags = (1 if c_blocked else 0) | (2 if a_blocked else 0) | (4 if splitk else 0) | (8 if tile128 else 0)
+    _check(lib().sc_diag_gemm_bf16_ex(None if rt is None else rt.handle, int(epi), flags, _ptr(Ad), _ptr(W), _ptr(bias), _ptr(R), M, N, K, _ptr(out),
+                                      _ptr(path)))
+    return (unblock64(out, M, N) if c_blocked else out), dict(zip(GEMM_PATH_FIELDS, (int(v) for v in path)))
+
+
+def diag_gemm_path(M: int = 0, N: int = 0, K: int = 0, cus: int = 0, splitk: bool = False) -> "dict[str, int]":
+    """The kernel the plain GEMM launcher picks for this shape under the current options, by GEMM_PATH_FIELDS; no launch, and no device
+    when cus > 0.  M == 0: what the most recent plain launch of this process ran."""
+    path = np.zeros(5, np.int32)
+    _check(lib().sc_diag_gemm_path(int(M), int(N), int(K), int(cus), 1 if splitk else 0, _ptr(path)))
+    return dict(zip(GEMM_PATH_FIELDS, (int(v) for v in path)))
+
+
+def diag_gemm_splitk(M: int, N: int, K: int, cus: int = 0) -> int:
+    """K slices the split-K rule gives this shape on a device with `cus` compute units (1 = no split; cus 0: the current device's)."""
+    return int(lib().sc_diag_gemm_splitk(int(M), int(N), int(K), int(cus)))
 
 
 def diag_qknorm_rope(rt: Runtime, x, heads: int, kv_heads: int, head_dim: int, S: int, theta: float, pos=None, gamma_q=None, gamma_k=None,

@@ -15,13 +15,18 @@ bool sc_gemm_bf16_supported(int M, int N, int K);
 void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C,
                          int ldc, int M, int N, int K, hipStream_t s, void* splitk_scratch = nullptr, size_t splitk_scratch_bytes = 0);
 int sc_gemm_splitk_factor(int M, int N, int K, int cus);
+// The kernel a plain launch takes: tile 128 or 256 (0: nothing was launched -- blocked A handed to a launch the per-tile 256-tile kernel
+// does not serve), K slices (1 = no split-K), the walk order word, the ring depth (0 = one barrier per K-tile) and non-temporal C stores.
+struct ScGemmPath { int tile, splitk, order, pp, nt; };
+ScGemmPath sc_gemm_plain_path(int M, int N, int K, int cus, size_t scratch_bytes);  // under the current options; host arithmetic
+ScGemmPath sc_gemm_last_path(void);                                                 // of the last sc_launch_gemm_bf16 of this process
 // LayerNorm-folded batch pipeline (EPI_LNA_* / EPI_RESLN_STATS)
 bool sc_gemm_ln_supported(int M, int N, int K);
 void sc_launch_gemm_bf16_ln(int epi, const void* A, int lda, const void* W, int ldw, const float* bias, const void* R, int ldr, void* C, int ldc, int M,
                             int N, int K, hipStream_t s, const float* c1, const float* stats_in, float* fin, const float* gam, float* stats_out, float eps,
                             const float* rope_cos = nullptr, const float* rope_sin = nullptr, int rope_S = 0, int rope_ncols = 0);
 void sc_launch_gemm_i8_diag(const void* A, const void* W, void* C, int M, int N, int K, hipStream_t s);
-// process-wide knobs of the launchers (sc_diag_set_option "gemm_pp" / "gemm_nt" / "gemm_strip" / "gemm_strip_n", sc_diag_gemm_trace,
+// process-wide knobs of the launchers (sc_diag_set_option "gemm_pp" / "gemm_nt" / "gemm_order" / "gemm_strip" / "gemm_strip_n", sc_diag_gemm_trace,
 // sc_diag_gemm_bench)
 void sc_gemm_set_debug(int v);
 void sc_gemm_set_order(int v);

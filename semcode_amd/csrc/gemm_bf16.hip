@@ -106,8 +106,10 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs a) {
             const int m = m0 + wm * 64 + mi * 16 + fr;
             f32x4 v = acc[ni][mi] + bv;
             if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752440f));
+                // the form of the 256-tile and split-K epilogues: 0.5 x (1 + erff(x / sqrt 2)) cancels in f32 for x < -3.4 and is off by
+                // more than a bf16 ulp of the result at |gelu| ~ 1e-5 .. 1e-4 (tests/test_gemm_plain_gpu.py)
+                const f32x2 g0 = gelu_erf_fast2(f32x2{v[0], v[1]}), g1 = gelu_erf_fast2(f32x2{v[2], v[3]});
+                v = f32x4{g0[0], g0[1], g1[0], g1[1]};
             }
             if (EPI == EPI_BIAS_RES) {
                 const u16x4 rv = *reinterpret_cast<const u16x4*>(a.R + (size_t)m * a.ldr + n);
@@ -711,7 +713,7 @@ bool sc_gemm_bf16_supported(int M, int N, int K) { return M > 0 && N > 0 && K > 
 // A panel then stays cached for all of its column tiles: encoder 19.50k -> 19.66k chunks/s in a same-box A/B); larger W walks
 // column-major inside groups of 8 row panels, which bounds the W re-reads (profiles/r1n_gemm_tile_order.log).  Both XCD-remapped.
 static int g_gemm_order = -1;
-void sc_gemm_set_order(int v) { g_gemm_order = v; }
+void sc_gemm_set_order(int v) { g_gemm_order = v < 0 ? -1 : v; }
 static unsigned long long* g_gemm_trace = nullptr;
 void sc_gemm_set_trace(unsigned long long* dev) { g_gemm_trace = dev; }
 static int g_gemm_dbg = 0;
@@ -795,6 +797,26 @@ static int gemm_nt(int M, int N) {
     static const char* env_nt = getenv("SC_GEMM_NT");
     return g_gemm_nt >= 0 ? g_gemm_nt : env_nt ? atoi(env_nt) : ((size_t)M * (size_t)N * 2 >= ((size_t)64 << 20));
 }
+// main loop a 256-tile launch of depth K gets: a single K-tile has no ring to ping-pong through
+static int gemm_pp_for(int K) { return K >= 2 * G_BK ? gemm_pp() : 0; }
+
+// Which kernel sc_launch_gemm_bf16 runs for a shape under the current options, as host arithmetic: the launcher dispatches on this and
+// keeps the last one (sc_diag_gemm_path; tests assert the path they name).  scratch_bytes = the split-K scratch on offer (0 = none).
+// The 128-tile kernel has no walk order, ring or non-temporal stores (order 0, pp 0, nt 0); the split-K pair walks row-major without
+// the XCD remap (order 1) on the one-barrier loop and stores plainly.
+static ScGemmPath g_gemm_last = {0, 1, 0, 0, 0};
+ScGemmPath sc_gemm_last_path(void) { return g_gemm_last; }
+ScGemmPath sc_gemm_plain_path(int M, int N, int K, int cus, size_t scratch_bytes) {
+    if ((M % T_BM) || (N % T_BN) || g_force_tile128) return ScGemmPath{G_BM, 1, 0, 0, 0};
+    if (scratch_bytes && !g_gemm_dbg && !g_gemm_trace) {
+        const int d = sc_gemm_splitk_factor(M, N, K, cus);
+        if (d > 1 && (size_t)d * M * N * sizeof(float) <= scratch_bytes) return ScGemmPath{T_BM, d, 1, 0, 0};
+    }
+    static const char* env_order = getenv("SC_GEMM_ORDER");  // A/B experiments
+    const int order = env_order ? atoi(env_order) : g_gemm_order >= 0 ? g_gemm_order : ((size_t)N * (size_t)K * 2 <= ((size_t)8 << 20) ? 0 : 16);
+    return ScGemmPath{T_BM, 1, order, gemm_pp_for(K) ? 4 : 0, gemm_nt(M, N) ? 1 : 0};
+}
+
 // Strip walk of the EPI_LNA_* GEMMs ("gemm_strip" of sc_diag_set_option, SC_GEMM_STRIP): -1 = by shape, 0 = one workgroup per tile,
 // L >= 1 = L column tiles per workgroup (clamped to the tiles of a row panel).  "gemm_strip_n" (scripts/strip_sweep.py) restricts a
 // forced value to the launches with that N; the others then run one workgroup per tile, so that a sweep measures one shape alone.  A strip needs the ping-pong loop, a row-major A and
@@ -842,7 +864,7 @@ static void launch256_pp(const GemmArgs& a, dim3 grid, dim3 block, hipStream_t s
 }
 template <int EPI, int DBG>
 static void launch256(const GemmArgs& a, dim3 grid, dim3 block, hipStream_t s) {
-    const int pp = a.K >= 2 * G_BK ? gemm_pp() : 0;
+    const int pp = gemm_pp_for(a.K);
     if (pp == 0) return launch256_pp<EPI, DBG, 0>(a, grid, block, s);
     if constexpr (DBG == 4) {  // other depths: only as the no-epilogue diagnostic
         if (pp == 3) return launch256_pp<EPI, DBG, 3>(a, grid, block, s);
@@ -903,32 +925,37 @@ void sc_launch_gemm_bf16(int epi, const void* A, int lda, const void* W, int ldw
     a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.bias = bias; a.R = (const bf16_t*)R; a.C = (bf16_t*)C;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldr = ldr; a.ldc = ldc;
     a.cblock = ldc == SC_LDC_BLOCKED64 ? 1 : 0;
-    a.ablock = lda == SC_LDC_BLOCKED64 ? 1 : 0;  // caller's contract: M % 256 == 0, N % 256 == 0, no split-K scratch (the 256-tile kernel)
-    static const char* env_order = getenv("SC_GEMM_ORDER");  // A/B experiments
-    a.order = env_order ? atoi(env_order) : g_gemm_order >= 0 ? g_gemm_order : ((size_t)N * (size_t)K * 2 <= ((size_t)8 << 20) ? 0 : 16);
+    a.ablock = lda == SC_LDC_BLOCKED64 ? 1 : 0;
+    const ScGemmPath p = sc_gemm_plain_path(M, N, K, splitk_scratch ? sc_device_cus() : 0, splitk_scratch ? splitk_scratch_bytes : 0);
+    // A in 64-column blocks is read by the per-tile 256-tile kernel alone (M % 256 == 0, N % 256 == 0, no split-K scratch): the other
+    // kernels would take the sentinel for a leading dimension.  Nothing is launched then, and the record says so (tile 0).
+    if (a.ablock && (p.tile != T_BM || p.splitk != 1)) {
+        g_gemm_last = ScGemmPath{0, 1, 0, 0, 0};
+        return;
+    }
+    g_gemm_last = p;
+    a.order = p.order;
     a.trace = g_gemm_trace;
     a.nt = gemm_nt(M, N);
-    if ((M % T_BM) == 0 && (N % T_BN) == 0 && !g_force_tile128) {
+    if (p.tile == T_BM) {
         a.tiles_n = N / T_BN;
         a.ntiles = (M / T_BM) * a.tiles_n;
         dim3 grid((unsigned)a.ntiles), block(512);
         a.splitk = 1;
         a.strip = 0;
         a.partial = nullptr;
-        if (splitk_scratch && !g_gemm_dbg && !g_gemm_trace) {
-            const int d = sc_gemm_splitk_factor(M, N, K, sc_device_cus());
-            if (d > 1 && (size_t)d * M * N * sizeof(float) <= splitk_scratch_bytes) {
-                a.splitk = d;
-                a.partial = (float*)splitk_scratch;
-                static ScDeviceOnce once_sk;
-                sc_device_once(once_sk, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_splitk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T_LDS_BYTES); });
-                hipLaunchKernelGGL(gemm256_splitk_kernel, dim3((unsigned)(a.ntiles * d)), block, T_LDS_BYTES, s, a);
-                const int rb = (int)std::min<int64_t>(((int64_t)M * (N / 4) + 255) / 256, 1024);
-                if (epi == EPI_BIAS_GELU) hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS_GELU>, dim3((unsigned)rb), dim3(256), 0, s, a);
-                else if (epi == EPI_BIAS_RES) hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS_RES>, dim3((unsigned)rb), dim3(256), 0, s, a);
-                else hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS>, dim3((unsigned)rb), dim3(256), 0, s, a);
-                return;
-            }
+        if (p.splitk > 1) {
+            const int d = p.splitk;
+            a.splitk = d;
+            a.partial = (float*)splitk_scratch;
+            static ScDeviceOnce once_sk;
+            sc_device_once(once_sk, [&] { hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256_splitk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T_LDS_BYTES); });
+            hipLaunchKernelGGL(gemm256_splitk_kernel, dim3((unsigned)(a.ntiles * d)), block, T_LDS_BYTES, s, a);
+            const int rb = (int)std::min<int64_t>(((int64_t)M * (N / 4) + 255) / 256, 1024);
+            if (epi == EPI_BIAS_GELU) hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS_GELU>, dim3((unsigned)rb), dim3(256), 0, s, a);
+            else if (epi == EPI_BIAS_RES) hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS_RES>, dim3((unsigned)rb), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(gemm_splitk_reduce_kernel<EPI_BIAS>, dim3((unsigned)rb), dim3(256), 0, s, a);
+            return;
         }
         switch (g_gemm_dbg) {  // ablations (sc_diag_gemm_bench): results are meaningless
             case 1: launch256<EPI_BIAS, 1>(a, grid, block, s); return;

@@ -203,7 +203,7 @@ extern "C" sc_status sc_diag_set_option(const char* name, int32_t value) {
         {"group_width0", sc_set_group_width0},                {"group_width1", sc_set_group_width1},
         {"mmr_chunk_q", sc_set_mmr_chunk_q},                  {"lex_chunk_q", sc_set_lex_chunk_q},
         {"gemm_strip", sc_gemm_set_strip},                    {"gemm_strip_n", sc_gemm_set_strip_n},
-        {"cls_prune", sc_encoder_set_cls_prune},
+        {"cls_prune", sc_encoder_set_cls_prune},              {"gemm_order", sc_gemm_set_order},
     };
     for (const auto& o : options)
         if (!strcmp(name, o.name)) {

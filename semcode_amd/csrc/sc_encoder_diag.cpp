@@ -69,29 +69,79 @@ sc_status download_bf16(const void* dev, int64_t n, float* host, hipStream_t s) 
 
 // ------------------------------------------------------------------ the GEMMs
 
-extern "C" sc_status sc_diag_gemm_bf16(sc_runtime* rt, int32_t epi, const float* A, const float* W, const float* bias, const float* R,
-                                       int32_t M, int32_t N, int32_t K, float* out) {
-    if (!rt || !A || !W || !bias || !out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bf16: NULL argument");
-    const bool allow_splitk = epi >= 0 && (epi & 16);
-    if (epi >= 0) epi &= 15;
-    if (epi < 0 || epi > 2 || (epi == EPI_BIAS_RES && !R)) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bf16: bad epilogue / missing residual");
-    if (!sc_gemm_bf16_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_bf16: need M%%128==0, N%%128==0, K%%64==0");
+// sc_diag_gemm_bf16_ex in three steps: the rules (host arithmetic, before the runtime is looked at), stage / launch / download, the path
+// the launcher took.  sc_diag_gemm_bf16 is the same with the flags its "+ 16" stands for and its own name in the messages.
+namespace {
+enum { GEMM_EX_CBLOCK = 1, GEMM_EX_ABLOCK = 2, GEMM_EX_SPLITK = 4, GEMM_EX_TILE128 = 8 };
+
+sc_status gemm_ex_validate(const char* who, int epi, int flags, const float* A, const float* W, const float* bias, const float* R, int M, int N, int K,
+                           const float* out) {
+    if (!A || !W || !bias || !out) return sc_fail(SC_ERR_INVALID, "%s: NULL argument", who);
+    if (epi < 0 || epi > 2 || (epi == EPI_BIAS_RES && !R)) return sc_fail(SC_ERR_INVALID, "%s: bad epilogue / missing residual", who);
+    if (flags & ~15) return sc_fail(SC_ERR_INVALID, "%s: flags %d has bits beyond 0 (C blocked), 1 (A blocked), 2 (split-K scratch), 3 (128-tile kernel)", who, flags);
+    if (!sc_gemm_bf16_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "%s: need M%%128==0, N%%128==0, K%%64==0", who);
+    // the launcher's contract for A in 64-column blocks: only the per-tile 256-tile kernel reads that layout
+    if ((flags & GEMM_EX_ABLOCK) && ((M % 256) || (N % 256) || (flags & (GEMM_EX_SPLITK | GEMM_EX_TILE128))))
+        return sc_fail(SC_ERR_UNSUPPORTED,
+                       "%s: blocked A (flags bit 1) is read by the per-tile 256-tile kernel only: needs M%%256==0, N%%256==0, no split-K scratch (bit 2) and "
+                       "no forced 128-tile kernel (bit 3); got M %d, N %d, flags %d", who, M, N, flags);
+    return SC_OK;
+}
+
+sc_status gemm_ex_run(const char* who, sc_runtime* rt, int epi, int flags, const float* A, const float* W, const float* bias, const float* R, int M, int N,
+                      int K, float* out, int32_t* path) {
+    SC_TRY(gemm_ex_validate(who, epi, flags, A, W, bias, R, M, N, K, out));
+    if (!rt) return sc_fail(SC_ERR_INVALID, "%s: the runtime is NULL", who);
     SC_HIP(hipSetDevice(rt->device));
     hipStream_t s = rt->stream;
     sc_devbuf fa, fw, fr, da, dw, dr, db, dc, sk;
     size_t sk_bytes = 0;
-    if (allow_splitk) {
+    if (flags & GEMM_EX_SPLITK) {
         sk_bytes = (size_t)sc_gemm_splitk_factor(M, N, K, rt->cus) * M * N * 4;
         SC_TRY(dev_alloc(sk, sk_bytes));
     }
-    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));
+    SC_TRY(upload_bf16(A, (int64_t)M * K, fa, da, s));  // blocked A is the same M K values in another order
     SC_TRY(upload_bf16(W, (int64_t)N * K, fw, dw, s));
     if (R) SC_TRY(upload_bf16(R, (int64_t)M * N, fr, dr, s));
     SC_TRY(upload(bias, (size_t)N * 4, db, s));
     SC_TRY(alloc_nan(dc, (size_t)M * N * 2, s));
-    sc_launch_gemm_bf16(epi, da.p, K, dw.p, K, (const float*)db.p, dr.p, N, dc.p, N, M, N, K, s, sk.p, sk_bytes);
+    sc_gemm_force_tile128((flags & GEMM_EX_TILE128) != 0);
+    sc_launch_gemm_bf16(epi, da.p, (flags & GEMM_EX_ABLOCK) ? SC_LDC_BLOCKED64 : K, dw.p, K, (const float*)db.p, dr.p, N, dc.p,
+                        (flags & GEMM_EX_CBLOCK) ? SC_LDC_BLOCKED64 : N, M, N, K, s, sk.p, sk_bytes);
+    sc_gemm_force_tile128(false);
+    const ScGemmPath p = sc_gemm_last_path();
+    if (path) path[0] = p.tile, path[1] = p.splitk, path[2] = p.order, path[3] = p.pp, path[4] = p.nt;
+    if (!p.tile) return sc_fail(SC_ERR_UNSUPPORTED, "%s: the launcher refused blocked A for this launch", who);
     return download_bf16(dc.p, (int64_t)M * N, out, s);
 }
+}  // namespace
+
+extern "C" sc_status sc_diag_gemm_bf16(sc_runtime* rt, int32_t epi, const float* A, const float* W, const float* bias, const float* R,
+                                       int32_t M, int32_t N, int32_t K, float* out) {
+    if (!rt) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_bf16: NULL argument");
+    const bool allow_splitk = epi >= 0 && (epi & 16);
+    if (epi >= 0) epi &= 15;
+    return gemm_ex_run("sc_diag_gemm_bf16", rt, epi, allow_splitk ? GEMM_EX_SPLITK : 0, A, W, bias, R, M, N, K, out, nullptr);
+}
+
+extern "C" sc_status sc_diag_gemm_bf16_ex(sc_runtime* rt, int32_t epi, int32_t flags, const float* A, const float* W, const float* bias, const float* R,
+                                          int32_t M, int32_t N, int32_t K, float* out, int32_t* path) {
+    return gemm_ex_run("sc_diag_gemm_bf16_ex", rt, epi, flags, A, W, bias, R, M, N, K, out, path);
+}
+
+// The plain launcher's choice without a launch, and without a device when cus > 0 (include/semcode_hip.h)
+extern "C" sc_status sc_diag_gemm_path(int32_t M, int32_t N, int32_t K, int32_t cus, int32_t splitk_scratch, int32_t* path) {
+    if (!path) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_path: NULL argument");
+    ScGemmPath p = sc_gemm_last_path();
+    if (M != 0) {
+        if (!sc_gemm_bf16_supported(M, N, K)) return sc_fail(SC_ERR_UNSUPPORTED, "sc_diag_gemm_path: need M%%128==0, N%%128==0, K%%64==0");
+        if (cus <= 0) cus = sc_device_cus();
+        p = sc_gemm_plain_path(M, N, K, cus, splitk_scratch ? (size_t)sc_gemm_splitk_factor(M, N, K, cus) * M * N * 4 : 0);
+    }
+    path[0] = p.tile, path[1] = p.splitk, path[2] = p.order, path[3] = p.pp, path[4] = p.nt;
+    return SC_OK;
+}
+extern "C" int32_t sc_diag_gemm_splitk(int32_t M, int32_t N, int32_t K, int32_t cus) { return sc_gemm_splitk_factor(M, N, K, cus > 0 ? cus : sc_device_cus()); }
 
 extern "C" sc_status sc_diag_gemm_i8(sc_runtime* rt, const int8_t* A, const int8_t* W, int32_t M, int32_t N, int32_t K, int32_t* out) {
     if (!rt || !A || !W || !out) return sc_fail(SC_ERR_INVALID, "sc_diag_gemm_i8: NULL argument");
@@ -192,7 +242,7 @@ extern "C" sc_status sc_diag_gemm_bench(sc_runtime* rt, int32_t epi, int32_t M, 
     hipError_t he = hipStreamSynchronize(s);
     sc_gemm_force_tile128(false);
     sc_gemm_set_debug(0);
-    sc_gemm_set_order(16);
+    sc_gemm_set_order(-1);  // back to "by shape", the resting value
     sc_gemm_set_pp(-1);
     float ms = 0;
     hipEventElapsedTime(&ms, e0, e1);

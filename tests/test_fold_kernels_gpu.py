@@ -15,8 +15,14 @@ Kernels launched by forward_locked / forward_folded_locked, and the test that na
     gemm256_bf16_kernel<EPI_LNA_BIAS_ROPE>            test_lna_gemm (rotary part)
     gemm256_bf16_kernel<EPI_RESLN_STATS>              test_resln_gemm, test_resln_output_feeds_an_lna_gemm
       cblock / ablock / nt stores / one-barrier loop  test_lna_gemm, test_resln_gemm (bit-identity of the variants)
-    gemm256_bf16_kernel<EPI_BIAS|_GELU|_RES>, gemm_bf16_kernel, gemm256_splitk_kernel + reduce
+    gemm256_bf16_kernel<EPI_BIAS|_GELU|_RES>          test_gemm_plain_gpu.py::test_256_tile_dense_and_blocked (cblock / ablock),
+                                                      test_256_tile_switches (nt stores, both main loops and residual hooks),
+                                                      test_walk_orders (tile_coords256), test_128_tile_against_256_tile;
                                                       test_encoder_gpu.py::test_gemm_kernel, test_gelu_epilogue_accuracy
+    gemm_bf16_kernel (128-tile)                       test_gemm_plain_gpu.py::test_128_tile_dense_and_blocked_c,
+                                                      test_128_tile_against_256_tile; test_encoder_gpu.py::test_gemm_kernel
+    gemm256_splitk_kernel + gemm_splitk_reduce_kernel test_gemm_plain_gpu.py::test_splitk; test_encoder_gpu.py::test_gemm_kernel
+    gemm256_i8_diag_kernel (the int8 tile loop)       test_gemm_plain_gpu.py::test_int8_tile_loop_is_exact
     attention_kernel / attention_long_kernel          test_encoder_gpu.py::test_attention_kernel (row-major, no bias);
                                                       test_attention_blocked_layout, test_attention_alibi (as the pipelines call it)
     rope_qk_kernel, glu_kernel<ActSilu>               test_nomic_gpu.py::test_rope_kernel, test_swiglu_kernel
